@@ -10,17 +10,24 @@ is the final reduce of the counters and the max over ranks of the wall time
 Workloads (--workload):
   pipeline  (default) BASELINE.json configs[4] per-GPU shard: 10k regexes + sentence delimiter ->
             lexems stay in HBM -> 10k two-term token rules; value = GB/s of text scanned.
-            Headline shape: 64 KiB documents; the same bytes cut into
-            16 KiB documents are timed beside it (config.shapes) unless --docbytes fixes one shape.
+            Headline shape: 64 KiB documents; with --full the same bytes
+            cut into 16 KiB documents are timed beside it (config.shapes) unless --docbytes fixes one shape.
   lexer     configs[1]: 256 regexes over 64 KiB ASCII documents, lexer kernel only
   l2        configs[2]: 10k rules over a pre-tokenized event stream, rule-automaton kernel only
   trees     configs[3]: depth-8 nested within/sequence expression trees (not flat: the general automaton kernel, state in HBM)
+
+A plain run sets up, warms up, times --steps steps of the headline shape, writes the outputs of the
+last timed step with --dump-outputs DIR, and prints the line.  --full adds everything else: the
+16 KiB shape, per-kernel times and rooflines, the CPU baseline with the oracle's parity sample, and
+the join prototype's rule stage.
 """
 import argparse
+import bisect
 import json
 import os
 import sys
 import time
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -41,12 +48,16 @@ def parse_args():
     ap.add_argument("--regexes", type=int, default=0)
     ap.add_argument("--rules", type=int, default=10000)
     ap.add_argument("--docs", type=int, default=0)
-    ap.add_argument("--docbytes", type=int, default=0, help="document size (default: 64 KiB headline + 16 KiB beside it in the pipeline workload, 64 KiB in the lexer workload)")
+    ap.add_argument("--docbytes", type=int, default=0, help="document size (default: 64 KiB headline, with --full + 16 KiB beside it, in the pipeline workload; 64 KiB in the lexer workload)")
     ap.add_argument("--docsize", type=int, default=1000, help="tokens per document (workload l2)")
     ap.add_argument("--features", type=int, default=10000, help="distinct tokens (workload l2)")
     ap.add_argument("--op", default="", help="fix the rule operator (default: the 5-way Zipf mix)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline, the parity sample and the join prototype")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="target size of the bounded CPU-baseline sample")
+    ap.add_argument("--full", action="store_true", help="also the 16 KiB shape, per-kernel times and rooflines, the CPU baseline "
+                                                        "with the oracle's parity sample and the join prototype (off: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed for a fixed sample "
+                                                                       "of documents (and the step's totals) to DIR/<name>.npy, float64")
     return ap.parse_args()
 
 
@@ -67,6 +78,255 @@ def size_until_ok(run, counters, status, reserve, grow, ndocs, what):
         if not (set(codes) <= {2, 9}):
             raise SystemExit("bench: %s documents failed with status codes %s" % (what, codes))
     raise SystemExit("bench: %s: %d documents still failing" % (what, c["failed_docs"]))
+
+
+def text_corpus(ndocs, docbytes, vocab, seed, utf8=False):
+    """The corpus of synth.text_documents(ndocs, docbytes, vocab, seed, utf8), byte for byte, in a
+    fraction of its time.  That generator draws from one PCG64 stream, per document 3 x nw doubles
+    (rank, variant and separator of token k at stream positions S+k, S+nw+k, S+2nw+k), then, for each
+    number token up to the one that ends the document, integers(0, 100000), random() and, below 0.3,
+    integers(0, 1000).  Here the stream is drawn raw and consumed as numpy's Generator consumes it:
+    random() takes one 64-bit draw (its top 53 bits); integers() below 2^32 runs Lemire's method on
+    32-bit halves, the upper half of a draw kept for the next 32-bit request.  What a token at stream
+    position p would be depends on p alone, so stretches of the stream are classified in worker
+    threads (each stretch from its own generator, advanced to it); the main thread walks the
+    documents through them and draws the number tokens one by one.
+    Returns (uint8 array of the text, doc_offsets u64)."""
+    from struspattern_amd import synth
+    nw = docbytes // 5 + 8
+    blk = 3 * nw
+    u64 = np.uint64
+    cum = synth.zipf_cum(len(vocab), 1.0)
+    scale = cum[-1]
+
+    def first_draw(t):
+        """smallest raw draw x with scale * u(x) >= t, u(x) = (x >> 11) * 2^-53 (monotone in x)"""
+        lo = np.zeros(len(t), np.int64)
+        hi = np.full(len(t), 1 << 53, np.int64)
+        while (lo < hi).any():
+            mid = (lo + hi) // 2
+            ge = scale * (mid.astype(np.float64) * 2.0 ** -53) >= t
+            hi = np.where(ge, mid, hi)
+            lo = np.where(ge, lo, mid + 1)
+        return np.where(lo == 1 << 53, u64(0xFFFFFFFFFFFFFFFF), lo.astype(u64) << u64(11))
+    # rank = first i with scale * u < cum[i]: in buckets of the top 20 bits of the draw a bucket spans
+    # at most two ranks, and one compare against the first draw of the upper one decides
+    B = 20
+    edges = first_draw(cum)
+    kb = np.arange((1 << B) + 1, dtype=u64) << u64(64 - B)
+    zlo = np.searchsorted(edges, kb[:-1], side="right").astype(np.int32)
+    if (np.searchsorted(edges, kb[1:] - u64(1), side="right") - zlo > 1).any():
+        raise ValueError("text_corpus: vocabulary too large for the bucketed rank lookup")
+    zcut = np.append(edges, u64(0xFFFFFFFFFFFFFFFF))[zlo]
+
+    def thr(t):   # u(x) < t  <=>  x < thr(t)
+        return u64(int(np.ceil(t * 2.0 ** 53)) << 11)
+    # variant code = number of thresholds <= x: 0 number, 1 capitalised, (utf8:) 2 with 'ö', 3 with '€',
+    # last plain; separator code: 0 ' ', 1 '. ', 2 '\n'
+    vthr = [thr(0.02), thr(0.10)] + ([thr(0.20), thr(0.22)] if utf8 else [])
+    sthr = [thr(0.85), thr(0.95)]
+    T30 = int(thr(0.30))
+    NV = len(vthr) + 1
+    seps = [" ", ". ", "\n"]
+    pieces = []                         # piece id (rank * NV + variant code) * 3 + separator code
+    for w in vocab:
+        pieces += [b""] * 3             # number tokens are drawn apart
+        for v in ((w.capitalize(), w[:1] + "ö" + w[1:], w + "€", w) if utf8 else (w.capitalize(), w)):
+            pieces += [(v + s).encode() for s in seps]
+    W = max(8, max(len(p) for p in pieces))
+    plen = np.array([len(p) for p in pieces], np.int32)
+    table = np.frombuffer(b"".join(p.ljust(W, b"\0") for p in pieces), np.uint8).reshape(-1, W)
+
+    nthreads = max(1, min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)))
+    CH = 1 << 20                        # stream positions per stretch
+    OV = 2 * blk + 1024                 # a stretch reaches this far into the next one
+
+    def classify(k):
+        """stretch k: stream positions [k*CH, (k+1)*CH + OV) -> piece id and byte offset of the token a
+        document would have at each position, and the positions of number tokens"""
+        bg = np.random.PCG64(seed)
+        bg.advance(k * CH)
+        x = bg.random_raw(CH + OV)
+        hb = (x >> u64(64 - B)).astype(np.intp)
+        z = zlo[hb]
+        z += x >= zcut[hb]
+        del hb
+        vc = np.zeros(len(x), np.int32)
+        for t in vthr:
+            vc += x >= t
+        sc = (x >= sthr[0]).astype(np.int32)
+        sc += x >= sthr[1]
+        m = CH + OV - 2 * nw
+        pid = z[:m]
+        pid *= NV
+        pid += vc[nw:nw + m]
+        pid *= 3
+        pid += sc[2 * nw:]
+        cl = np.zeros(m + 1, np.int64)
+        np.cumsum(plen[pid], out=cl[1:])
+        dpos = np.flatnonzero(vc[nw:nw + m] == 0)
+        return x, pid, cl, dpos.tolist(), cl[dpos].tolist(), sc[dpos + 2 * nw].tolist()
+
+    out = np.empty(ndocs * docbytes, np.uint8)
+    offs = np.zeros(ndocs + 1, np.uint64)
+
+    def assemble(pid, S, ntok, digs, obase):
+        """bytes of the documents of one stretch: rows of the piece table, number tokens patched in"""
+        ntok = np.asarray(ntok, np.int64)
+        tstart = np.zeros(len(ntok) + 1, np.int64)
+        np.cumsum(ntok, out=tstart[1:])
+        p = pid[np.repeat(np.asarray(S, np.int64) - tstart[:-1], ntok) + np.arange(tstart[-1])]
+        rows = table[p]
+        ln = plen[p]
+        if digs:
+            ti = np.array([tstart[d] + k for d, k, _ in digs], np.int64)
+            rows[ti] = np.frombuffer(b"".join(s.ljust(W, b"\0") for _, _, s in digs), np.uint8).reshape(-1, W)
+            ln[ti] = [len(s) for _, _, s in digs]
+        b = rows[np.arange(W) < ln[:, None]]
+        out[obase:obase + len(b)] = b
+
+    pool = ThreadPoolExecutor(nthreads)
+    try:
+        # (a document takes its block and about 2 % of nw number tokens of 1.65 draws each)
+        kneed = (ndocs * (blk + nw // 16 + 8)) // CH
+        ahead = {}
+        assembled = []
+        has32, buf32 = False, 0
+        d = 0
+        total = 0
+        Sabs = 0                        # stream position of the next document
+        k = 0
+        while d < ndocs:
+            for j in range(k, max(k + 1, min(k + nthreads + 1, kneed + 1))):
+                if j not in ahead:
+                    ahead[j] = pool.submit(classify, j)
+            x, pid, cl, dpos, dcl, dsep = ahead.pop(k).result()
+            nd = len(dpos)
+            S = Sabs - k * CH
+            dj = 0
+            starts, counts, digs = [], [], []
+            obase = total
+            while d < ndocs and S < CH:
+                base = int(cl[S])
+                lim = base + docbytes
+                dj = bisect.bisect_left(dpos, S, dj)
+                end = S + nw
+                o0 = S + blk            # the number tokens' draws follow the document's block
+                win = None
+                o = 0
+                DL = 0
+                ntok = -1
+                while dj < nd and dpos[dj] < end:
+                    before = dcl[dj] + DL
+                    if before > lim:    # an earlier token ends the document
+                        break
+                    if win is None:
+                        win = x[o0:o0 + 256].tolist()
+                    if o + 4 > len(win):
+                        win += x[o0 + len(win):o0 + len(win) + 256].tolist()
+                    while True:         # integers(0, 100000)
+                        if has32:
+                            a = buf32
+                            has32 = False
+                        else:
+                            r = win[o]
+                            o += 1
+                            a = r & 0xFFFFFFFF
+                            buf32 = r >> 32
+                            has32 = True
+                        m = a * 100000
+                        if (m & 0xFFFFFFFF) >= 67296:
+                            break
+                        if o + 4 > len(win):
+                            win += x[o0 + len(win):o0 + len(win) + 256].tolist()
+                    w = str(m >> 32)
+                    r = win[o]          # random()
+                    o += 1
+                    if r < T30:
+                        while True:     # integers(0, 1000)
+                            if has32:
+                                a = buf32
+                                has32 = False
+                            else:
+                                r = win[o]
+                                o += 1
+                                a = r & 0xFFFFFFFF
+                                buf32 = r >> 32
+                                has32 = True
+                            m = a * 1000
+                            if (m & 0xFFFFFFFF) >= 296:
+                                break
+                            if o + 4 > len(win):
+                                win += x[o0 + len(win):o0 + len(win) + 256].tolist()
+                        w = w[:2] + "'" + "%03d" % (m >> 32)
+                    piece = (w + seps[dsep[dj]]).encode()
+                    if before - base + len(piece) > docbytes:
+                        ntok = dpos[dj] - S
+                        break
+                    DL += len(piece)
+                    digs.append((len(starts), dpos[dj] - S, piece))
+                    dj += 1
+                if ntok < 0:
+                    # the first other token that passes docbytes ends the document, else nw tokens
+                    if int(cl[end]) + DL > lim:
+                        ntok = int(np.searchsorted(cl, lim - DL, side="right")) - 1 - S
+                    else:
+                        ntok = nw
+                total += int(cl[S + ntok]) - base + DL
+                starts.append(S)
+                counts.append(ntok)
+                d += 1
+                offs[d] = total
+                S = o0 + o
+            assembled.append(pool.submit(assemble, pid, starts, counts, digs, obase))
+            Sabs = S + k * CH
+            k += 1
+        for f in assembled:
+            f.result()
+    finally:
+        pool.shutdown(cancel_futures=True)
+    return out[:total], offs
+
+
+DUMP_LIMIT = 64 << 20      # bytes of all the .npy files of --dump-outputs together
+DUMP_DOCS = 16             # documents of the fixed sample (fewer when their outputs pass DUMP_LIMIT)
+
+
+def dump_outputs(path, head, lctx, mctx):
+    """--dump-outputs: what a caller of the timed path receives from its last step, for a fixed sample of
+    the documents (seeded, the same for every run of the same arguments), as float64 .npy files:
+    sample_docs (the document indices); lexems (n, 4) [id, ordpos, origpos, origsize] and lexem_counts
+    per sampled document; results (n, 9), items (m, 7), result_counts and stats (k, 4) of the rule
+    automaton; and counters, the step's totals over all documents (lexems, results, items, events)."""
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.default_rng(20250101)
+    sample = np.sort(rng.choice(head.ndocs, size=min(DUMP_DOCS, head.ndocs), replace=False))
+    out = {"lexems": [], "lexem_counts": [], "results": [], "result_counts": [], "items": [], "stats": []}
+    taken, size = [], 0
+    for di in sample.tolist():
+        got = {}
+        if lctx is not None:
+            lb = lctx.batchFetch(di, 1)
+            got["lexems"], got["lexem_counts"] = lb.lexems, [len(lb.lexems)]
+        if mctx is not None:
+            mb = mctx.batchFetch(di, 1)
+            got["results"], got["result_counts"], got["items"], got["stats"] = mb.results, [len(mb.results)], mb.items, mb.stats
+        n = 8 * sum(np.size(v) for v in got.values())
+        if size + n > DUMP_LIMIT - (1 << 20):       # (the counters and the sample's indices fit in the rest)
+            break
+        taken.append(di)
+        size += n
+        for k, v in got.items():
+            out[k].append(np.asarray(v, np.float64))
+    arrays = {"sample_docs": np.array(taken, np.float64)}
+    for k, parts in out.items():
+        if parts:
+            arrays[k] = np.concatenate(parts)
+    lc = lctx.batchCounters() if lctx is not None else {"lexems": 0}
+    mc = mctx.batchCounters() if mctx is not None else {"results": 0, "items": 0, "events": 0}
+    arrays["counters"] = np.array([lc["lexems"], mc["results"], mc["items"], mc["events"]], np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 class Shape:
@@ -123,12 +383,15 @@ def main():
             piece = args.docbytes or 65536
             group = [("%dKiB" % (piece // 1024), 1)]
         npieces = args.docs * group[0][1] if args.docs else (805306368 // piece)
-        text, offs = synth.text_documents(npieces, piece, vocab, seed=1000 + rank, utf8=(wl == "pipeline"))
+        if not args.full:
+            group = group[:1]
+        # (the bytes of synth.text_documents with the same arguments, tests/test_bench_corpus.py)
+        text, offs = text_corpus(npieces, piece, vocab, seed=1000 + rank, utf8=(wl == "pipeline"))
         nbytes = len(text)
         lxi = spa.PatternLexerInstance()
         synth.apply_lexer_patterns(lxi, pats)
         lctx = lxi.createContext(local_rank)
-        host_text = torch.frombuffer(bytearray(text), dtype=torch.uint8)
+        host_text = torch.from_numpy(text)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         d_text = host_text.cuda()
@@ -184,7 +447,7 @@ def main():
                           lambda c: mctx.reserveOutput(int(c["results"] * 1.2) + 1024, int(c["items"] * 1.2) + 1024),
                           mctx.growArena, sh.ndocs, "matcher")
 
-    def measure(sh, steps, warmup, collective):
+    def measure(sh, steps, warmup, collective, after_timing=None):
         for _ in range(warmup):
             step(sh)
         torch.cuda.synchronize()
@@ -199,9 +462,11 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        # per-kernel launch durations: HIP events recorded by the library on the launch stream
+        if after_timing is not None:
+            after_timing()          # the device buffers still hold what the last timed step computed
+        # per-kernel launch durations (--full): HIP events recorded by the library on the launch stream
         l1_ms, l2_ms, scan_ms, words_ms, post_ms = [], [], [], [], []
-        for _ in range(min(steps, 5)):
+        for _ in range(min(steps, 5) if args.full else 0):
             step(sh)
             if lctx is not None:
                 l1_ms.append(lctx.lastKernelMs())
@@ -228,7 +493,10 @@ def main():
     for sh in shapes[1:]:
         secondary[sh.name] = measure(sh, max(2, min(args.steps, 5)), 1, False)
     head = shapes[0]
-    m = measure(head, args.steps, args.warmup, True)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        dump = lambda: dump_outputs(args.dump_outputs, head, lctx, mctx)
+    m = measure(head, args.steps, args.warmup, True, dump)
 
     # the path's only collective: integer counters summed, wall time maxed over the ranks
     local = {"bytes": nbytes, "lexems": m["lexems"], "events": m["events"], "results": m["results"]}
@@ -236,14 +504,14 @@ def main():
 
     if rank == 0:
         out = report(args, wl, world, pats, head, m, tot, dt, secondary, nbytes, h2d_ms)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             base, parity = cpu_baseline(args, wl, pats, rules, text, head, lex, lctx, mctx)
             ref = base.get("l1_reference") or {}
             if ref.get("GBps_allcores_extrapolated") and m["l1_ms"] > 0:
                 base["gpu_vs_reference_cpu"] = (nbytes / (m["l1_ms"] * 1e-3) / 1e9) / ref["GBps_allcores_extrapolated"]
             out["cpu_baseline"] = base
             out["parity_sample"] = parity
-        if world == 1 and mctx is not None and not args.no_cpu_baseline:
+        if args.full and world == 1 and mctx is not None and not args.no_cpu_baseline:
             if wl != "trees":
                 out["canonical_order_mode"] = canonical_order_mode(wl, rules, head, d_lex if wl == "l2" else None, local_rank, m, nbytes)
         print(json.dumps(out))
@@ -294,10 +562,10 @@ def report(args, wl, world, pats, head, m, tot, dt, secondary, nbytes, h2d_ms):
     l2name = m.get("l2_kernel") or "spa_l2_match_kernel"
     if m["l2_ms"] > 0:
         roofs[l2name] = roofline_of(l2name, m["l2_ms"], b_l2, *pmc_traffic(l2name, wl, args, m["l2_ms"]))
-    dominant = max(roofs.values(), key=lambda r: r["kernel_ms"])
+    dominant = max(roofs.values(), key=lambda r: r["kernel_ms"], default=None)   # (per-kernel times: --full)
     if m["l1_ms"] > 0:
         roofs["lexer"] = roofline_of("scan + post", m["l1_ms"], b_l1)
-    if wl == "pipeline":
+    if wl == "pipeline" and roofs:
         roofs["pipeline"] = roofline_of("lexer + automaton", m["l1_ms"] + m["l2_ms"], float(nbytes) + 36.0 * m["results"])
     workload = {
         "pipeline": "configs[4] per-GPU shard: %d regexes + %d token rules, %d docs x %s UTF-8 per step (the same %d MB resident in HBM every step; configs[4] asks 32 GB per GPU: %d such steps)" % (
@@ -315,10 +583,11 @@ def report(args, wl, world, pats, head, m, tot, dt, secondary, nbytes, h2d_ms):
         "matches_per_s": gresults * steps / dt,
         "events_per_s": gevents * steps / dt,
         "lexems_per_s": glexems * steps / dt,
-        "kernel_ms": {scanname: m["l1_scan_ms"], wordsname: m["l1_words_ms"], "spa_l1_post_kernel": m["l1_post_ms"], l2name: m["l2_ms"]},
-        "roofline": dominant,
-        "roofline_all": roofs,
     }
+    if roofs:
+        out["kernel_ms"] = {scanname: m["l1_scan_ms"], wordsname: m["l1_words_ms"], "spa_l1_post_kernel": m["l1_post_ms"], l2name: m["l2_ms"]}
+        out["roofline"] = dominant
+        out["roofline_all"] = roofs
     if secondary:
         out["config"]["shapes"] = {head.name: {"GB/s": value / world if wl in ("pipeline", "lexer") else None, "ms_per_step": dt / steps * 1e3,
                                                "kernel_ms": [m["l1_ms"], m["l2_ms"]], "matches": m["results"]}}
@@ -509,7 +778,7 @@ def cpu_baseline(args, wl, pats, rules, text, head, lex, lctx, mctx):
     doc_bytes = int(offs[1]) if len(offs) > 1 else 1
     nd = max(1, min(len(offs) - 1, int(args.cpu_seconds * ncores / (t_byte * doc_bytes) / 1.5)))
     nthreads = min(ncores, nd)
-    sub_text = text[:int(offs[nd])]
+    sub_text = bytes(text[:int(offs[nd])])
     t0 = time.perf_counter()
     lexems, loffs = ol.matchDocs(sub_text, offs[:nd + 1], nthreads=nthreads)
     t1 = time.perf_counter()
