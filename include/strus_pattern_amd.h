@@ -25,6 +25,7 @@ extern "C" {
 #define SP_ERR_DEVICE           -3   /* HIP runtime error, or no GPU / HIP extension unusable */
 #define SP_ERR_COMPILE          -4   /* rule / regex compilation failed */
 #define SP_ERR_MATCH            -5   /* at least one document failed, see per-document status */
+#define SP_ERR_UNAVAILABLE      -6   /* the value does not exist for this context (statistics of a result-set context) */
 
 /* per-document status codes written by the kernels (0 = ok) */
 #define SP_DOC_OK                0
@@ -134,6 +135,12 @@ size_t sp_matcher_dump_table(const sp_matcher_t* m, uint32_t** out);
  * documents run with their whole hot state in LDS; 0 = general kernel, `why` says what disqualifies it.
  * Both kernels produce the reference's results (src/ruleMatcherAutomaton.cpp:772-1334); the choice is not observable. */
 int sp_matcher_fast_tier(const sp_matcher_t* m, char* why, size_t whysize);
+/* whether a context created with SP_CTX_RESULT_SETS runs this compiled matcher on the join kernel (result-set mode,
+ * csrc/l2_join.h): 1 = it does, and `alt_programs` (may be NULL) receives the number of programs whose key the optimizer
+ * moved off a frequent event (they follow the reference's replay of the latest logged key event); 0 = it runs on the exact
+ * engine, `why` says what disqualifies it (programs of more or fewer than two terms, nested programs, `and`, more than one
+ * delimiter, the `exclusive` option -- whose outcome depends on the order of the results). */
+int sp_matcher_result_set_tier(const sp_matcher_t* m, char* why, size_t whysize, uint32_t* alt_programs);
 
 /* Compiled-table serialisation (the reference has none -- every process recompiles, and with
  * Hyperscan that takes seconds for 10k patterns, src/patternLexer.cpp:1068-1118): the rule set with its key
@@ -161,6 +168,13 @@ const char* sp_matcher_format_string(const sp_matcher_t* m, uint32_t format_hand
 /* PatternMatcherInstanceInterface::createContext (src/patternMatcher.cpp:586).  `device` is the
  * HIP device ordinal.  Fails with SP_ERR_DEVICE when no GPU is usable: there is no CPU fallback. */
 sp_matcher_ctx_t* sp_matcher_ctx_create(const sp_matcher_t* m, int device);
+/* sp_matcher_ctx_create with flags.  SP_CTX_RESULT_SETS: the context returns, per document, the right MULTISET of results
+ * with their items -- not the reference's order of the results inside a document, and no statistics
+ * (sp_matcher_ctx_statistics returns SP_ERR_UNAVAILABLE).  An eligible rule set (sp_matcher_result_set_tier) runs on the
+ * join kernel (sp_matcher_ctx_kernel_kind 2), any other on the exact engine, whose results are a correct multiset too.
+ * The environment variable SPA_L2_JOIN=1 at context creation sets this flag on every context (sp_matcher_ctx_create too). */
+#define SP_CTX_RESULT_SETS       1u
+sp_matcher_ctx_t* sp_matcher_ctx_create_ex(const sp_matcher_t* m, int device, uint32_t flags);
 void sp_matcher_ctx_free(sp_matcher_ctx_t* c);
 const char* sp_matcher_ctx_last_error(const sp_matcher_ctx_t* c);
 
@@ -173,7 +187,8 @@ int sp_matcher_ctx_fetch_results(sp_matcher_ctx_t* c, sp_result_t** results, siz
 /* format handles of the results / items of the last sp_matcher_ctx_fetch_results (borrowed pointers,
  * valid until the next fetch or reset; NULL when the matcher has no format strings) */
 int sp_matcher_ctx_fetch_formats(sp_matcher_ctx_t* c, const uint32_t** result_format, const uint32_t** item_format);
-/* PatternMatcherContextInterface::getStatistics (:303) of the last fetch */
+/* PatternMatcherContextInterface::getStatistics (:303) of the last fetch; SP_ERR_UNAVAILABLE (and zeros) on a context
+ * that runs in result-set mode on the join kernel, which installs nothing */
 int sp_matcher_ctx_statistics(sp_matcher_ctx_t* c, sp_matcher_stats_t* out);
 /* PatternMatcherContextInterface::reset (:320) */
 int sp_matcher_ctx_reset(sp_matcher_ctx_t* c);
@@ -232,7 +247,8 @@ int sp_matcher_ctx_batch_counters(sp_matcher_ctx_t* c, uint64_t counters[8]);
 /* duration of the last rule-automaton kernel in milliseconds (HIP events on the launch stream) */
 double sp_matcher_ctx_last_kernel_ms(sp_matcher_ctx_t* c);
 /* which kernel the context runs its batches on: 0 general automaton, 1 LDS-resident automaton (flat rule sets),
- * 2 the opt-in join prototype (environment SPA_L2_JOIN=1 at context creation; result SETS with their items, no statistics) */
+ * 2 the join kernel of result-set mode (SP_CTX_RESULT_SETS or SPA_L2_JOIN=1 at context creation, eligible rule set; result
+ * MULTISETS with their items, no order inside a document, no statistics) */
 int sp_matcher_ctx_kernel_kind(const sp_matcher_ctx_t* c);
 /* name of the kernel that does the work of this context's batches (what rocprofv3 lists) */
 const char* sp_matcher_ctx_kernel_name(const sp_matcher_ctx_t* c);

@@ -15,6 +15,9 @@ from .capi import SpLexem, SpResult, SpResultItem
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
            "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND"]
 
+SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
+SP_ERR_UNAVAILABLE = -6     # include/strus_pattern_amd.h: a value that does not exist for the context
+
 JOIN_OP = {"sequence": 0, "sequence_imm": 1, "sequence_struct": 2, "within": 3, "within_struct": 4, "any": 5, "and": 6}
 
 DOC_STATUS = {
@@ -55,10 +58,10 @@ def _formats_of(b):
 class PatternMatcherContext:
     """PatternMatcherContextInterface (src/patternMatcher.cpp:107-341) + batch mode."""
 
-    def __init__(self, instance, device=0):
+    def __init__(self, instance, device=0, result_sets=False):
         self._L = capi.lib()
         self._inst = instance  # keeps the instance alive: a context borrows its tables
-        self._h = self._L.sp_matcher_ctx_create(instance._h, device)
+        self._h = self._L.sp_matcher_ctx_create_ex(instance._h, device, SP_CTX_RESULT_SETS if result_sets else 0)
         if not self._h:
             raise PatternError("failed to create pattern match context: " + self._L.sp_matcher_last_error(instance._h).decode())
 
@@ -111,8 +114,10 @@ class PatternMatcherContext:
         return r, i
 
     def getStatistics(self):
+        """the statistics of the last fetch; None in result-set mode on the join kernel, which installs nothing"""
         st = capi.SpMatcherStats()
-        self._L.sp_matcher_ctx_statistics(self._h, ctypes.byref(st))
+        if self._L.sp_matcher_ctx_statistics(self._h, ctypes.byref(st)) == SP_ERR_UNAVAILABLE:
+            return None
         return {n: getattr(st, n) for n, _ in capi.SpMatcherStats._fields_}
 
     def reset(self):
@@ -207,7 +212,7 @@ class PatternMatcherContext:
         return self._L.sp_matcher_ctx_last_kernel_ms(self._h)
 
     def kernelKind(self):
-        """0 general automaton kernel, 1 LDS-resident kernel (flat rule sets), 2 join prototype (SPA_L2_JOIN=1)"""
+        """0 general automaton kernel, 1 LDS-resident kernel (flat rule sets), 2 join kernel (result-set mode)"""
         return self._L.sp_matcher_ctx_kernel_kind(self._h)
 
     def kernelName(self):
@@ -285,8 +290,11 @@ class PatternMatcherInstance:
         self._chk(self._L.sp_matcher_compile(self._h), "failed to compile (optimize) pattern matching automaton")
         return True
 
-    def createContext(self, device=0):
-        return PatternMatcherContext(self, device)
+    def createContext(self, device=0, result_sets=False):
+        """result_sets=True: the context returns per document the right multiset of results and items, not their order
+        inside the document and no statistics (getStatistics() is None) -- on the join kernel when resultSetTier() says
+        the rule set is eligible, else on the exact engine (include/strus_pattern_amd.h, SP_CTX_RESULT_SETS)."""
+        return PatternMatcherContext(self, device, result_sets)
 
     def patternId(self, name):
         return self._L.sp_matcher_pattern_id(self._h, name.encode())
@@ -314,6 +322,14 @@ class PatternMatcherInstance:
         buf = ctypes.create_string_buffer(256)
         ok = self._L.sp_matcher_fast_tier(self._h, buf, 256)
         return bool(ok), buf.value.decode()
+
+    def resultSetTier(self):
+        """(True, "", alt-keyed programs) when a result-set context runs this rule set on the join kernel, else
+        (False, reason, 0): the reason why it stays on the exact engine."""
+        buf = ctypes.create_string_buffer(256)
+        alt = ctypes.c_uint32(0)
+        ok = self._L.sp_matcher_result_set_tier(self._h, buf, 256, ctypes.byref(alt))
+        return bool(ok), buf.value.decode(), int(alt.value)
 
     def dumpTable(self):
         p = ctypes.POINTER(ctypes.c_uint32)()

@@ -81,6 +81,7 @@ SIGNATURES = {
     "sp_matcher_variable_name": (c_cp, [c_vp, c_u32]),
     "sp_matcher_dump_table": (ctypes.c_size_t, [c_vp, P(P(c_u32))]),
     "sp_matcher_fast_tier": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_matcher_result_set_tier": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u32)]),
     "sp_matcher_serialize": (ctypes.c_int, [c_vp, P(c_vp), P(ctypes.c_size_t)]),
     "sp_matcher_deserialize": (c_vp, [c_vp, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t]),
     "sp_lexer_serialize": (ctypes.c_int, [c_vp, P(c_vp), P(ctypes.c_size_t)]),
@@ -89,6 +90,7 @@ SIGNATURES = {
     "sp_matcher_format_string": (c_cp, [c_vp, c_u32]),
     "sp_matcher_ctx_fetch_formats": (ctypes.c_int, [c_vp, P(P(c_u32)), P(P(c_u32))]),
     "sp_matcher_ctx_create": (c_vp, [c_vp, ctypes.c_int]),
+    "sp_matcher_ctx_create_ex": (c_vp, [c_vp, ctypes.c_int, c_u32]),
     "sp_matcher_ctx_free": (None, [c_vp]),
     "sp_matcher_ctx_last_error": (c_cp, [c_vp]),
     "sp_matcher_ctx_put_input": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_size_t]),

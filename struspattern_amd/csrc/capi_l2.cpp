@@ -22,7 +22,7 @@ hipError_t launchL2Fast( const FastParams& P, unsigned variant, unsigned nblocks
 int fastBlocksPerCU( unsigned variant);
 void fastCapacities( unsigned variant, uint32_t& R, uint32_t& T);
 std::string buildFastTables( const FlatTables& ft, std::vector<FastKeyInst>& out, std::vector<FastStatic>* statics);
-std::string buildJoinTables( const FlatTables& ft, std::vector<JoinKey>& keytab, std::vector<JoinRule>& rules, std::vector<uint32_t>& filter, uint32_t& maxRange, uint32_t& delimiter);
+std::string buildJoinTables( const FlatTables& ft, std::vector<JoinKey>& keytab, std::vector<JoinRule>& rules, std::vector<uint32_t>& filter, uint32_t& maxRange, uint32_t& delimiter, uint32_t& altPrograms);
 hipError_t launchL2Join( const JoinParams& P, unsigned nwaves, hipStream_t stream);
 void layoutFast( FastSpillLayout& S, uint32_t bucketMeta[16], uint32_t& expShift, const std::vector<FastKeyInst>& keyinst, uint32_t R, uint32_t T, uint32_t maxRules, uint32_t maxStaged);
 }
@@ -98,8 +98,8 @@ struct sp_matcher_ctx
 	bool fast;
 	std::string whyNotFast;
 	DeviceBuffer dKeyinst, dStatics, dSpill, dFallbackList;
-	// join prototype (l2_join.h, opt-in by SPA_L2_JOIN=1): result sets without materialised rule instances
-	bool join; std::string whyNotJoin; uint32_t joinKeymask, joinMaxRange, joinDelimiter; DeviceBuffer dJoinKeytab, dJoinRules, dJoinFilter, dJoinCounts;
+	// result-set mode (l2_join.h; SP_CTX_RESULT_SETS or SPA_L2_JOIN=1): result multisets without materialised rule instances
+	bool join, joinAltRules; std::string whyNotJoin; uint32_t joinKeymask, joinMaxRange, joinDelimiter; DeviceBuffer dJoinKeytab, dJoinRules, dJoinFilter, dJoinCounts;
 	std::vector<FastKeyInst> fastKeyinst;
 	FastSpillLayout fastSpill; uint32_t fastBucketMeta[ 16]; uint32_t fastExpShift;
 	unsigned fastWaves, fastBlocksPerCU, fastVariant;	// variant: kernel instance = LDS capacities (l2_fast_kernel.hip)
@@ -125,7 +125,7 @@ struct sp_matcher_ctx
 	std::vector<uint32_t> curOrigseg; bool curHasSeg;
 	sp_matcher_stats_t lastStats;
 
-	sp_matcher_ctx() :inst(0),device(0),keymask(0),nofStopWords(0),fast(false),join(false),joinKeymask(0),joinMaxRange(0),joinDelimiter(0),fastWaves(0),fastBlocksPerCU(0),fastVariant(4),fastMaxRules(2048),fastMaxStaged(32768),arenaWaves(0),withFormats(false),resultCapacity(0),itemCapacity(0),minResultCapacity(0),minItemCapacity(0)
+	sp_matcher_ctx() :inst(0),device(0),keymask(0),nofStopWords(0),fast(false),join(false),joinAltRules(false),joinKeymask(0),joinMaxRange(0),joinDelimiter(0),fastWaves(0),fastBlocksPerCU(0),fastVariant(4),fastMaxRules(2048),fastMaxStaged(32768),arenaWaves(0),withFormats(false),resultCapacity(0),itemCapacity(0),minResultCapacity(0),minItemCapacity(0)
 		,lastNdocs(0),evStart(0),evStop(0),evValid(false),lastStream(0),own(0),withItems(true),numCUs(256),curHasSeg(false)
 	{
 		std::memset( &arena, 0, sizeof(arena));
@@ -197,7 +197,7 @@ const char* sp_matcher_variable_name( const sp_matcher_t* m, uint32_t variable) 
 uint32_t sp_matcher_format_count( const sp_matcher_t* m) { return m->compiler.formatCount(); }
 const char* sp_matcher_format_string( const sp_matcher_t* m, uint32_t format_handle) { return m->compiler.formatString( format_handle); }
 
-// which kernel the context's batches run on: 0 = general, 1 = LDS-resident (flat rule sets), 2 = join prototype (SPA_L2_JOIN=1)
+// which kernel the context's batches run on: 0 = general, 1 = LDS-resident (flat rule sets), 2 = join kernel (result-set mode)
 int sp_matcher_ctx_kernel_kind( const sp_matcher_ctx_t* c) { return c->join ? 2 : c->fast ? 1 : 0; }
 // name of the kernel that does a batch's work (the instance of the LDS-resident kernel is picked by SPA_L2_FAST_SIZE, default n)
 const char* sp_matcher_ctx_kernel_name( const sp_matcher_ctx_t* c)
@@ -218,6 +218,37 @@ int sp_matcher_fast_tier( const sp_matcher_t* m, char* why, size_t whysize)
 		std::vector<FastKeyInst> ki;
 		const std::string reason = buildFastTables( ft, ki, 0);
 		if (why && whysize) { std::strncpy( why, reason.c_str(), whysize-1); why[ whysize-1] = 0; }
+		return reason.empty() ? 1 : 0;
+	}
+	catch (const std::exception& e)
+	{
+		if (why && whysize) { std::strncpy( why, e.what(), whysize-1); why[ whysize-1] = 0; }
+		return 0;
+	}
+}
+
+// result-set mode: the join tables of the compiled rule set, or the reason why it stays on the exact engine
+static std::string buildResultSetTables( const sp_matcher* m, const FlatTables& ft, std::vector<JoinKey>& keytab, std::vector<JoinRule>& rules,
+					std::vector<uint32_t>& filter, uint32_t& maxRange, uint32_t& delimiter, uint32_t& altPrograms)
+{
+	altPrograms = 0;
+	// (`exclusive` drops the results covered by another one in a scan that follows the order of the results, copyOutBatch)
+	if (m->compiler.exclusive()) return "the `exclusive` option (its outcome depends on the order of the results)";
+	return buildJoinTables( ft, keytab, rules, filter, maxRange, delimiter, altPrograms);
+}
+
+int sp_matcher_result_set_tier( const sp_matcher_t* m, char* why, size_t whysize, uint32_t* alt_programs)
+{
+	if (alt_programs) *alt_programs = 0;
+	try
+	{
+		FlatTables ft;
+		m->compiler.flatten( ft);
+		std::vector<JoinKey> jk; std::vector<JoinRule> jr; std::vector<uint32_t> jf;
+		uint32_t maxRange = 0, delimiter = 0, alt = 0;
+		const std::string reason = buildResultSetTables( m, ft, jk, jr, jf, maxRange, delimiter, alt);
+		if (why && whysize) { std::strncpy( why, reason.c_str(), whysize-1); why[ whysize-1] = 0; }
+		if (alt_programs && reason.empty()) *alt_programs = alt;
 		return reason.empty() ? 1 : 0;
 	}
 	catch (const std::exception& e)
@@ -269,7 +300,17 @@ size_t sp_matcher_dump_table( const sp_matcher_t* m, uint32_t** out)
 // ------------------------------------------------------------------ context
 sp_matcher_ctx_t* sp_matcher_ctx_create( const sp_matcher_t* m, int device)
 {
+	return sp_matcher_ctx_create_ex( m, device, 0);
+}
+
+sp_matcher_ctx_t* sp_matcher_ctx_create_ex( const sp_matcher_t* m, int device, uint32_t flags)
+{
 	sp_matcher_ctx* c = 0;
+	if (flags & ~(uint32_t)SP_CTX_RESULT_SETS)
+	{
+		m->lasterror = "unknown context flags";
+		return 0;
+	}
 	try
 	{
 		c = new sp_matcher_ctx();
@@ -318,20 +359,22 @@ sp_matcher_ctx_t* sp_matcher_ctx_create( const sp_matcher_t* m, int device)
 			}
 			if (getenv( "SPA_L2_VERBOSE")) fprintf( stderr, "[spa] fast tier: %s\n", c->fast ? "on" : c->whyNotFast.c_str());
 		}
-		if (const char* e = getenv( "SPA_L2_JOIN"))
+		// result-set mode: asked for by the flag, or for every context by SPA_L2_JOIN=1; ineligible rule sets stay on the
+		// exact engine, whose results are a correct multiset too
+		if (const char* e = getenv( "SPA_L2_JOIN")) if (e[0] == '1') flags |= SP_CTX_RESULT_SETS;
+		if (flags & SP_CTX_RESULT_SETS)
 		{
-			if (e[0] == '1')
+			std::vector<JoinKey> jk; std::vector<JoinRule> jr; std::vector<uint32_t> jf;
+			uint32_t altPrograms = 0;
+			c->whyNotJoin = buildResultSetTables( m, ft, jk, jr, jf, c->joinMaxRange, c->joinDelimiter, altPrograms);
+			c->join = c->whyNotJoin.empty();
+			if (c->join)
 			{
-				std::vector<JoinKey> jk; std::vector<JoinRule> jr; std::vector<uint32_t> jf;
-				c->whyNotJoin = buildJoinTables( ft, jk, jr, jf, c->joinMaxRange, c->joinDelimiter);
-				c->join = c->whyNotJoin.empty();
-				if (c->join)
-				{
-					c->dJoinKeytab.upload( jk.data(), jk.size()*sizeof(JoinKey)); c->dJoinRules.upload( jr.data(), jr.size()*sizeof(JoinRule)); c->dJoinFilter.upload( jf.data(), jf.size()*sizeof(uint32_t));
-					c->joinKeymask = (uint32_t)jk.size()-1;
-				}
-				if (getenv( "SPA_L2_VERBOSE")) fprintf( stderr, "[spa] join prototype: %s\n", c->join ? "on" : c->whyNotJoin.c_str());
+				c->dJoinKeytab.upload( jk.data(), jk.size()*sizeof(JoinKey)); c->dJoinRules.upload( jr.data(), jr.size()*sizeof(JoinRule)); c->dJoinFilter.upload( jf.data(), jf.size()*sizeof(uint32_t));
+				c->joinKeymask = (uint32_t)jk.size()-1;
+				c->joinAltRules = altPrograms != 0;
 			}
+			if (getenv( "SPA_L2_VERBOSE")) fprintf( stderr, "[spa] result-set mode: %s\n", c->join ? "join kernel" : c->whyNotJoin.c_str());
 		}
 		c->dCursor.alloc( 256);		// u32: [0] fast cursor, [1] general cursor (list mode), [2] hand-over count, [16..31] hand-over reasons, [32..47] phase profile (u64 x 8)
 		c->dCounters.alloc( SPC_COUNT*sizeof(uint64_t));
@@ -692,12 +735,12 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 	}
 	else if (c->join)
 	{
-		// opt-in prototype: result sets by joining positions, nothing installed (l2_join.h)
+		// result-set mode: result multisets by joining positions, nothing installed (l2_join.h)
 		JoinParams J;
 		std::memset( &J, 0, sizeof(J));
 		c->dJoinCounts.reserve( (nlexems + 64) * sizeof(uint32_t));
 		J.filter = (const uint32_t*)c->dJoinFilter.ptr; J.counts = (uint32_t*)c->dJoinCounts.ptr; J.countsCapacity = nlexems;
-		J.keytab = (const JoinKey*)c->dJoinKeytab.ptr; J.keymask = c->joinKeymask; J.rules = (const JoinRule*)c->dJoinRules.ptr; J.maxRange = c->joinMaxRange; J.delimiter = c->joinDelimiter;
+		J.keytab = (const JoinKey*)c->dJoinKeytab.ptr; J.keymask = c->joinKeymask; J.rules = (const JoinRule*)c->dJoinRules.ptr; J.maxRange = c->joinMaxRange; J.delimiter = c->joinDelimiter; J.altRules = c->joinAltRules ? 1u : 0u;
 		J.lexems = P.lexems; J.origseg = P.origseg; J.docOffsets = P.docOffsets; J.docRangesIn = P.docRangesIn; J.ndocs = P.ndocs;
 		J.docCursor = (uint32_t*)c->dCursor.ptr;
 		J.counters = P.counters; J.results = P.results; J.resultCapacity = P.resultCapacity;
@@ -994,6 +1037,13 @@ int sp_matcher_ctx_fetch_formats( sp_matcher_ctx_t* c, const uint32_t** result_f
 
 int sp_matcher_ctx_statistics( sp_matcher_ctx_t* c, sp_matcher_stats_t* out)
 {
+	if (c->join)
+	{
+		// result-set mode installs nothing: no numbers that would look real
+		std::memset( out, 0, sizeof(*out));
+		c->lasterror = "no statistics in result-set mode (nothing is installed)";
+		return SP_ERR_UNAVAILABLE;
+	}
 	*out = c->lastStats;
 	return SP_OK;
 }

@@ -1,16 +1,21 @@
-// PROTOTYPE, opt-in (SPA_L2_JOIN=1): the rule automaton WITHOUT materialised rule instances, for rule sets made of two-term
-// `sequence( A, B | range )` programs that nobody listens to ("The ceiling").
-// The reference installs an instance at every A and retires it at the first later B or when it expires
-// (src/ruleMatcherAutomaton.cpp:589-1334); the result SET of a document follows from the positions alone:
+// RESULT-SET MODE (sp_matcher_ctx_create_ex( .., SP_CTX_RESULT_SETS), or SPA_L2_JOIN=1): the rule automaton WITHOUT
+// materialised rule instances, for rule sets made of two-term programs (sequence, within, their _struct forms, any) that
+// nobody listens to ("The ceiling").
+// The reference installs an instance at every key event and retires it at the first later completing term or when it expires
+// (src/ruleMatcherAutomaton.cpp:589-1334); the result MULTISET of a document follows from the positions alone:
 //   (A at lexem i, B at lexem j) matches  iff  ordpos(i) < ordpos(j) <= ordpos(i) + range  and no B lies between them at a
 //   position behind i's (that B would have taken the instance).
+// Programs that the optimizer moved off a frequent key event A onto their other term B (DevKeyRef::pastEvent,
+// ruleMatcherAutomaton.cpp:512-586) follow another predicate: an instance at every B that replays only the LATEST logged A,
+// is cancelled by a delimiter logged after it, and lingers until it expires when it does not complete at once -- so a pair
+// can match more than once.  JOIN_ALT_* below and tests/result_set_model.py (checked against the oracle) give its terms.
 // So every lexem j looks back over the lexems of the last `maxRange` positions and asks a hash table keyed by the PAIR of event
 // ids (id(i), id(j)) for the programs it completes -- lane-parallel over the lexems, no per-document state at all (a first
 // version that sorted the document's (id, index) pairs in LDS and searched them per rule was 7 x SLOWER than the exact
 // engine: it pays per (lexem, rule that ends with it) pair, which is as many as the exact engine's installs).
 // What this mode does NOT reproduce: the order of the results inside a document (the reference's depends on the swap history
 // of its trigger buckets) and the statistics (nothing is installed); results come in (end lexem, start lexem descending,
-// rule) order.  Parity is therefore checked on result SETS (tests/test_l2_join_gpu.py).
+// rule) order.  Parity is therefore checked on result multisets (tests/test_l2_join_gpu.py, tests/test_result_sets_gpu.py).
 #ifndef SPA_L2_JOIN_H
 #define SPA_L2_JOIN_H
 #include <stdint.h>
@@ -28,6 +33,18 @@ enum {JOIN_FILTER_WORDS=4096};		// 16 KB = 131072 bits
 enum {JOIN_SELF=0xFFFFFFFFu};		// `first` of the entries for any( .. ): the lexem alone is the match
 enum {JOIN_STRUCT=1u};			// JoinRule::flags: no delimiter lexem may lie between the two terms (*_struct);
 					// bits 8..15 / 16..23: the variable attached to the first / the completing term (0 = none)
+// JoinRule::flags, entries of moved key references (A = id(i), B = id(j) of the pair (i, j), "taken": a B in (i, j) at a
+// position behind i's):
+enum {
+	JOIN_ALT_SEQ=2u,		// sequence( A, B) keyed at B, past A:  [no A in (i, j)]  (the replay of the instance at j)
+					//  + [not taken] * #{B in (i, next A) at ordpos(i)}  (instances of Bs beside i that replayed i)
+					//  + [not taken] * #{B at k < i: ordpos(k) + range >= ordpos(j), ordpos(k) > ordpos(latest A before i)
+					//     + range, no delimiter in (k, i)}  (instances of Bs without a replay that took i as their A)
+	JOIN_ALT_REPLAY=4u,		// within( A, B) keyed at B, past A:  [no A in (i, j)]
+	JOIN_ALT_LINGER=8u,		// within( .., ..) keyed at A, past B (pair A at i, B at j):  [not taken] *
+					//  [no B before i at a position >= ordpos(i) - range]  (no replay: the instance waited for a B)
+	JOIN_ALT=14u
+};
 struct JoinRule			// 16 B
 {
 	uint32_t range;
@@ -67,6 +84,7 @@ struct JoinParams
 	uint32_t* items; uint64_t itemCapacity; uint32_t withItems; uint32_t* itemFormat;	// sp_result_item_t[] (7 words each)
 	uint64_t* docRange; uint64_t* docStats; int32_t* docStatus;
 	uint32_t withFormats; uint32_t* resultFormat;
+	uint32_t altRules;		// some rule has a JOIN_ALT_* flag: the look-back goes on behind a taking lexem
 };
 
 } // namespace

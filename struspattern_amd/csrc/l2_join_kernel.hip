@@ -1,4 +1,4 @@
-// PROTOTYPE of the non-materialising rule automaton (l2_join.h): lane-parallel over the lexems of a document, no state.
+// Result-set mode, the non-materialising rule automaton (l2_join.h): lane-parallel over the lexems of a document, no state.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "l2_join.h"
@@ -32,6 +32,50 @@ __device__ __forceinline__ void putItem( const JoinParams& P, u64 at, u32 variab
 	st4( io, variable, t.y, t.y + 1u, st); st3( io+4, t.z, st, t.z + t.w);
 	if (P.withFormats) { P.itemFormat[ 2*at] = 0; P.itemFormat[ 2*at+1] = 0; }
 }
+// how many times the pair (i, j) matches for a rule of a moved key reference (JOIN_ALT_* in l2_join.h); the caller has checked
+// ordpos(i) < ordpos(j) <= ordpos(i) + range and the delimiter between them.  Lane-private scans over the few lexems of the
+// last 2 x range positions (range <= the optimizer's maxRange, 5 by default), read through the cache like the main look-back.
+__device__ __forceinline__ u32 altMatches( const JoinParams& P, const uint4* lex, u32 i, u32 j, u32 a, u32 b, u32 pi, u32 pj, u32 range, u32 flags, bool taken)
+{
+	if (flags & JOIN_ALT_LINGER)
+	{
+		if (taken) return 0;
+		for (u32 k=i; k-- > 0;)
+		{
+			const uint2 lk = make_uint2( lex[ k].x, lex[ k].y);
+			if (lk.y + range < pi) break;
+			if (lk.x == b) return 0;		// the instance at i replayed that b (or gave up on it) instead of waiting
+		}
+		return 1;
+	}
+	// the replay of the instance installed at j: i must be the latest a before j
+	u32 m = 1, nb = 0;
+	for (u32 k=i+1; k<j; ++k)
+	{
+		const u32 x = lex[ k].x;
+		if (x == a) { m = 0; break; }
+		if (x == b && lex[ k].y == pi) ++nb;		// (JOIN_ALT_SEQ: a b beside i that replayed i and waited for a later b)
+	}
+	if (!(flags & JOIN_ALT_SEQ) || taken) return m;
+	m += nb;
+	// instances of earlier bs without a replay (no a within range before them) that took i as their first a
+	u32 lim = 0; bool prevA = false;
+	for (u32 k=i; k-- > 0;)
+	{
+		const uint2 lk = make_uint2( lex[ k].x, lex[ k].y);
+		if (lk.y + 2u*range < pj) break;
+		if (lk.x == a) { lim = lk.y + range; prevA = true; break; }
+	}
+	for (u32 k=i; k-- > 0;)
+	{
+		const uint2 lk = make_uint2( lex[ k].x, lex[ k].y);
+		if (lk.y + range < pj || (prevA && lk.y <= lim)) break;
+		if ((flags & JOIN_STRUCT) && lk.x == P.delimiter) break;
+		if (lk.x == b) ++m;
+	}
+	return m;
+}
+
 // returns matches | items << 16
 template <bool WRITE>
 __device__ __forceinline__ u32 matchesEndingAt( const JoinParams& P, const uint4* lex, const u32* seg, u32 j, uint4 lj, u32* out, u32* fmtOut, u64 itemAt)
@@ -77,7 +121,8 @@ __device__ __forceinline__ u32 matchesEndingAt( const JoinParams& P, const uint4
 	{
 		const uint4 li = lex[ i];
 		if (lj.y - li.y > P.maxRange) break;		// every instance that old has expired
-		if (takenPos > li.y) break;			// this one and all earlier ones were completed by that occurrence
+		const bool taken = takenPos > li.y;		// this one and all earlier ones were completed by that occurrence
+		if (taken && !P.altRules) break;		// (the replays of moved key references are not)
 		if (li.x && lj.y > li.y && maybeKey( li.x, e))
 		{
 			u32 slot = joinHash( li.x, e) & P.keymask;
@@ -91,19 +136,25 @@ __device__ __forceinline__ u32 matchesEndingAt( const JoinParams& P, const uint4
 					{
 						const JoinRule rule = P.rules[ k.begin + r];
 						if (lj.y - li.y > rule.range || (delimited && (rule.flags & JOIN_STRUCT))) continue;
+						u32 times = 1;
+						if (rule.flags & JOIN_ALT) times = altMatches( P, lex, i, j, li.x, e, li.y, lj.y, rule.range, rule.flags, taken);
+						else if (taken) continue;
 						// captured items, latest first (as the reference lists them): the completing lexem's, then the first one's
 						const u32 vi = P.withItems ? (rule.flags >> 8) & 0xFFu : 0u, vj = P.withItems ? (rule.flags >> 16) & 0xFFu : 0u;
 						const u32 ni = (vi ? 1u : 0u) + (vj ? 1u : 0u);
-						if (WRITE)
+						for (u32 t=0; t<times; ++t)
 						{
-							u32* o = out + 9*(u64)cnt;
-							const u32 si = seg ? seg[ i] : 0u, sj = seg ? seg[ j] : 0u;
-							st4( o, rule.resultHandle, li.y, lj.y + 1u, si); st4( o+4, li.z, sj, lj.z + lj.w, P.withItems ? (u32)(itemAt + icnt) : 0u); o[8] = ni;
-							if (fmtOut) fmtOut[ cnt] = rule.formatHandle;
-							if (vj) putItem( P, itemAt + icnt, vj, lj, sj);
-							if (vi) putItem( P, itemAt + icnt + (vj ? 1u : 0u), vi, li, si);
+							if (WRITE)
+							{
+								u32* o = out + 9*(u64)cnt;
+								const u32 si = seg ? seg[ i] : 0u, sj = seg ? seg[ j] : 0u;
+								st4( o, rule.resultHandle, li.y, lj.y + 1u, si); st4( o+4, li.z, sj, lj.z + lj.w, P.withItems ? (u32)(itemAt + icnt) : 0u); o[8] = ni;
+								if (fmtOut) fmtOut[ cnt] = rule.formatHandle;
+								if (vj) putItem( P, itemAt + icnt, vj, lj, sj);
+								if (vi) putItem( P, itemAt + icnt + (vj ? 1u : 0u), vi, li, si);
+							}
+							++cnt; icnt += ni;
 						}
-						++cnt; icnt += ni;
 					}
 					break;
 				}
