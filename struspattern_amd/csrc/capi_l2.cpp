@@ -9,7 +9,6 @@
 #include <hip/hip_runtime_api.h>
 #include <cstdlib>
 #include <cstdio>
-#include <unistd.h>
 #include <cstring>
 #include <new>
 #include <stdexcept>
@@ -21,6 +20,8 @@ hipError_t launchL2Match( const L2Params& P, unsigned nblocks, hipStream_t strea
 hipError_t launchL2Fast( const FastParams& P, unsigned variant, unsigned nblocks, hipStream_t stream);
 int fastBlocksPerCU( unsigned variant);
 void fastCapacities( unsigned variant, uint32_t& R, uint32_t& T);
+unsigned fastVariantNamed( const char* size);
+const char* fastKernelName( unsigned variant);
 std::string buildFastTables( const FlatTables& ft, std::vector<FastKeyInst>& out, std::vector<FastStatic>* statics);
 std::string buildJoinTables( const FlatTables& ft, std::vector<JoinKey>& keytab, std::vector<JoinRule>& rules, std::vector<uint32_t>& filter, uint32_t& maxRange, uint32_t& delimiter, uint32_t& altPrograms);
 hipError_t launchL2Join( const JoinParams& P, unsigned nwaves, hipStream_t stream);
@@ -204,8 +205,7 @@ const char* sp_matcher_ctx_kernel_name( const sp_matcher_ctx_t* c)
 {
 	if (c->join) return "spa_l2_join_kernel";
 	if (!c->fast) return "spa_l2_match_kernel";
-	static const char* names[ 5] = {"spa_l2_fast_kernel_s", "spa_l2_fast_kernel_m", "spa_l2_fast_kernel_l", "spa_l2_fast_kernel_t", "spa_l2_fast_kernel_n"};
-	return names[ c->fastVariant < 5 ? c->fastVariant : 4];
+	return fastKernelName( c->fastVariant);
 }
 
 // 1 when the compiled rule set is flat (l2_fast.h) and runs on the LDS-resident kernel, else 0 with the reason
@@ -352,7 +352,7 @@ sp_matcher_ctx_t* sp_matcher_ctx_create_ex( const sp_matcher_t* m, int device, u
 				c->dStatics.upload( ks.data(), ks.size()*sizeof(FastStatic));
 				c->fastKeyinst.swap( ki);
 				// SPA_L2_FAST_SIZE=s|m|l picks the kernel instance (LDS capacities; t = the tiny one of the tests); the spill area takes what does not fit
-				if (const char* e = getenv( "SPA_L2_FAST_SIZE")) c->fastVariant = (e[0] == 's') ? 0u : (e[0] == 'm') ? 1u : (e[0] == 'l') ? 2u : (e[0] == 't') ? 3u : 4u;
+				if (const char* e = getenv( "SPA_L2_FAST_SIZE")) c->fastVariant = fastVariantNamed( e);
 				if (const char* e = getenv( "SPA_L2_FAST_MAXRULES")) c->fastMaxRules = (uint32_t)atoi( e);
 				if (const char* e = getenv( "SPA_L2_FAST_MAXSTAGED")) c->fastMaxStaged = (uint32_t)atoi( e);
 				if (c->fastMaxRules > 4095) c->fastMaxRules = 4095;		// trigger ids are 14 bits (rule << 2 | slot)
@@ -613,6 +613,24 @@ int sp_matcher_ctx_reserve_output( sp_matcher_ctx_t* c, uint64_t results, uint64
 
 namespace {
 
+// the batch contract of every rule kernel (l2_device.h): this batch's input, the context's output buffers
+L2BatchIO batchIO( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg, const void* d_doc_offsets, const void* d_doc_ranges, size_t ndocs)
+{
+	L2BatchIO io;
+	std::memset( &io, 0, sizeof(io));
+	io.lexems = (const uint32_t*)d_lexems; io.origseg = (const uint32_t*)d_origseg;
+	io.docOffsets = (const uint64_t*)d_doc_offsets; io.docRangesIn = (const uint64_t*)d_doc_ranges;
+	io.ndocs = (uint32_t)ndocs; io.withItems = c->withItems ? 1u : 0u;
+	io.docCursor = (uint32_t*)c->dCursor.ptr;
+	io.counters = (uint64_t*)c->dCounters.ptr;
+	io.results = (uint32_t*)c->dResults.ptr; io.resultCapacity = c->resultCapacity;
+	io.items = (uint32_t*)c->dItems.ptr; io.itemCapacity = c->itemCapacity;
+	io.docRange = (uint64_t*)c->dDocRange.ptr; io.docStats = (uint64_t*)c->dDocStats.ptr; io.docStatus = (int32_t*)c->dDocStatus.ptr;
+	io.withFormats = c->withFormats ? 1u : 0u;
+	io.resultFormat = (uint32_t*)c->dResultFormat.ptr; io.itemFormat = (uint32_t*)c->dItemFormat.ptr;
+	return io;
+}
+
 // enqueue one batch on `stream`; all inputs are device pointers
 // `rerun` (host entry points): only these documents of the batch already in the output buffers run again, on the
 // general kernel in list mode with the working set the caller has just grown -- the results of the other
@@ -689,38 +707,8 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 	P.keytab = (const DevKeyEntry*)c->dKeytab.ptr;
 	P.keylist = (const DevKeyRef*)c->dKeylist.ptr;
 	P.keymask = c->keymask; P.nofStopWords = c->nofStopWords;
-	P.lexems = (const uint32_t*)d_lexems; P.origseg = (const uint32_t*)d_origseg;
-	P.docOffsets = (const uint64_t*)d_doc_offsets;
-	P.docRangesIn = (const uint64_t*)d_doc_ranges;
-	P.ndocs = (uint32_t)ndocs; P.withItems = c->withItems ? 1u : 0u;
+	P.io = batchIO( c, d_lexems, d_origseg, d_doc_offsets, d_doc_ranges, ndocs);
 	P.arenaBase = (uint32_t*)c->dArena.ptr; P.arena = c->arena;
-	P.docCursor = (uint32_t*)c->dCursor.ptr;
-	P.counters = (uint64_t*)c->dCounters.ptr;
-	P.results = (uint32_t*)c->dResults.ptr; P.resultCapacity = c->resultCapacity;
-	P.items = (uint32_t*)c->dItems.ptr; P.itemCapacity = c->itemCapacity;
-	P.docRange = (uint64_t*)c->dDocRange.ptr;
-	P.docStats = (uint64_t*)c->dDocStats.ptr;
-	P.docStatus = (int32_t*)c->dDocStatus.ptr;
-	P.withFormats = c->withFormats ? 1u : 0u;
-	P.resultFormat = (uint32_t*)c->dResultFormat.ptr; P.itemFormat = (uint32_t*)c->dItemFormat.ptr;
-
-#if defined(SPA_TRACE) || defined(SPA_POLL)
-	static uint32_t* traceHost = 0;
-	if (!traceHost && (getenv("SPA_HOSTALLOC") || 
-#ifdef SPA_TRACE
-		1
-#else
-		0
-#endif
-		))
-	{
-		HIP_CHECK( hipHostMalloc( (void**)&traceHost, 4096, hipHostMallocMapped));
-		std::memset( traceHost, 0xEE, 4096);
-	}
-	void* traceDev = 0;
-	if (traceHost) HIP_CHECK( hipHostGetDevicePointer( &traceDev, traceHost, 0));
-	P.trace = (uint32_t*)traceDev;
-#endif
 	HIP_CHECK( hipEventRecord( c->evStart, stream));
 	if (rerun)
 	{
@@ -730,7 +718,7 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 		HIP_CHECK( hipMemcpyAsync( (uint32_t*)c->dCursor.ptr + 2, &n, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
 		HIP_CHECK( hipStreamSynchronize( stream));		// (the list and its count are host temporaries)
 		P.docList = (const uint32_t*)c->dFallbackList.ptr; P.docListCount = (const uint32_t*)c->dCursor.ptr + 2;
-		P.docCursor = (uint32_t*)c->dCursor.ptr + 1;
+		P.io.docCursor = (uint32_t*)c->dCursor.ptr + 1;
 		HIP_CHECK( launchL2Match( P, nblocks, stream));
 	}
 	else if (c->join)
@@ -741,12 +729,7 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 		c->dJoinCounts.reserve( (nlexems + 64) * sizeof(uint32_t));
 		J.filter = (const uint32_t*)c->dJoinFilter.ptr; J.counts = (uint32_t*)c->dJoinCounts.ptr; J.countsCapacity = nlexems;
 		J.keytab = (const JoinKey*)c->dJoinKeytab.ptr; J.keymask = c->joinKeymask; J.rules = (const JoinRule*)c->dJoinRules.ptr; J.maxRange = c->joinMaxRange; J.delimiter = c->joinDelimiter; J.altRules = c->joinAltRules ? 1u : 0u;
-		J.lexems = P.lexems; J.origseg = P.origseg; J.docOffsets = P.docOffsets; J.docRangesIn = P.docRangesIn; J.ndocs = P.ndocs;
-		J.docCursor = (uint32_t*)c->dCursor.ptr;
-		J.counters = P.counters; J.results = P.results; J.resultCapacity = P.resultCapacity;
-		J.items = P.items; J.itemCapacity = P.itemCapacity; J.withItems = P.withItems; J.itemFormat = P.itemFormat;
-		J.docRange = P.docRange; J.docStats = P.docStats; J.docStatus = P.docStatus;
-		J.withFormats = P.withFormats; J.resultFormat = P.resultFormat;
+		J.io = P.io;
 		const size_t jslots = (size_t)c->numCUs * 32;		// one wave per document, no LDS, few registers
 		HIP_CHECK( launchL2Join( J, (unsigned)(ndocs < jslots ? (ndocs ? ndocs : 1) : jslots), stream));
 	}
@@ -774,19 +757,14 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 		std::memset( &F, 0, sizeof(F));
 		F.keyinst = (const FastKeyInst*)c->dKeyinst.ptr; F.statics = (const FastStatic*)c->dStatics.ptr; F.keytab = (const FastKeyEntry*)c->dKeytab.ptr;
 		F.keymask = c->keymask; F.nofStopWords = c->nofStopWords;
-		F.lexems = P.lexems; F.origseg = P.origseg; F.docOffsets = P.docOffsets; F.docRangesIn = P.docRangesIn;
-		F.ndocs = P.ndocs; F.withItems = P.withItems;
+		F.io = P.io;
 		std::memcpy( F.bucketMeta, c->fastBucketMeta, sizeof(F.bucketMeta)); F.expShift = c->fastExpShift;
 		F.spill = c->fastSpill; F.spillBase = (uint32_t*)c->dSpill.ptr;
-		F.docCursor = (uint32_t*)c->dCursor.ptr;
-		F.counters = P.counters; F.results = P.results; F.resultCapacity = P.resultCapacity; F.items = P.items; F.itemCapacity = P.itemCapacity;
-		F.docRange = P.docRange; F.docStats = P.docStats; F.docStatus = P.docStatus;
-		F.withFormats = P.withFormats; F.resultFormat = P.resultFormat; F.itemFormat = P.itemFormat;
 		F.fallbackList = (uint32_t*)c->dFallbackList.ptr; F.fallbackCount = (uint32_t*)c->dCursor.ptr + 2;
 		F.diag = (uint32_t*)c->dCursor.ptr + 16; F.prof = (uint64_t*)((uint32_t*)c->dCursor.ptr + 32);
 		HIP_CHECK( launchL2Fast( F, c->fastVariant, fblocks, stream));
 		P.docList = F.fallbackList; P.docListCount = F.fallbackCount;
-		P.docCursor = (uint32_t*)c->dCursor.ptr + 1;
+		P.io.docCursor = (uint32_t*)c->dCursor.ptr + 1;
 		const unsigned listBlocks = nblocks < 2*c->numCUs ? nblocks : 2*c->numCUs;
 		HIP_CHECK( launchL2Match( P, listBlocks, stream));
 	}
@@ -795,22 +773,19 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 		HIP_CHECK( launchL2Match( P, nblocks, stream));
 	}
 	HIP_CHECK( hipEventRecord( c->evStop, stream));
-#if defined(SPA_TRACE) || defined(SPA_POLL)
-	static uint32_t traceDummy[16];
-	uint32_t* traceShow = traceHost ? traceHost : traceDummy;
-	for (int waited=0; hipStreamQuery( stream) == hipErrorNotReady; ++waited)
-	{
-		usleep( 100000);
-		if (waited == 100 || waited == 150)
-		{
-			fprintf( stderr, "[spa trace] kernel still running after %d ms:", waited*100);
-			for (int i=0; i<16; ++i) fprintf( stderr, " [%d]=%u", i, traceShow[i]);
-			fprintf( stderr, "\n");
-			if (waited == 150) { fflush( stderr); _exit( 3); }
-		}
-	}
-#endif
 	c->evValid = true; c->lastStream = stream; c->lastNdocs = ndocs;
+}
+
+// where the batch just enqueued leaves its output (device entry points)
+void deviceBatch( const sp_matcher_ctx* c, size_t ndocs, sp_match_device_batch_t* out)
+{
+	out->ndocs = ndocs;
+	out->d_results = c->dResults.ptr; out->d_items = c->dItems.ptr;
+	out->d_doc_result_offsets = c->dDocRange.ptr;
+	out->d_doc_stats = c->dDocStats.ptr; out->d_doc_status = c->dDocStatus.ptr;
+	out->d_counters = c->dCounters.ptr;
+	out->d_result_format = c->withFormats ? c->dResultFormat.ptr : 0;
+	out->d_item_format = c->withFormats ? c->dItemFormat.ptr : 0;
 }
 
 } // namespace
@@ -824,16 +799,7 @@ int sp_matcher_ctx_match_docs_device( sp_matcher_ctx_t* c, const void* d_lexems,
 	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
 		if (ndocs >= 0xFFFFFFFFull) throw std::runtime_error( "too many documents in one batch");
 		launchBatch( c, d_lexems, d_origseg, d_doc_offsets, ndocs, nlexems, (hipStream_t)stream);
-		if (out)
-		{
-			out->ndocs = ndocs;
-			out->d_results = c->dResults.ptr; out->d_items = c->dItems.ptr;
-			out->d_doc_result_offsets = c->dDocRange.ptr;
-			out->d_doc_stats = c->dDocStats.ptr; out->d_doc_status = c->dDocStatus.ptr;
-			out->d_counters = c->dCounters.ptr;
-			out->d_result_format = c->withFormats ? c->dResultFormat.ptr : 0;
-			out->d_item_format = c->withFormats ? c->dItemFormat.ptr : 0;
-		}
+		if (out) deviceBatch( c, ndocs, out);
 	});
 }
 
@@ -843,16 +809,7 @@ int sp_matcher_ctx_match_lexed_device( sp_matcher_ctx_t* c, const void* d_lexems
 	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
 		if (ndocs >= 0xFFFFFFFFull) throw std::runtime_error( "too many documents in one batch");
 		launchBatch( c, d_lexems, 0, 0, ndocs, nlexems_hint, (hipStream_t)stream, d_doc_ranges);
-		if (out)
-		{
-			out->ndocs = ndocs;
-			out->d_results = c->dResults.ptr; out->d_items = c->dItems.ptr;
-			out->d_doc_result_offsets = c->dDocRange.ptr;
-			out->d_doc_stats = c->dDocStats.ptr; out->d_doc_status = c->dDocStatus.ptr;
-			out->d_counters = c->dCounters.ptr;
-			out->d_result_format = c->withFormats ? c->dResultFormat.ptr : 0;
-			out->d_item_format = c->withFormats ? c->dItemFormat.ptr : 0;
-		}
+		if (out) deviceBatch( c, ndocs, out);
 	});
 }
 

@@ -36,11 +36,6 @@ using namespace spa;
 
 namespace {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
-
-#define LANE ((u32)(threadIdx.x & 63u))
-
 #ifdef SPA_PROF
 #define PROF_T() __builtin_amdgcn_s_memtime()
 #define PROF_ACC( SLOT, T0) do { w.prof[ SLOT] += __builtin_amdgcn_s_memtime() - (T0); } while (0)
@@ -51,9 +46,6 @@ typedef uint64_t u64;
 
 enum {L1D_OK=0, L1D_ERR_ARENA=2, L1D_ERR_LEXEMSIZE=7, L1D_ERR_INTERNAL=8, L1D_ERR_OUTPUT=9,
       L1D_CHUNK_UNPROVEN=100};	// (internal: the document goes to the sequential re-scan)
-
-__device__ __forceinline__ u32 uni( u32 v) { return __builtin_amdgcn_readfirstlane( v); }
-__device__ __forceinline__ u32 ldu( const u32* p) { return __builtin_amdgcn_readfirstlane( *p); }
 
 struct Event { u32 id, origpos, origsize, levelBind; };	// levelBind = level | posbind<<8   (MatchEvent, patternLexer.cpp:665-679)
 

@@ -15,6 +15,7 @@
 #define SPA_L2_FAST_H
 #include <stdint.h>
 #include "l2_tables.h"
+#include "l2_device.h"
 
 namespace spa {
 
@@ -187,28 +188,15 @@ struct FastParams
 	const FastKeyEntry* keytab;
 	uint32_t keymask;
 	uint32_t nofStopWords;
-	// input
-	const uint32_t* lexems;		// sp_lexem_t[]: id, ordpos, origpos, origsize
-	const uint32_t* origseg;	// optional
-	const uint64_t* docOffsets;	// ndocs+1 lexem indices, or NULL when docRangesIn is given
-	const uint64_t* docRangesIn;	// ndocs x (first lexem, count)
-	uint32_t ndocs;
-	uint32_t withItems;
 	// working memory
 	uint32_t expShift;		// W = 1 << expShift expiry rows: the smallest power of two above the largest position range
 	uint32_t bucketMeta[ 16];	// LDS region of each trigger bucket: first entry | capacity << 16 (sized from the rule set)
 	FastSpillLayout spill;
 	uint32_t* spillBase;		// per wave: spill.totalWords
-	uint32_t* docCursor;
-	// output (same buffers and formats as the general kernel)
-	uint64_t* counters;		// SPC_*
-	uint32_t* results; uint64_t resultCapacity;
-	uint32_t* items; uint64_t itemCapacity;
-	uint64_t* docRange; uint64_t* docStats; int32_t* docStatus;
-	uint32_t withFormats; uint32_t* resultFormat; uint32_t* itemFormat;
 	// documents the fast tier hands to the general kernel: fallbackList[ atomicAdd( fallbackCount)]
 	uint32_t* fallbackList; uint32_t* fallbackCount;
 	uint32_t* diag;			// [16] hand-overs in all / by reason (FB_* of l2_fast_kernel.hip), may be NULL
+	L2BatchIO io;			// (after the tier's own fields: right behind the tables, the kernel ran 2.5 % slower)
 	uint64_t* prof;			// [8] wave-cycles per phase (make PROF=1 builds), may be NULL
 };
 

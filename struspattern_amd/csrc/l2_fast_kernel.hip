@@ -45,13 +45,8 @@ using namespace spa;
 
 namespace {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
 typedef uint16_t u16;
 typedef uint8_t u8;
-
-#define LANE ((u32)(threadIdx.x & 63u))
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 
 typedef const __attribute__((address_space(4))) FastParams& KP;
 __device__ __forceinline__ KP kernelParams() { return *(const __attribute__((address_space(4))) FastParams*)__builtin_amdgcn_kernarg_segment_ptr(); }
@@ -72,7 +67,6 @@ enum {NIL16=0xFFFFu};
 #define PROF_ADD( SLOT) do {} while (0)
 #endif
 
-__device__ __forceinline__ u32 bcast0( u32 v) { return __builtin_amdgcn_readfirstlane( v); }
 __device__ __forceinline__ u64 lanesBelow() { return (1ull << LANE) - 1ull; }
 __device__ __forceinline__ u32 evhash( u32 a)		// src/ruleMatcherAutomaton.cpp:34-40
 {
@@ -81,13 +75,11 @@ __device__ __forceinline__ u32 evhash( u32 a)		// src/ruleMatcherAutomaton.cpp:3
 	a ^=  (a>>4);
 	return a;
 }
-__device__ __forceinline__ uint4 ld4( const void* p) { const u32x4 v = *(const u32x4*)p; return make_uint4( v.x, v.y, v.z, v.w); }
 __device__ __forceinline__ void st4( void* p, u32 a, u32 b, u32 c, u32 d) { u32x4 v; v.x = a; v.y = b; v.z = c; v.w = d; *(u32x4*)p = v; }
-__device__ __forceinline__ u32 ldu( const u32* p) { return __builtin_amdgcn_readfirstlane( *p); }
 __device__ __forceinline__ uint4 ldu4( const void* p)
 {
 	uint4 v = ld4( p);
-	v.x = bcast0( v.x); v.y = bcast0( v.y); v.z = bcast0( v.z); v.w = bcast0( v.w);
+	v.x = uni( v.x); v.y = uni( v.y); v.z = uni( v.z); v.w = uni( v.w);
 	return v;
 }
 __device__ __forceinline__ u32 waveScanOr( u32 v)		// inclusive, all 64 lanes active
@@ -245,7 +237,7 @@ static __device__ __forceinline__ void fireSignal( LR L, Wave& w, KP P, u32 tsv,
 {
 	const u32 tid = tsv & 0xFFFFu, r = tid >> 2;
 	const u32 sigval = (tsv >> 16) & 0xFu, sigtype = (tsv >> 20) & 0x7u, hasVar = (tsv >> 23) & 1u, variable = tsv >> 24;
-	u32 hw = bcast0( ldHot<SP>( L, w, P, r));
+	u32 hw = uni( ldHot<SP>( L, w, P, r));
 	w.nSignals += 1;
 	u32 value = hw & H_VALUE_MASK, count = (hw >> H_COUNT_SHIFT) & H_COUNT_MASK;
 	bool match = false, take = false, fin = false;
@@ -287,7 +279,7 @@ static __device__ __forceinline__ void fireSignal( LR L, Wave& w, KP P, u32 tsv,
 	bool newItem = false, newStart = false;
 	if (take)
 	{
-		if (hasVar && P.withItems)
+		if (hasVar && P.io.withItems)
 		{
 			if (done)
 			{
@@ -307,7 +299,7 @@ static __device__ __forceinline__ void fireSignal( LR L, Wave& w, KP P, u32 tsv,
 		{
 			if (w.nStaged < P.spill.maxStaged)
 			{
-				const u32 kl = bcast0( ldKl<SP>( L, w, P, r)), lx = keyLexemOf( kl, w.lbase);
+				const u32 kl = uni( ldKl<SP>( L, w, P, r)), lx = keyLexemOf( kl, w.lbase);
 				if (LANE == 0) stageLineResult( w, P, w.nStaged, kl & 0xFFFFFu, newStart ? w.lbase : lx, w.lbase, nItems, newItem ? 1u : 0u, variable, lx);
 				w.nStaged += 1; w.nStagedItems += nItems + (newItem ? 1u : 0u);
 			}
@@ -327,7 +319,7 @@ static __device__ __forceinline__ void fireSignal( LR L, Wave& w, KP P, u32 tsv,
 		}
 		else
 		{
-			const u32 kl = bcast0( ldKl<SP>( L, w, P, r)), lx = keyLexemOf( kl, w.lbase);
+			const u32 kl = uni( ldKl<SP>( L, w, P, r)), lx = keyLexemOf( kl, w.lbase);
 			const u32* K = (const u32*)&P.keyinst[ kl & 0xFFFFFu];
 			handle = ldu( K); fmt = ldu( K+1);
 			const u32 vars = ldu( K+14);
@@ -429,7 +421,7 @@ static __device__ __forceinline__ bool fireBatch( LR L, Wave& w, KP P, const u64
 	u32 why = 0;
 	if (take)
 	{
-		if (hasVar && P.withItems)
+		if (hasVar && P.io.withItems)
 		{
 			if (done) { if (nItems) why = FB_ITEM_AFTER_RESULT; }
 			else if (nItems < 3u) newItem = true;
@@ -854,7 +846,7 @@ static __device__ __forceinline__ void installStaticT( LR L, Wave& w, KP P, u32 
 	const u32 tEv[ 3] = {q1.x, q1.z, q2.x};
 	const u32 tInfo[ 3] = {q1.y, q1.w, q2.y};
 	const u32 hw0 = q2.z, ranksA = q2.w, ranksB = q3.x, fl = q3.w;
-	const u32 totals = bcast0( q3.y), itemsTotal = bcast0( q3.z) >> 24;		// (the same in every line of the batch)
+	const u32 totals = uni( q3.y), itemsTotal = uni( q3.z) >> 24;		// (the same in every line of the batch)
 	const u32 range = (meta >> FKI_RANGE_SHIFT) & FKI_RANGE_MASK;
 	const u32 row = (sord + range) & ((1u << P.expShift) - 1u);
 	// ---- expiry row of position sord+range (cpp:1066-1082) and the triggers (cpp:1204-1250 -> EventTriggerTable::add :114-131)
@@ -878,7 +870,7 @@ static __device__ __forceinline__ void installStaticT( LR L, Wave& w, KP P, u32 
 		}
 	}
 	WAVE_FENCE();
-	const u32 nItems = P.withItems ? ((hw0 >> H_NITEMS_SHIFT) & H_NITEMS_MASK) : 0u;
+	const u32 nItems = P.io.withItems ? ((hw0 >> H_NITEMS_SHIFT) & H_NITEMS_MASK) : 0u;
 	if (have)
 	{
 		// the last lane of an expiry group / of a bucket's entries closes it (every lane has read the old counts above)
@@ -909,7 +901,7 @@ static __device__ __forceinline__ void installStaticT( LR L, Wave& w, KP P, u32 
 			stageResult( w, P, w.nStaged + ((ranksA >> 16) & 0xFFu), handle, fmt, (fl & FKF_START_SET) ? w.lbase : 0u, w.lbase, nItems, vars, w.lbase, w.lbase, w.lbase);
 		}
 		w.nStaged += nres;
-		if (P.withItems) w.nStagedItems += itemsTotal;
+		if (P.io.withItems) w.nStagedItems += itemsTotal;
 	}
 	// ---- rules that finished or were deleted by their own key event: deactivated after the installs (cpp:1030-1034)
 	const u32 nd = totals >> 24;
@@ -1003,7 +995,7 @@ static __device__ __forceinline__ void installCompactT( LR L, Wave& w, KP P, u32
 	const bool have = LANE < nb;
 	const u32 ev[ 2] = {c0.x, c0.z}, info[ 2] = {c0.y, c0.w};
 	const u32 hw0 = c1.x, misc = c1.y, ranks = c1.z;
-	const u32 totals = bcast0( c1.w), itemsTotal = (bcast0( c1.z) >> 16) & 0xFFu;		// (the same in every line of the batch)
+	const u32 totals = uni( c1.w), itemsTotal = (uni( c1.z) >> 16) & 0xFFu;		// (the same in every line of the batch)
 	if (have)
 	{
 		// ---- expiry row of position sord+range (cpp:1066-1082), triggers (cpp:1204-1250 -> EventTriggerTable::add :114-131)
@@ -1021,7 +1013,7 @@ static __device__ __forceinline__ void installCompactT( LR L, Wave& w, KP P, u32
 		}
 	}
 	WAVE_FENCE();
-	const u32 nItems = P.withItems ? ((hw0 >> H_NITEMS_SHIFT) & H_NITEMS_MASK) : 0u;
+	const u32 nItems = P.io.withItems ? ((hw0 >> H_NITEMS_SHIFT) & H_NITEMS_MASK) : 0u;
 	if (have)
 	{
 		// the last lane of an expiry group / of a bucket's entries closes it (every lane has read the old counts before)
@@ -1043,7 +1035,7 @@ static __device__ __forceinline__ void installCompactT( LR L, Wave& w, KP P, u32
 		if (have && (misc & FSM_RESULT_NOW))
 			stageLineResult( w, P, w.nStaged + (ranks & 0xFFu), ki0 + LANE, (misc & FSM_START_SET) ? w.lbase : 0u, w.lbase, nItems, 0u, 0u, w.lbase);
 		w.nStaged += nres;
-		if (P.withItems) w.nStagedItems += itemsTotal;
+		if (P.io.withItems) w.nStagedItems += itemsTotal;
 	}
 	// ---- rules that finished or were deleted by their own key event: deactivated after the installs (cpp:1030-1034)
 	const u32 nd = totals >> 24;
@@ -1083,7 +1075,7 @@ static __device__ __forceinline__ void installBatch( LR L, Wave& w, KP P, u32 kb
 #else
 #define PROF_I( SLOT, V) do {} while (0)
 #endif
-		if ((bcast0( c1.y) & FSM_BATCH_COMPACT) && sord != 0)
+		if ((uni( c1.y) & FSM_BATCH_COMPACT) && sord != 0)
 		{
 			PROF_I( 6, c1.y);
 			// ---- compact static batch: everything but the absolute positions is in the lines
@@ -1107,7 +1099,7 @@ static __device__ __forceinline__ void installBatch( LR L, Wave& w, KP P, u32 kb
 			{
 				if (__ballot( have && cnt + nb > ((u32)FAST_EXPCAP >> P.expShift))) w.spill = 1;	// (upper bound: the whole batch in my row)
 			}
-			if (!checkBuckets( L, w, P, bcast0( c1.w) & 0xFFu, inst, hB)) return;
+			if (!checkBuckets( L, w, P, uni( c1.w) & 0xFFu, inst, hB)) return;
 			PROF_I( 7, cnt + oldB[ 0] + oldB[ 1] + r);
 			if (w.spill) installCompactT<true>( L, w, P, kb + base, nb, sord, r, c0, c1, row, cnt, oldB, metaB);
 			else installCompactT<false>( L, w, P, kb + base, nb, sord, r, c0, c1, row, cnt, oldB, metaB);
@@ -1122,7 +1114,7 @@ static __device__ __forceinline__ void installBatch( LR L, Wave& w, KP P, u32 kb
 			q0 = ld4( K); q1 = ld4( (const u32*)K + 4); q2 = ld4( (const u32*)K + 8); q3 = ld4( (const u32*)K + 12);
 		}
 		// a static batch at a position other than 0: the key fires and all ranks are in the lines (l2_fast.h)
-		const bool isStatic = (bcast0( q3.w) & FKF_BATCH_STATIC) != 0 && sord != 0;
+		const bool isStatic = (uni( q3.w) & FKF_BATCH_STATIC) != 0 && sord != 0;
 		const u32 pastEvent = q0.z, meta = q0.w;
 		const u32 tEv[ 3] = {q1.x, q1.z, q2.x};
 		const u32 tInfo[ 3] = {q1.y, q1.w, q2.y};		// (templates beyond the program's count are all zero)
@@ -1155,7 +1147,7 @@ static __device__ __forceinline__ void installBatch( LR L, Wave& w, KP P, u32 kb
 #pragma unroll
 					for (int j=2; j>=0; --j)		// the rule's trigger list: last installed first
 					{
-						if ((tInfo[ j] & FTI_INSTALL) && tEv[ j] == pastEvent) fireLocal( sim, tInfo[ j], psord, plex, P.withItems);
+						if ((tInfo[ j] & FTI_INSTALL) && tEv[ j] == pastEvent) fireLocal( sim, tInfo[ j], psord, plex, P.io.withItems);
 					}
 					// a structure delimiter logged after the replayed event cancels the rule (cpp:1306-1321)
 					bool cancelled = false;
@@ -1178,7 +1170,7 @@ static __device__ __forceinline__ void installBatch( LR L, Wave& w, KP P, u32 kb
 			if (have && !dropped)
 			{
 #pragma unroll
-				for (int j=0; j<3; ++j) if (tInfo[ j] & FTI_KEY) fireLocal( sim, tInfo[ j], sord, w.lbase, P.withItems);
+				for (int j=0; j<3; ++j) if (tInfo[ j] & FTI_KEY) fireLocal( sim, tInfo[ j], sord, w.lbase, P.io.withItems);
 			}
 			if (__ballot( (sim.flags & S_ODD) != 0)) { FALLBACK( FB_ITEMS); return; }
 		}
@@ -1187,7 +1179,7 @@ static __device__ __forceinline__ void installBatch( LR L, Wave& w, KP P, u32 kb
 		const u32 nmat = (u32)__popcll( matMask);
 		// ---- statistics (cpp:1251, :780)
 		w.nInstalled += nb;
-		if (isStatic) w.nSignals += (bcast0( q3.y) >> 8) & 0xFFu;
+		if (isStatic) w.nSignals += (uni( q3.y) >> 8) & 0xFFu;
 		else
 		{
 			u32 incl = waveScanAdd( have ? sim.nFires : 0u);
@@ -1207,7 +1199,7 @@ static __device__ __forceinline__ void installBatch( LR L, Wave& w, KP P, u32 kb
 #pragma unroll
 			for (int j=0; j<3; ++j) { inst[ j] = mat && (tInfo[ j] & FTI_INSTALL); hB[ j] = (tInfo[ j] >> FTI_BUCKET_SHIFT) & 15u; }
 			// upper bound without the scan: the batch adds at most nmat x 3 entries to a bucket (a static batch: its total)
-			if (!checkBuckets( L, w, P, isStatic ? (bcast0( q3.y) & 0xFFu) : 3*nmat, inst, hB)) return;
+			if (!checkBuckets( L, w, P, isStatic ? (uni( q3.y) & 0xFFu) : 3*nmat, inst, hB)) return;
 		}
 		if (isStatic)
 		{
@@ -1259,7 +1251,7 @@ static __device__ __forceinline__ void runKernel()
 	LR L = *(__attribute__((address_space(3))) Lds*)&ldsDoc;
 	Wave w;
 	w.sp = P.spillBase + (u64)blockIdx.x * P.spill.totalWords;
-	const u32 ndocs = P.ndocs;
+	const u32 ndocs = P.io.ndocs;
 	const u32 waveSlot = blockIdx.x, nWaveSlots = gridDim.x;
 
 	for (u32 round=0; round<=ndocs; ++round)
@@ -1268,8 +1260,8 @@ static __device__ __forceinline__ void runKernel()
 		if (round)
 		{
 			u32 nx = 0;
-			if (LANE == 0) nx = atomicAdd( P.docCursor, 1u);
-			doc = nWaveSlots + bcast0( nx);
+			if (LANE == 0) nx = atomicAdd( P.io.docCursor, 1u);
+			doc = nWaveSlots + uni( nx);
 		}
 		if (doc >= ndocs) break;
 		// per-document reset
@@ -1286,17 +1278,7 @@ static __device__ __forceinline__ void runKernel()
 		WAVE_FENCE();
 
 		u64 lbeg, lend;
-		if (P.docRangesIn)
-		{
-			const u32* rp = (const u32*)&P.docRangesIn[ 2*(u64)doc];
-			lbeg = ((u64)ldu( rp+1) << 32) | ldu( rp);
-			lend = lbeg + (((u64)ldu( rp+3) << 32) | ldu( rp+2));
-		}
-		else
-		{
-			lbeg = ((u64)ldu( (const u32*)&P.docOffsets[ doc]+1) << 32) | ldu( (const u32*)&P.docOffsets[ doc]);
-			lend = ((u64)ldu( (const u32*)&P.docOffsets[ doc+1]+1) << 32) | ldu( (const u32*)&P.docOffsets[ doc+1]);
-		}
+		docLexems( P.io, doc, lbeg, lend);
 		if (lend - lbeg >= (1ull << 24)) FALLBACK( FB_LEXEMS);	// lexem indices are kept in 24 bits beside the variable
 		u32 curPosition = 0, nEvents = 0;
 		for (u64 tile=lbeg; tile<lend && !w.err; tile+=64)
@@ -1308,8 +1290,8 @@ static __device__ __forceinline__ void runKernel()
 			const bool mine = tile + LANE < lend;
 			if (mine)
 			{
-				lx = ((const uint4*)P.lexems)[ tile + LANE];
-				if (P.origseg) seg = P.origseg[ tile + LANE];
+				lx = ((const uint4*)P.io.lexems)[ tile + LANE];
+				if (P.io.origseg) seg = P.io.origseg[ tile + LANE];
 			}
 			u32 kBegin = 0, kCount = 0, kStop = 0;
 			if (mine && lx.x && lx.x < (1u<<29))
@@ -1378,22 +1360,10 @@ static __device__ __forceinline__ void runKernel()
 		// ---- fetchResults (patternMatcher.cpp:271-301): the staged results become sp_result_t / sp_result_item_t records
 		PROF_DECL;
 		u32 nres = w.err ? 0 : w.nStaged;
-		const u32 nitems = (w.err || !P.withItems) ? 0 : w.nStagedItems;
+		const u32 nitems = (w.err || !P.io.withItems) ? 0 : w.nStagedItems;
 		u64 resBase = 0, itemBase = 0;
-		if (nres)
-		{
-			u64 b = 0;
-			if (LANE == 0) b = atomicAdd( (unsigned long long*)&P.counters[ SPC_RESULTS], (unsigned long long)nres);
-			resBase = ((u64)bcast0( (u32)(b >> 32)) << 32) | bcast0( (u32)b);
-			if (resBase + nres > P.resultCapacity) { w.err = SPD_ERR_OUTPUT; nres = 0; }
-		}
-		if (nres && nitems)
-		{
-			u64 b = 0;
-			if (LANE == 0) b = atomicAdd( (unsigned long long*)&P.counters[ SPC_ITEMS], (unsigned long long)nitems);
-			itemBase = ((u64)bcast0( (u32)(b >> 32)) << 32) | bcast0( (u32)b);
-			if (itemBase + nitems > P.itemCapacity) { w.err = SPD_ERR_OUTPUT; nres = 0; }
-		}
+		if (nres && !reserveOutput( P.io, SPC_RESULTS, nres, resBase)) { w.err = SPD_ERR_OUTPUT; nres = 0; }
+		if (nres && nitems && !reserveOutput( P.io, SPC_ITEMS, nitems, itemBase)) { w.err = SPD_ERR_OUTPUT; nres = 0; }
 		if (nres)
 		{
 			WAVE_FENCE();
@@ -1426,28 +1396,28 @@ static __device__ __forceinline__ void runKernel()
 					s0.x = handle; s0.y = fmt;
 					s1.x = n | (vv[ 0] << 8) | (vv[ 1] << 16) | (vv[ 2] << 24); s1.y = ll[ 0]; s1.z = ll[ 1]; s1.w = ll[ 2];
 				}
-				const u32 ni = P.withItems ? (s1.x & 0xFFu) : 0u;
+				const u32 ni = P.io.withItems ? (s1.x & 0xFFu) : 0u;
 				u32 incl = waveScanAdd( ni);
 				const u64 mine = ip + (incl - ni);
 				if (hv)
 				{
-					const uint4 a = ((const uint4*)P.lexems)[ lbeg + s0.z], z = ((const uint4*)P.lexems)[ lbeg + s0.w];	// first taken / matching lexem {id, ordpos, origpos, origsize}
-					const u32 sa = P.origseg ? P.origseg[ lbeg + s0.z] : 0u, sz = P.origseg ? P.origseg[ lbeg + s0.w] : 0u;
-					u32* o = P.results + (resBase + ri)*9;
+					const uint4 a = ((const uint4*)P.io.lexems)[ lbeg + s0.z], z = ((const uint4*)P.io.lexems)[ lbeg + s0.w];	// first taken / matching lexem {id, ordpos, origpos, origsize}
+					const u32 sa = P.io.origseg ? P.io.origseg[ lbeg + s0.z] : 0u, sz = P.io.origseg ? P.io.origseg[ lbeg + s0.w] : 0u;
+					u32* o = P.io.results + (resBase + ri)*9;
 					o[0] = s0.x; o[1] = a.y; o[2] = z.y + 1u; o[3] = sa; o[4] = a.z; o[5] = sz; o[6] = z.z + z.w;
-					o[7] = P.withItems ? (u32)mine : 0u; o[8] = ni;
-					if (P.withFormats) P.resultFormat[ resBase + ri] = s0.y;
+					o[7] = P.io.withItems ? (u32)mine : 0u; o[8] = ni;
+					if (P.io.withFormats) P.io.resultFormat[ resBase + ri] = s0.y;
 					const u32 il[ 3] = {s1.y, s1.z, s1.w};
 #pragma unroll
 					for (int q=0; q<3; ++q)
 					{
 						if ((u32)q < ni)
 						{
-							const uint4 t = ((const uint4*)P.lexems)[ lbeg + il[ q]];
-							const u32 st = P.origseg ? P.origseg[ lbeg + il[ q]] : 0u;
-							u32* io = P.items + (mine + (u32)q)*7;
+							const uint4 t = ((const uint4*)P.io.lexems)[ lbeg + il[ q]];
+							const u32 st = P.io.origseg ? P.io.origseg[ lbeg + il[ q]] : 0u;
+							u32* io = P.io.items + (mine + (u32)q)*7;
 							io[0] = (s1.x >> (8 + 8*q)) & 0xFFu; io[1] = t.y; io[2] = t.y + 1u; io[3] = st; io[4] = t.z; io[5] = st; io[6] = t.z + t.w;
-							if (P.withFormats) { P.itemFormat[ 2*(mine + (u32)q)] = 0; P.itemFormat[ 2*(mine + (u32)q)+1] = 0; }
+							if (P.io.withFormats) { P.io.itemFormat[ 2*(mine + (u32)q)] = 0; P.io.itemFormat[ 2*(mine + (u32)q)+1] = 0; }
 						}
 					}
 				}
@@ -1458,26 +1428,15 @@ static __device__ __forceinline__ void runKernel()
 #ifdef SPA_PROF
 		if (LANE == 0 && P.prof) for (int pi=0; pi<12; ++pi) atomicAdd( (unsigned long long*)&P.prof[ pi], (unsigned long long)w.prof[ pi]);
 #endif
-		if (LANE == 0)
+		if (w.err != SPD_FAST_FALLBACK) finishDocument( P.io, doc, resBase, nres, w.nInstalled, w.nAlt, w.nSignals, ((u64)w.openHi << 32) | w.openLo, w.err, nEvents);
+		else if (LANE == 0)
 		{
-			if (w.err == SPD_FAST_FALLBACK)
-			{
-				const u32 at = atomicAdd( P.fallbackCount, 1u);
-				P.fallbackList[ at] = doc;
-				P.docRange[ 2*(u64)doc] = 0; P.docRange[ 2*(u64)doc+1] = 0;
-				P.docStatus[ doc] = (int32_t)SPD_FAST_FALLBACK;
-				atomicAdd( (unsigned long long*)&P.counters[ SPC_HANDOVER], 1ull);
-				if (P.diag) { atomicAdd( &P.diag[ 0], 1u); atomicAdd( &P.diag[ w.why & 15u], 1u); }
-			}
-			else
-			{
-				P.docRange[ 2*(u64)doc] = resBase; P.docRange[ 2*(u64)doc+1] = nres;
-				u64* st = P.docStats + 4*(u64)doc;
-				st[0] = w.nInstalled; st[1] = w.nAlt; st[2] = w.nSignals; st[3] = ((u64)w.openHi << 32) | w.openLo;
-				P.docStatus[ doc] = (int32_t)w.err;
-				atomicAdd( (unsigned long long*)&P.counters[ SPC_EVENTS], (unsigned long long)nEvents);
-				if (w.err) atomicAdd( (unsigned long long*)&P.counters[ SPC_FAILED], 1ull);
-			}
+			const u32 at = atomicAdd( P.fallbackCount, 1u);
+			P.fallbackList[ at] = doc;
+			P.io.docRange[ 2*(u64)doc] = 0; P.io.docRange[ 2*(u64)doc+1] = 0;
+			P.io.docStatus[ doc] = (int32_t)SPD_FAST_FALLBACK;
+			atomicAdd( (unsigned long long*)&P.io.counters[ SPC_HANDOVER], 1ull);
+			if (P.diag) { atomicAdd( &P.diag[ 0], 1u); atomicAdd( &P.diag[ w.why & 15u], 1u); }
 		}
 	}
 }
@@ -1492,38 +1451,42 @@ static __device__ __forceinline__ void runKernel()
 #define SPA_L2_FAST_WAVES_PER_EU 4
 #endif
 #define SPA_L2_FAST_OCC __attribute__((amdgpu_waves_per_eu( SPA_L2_FAST_WAVES_PER_EU, SPA_L2_FAST_WAVES_PER_EU)))
-#define SPA_FAST_INSTANCE( NAME, RR, TT) \
-	extern "C" __global__ __launch_bounds__(64) SPA_L2_FAST_OCC void NAME( FastParams kernelArgs) { Engine<RR,TT>::runKernel(); }
-SPA_FAST_INSTANCE( spa_l2_fast_kernel_s, 192, 312)
-SPA_FAST_INSTANCE( spa_l2_fast_kernel_m, 320, 512)
-SPA_FAST_INSTANCE( spa_l2_fast_kernel_l, 512, 1024)
-SPA_FAST_INSTANCE( spa_l2_fast_kernel_n, 256, 448)		// 10 KB of LDS: 16 waves per CU
-SPA_FAST_INSTANCE( spa_l2_fast_kernel_t, 8, 128)		// tests: everything beyond a handful of rules runs through the spill area
+// The variants of SPA_L2_FAST_SIZE, by number: letter, LDS capacities R (rules) and T (bucket entries); n is the default
+#define SPA_FAST_VARIANTS( V) \
+	V( s, 192, 312) \
+	V( m, 320, 512) \
+	V( l, 512, 1024) \
+	V( t, 8, 128)		/* tests: everything beyond a handful of rules runs through the spill area */ \
+	V( n, 256, 448)		/* 10 KB of LDS: 16 waves per CU */
+#define SPA_FAST_INSTANCE( X, RR, TT) \
+	extern "C" __global__ __launch_bounds__(64) SPA_L2_FAST_OCC void spa_l2_fast_kernel_##X( FastParams kernelArgs) { Engine<RR,TT>::runKernel(); }
+SPA_FAST_VARIANTS( SPA_FAST_INSTANCE)
 
 namespace spa {
-static const void* fastInstance( unsigned variant)
+struct FastVariant { void (*kernel)( FastParams); uint32_t R, T; const char* name; };
+#define SPA_FAST_ENTRY( X, RR, TT) {spa_l2_fast_kernel_##X, RR, TT, "spa_l2_fast_kernel_" #X},
+static const FastVariant fastVariants[ FAST_VARIANTS] = { SPA_FAST_VARIANTS( SPA_FAST_ENTRY) };
+static const FastVariant& fastVariantOf( unsigned variant) { return fastVariants[ variant < FAST_VARIANTS ? variant : FAST_VARIANTS-1]; }
+
+// the variant an SPA_L2_FAST_SIZE value names (its first letter), else n
+unsigned fastVariantNamed( const char* size)
 {
-	return variant == 0 ? (const void*)spa_l2_fast_kernel_s : variant == 1 ? (const void*)spa_l2_fast_kernel_m : variant == 2 ? (const void*)spa_l2_fast_kernel_l : variant == 4 ? (const void*)spa_l2_fast_kernel_n : (const void*)spa_l2_fast_kernel_t;
+	for (unsigned v=0; v<FAST_VARIANTS; ++v) if (size[ 0] == fastVariants[ v].name[ sizeof("spa_l2_fast_kernel_")-1]) return v;
+	return FAST_VARIANTS-1;
 }
-void fastCapacities( unsigned variant, uint32_t& R, uint32_t& T)
-{
-	if (variant == 0) { R = 192; T = 312; } else if (variant == 1) { R = 320; T = 512; } else if (variant == 2) { R = 512; T = 1024; } else if (variant == 4) { R = 256; T = 448; } else { R = 8; T = 128; }
-}
+const char* fastKernelName( unsigned variant) { return fastVariantOf( variant).name; }
+void fastCapacities( unsigned variant, uint32_t& R, uint32_t& T) { R = fastVariantOf( variant).R; T = fastVariantOf( variant).T; }
 // resident single-wave workgroups per CU of a kernel instance (registers and LDS both limit it)
 int fastBlocksPerCU( unsigned variant)
 {
 	int n = 0;
-	if (hipOccupancyMaxActiveBlocksPerMultiprocessor( &n, fastInstance( variant), 64, 0) != hipSuccess || n < 1) n = 1;
+	if (hipOccupancyMaxActiveBlocksPerMultiprocessor( &n, (const void*)fastVariantOf( variant).kernel, 64, 0) != hipSuccess || n < 1) n = 1;
 	if (n > 32) n = 32;
 	return n;
 }
 hipError_t launchL2Fast( const FastParams& P, unsigned variant, unsigned nblocks, hipStream_t stream)
 {
-	if (variant == 0) hipLaunchKernelGGL( spa_l2_fast_kernel_s, dim3( nblocks), dim3( 64), 0, stream, P);
-	else if (variant == 1) hipLaunchKernelGGL( spa_l2_fast_kernel_m, dim3( nblocks), dim3( 64), 0, stream, P);
-	else if (variant == 2) hipLaunchKernelGGL( spa_l2_fast_kernel_l, dim3( nblocks), dim3( 64), 0, stream, P);
-	else if (variant == 4) hipLaunchKernelGGL( spa_l2_fast_kernel_n, dim3( nblocks), dim3( 64), 0, stream, P);
-	else hipLaunchKernelGGL( spa_l2_fast_kernel_t, dim3( nblocks), dim3( 64), 0, stream, P);
+	hipLaunchKernelGGL( fastVariantOf( variant).kernel, dim3( nblocks), dim3( 64), 0, stream, P);
 	return hipGetLastError();
 }
 }

@@ -19,6 +19,7 @@
 #ifndef SPA_L2_JOIN_H
 #define SPA_L2_JOIN_H
 #include <stdint.h>
+#include "l2_device.h"
 
 namespace spa {
 
@@ -73,17 +74,7 @@ struct JoinParams
 	uint64_t countsCapacity;	// lexem indices below it have a slot (a document beyond it counts twice instead)
 	uint32_t maxRange;		// the largest position range of any program
 	uint32_t delimiter;		// the delimiter event of the *_struct programs (0 = none)
-	const uint32_t* lexems;		// sp_lexem_t[]: id, ordpos, origpos, origsize
-	const uint32_t* origseg;	// optional
-	const uint64_t* docOffsets;	// ndocs+1 lexem indices, or NULL when docRangesIn is given
-	const uint64_t* docRangesIn;	// ndocs x (first lexem, count)
-	uint32_t ndocs;
-	uint32_t* docCursor;
-	uint64_t* counters;		// SPC_*
-	uint32_t* results; uint64_t resultCapacity;
-	uint32_t* items; uint64_t itemCapacity; uint32_t withItems; uint32_t* itemFormat;	// sp_result_item_t[] (7 words each)
-	uint64_t* docRange; uint64_t* docStats; int32_t* docStatus;
-	uint32_t withFormats; uint32_t* resultFormat;
+	L2BatchIO io;
 	uint32_t altRules;		// some rule has a JOIN_ALT_* flag: the look-back goes on behind a taking lexem
 };
 

@@ -7,12 +7,8 @@
 #include "wave_scan.h"
 
 using namespace spa;
-typedef uint32_t u32;
-typedef uint64_t u64;
 
 namespace {
-#define LANE ((u32)(threadIdx.x & 63u))
-__device__ __forceinline__ u32 uni( u32 v) { return __builtin_amdgcn_readfirstlane( v); }
 __shared__ u32 pairFilter[ JOIN_FILTER_WORDS];
 __device__ __forceinline__ bool maybeKey( u32 first, u32 second)
 {
@@ -28,9 +24,9 @@ __device__ __forceinline__ void st4( u32* p, u32 a, u32 b, u32 c, u32 d) { const
 __device__ __forceinline__ void st3( u32* p, u32 a, u32 b, u32 c) { const u32 v[ 3] = {a, b, c}; __builtin_memcpy( p, v, 12); }
 __device__ __forceinline__ void putItem( const JoinParams& P, u64 at, u32 variable, uint4 t, u32 st)
 {
-	u32* io = P.items + at*7;
+	u32* io = P.io.items + at*7;
 	st4( io, variable, t.y, t.y + 1u, st); st3( io+4, t.z, st, t.z + t.w);
-	if (P.withFormats) { P.itemFormat[ 2*at] = 0; P.itemFormat[ 2*at+1] = 0; }
+	if (P.io.withFormats) { P.io.itemFormat[ 2*at] = 0; P.io.itemFormat[ 2*at+1] = 0; }
 }
 // how many times the pair (i, j) matches for a rule of a moved key reference (JOIN_ALT_* in l2_join.h); the caller has checked
 // ordpos(i) < ordpos(j) <= ordpos(i) + range and the delimiter between them.  Lane-private scans over the few lexems of the
@@ -97,13 +93,13 @@ __device__ __forceinline__ u32 matchesEndingAt( const JoinParams& P, const uint4
 				{
 					const JoinRule rule = P.rules[ k.begin + r];
 					// (any( e, e ): both triggers of the instance take the lexem, the second field is the one that fired first)
-					const u32 vj = P.withItems ? (rule.flags >> 16) & 0xFFu : 0u, vi = P.withItems ? (rule.flags >> 8) & 0xFFu : 0u;
+					const u32 vj = P.io.withItems ? (rule.flags >> 16) & 0xFFu : 0u, vi = P.io.withItems ? (rule.flags >> 8) & 0xFFu : 0u;
 					const u32 ni = (vj ? 1u : 0u) + (vi ? 1u : 0u);
 					if (WRITE)
 					{
 						u32* o = out + 9*(u64)cnt;
 						const u32 sj = seg ? seg[ j] : 0u;
-						st4( o, rule.resultHandle, lj.y, lj.y + 1u, sj); st4( o+4, lj.z, sj, lj.z + lj.w, P.withItems ? (u32)(itemAt + icnt) : 0u); o[8] = ni;
+						st4( o, rule.resultHandle, lj.y, lj.y + 1u, sj); st4( o+4, lj.z, sj, lj.z + lj.w, P.io.withItems ? (u32)(itemAt + icnt) : 0u); o[8] = ni;
 						if (fmtOut) fmtOut[ cnt] = rule.formatHandle;
 						if (vj) putItem( P, itemAt + icnt, vj, lj, sj);
 						if (vi) putItem( P, itemAt + icnt + (vj ? 1u : 0u), vi, lj, sj);
@@ -140,7 +136,7 @@ __device__ __forceinline__ u32 matchesEndingAt( const JoinParams& P, const uint4
 						if (rule.flags & JOIN_ALT) times = altMatches( P, lex, i, j, li.x, e, li.y, lj.y, rule.range, rule.flags, taken);
 						else if (taken) continue;
 						// captured items, latest first (as the reference lists them): the completing lexem's, then the first one's
-						const u32 vi = P.withItems ? (rule.flags >> 8) & 0xFFu : 0u, vj = P.withItems ? (rule.flags >> 16) & 0xFFu : 0u;
+						const u32 vi = P.io.withItems ? (rule.flags >> 8) & 0xFFu : 0u, vj = P.io.withItems ? (rule.flags >> 16) & 0xFFu : 0u;
 						const u32 ni = (vi ? 1u : 0u) + (vj ? 1u : 0u);
 						for (u32 t=0; t<times; ++t)
 						{
@@ -148,7 +144,7 @@ __device__ __forceinline__ u32 matchesEndingAt( const JoinParams& P, const uint4
 							{
 								u32* o = out + 9*(u64)cnt;
 								const u32 si = seg ? seg[ i] : 0u, sj = seg ? seg[ j] : 0u;
-								st4( o, rule.resultHandle, li.y, lj.y + 1u, si); st4( o+4, li.z, sj, lj.z + lj.w, P.withItems ? (u32)(itemAt + icnt) : 0u); o[8] = ni;
+								st4( o, rule.resultHandle, li.y, lj.y + 1u, si); st4( o+4, li.z, sj, lj.z + lj.w, P.io.withItems ? (u32)(itemAt + icnt) : 0u); o[8] = ni;
 								if (fmtOut) fmtOut[ cnt] = rule.formatHandle;
 								if (vj) putItem( P, itemAt + icnt, vj, lj, sj);
 								if (vi) putItem( P, itemAt + icnt + (vj ? 1u : 0u), vi, li, si);
@@ -171,19 +167,20 @@ __device__ void joinDocuments( const JoinParams& P)
 {
 	for (u32 k=threadIdx.x; k<(u32)JOIN_FILTER_WORDS; k+=blockDim.x) pairFilter[ k] = P.filter[ k];
 	__syncthreads();
-	for (u32 round=0; round<=P.ndocs; ++round)
+	for (u32 round=0; round<=P.io.ndocs; ++round)
 	{
 		u32 doc = 0;
-		if (LANE == 0) doc = atomicAdd( P.docCursor, 1u);
+		if (LANE == 0) doc = atomicAdd( P.io.docCursor, 1u);
 		doc = uni( doc);
-		if (doc >= P.ndocs) break;
+		if (doc >= P.io.ndocs) break;
+		// (docLexems of l2_device.h reads the range into scalar registers: 5 more SGPR spills here than this vector read)
 		u64 beg, n64;
-		if (P.docRangesIn) { beg = P.docRangesIn[ 2*(u64)doc]; n64 = P.docRangesIn[ 2*(u64)doc+1]; }
-		else { beg = P.docOffsets[ doc]; n64 = P.docOffsets[ doc+1] - beg; }
+		if (P.io.docRangesIn) { beg = P.io.docRangesIn[ 2*(u64)doc]; n64 = P.io.docRangesIn[ 2*(u64)doc+1]; }
+		else { beg = P.io.docOffsets[ doc]; n64 = P.io.docOffsets[ doc+1] - beg; }
 		beg = ((u64)uni( (u32)(beg >> 32)) << 32) | uni( (u32)beg);
 		const u32 n = uni( (u32)n64);
-		const uint4* lex = (const uint4*)P.lexems + beg;
-		const u32* seg = P.origseg ? P.origseg + beg : 0;
+		const uint4* lex = (const uint4*)P.io.lexems + beg;
+		const u32* seg = P.io.origseg ? P.io.origseg + beg : 0;
 		u32 err = 0;
 		if (n64 >= (1ull << 32)) err = SPD_ERR_RANGE;
 		const bool stored = beg + n64 <= P.countsCapacity;
@@ -211,22 +208,9 @@ __device__ void joinDocuments( const JoinParams& P)
 			}
 			if (__ballot( order)) err = SPD_ERR_ORDER; else if (__ballot( bad)) err = SPD_ERR_RANGE;
 		}
-		u64 resBase = 0;
-		if (!err && total)
-		{
-			u64 b = 0;
-			if (LANE == 0) b = atomicAdd( (unsigned long long*)&P.counters[ SPC_RESULTS], (unsigned long long)total);
-			resBase = ((u64)uni( (u32)(b >> 32)) << 32) | uni( (u32)b);
-			if (resBase + total > P.resultCapacity) { err = SPD_ERR_OUTPUT; total = 0; }
-		}
-		u64 itemBase = 0;
-		if (!err && total && itotal)
-		{
-			u64 b = 0;
-			if (LANE == 0) b = atomicAdd( (unsigned long long*)&P.counters[ SPC_ITEMS], (unsigned long long)itotal);
-			itemBase = ((u64)uni( (u32)(b >> 32)) << 32) | uni( (u32)b);
-			if (itemBase + itotal > P.itemCapacity) { err = SPD_ERR_OUTPUT; total = 0; }
-		}
+		u64 resBase = 0, itemBase = 0;
+		if (!err && total && !reserveOutput( P.io, SPC_RESULTS, total, resBase)) { err = SPD_ERR_OUTPUT; total = 0; }
+		if (!err && total && itotal && !reserveOutput( P.io, SPC_ITEMS, itotal, itemBase)) { err = SPD_ERR_OUTPUT; total = 0; }
 		if (!err && total)
 		{
 			u32 at = 0, iat = 0;
@@ -245,21 +229,13 @@ __device__ void joinDocuments( const JoinParams& P)
 				if (cm)
 				{
 					const u64 mine = resBase + at + incl - cm;
-					(void)matchesEndingAt<true>( P, lex, seg, j, lj, P.results + 9*mine, P.withFormats ? P.resultFormat + mine : 0, itemBase + iat + iincl - ci);
+					(void)matchesEndingAt<true>( P, lex, seg, j, lj, P.io.results + 9*mine, P.io.withFormats ? P.io.resultFormat + mine : 0, itemBase + iat + iincl - ci);
 				}
 				at += uni( (u32)__shfl( (int)incl, 63));
 				iat += uni( (u32)__shfl( (int)iincl, 63));
 			}
 		}
-		if (LANE == 0)
-		{
-			P.docRange[ 2*(u64)doc] = resBase; P.docRange[ 2*(u64)doc+1] = err ? 0 : total;
-			u64* st = P.docStats + 4*(u64)doc;
-			st[0] = 0; st[1] = 0; st[2] = 0; st[3] = 0;
-			P.docStatus[ doc] = (int32_t)err;
-			atomicAdd( (unsigned long long*)&P.counters[ SPC_EVENTS], (unsigned long long)(err ? 0 : n));
-			if (err) atomicAdd( (unsigned long long*)&P.counters[ SPC_FAILED], 1ull);
-		}
+		finishDocument( P.io, doc, resBase, err ? 0 : total, 0, 0, 0, 0, err, err ? 0 : n);
 	}
 }
 } // anonymous namespace

@@ -33,10 +33,6 @@ using namespace spa;
 
 namespace {
 
-typedef uint32_t u32;
-typedef uint64_t u64;
-
-#define LANE ((u32)(threadIdx.x & 63u))
 #ifndef SPA_L2_BATCH_MIN
 #define SPA_L2_BATCH_MIN 1	/* key lists of at least this many programs are installed lane-parallel */
 #endif
@@ -47,13 +43,6 @@ typedef uint64_t u64;
 #define SPA_L2_WAVES_PER_EU 3
 #endif
 
-// Debug build only (make TRACE=1): progress words written to host-mapped memory by wave 0 so a
-// stuck kernel can be diagnosed from the host without waiting for it.
-#ifdef SPA_TRACE
-#define TRACE( SLOT, VALUE) do { if (P.trace && LANE == 0 && blockIdx.x == 0 && threadIdx.x < 64) { *(volatile u32*)&P.trace[ SLOT] = (u32)(VALUE); } } while (0)
-#else
-#define TRACE( SLOT, VALUE) do {} while (0)
-#endif
 // Phase profile (make PROF=1): wave-cycles per phase summed into counters[4..7]
 #ifdef SPA_PROF
 #define PROF_DECL u64 prof_t0 = __builtin_amdgcn_s_memtime()
@@ -76,11 +65,6 @@ typedef uint64_t u64;
 #define ARENA_FAIL do { w.err = SPD_ERR_ARENA; w.raw->prof[3] = __LINE__; } while (0)
 #else
 #define ARENA_FAIL w.err = SPD_ERR_ARENA
-#endif
-#ifdef SPA_TRACE2
-#define TRACE2( SLOT, VALUE) TRACE( SLOT, VALUE)
-#else
-#define TRACE2( SLOT, VALUE) do {} while (0)
 #endif
 
 // The launch parameters are read where they are: in the kernel argument segment (constant address
@@ -228,16 +212,8 @@ __device__ __forceinline__ u32 evhash( u32 a)		// src/ruleMatcherAutomaton.cpp:3
 	return a;
 }
 
-__device__ __forceinline__ u32 bcast0( u32 v) { return __builtin_amdgcn_readfirstlane( v); }
-
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-
-// Wave-uniform load: every lane reads the same address; the value is moved to a scalar register so
-// that everything computed from it (indices, loop bounds, branch conditions) stays scalar and the
-// control flow of the automaton is made of scalar branches, not exec-masked vector loops.
-__device__ __forceinline__ u32 ldu( const u32* p) { return __builtin_amdgcn_readfirstlane( *p); }
-// 16-byte accesses: one memory instruction moves a quarter/third/half of a record
-__device__ __forceinline__ uint4 ld4( const void* p) { const u32x4 v = *(const u32x4*)p; return make_uint4( v.x, v.y, v.z, v.w); }
+// 16-byte stores; the LDS forms of ldu and ld4 beside those of wave_scan.h
+using spa::ldu; using spa::ld4;
 __device__ __forceinline__ void st4( void* p, u32 a, u32 b, u32 c, u32 d) { u32x4 v; v.x = a; v.y = b; v.z = c; v.w = d; *(u32x4*)p = v; }
 __device__ __forceinline__ u32* W( void* p) { return (u32*)p; }
 __device__ __forceinline__ const u32* W( const void* p) { return (const u32*)p; }
@@ -488,7 +464,7 @@ __device__ __forceinline__ void deactivateBatch( HWS* wsBlock, u32* wsArena, KP 
 		}
 		// the data reference of my rule {list head, count}: requested now, used after the trigger work
 		uint2 refRec = make_uint2( 0, 0);
-		if (P.withItems && act && ref) refRec = *(const uint2*)&REFS[ 2*(ref-1)];
+		if (P.io.withItems && act && ref) refRec = *(const uint2*)&REFS[ 2*(ref-1)];
 		if (checkDup)
 		{
 			// the same rule may be listed twice (deleted and finished in one step): only its first entry acts
@@ -672,7 +648,7 @@ __device__ __forceinline__ void deactivateBatch( HWS* wsBlock, u32* wsArena, KP 
 		// the trigger slots go with their rule blocks: only the count of installed triggers changes
 		w.nTrig -= (u32)__popcll( __ballot( ntot & 1u)) + 2u*(u32)__popcll( __ballot( ntot & 2u)) + 4u*(u32)__popcll( __ballot( ntot & 4u));
 		// release the data references (cpp:696-700 -> :710-732): one rule per lane
-		if (P.withItems)
+		if (P.io.withItems)
 		{
 			bool bad = false;
 			u32 nfree = 0; bool freeRef = false;
@@ -939,7 +915,7 @@ __device__ __forceinline__ void fireSignal( WSR w, KP P, u32 r, u32 sigtype, u32
 	u32 dataRef = ldu( &R->dataRef);
 	if (take)
 	{
-		if (P.withItems)
+		if (P.io.withItems)
 		{
 			if (variable)
 			{
@@ -988,7 +964,7 @@ __device__ __forceinline__ void fireSignal( WSR w, KP P, u32 r, u32 sigtype, u32
 			const uint4 g0 = ldu4( &P.programs[ q1.w]), g1 = ldu4( W( &P.programs[ q1.w]) + 4);	// {initsigval,initcount,event,resultHandle} {formatHandle,..}
 			u32 fevent = g0.z, handle = g0.w, fmt = g1.x;
 			// a follow event / result shares the captured items from here on: an item kept in the block moves to a list
-			if (P.withItems && !dataRef && (fevent || handle) && ldu( &R->nInline)) dataRef = materializeItems( w, P, R);
+			if (P.io.withItems && !dataRef && (fevent || handle) && ldu( &R->nInline)) dataRef = materializeItems( w, P, R);
 			if (fevent)
 			{
 				if (w.nFollow < CAP_FOLLOW)
@@ -1349,7 +1325,7 @@ __device__ __forceinline__ void installBatch( WSR w, KP P, u32 keyevent, u32 lb,
 			}
 		}
 		if (nofKey > 1 && del) odd = true;		// several key triggers where one deletes: sequential path
-		if (!P.withItems) { itemVar0 = 0; for (int j=0; j<MAXT; ++j) keyVar[ j] = 0; }
+		if (!P.io.withItems) { itemVar0 = 0; for (int j=0; j<MAXT; ++j) keyVar[ j] = 0; }
 		u32 nItems = itemVar0 ? 1u : 0u;
 #pragma unroll
 		for (int j=0; j<MAXT; ++j) if (keyVar[ j]) ++nItems;
@@ -1584,7 +1560,6 @@ __device__ __forceinline__ void doTransition( HWS* wsBlock, u32* wsArena, KP P, 
 		u32 ev = event;
 		if (fi) { ldEv( d, &FOLLOW[ fi].d); ev = ldu( &FOLLOW[ fi].event); }
 		w.nDispose = 0;
-		TRACE2( 6, fi); TRACE2( 7, ev);
 
 		PROF_DECL;
 		// fire the triggers waiting for this event: 64 bucket entries per step, one ballot
@@ -1611,7 +1586,6 @@ __device__ __forceinline__ void doTransition( HWS* wsBlock, u32* wsArena, KP P, 
 		}
 		PROF_ADD( 0);
 		// install the programs keyed by this event
-		TRACE2( 9, 1);
 		uint4 eq = make_uint4( 0, 0, 0, 0);			// {event, listBegin, listCount, stopIdx}
 		bool e = false;
 		if (ev)
@@ -1625,17 +1599,14 @@ __device__ __forceinline__ void doTransition( HWS* wsBlock, u32* wsArena, KP P, 
 				slot = (slot+1) & P.keymask;
 			}
 		}
-		TRACE2( 9, 2);
 		u32 stopIdx = 0;
 		if (e)
 		{
 			stopIdx = eq.w;
 			u32 lb = eq.y, lc = eq.z;
-			TRACE2( 10, lc);
-			if (lc >= SPA_L2_BATCH_MIN && !(P.withItems && d.sub)) installBatch( w, P, ev, lb, lc, d);
-			else for (u32 k=0; k<lc && !w.err; ++k) { TRACE2( 11, k); installProgram( w, P, ev, &P.keylist[ lb+k], d); }
+			if (lc >= SPA_L2_BATCH_MIN && !(P.io.withItems && d.sub)) installBatch( w, P, ev, lb, lc, d);
+			else for (u32 k=0; k<lc && !w.err; ++k) installProgram( w, P, ev, &P.keylist[ lb+k], d);
 		}
-		TRACE2( 9, 3);
 		PROF_ADD( 1);
 		// deactivate rules that finished or were deleted
 		if (w.nDispose >= SPA_L2_DEACT_MIN) deactivateBatch( w.raw, w.arena, P, DISPOSE, w.nDispose, false, false, true);
@@ -1647,7 +1618,7 @@ __device__ __forceinline__ void doTransition( HWS* wsBlock, u32* wsArena, KP P, 
 			StopLog* L = &STOP[ stopIdx-1];
 			stEv( &L->d, d); L->timestamp = ++w.timestamp;
 		}
-		else if (d.sub && P.withItems)
+		else if (d.sub && P.io.withItems)
 		{
 			disposeRef( w, P, d.sub);
 		}
@@ -1776,7 +1747,7 @@ void spa_l2_match_kernel( L2Params kernelArgs)
 	KP P = kernelParams();
 	__shared__ __attribute__((aligned(16))) u32 ldsSlice[ 64 + 16 + 64 + 512 + 16*SCRLDS_CAP + EXPLIST_CAP];
 	const WSV w( (HWS*)ldsSlice, P.arenaBase + (u64)blockIdx.x * P.arena.totalWords);
-	const u32 ndocs = P.docList ? ldu( P.docListCount) : P.ndocs;
+	const u32 ndocs = P.docList ? ldu( P.docListCount) : P.io.ndocs;
 	const u32 waveSlot = blockIdx.x;
 	const u32 nWaveSlots = gridDim.x;
 
@@ -1789,12 +1760,11 @@ void spa_l2_match_kernel( L2Params kernelArgs)
 		if (round)
 		{
 			u32 nx = 0;
-			if (LANE == 0) nx = atomicAdd( P.docCursor, 1u);
-			doc = nWaveSlots + bcast0( nx);
+			if (LANE == 0) nx = atomicAdd( P.io.docCursor, 1u);
+			doc = nWaveSlots + uni( nx);
 		}
 		if (doc >= ndocs) break;
 		if (P.docList) doc = ldu( &P.docList[ doc]);
-		TRACE( 1, doc);
 		// per-document reset (lane-parallel)
 		if (LANE < 16) BSIZE[ LANE] = 0;
 		WINDOW[ LANE] = 0;
@@ -1808,17 +1778,7 @@ void spa_l2_match_kernel( L2Params kernelArgs)
 		w.refFreeN = 0; w.refUsed = 0; w.heapSize = 0; w.nFollow = 0; w.nDispose = 0; w.nStaged = 0; w.err = 0;
 
 		u64 lbeg, lend;
-		if (P.docRangesIn)
-		{
-			const u32* rp = (const u32*)&P.docRangesIn[ 2*(u64)doc];
-			lbeg = ((u64)ldu( rp+1) << 32) | ldu( rp);
-			lend = lbeg + (((u64)ldu( rp+3) << 32) | ldu( rp+2));
-		}
-		else
-		{
-			lbeg = ((u64)ldu( (const u32*)&P.docOffsets[ doc]+1) << 32) | ldu( (const u32*)&P.docOffsets[ doc]);
-			lend = ((u64)ldu( (const u32*)&P.docOffsets[ doc+1]+1) << 32) | ldu( (const u32*)&P.docOffsets[ doc+1]);
-		}
+		docLexems( P.io, doc, lbeg, lend);
 		u32 curPosition = 0, nEvents = 0;
 		for (u64 lbase=lbeg; lbase<lend && !w.err; lbase+=64)
 		{
@@ -1826,8 +1786,8 @@ void spa_l2_match_kernel( L2Params kernelArgs)
 			uint4 lx = make_uint4( 0,0,0,0); u32 seg = 0;
 			if (lbase + LANE < lend)
 			{
-				lx = ((const uint4*)P.lexems)[ lbase + LANE];
-				if (P.origseg) seg = P.origseg[ lbase + LANE];
+				lx = ((const uint4*)P.io.lexems)[ lbase + LANE];
+				if (P.io.origseg) seg = P.io.origseg[ lbase + LANE];
 			}
 			u32 cnt = (lend - lbase) < 64 ? (u32)(lend - lbase) : 64u;
 			for (u32 k=0; k<cnt && !w.err; ++k)
@@ -1843,30 +1803,28 @@ void spa_l2_match_kernel( L2Params kernelArgs)
 				EvData d;
 				d.sseg = origseg; d.eseg = origseg; d.spos = origpos; d.epos = origpos + origsize;
 				d.sord = ordpos; d.eord = ordpos+1; d.sub = 0; d.fmt = 0;
-				TRACE2( 2, nEvents); TRACE2( 3, id); TRACE2( 4, ordpos);
 				doTransition( w.raw, w.arena, P, id /*TermEvent: type bits 0*/, d);
-				TRACE2( 5, nEvents);
 				++nEvents;
 			}
 		}
 
 		// fetchResults: the results are reserved first (their records double as the place where the item
 		// counts wait), then the items (one reservation per document)
-		TRACE2( 12, w.nStaged); TRACE2( 13, w.err);
 		u32 nres = w.err ? 0 : w.nStaged;
 		u64 resBase = 0;
 		if (nres)
 		{
+			// (reserveOutput of l2_device.h, spelled out: through the helper this kernel spills 8 bytes more)
 			u64 b = 0;
-			if (LANE == 0) b = atomicAdd( (unsigned long long*)&P.counters[ SPC_RESULTS], (unsigned long long)nres);
-			resBase = ((u64)bcast0( (u32)(b >> 32)) << 32) | bcast0( (u32)b);
-			if (resBase + nres > P.resultCapacity) { w.err = SPD_ERR_OUTPUT; nres = 0; }
+			if (LANE == 0) b = atomicAdd( (unsigned long long*)&P.io.counters[ SPC_RESULTS], (unsigned long long)nres);
+			resBase = ((u64)uni( (u32)(b >> 32)) << 32) | uni( (u32)b);
+			if (resBase + nres > P.io.resultCapacity) { w.err = SPD_ERR_OUTPUT; nres = 0; }
 		}
-		if (P.withItems && nres)
+		if (P.io.withItems && nres)
 		{
 			// pass 1: every lane walks the item list of its own result and counts
 			u32 total = 0;
-			bool sequential = P.withFormats != 0;	// format arguments nest: those item lists are walked one by one
+			bool sequential = P.io.withFormats != 0;	// format arguments nest: those item lists are walked one by one
 			for (u32 base=0; base<nres && !sequential; base+=64)
 			{
 				const u32 ri = base + LANE;
@@ -1875,7 +1833,7 @@ void spa_l2_match_kernel( L2Params kernelArgs)
 				{
 					const u32 ref = STAGED[ ri].dataRef;
 					if (ref) n = walkItemsLane( w, P, ref, 0, deep);
-					P.results[ (resBase + ri)*9 + 8] = n;
+					P.io.results[ (resBase + ri)*9 + 8] = n;
 				}
 				if (__ballot( deep)) { sequential = true; break; }
 				u32 incl = n;
@@ -1888,18 +1846,12 @@ void spa_l2_match_kernel( L2Params kernelArgs)
 				for (u32 ri=0; ri<nres && !w.err; ++ri)
 				{
 					u32 ref = ldu( &STAGED[ ri].dataRef);
-					if (ref) total += P.withFormats ? walkItemsFormatted( w, P, ref, 0, 0) : walkItems( w, P, ref, 0);
+					if (ref) total += P.io.withFormats ? walkItemsFormatted( w, P, ref, 0, 0) : walkItems( w, P, ref, 0);
 				}
 			}
 			u64 itemBase = 0;
 			if (w.err) nres = 0;
-			else if (total)
-			{
-				u64 b = 0;
-				if (LANE == 0) b = atomicAdd( (unsigned long long*)&P.counters[ SPC_ITEMS], (unsigned long long)total);
-				itemBase = ((u64)bcast0( (u32)(b >> 32)) << 32) | bcast0( (u32)b);
-				if (itemBase + total > P.itemCapacity) { w.err = SPD_ERR_OUTPUT; nres = 0; }
-			}
+			else if (total && !reserveOutput( P.io, SPC_ITEMS, total, itemBase)) { w.err = SPD_ERR_OUTPUT; nres = 0; }
 			if (nres && sequential)
 			{
 				// deeply nested item lists: walked one result after the other
@@ -1907,8 +1859,8 @@ void spa_l2_match_kernel( L2Params kernelArgs)
 				for (u32 ri=0; ri<nres; ++ri)
 				{
 					u32 ref = ldu( &STAGED[ ri].dataRef);
-					u32 n = !ref ? 0u : P.withFormats ? walkItemsFormatted( w, P, ref, P.items + ip*7, P.itemFormat + ip*2) : walkItems( w, P, ref, P.items + ip*7);
-					u32* o = P.results + (resBase + ri)*9;
+					u32 n = !ref ? 0u : P.io.withFormats ? walkItemsFormatted( w, P, ref, P.io.items + ip*7, P.io.itemFormat + ip*2) : walkItems( w, P, ref, P.io.items + ip*7);
+					u32* o = P.io.results + (resBase + ri)*9;
 					o[7] = (u32)ip; o[8] = n;
 					ip += n;
 				}
@@ -1921,16 +1873,16 @@ void spa_l2_match_kernel( L2Params kernelArgs)
 				{
 					const u32 ri = base + LANE;
 					u32 n = 0;
-					if (ri < nres) n = P.results[ (resBase + ri)*9 + 8];
+					if (ri < nres) n = P.io.results[ (resBase + ri)*9 + 8];
 					u32 incl = n;
 					incl = waveScanAdd( incl);
 					if (ri < nres)
 					{
 						const u64 mine = ip + (incl - n);
-						P.results[ (resBase + ri)*9 + 7] = (u32)mine;
+						P.io.results[ (resBase + ri)*9 + 7] = (u32)mine;
 						const u32 ref = STAGED[ ri].dataRef;
 						bool deep = false;
-						if (ref) (void)walkItemsLane( w, P, ref, P.items + mine*7, deep);
+						if (ref) (void)walkItemsLane( w, P, ref, P.io.items + mine*7, deep);
 					}
 					ip += (u32)__builtin_amdgcn_readlane( incl, 63);
 				}
@@ -1942,28 +1894,22 @@ void spa_l2_match_kernel( L2Params kernelArgs)
 			for (u32 ri=LANE; ri<nres; ri+=64)
 			{
 				const StagedResult* S = &STAGED[ ri];
-				u32* o = P.results + (resBase + ri)*9;
+				u32* o = P.io.results + (resBase + ri)*9;
 				const uint4 g0 = ld4( &P.programs[ S->program]);		// {initsigval,initcount,event,resultHandle}
 				o[0] = g0.w; o[1] = S->sord; o[2] = S->eord; o[3] = S->sseg; o[4] = S->spos; o[5] = S->eseg; o[6] = S->epos;
-				if (P.withFormats) P.resultFormat[ resBase + ri] = P.programs[ S->program].formatHandle;
-				if (!P.withItems) { o[7] = 0; o[8] = 0; }
+				if (P.io.withFormats) P.io.resultFormat[ resBase + ri] = P.programs[ S->program].formatHandle;
+				if (!P.io.withItems) { o[7] = 0; o[8] = 0; }
 			}
 		}
-		if (LANE == 0)
-		{
-			P.docRange[ 2*(u64)doc] = resBase; P.docRange[ 2*(u64)doc+1] = nres;
-			u64* st = P.docStats + 4*(u64)doc;
-			st[0] = w.nInstalled; st[1] = w.nAlt; st[2] = w.nSignals; st[3] = w.open;
+		// (a failed document runs again: its events count then)
 #ifdef SPA_PROF2
-			st[0] = w.refUsed; st[1] = w.ruleUsed; st[2] = w.nTrig; st[3] = w.itemUsed;	// high-water marks
+		finishDocument( P.io, doc, resBase, nres, w.refUsed, w.ruleUsed, w.nTrig, w.itemUsed, w.err, w.err ? 0 : nEvents);	// high-water marks
+#else
+		finishDocument( P.io, doc, resBase, nres, w.nInstalled, w.nAlt, w.nSignals, w.open, w.err, w.err ? 0 : nEvents);
 #endif
-			P.docStatus[ doc] = (int32_t)w.err;
-			if (w.err) atomicAdd( (unsigned long long*)&P.counters[ SPC_FAILED], 1ull);
-			else atomicAdd( (unsigned long long*)&P.counters[ SPC_EVENTS], (unsigned long long)nEvents);	// (a failed document runs again: its events count then)
 #if defined(SPA_PROF) || defined(SPA_PROF2)
-			for (int pi=0; pi<4; ++pi) atomicAdd( (unsigned long long*)&P.counters[ 4+pi], (unsigned long long)w.raw->prof[ pi]);
+		if (LANE == 0) for (int pi=0; pi<4; ++pi) atomicAdd( (unsigned long long*)&P.io.counters[ 4+pi], (unsigned long long)w.raw->prof[ pi]);
 #endif
-		}
 	}
 }
 
