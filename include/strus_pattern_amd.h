@@ -219,9 +219,10 @@ void sp_match_batch_free(sp_match_batch_t* b);
  * the launch is asynchronous on `stream` (a hipStream_t, NULL = default stream); results stay in HBM. */
 typedef struct sp_match_device_batch {
 	size_t ndocs;
-	void* d_results;             /* sp_result_t[result_capacity], grouped by document after sp_..._finish */
+	void* d_results;             /* sp_result_t[result_capacity]: whole documents in COMPLETION order, not document order;
+	                                sp_matcher_ctx_batch_finish_device puts them in document order */
 	void* d_items;               /* sp_result_item_t[] */
-	void* d_doc_result_offsets;  /* uint64_t[ndocs+1] */
+	void* d_doc_result_offsets;  /* uint64_t[ndocs][2] = (first result, count) of every document */
 	void* d_doc_stats;           /* uint64_t[ndocs*4] */
 	void* d_doc_status;          /* int32_t[ndocs] */
 	void* d_counters;            /* uint64_t[8]: results, items, events, failed docs, ... */
@@ -235,6 +236,34 @@ int sp_matcher_ctx_match_docs_device(sp_matcher_ctx_t* c, const void* d_lexems, 
  * sp_lexer_ctx_match_docs_device are consumed in place, nothing leaves HBM in between */
 int sp_matcher_ctx_match_lexed_device(sp_matcher_ctx_t* c, const void* d_lexems, const void* d_doc_ranges,
                                       size_t ndocs, size_t nlexems_hint, void* stream, sp_match_device_batch_t* out);
+/* Finishes the last batch of this context on the device: what sp_matcher_ctx_batch_fetch returns, left in HBM.  The raw
+ * batch above is in completion order, with results of failed documents, without the `exclusive` elimination
+ * (src/patternMatcher.cpp:192-246, :278-289) and with item indices into a buffer with gaps; the finished one has none of
+ * that.  The buffers belong to the context (allocated at the first call, a context that never finishes has none) and
+ * are valid until the next finish on it; the raw batch stays as it is. */
+typedef struct sp_match_finished_batch {
+	size_t ndocs;
+	void* d_results;             /* sp_result_t[]: document 0's results first; inside a document the order the
+	                                engine produced; `exclusive` applied; item_begin indexes d_items below */
+	void* d_items;               /* sp_result_item_t[], in result order, no gaps */
+	void* d_doc_result_offsets;  /* uint64_t[ndocs+1]; a failed document (d_doc_status != 0) has an empty range */
+	void* d_doc_item_offsets;    /* uint64_t[ndocs+1] */
+	void* d_result_format;       /* parallel to d_results / d_items, NULL without format strings */
+	void* d_item_format;
+	void* d_totals;              /* uint64_t[2]: results, items */
+} sp_match_finished_batch_t;
+/* Enqueues the finishing passes (count, offsets, place: csrc/l2_finish.h) on `stream` and returns; the call itself waits
+ * for the batch only to read its counters, from which it sizes the buffers.  A `stream` other than the batch's is ordered
+ * behind the batch with an event.  SP_ERR_INVALID before any batch has run on the context.  The next batch on the
+ * context invalidates the finished state (not the buffers: a consumer still reading them orders itself as with any
+ * stream work); it works on whatever the last launch sequence left, the reruns of sp_matcher_ctx_match_docs included. */
+int sp_matcher_ctx_batch_finish_device(sp_matcher_ctx_t* c, void* stream, sp_match_finished_batch_t* out);
+/* plain copy of the finished buffers to the host (plus doc_stats and doc_status of the batch): NO regrouping and NO
+ * elimination on the host; field for field what sp_matcher_ctx_batch_fetch returns for the same batch.
+ * SP_ERR_INVALID when the last batch has not been finished. */
+int sp_matcher_ctx_finished_fetch(sp_matcher_ctx_t* c, sp_match_batch_t* out);
+/* durations of the three passes of the last finish in milliseconds (HIP events on its stream; waits for them) */
+int sp_matcher_ctx_last_finish_ms(sp_matcher_ctx_t* c, double* count_ms, double* offsets_ms, double* place_ms);
 /* copies the results of the last device batch to the host, grouped by document (as sp_matcher_ctx_match_docs
  * returns them, `exclusive` elimination included) */
 int sp_matcher_ctx_batch_fetch(sp_matcher_ctx_t* c, sp_match_batch_t* out);

@@ -165,14 +165,36 @@ class PatternMatcherContext:
             raise PatternError("device batch match failed (%d): %s" % (rc, self._err()))
         return out
 
+    def batchFinishDevice(self, stream=0):
+        """finish the last batch on the device (asynchronous on `stream`): document order, `exclusive` applied, failed
+        documents empty, items without gaps; returns the device pointers (capi.SpMatchFinishedBatch)."""
+        out = capi.SpMatchFinishedBatch()
+        rc = self._L.sp_matcher_ctx_batch_finish_device(self._h, stream or None, ctypes.byref(out))
+        if rc != 0:
+            raise PatternError("finishing the batch on the device failed (%d): %s" % (rc, self._err()))
+        return out
+
+    def finishedFetch(self):
+        """plain host copy of the batch finished by batchFinishDevice: what batchFetch() returns, with no work on the host."""
+        return self._fetched(lambda b: self._L.sp_matcher_ctx_finished_fetch(self._h, ctypes.byref(b)))
+
+    def lastFinishMs(self):
+        """(count, offsets, place) pass durations of the last batchFinishDevice in milliseconds"""
+        a, b, d = ctypes.c_double(-1.0), ctypes.c_double(-1.0), ctypes.c_double(-1.0)
+        if self._L.sp_matcher_ctx_last_finish_ms(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(d)) != 0:
+            raise PatternError("no timed finish")
+        return a.value, b.value, d.value
+
     def batchFetch(self, first_doc=None, ndocs=None):
         """host copy of the last device batch, grouped by document; with (first_doc, ndocs) only of
         that range of documents."""
-        b = capi.SpMatchBatch()
         if first_doc is None:
-            rc = self._L.sp_matcher_ctx_batch_fetch(self._h, ctypes.byref(b))
-        else:
-            rc = self._L.sp_matcher_ctx_batch_fetch_docs(self._h, first_doc, ndocs, ctypes.byref(b))
+            return self._fetched(lambda b: self._L.sp_matcher_ctx_batch_fetch(self._h, ctypes.byref(b)))
+        return self._fetched(lambda b: self._L.sp_matcher_ctx_batch_fetch_docs(self._h, first_doc, ndocs, ctypes.byref(b)))
+
+    def _fetched(self, call):
+        b = capi.SpMatchBatch()
+        rc = call(b)
         try:
             if rc != 0:
                 raise PatternError("fetching the batch failed (%d): %s" % (rc, self._err()))

@@ -58,6 +58,13 @@ class SpMatchDeviceBatch(ctypes.Structure):
     ]
 
 
+class SpMatchFinishedBatch(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("d_results", c_vp), ("d_items", c_vp), ("d_doc_result_offsets", c_vp),
+        ("d_doc_item_offsets", c_vp), ("d_result_format", c_vp), ("d_item_format", c_vp), ("d_totals", c_vp),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/strus_pattern_amd.h
 SIGNATURES = {
     "sp_version": (c_cp, []),
@@ -103,6 +110,9 @@ SIGNATURES = {
     "sp_matcher_ctx_match_lexed_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_size_t, ctypes.c_size_t, c_vp, P(SpMatchDeviceBatch)]),
     "sp_matcher_ctx_batch_fetch": (ctypes.c_int, [c_vp, P(SpMatchBatch)]),
     "sp_matcher_ctx_batch_fetch_docs": (ctypes.c_int, [c_vp, ctypes.c_size_t, ctypes.c_size_t, P(SpMatchBatch)]),
+    "sp_matcher_ctx_batch_finish_device": (ctypes.c_int, [c_vp, c_vp, P(SpMatchFinishedBatch)]),
+    "sp_matcher_ctx_finished_fetch": (ctypes.c_int, [c_vp, P(SpMatchBatch)]),
+    "sp_matcher_ctx_last_finish_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_double)]),
     "sp_matcher_ctx_batch_counters": (ctypes.c_int, [c_vp, P(c_u64)]),
     "sp_matcher_ctx_last_kernel_ms": (ctypes.c_double, [c_vp]),
     "sp_matcher_ctx_kernel_kind": (ctypes.c_int, [c_vp]),

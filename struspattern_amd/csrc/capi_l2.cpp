@@ -5,6 +5,7 @@
 #include "l2_device.h"
 #include "l2_fast.h"
 #include "l2_join.h"
+#include "l2_finish.h"
 #include "hip_util.hpp"
 #include <hip/hip_runtime_api.h>
 #include <cstdlib>
@@ -125,10 +126,16 @@ struct sp_matcher_ctx
 	std::vector<sp_lexem_t> curLexems;
 	std::vector<uint32_t> curOrigseg; bool curHasSeg;
 	sp_matcher_stats_t lastStats;
+	// the last batch finished on the device (l2_finish.h); nothing is allocated before the first sp_matcher_ctx_batch_finish_device
+	DeviceBuffer fResults, fItems, fResultFormat, fItemFormat, fDocResultOffsets, fDocItemOffsets, fTotals, fKept, fCovered, fCursor;
+	bool haveBatch, finished;
+	hipStream_t finishStream;
+	hipEvent_t evFinish[ 4]; bool evFinishValid;
 
 	sp_matcher_ctx() :inst(0),device(0),keymask(0),nofStopWords(0),fast(false),join(false),joinAltRules(false),joinKeymask(0),joinMaxRange(0),joinDelimiter(0),fastWaves(0),fastBlocksPerCU(0),fastVariant(4),fastMaxRules(2048),fastMaxStaged(32768),arenaWaves(0),withFormats(false),resultCapacity(0),itemCapacity(0),minResultCapacity(0),minItemCapacity(0)
-		,lastNdocs(0),evStart(0),evStop(0),evValid(false),lastStream(0),own(0),withItems(true),numCUs(256),curHasSeg(false)
+		,lastNdocs(0),evStart(0),evStop(0),evValid(false),lastStream(0),own(0),withItems(true),numCUs(256),curHasSeg(false),haveBatch(false),finished(false),finishStream(0),evFinishValid(false)
 	{
+		std::memset( evFinish, 0, sizeof(evFinish));
 		std::memset( &arena, 0, sizeof(arena));
 		std::memset( &fastSpill, 0, sizeof(fastSpill)); std::memset( fastBucketMeta, 0, sizeof(fastBucketMeta));
 		std::memset( &lastStats, 0, sizeof(lastStats));
@@ -397,6 +404,7 @@ void sp_matcher_ctx_free( sp_matcher_ctx_t* c)
 	if (c->own) { (void)hipSetDevice( c->device); (void)hipStreamSynchronize( c->own); (void)hipStreamDestroy( c->own); }
 	if (c->evStart) (void)hipEventDestroy( c->evStart);
 	if (c->evStop) (void)hipEventDestroy( c->evStop);
+	for (int i=0; i<4; ++i) if (c->evFinish[ i]) (void)hipEventDestroy( c->evFinish[ i]);
 	delete c;
 }
 const char* sp_matcher_ctx_last_error( const sp_matcher_ctx_t* c) { return c->lasterror.c_str(); }
@@ -639,6 +647,7 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 		  size_t ndocs, size_t nlexems, hipStream_t stream, const void* d_doc_ranges=0, const std::vector<uint32_t>* rerun=0)
 {
 	HIP_CHECK( hipSetDevice( c->device));
+	c->finished = false;		// (a new batch: what was finished is of the one before)
 	// geometry: one wave per workgroup; as many as keep every CU busy, never more waves than documents
 	size_t waveSlots = (size_t)c->numCUs*SPA_L2_WAVES_PER_CU;
 	const size_t ndocsToRun = rerun ? rerun->size() : ndocs;
@@ -773,7 +782,7 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 		HIP_CHECK( launchL2Match( P, nblocks, stream));
 	}
 	HIP_CHECK( hipEventRecord( c->evStop, stream));
-	c->evValid = true; c->lastStream = stream; c->lastNdocs = ndocs;
+	c->evValid = true; c->lastStream = stream; c->lastNdocs = ndocs; c->haveBatch = true;
 }
 
 // where the batch just enqueued leaves its output (device entry points)
@@ -841,6 +850,123 @@ int sp_matcher_ctx_batch_counters( sp_matcher_ctx_t* c, uint64_t counters[8])
 			}
 		}
 	});
+}
+
+// ---- the last device batch finished on the device: document order, `exclusive` applied, items without gaps (l2_finish.h)
+int sp_matcher_ctx_batch_finish_device( sp_matcher_ctx_t* c, void* stream_, sp_match_finished_batch_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (!c->haveBatch) throw std::runtime_error( "no batch to finish: no batch has run on this context");
+		hipStream_t stream = (hipStream_t)stream_;
+		HIP_CHECK( hipSetDevice( c->device));
+		c->finished = false;
+		// the buffers are sized from what the batch counted: this read waits for the batch, the passes below do not
+		uint64_t counters[ SPC_COUNT];
+		HIP_CHECK( hipStreamSynchronize( c->lastStream));
+		copySync( c, counters, c->dCounters.ptr, sizeof(counters), hipMemcpyDeviceToHost);
+		const uint64_t devResults = counters[ SPC_RESULTS] < c->resultCapacity ? counters[ SPC_RESULTS] : c->resultCapacity;
+		const uint64_t devItems = counters[ SPC_ITEMS] < c->itemCapacity ? counters[ SPC_ITEMS] : c->itemCapacity;
+		const size_t ndocs = c->lastNdocs;
+		const bool exclusive = c->inst->compiler.exclusive();
+		c->fResults.reserve( (devResults+1)*sizeof(sp_result_t));
+		c->fItems.reserve( (devItems+1)*sizeof(sp_result_item_t));
+		if (c->withFormats)
+		{
+			c->fResultFormat.reserve( (devResults+1)*sizeof(uint32_t));
+			c->fItemFormat.reserve( (devItems+1)*2*sizeof(uint32_t));
+		}
+		c->fDocResultOffsets.reserve( (ndocs+1)*sizeof(uint64_t));
+		c->fDocItemOffsets.reserve( (ndocs+1)*sizeof(uint64_t));
+		c->fKept.reserve( (ndocs+1)*2*sizeof(uint32_t));
+		if (!c->fTotals.ptr) c->fTotals.alloc( 2*sizeof(uint64_t));
+		if (!c->fCursor.ptr) c->fCursor.alloc( 2*sizeof(uint32_t));
+		if (exclusive) c->fCovered.reserve( devResults+1);
+		for (int i=0; i<4; ++i) if (!c->evFinish[ i]) HIP_CHECK( hipEventCreate( &c->evFinish[ i]));
+
+		// another stream than the batch's runs behind the batch (evStop closes every launch sequence, reruns included)
+		if (stream != c->lastStream) HIP_CHECK( hipStreamWaitEvent( stream, c->evStop, 0));
+		HIP_CHECK( hipMemsetAsync( c->fCursor.ptr, 0, 2*sizeof(uint32_t), stream));
+		if (exclusive) HIP_CHECK( hipMemsetAsync( c->fCovered.ptr, 0, devResults+1, stream));
+		FinishParams F;
+		std::memset( &F, 0, sizeof(F));
+		F.results = (const uint32_t*)c->dResults.ptr; F.items = (const uint32_t*)c->dItems.ptr;
+		F.docRange = (const uint64_t*)c->dDocRange.ptr; F.docStatus = (const int32_t*)c->dDocStatus.ptr;
+		F.resultFormat = (const uint32_t*)c->dResultFormat.ptr; F.itemFormat = (const uint32_t*)c->dItemFormat.ptr;
+		F.nofResults = devResults; F.nofItems = devItems;
+		F.ndocs = (uint32_t)ndocs; F.withFormats = c->withFormats ? 1u : 0u;
+		F.exclusive = exclusive ? 1u : 0u; F.maxResultSize = c->inst->compiler.maxResultSize();
+		F.covered = (uint8_t*)c->fCovered.ptr; F.kept = (uint32_t*)c->fKept.ptr; F.cursor = (uint32_t*)c->fCursor.ptr;
+		F.outResults = (uint32_t*)c->fResults.ptr; F.outItems = (uint32_t*)c->fItems.ptr;
+		F.docResultOffsets = (uint64_t*)c->fDocResultOffsets.ptr; F.docItemOffsets = (uint64_t*)c->fDocItemOffsets.ptr;
+		F.outResultFormat = (uint32_t*)c->fResultFormat.ptr; F.outItemFormat = (uint32_t*)c->fItemFormat.ptr;
+		F.totals = (uint64_t*)c->fTotals.ptr;
+		c->evFinishValid = false;
+		HIP_CHECK( launchL2Finish( F, c->numCUs, stream, c->evFinish));
+		c->evFinishValid = true; c->finished = true; c->finishStream = stream;
+		if (out)
+		{
+			out->ndocs = ndocs;
+			out->d_results = c->fResults.ptr; out->d_items = c->fItems.ptr;
+			out->d_doc_result_offsets = c->fDocResultOffsets.ptr; out->d_doc_item_offsets = c->fDocItemOffsets.ptr;
+			out->d_result_format = c->withFormats ? c->fResultFormat.ptr : 0;
+			out->d_item_format = c->withFormats ? c->fItemFormat.ptr : 0;
+			out->d_totals = c->fTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the finished buffers: nothing is regrouped or eliminated on the host
+int sp_matcher_ctx_finished_fetch( sp_matcher_ctx_t* c, sp_match_batch_t* out)
+{
+	std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (!c->finished) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
+		HIP_CHECK( hipSetDevice( c->device));
+		HIP_CHECK( hipStreamSynchronize( c->finishStream));
+		const size_t ndocs = c->lastNdocs;
+		uint64_t totals[ 2];
+		copySync( c, totals, c->fTotals.ptr, sizeof(totals), hipMemcpyDeviceToHost);
+		out->ndocs = ndocs; out->nresults = (size_t)totals[ 0]; out->nitems = (size_t)totals[ 1];
+		out->results = (sp_result_t*)std::malloc( (totals[ 0]+1)*sizeof(sp_result_t));
+		out->items = (sp_result_item_t*)std::malloc( (totals[ 1]+1)*sizeof(sp_result_item_t));
+		out->doc_result_offsets = (uint64_t*)std::malloc( (ndocs+1)*sizeof(uint64_t));
+		out->doc_stats = (uint64_t*)std::malloc( (ndocs*4+1)*sizeof(uint64_t));
+		out->doc_status = (int32_t*)std::malloc( (ndocs+1)*sizeof(int32_t));
+		if (!out->results || !out->items || !out->doc_result_offsets || !out->doc_stats || !out->doc_status) throw std::bad_alloc();
+		if (totals[ 0]) copySync( c, out->results, c->fResults.ptr, totals[ 0]*sizeof(sp_result_t), hipMemcpyDeviceToHost);
+		if (totals[ 1]) copySync( c, out->items, c->fItems.ptr, totals[ 1]*sizeof(sp_result_item_t), hipMemcpyDeviceToHost);
+		copySync( c, out->doc_result_offsets, c->fDocResultOffsets.ptr, (ndocs+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		if (ndocs)
+		{
+			copySync( c, out->doc_stats, c->dDocStats.ptr, ndocs*4*sizeof(uint64_t), hipMemcpyDeviceToHost);
+			copySync( c, out->doc_status, c->dDocStatus.ptr, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+		}
+		if (c->withFormats)
+		{
+			out->result_format = (uint32_t*)std::malloc( (totals[ 0]+1)*sizeof(uint32_t));
+			out->item_format = (uint32_t*)std::malloc( (totals[ 1]+1)*2*sizeof(uint32_t));
+			if (!out->result_format || !out->item_format) throw std::bad_alloc();
+			if (totals[ 0]) copySync( c, out->result_format, c->fResultFormat.ptr, totals[ 0]*sizeof(uint32_t), hipMemcpyDeviceToHost);
+			if (totals[ 1]) copySync( c, out->item_format, c->fItemFormat.ptr, totals[ 1]*2*sizeof(uint32_t), hipMemcpyDeviceToHost);
+		}
+	});
+}
+
+// durations of the three passes of the last finish in milliseconds (HIP events on its stream)
+int sp_matcher_ctx_last_finish_ms( sp_matcher_ctx_t* c, double* count_ms, double* offsets_ms, double* place_ms)
+{
+	*count_ms = *offsets_ms = *place_ms = -1.0;
+	if (!c->evFinishValid) return SP_ERR_INVALID;
+	if (hipEventSynchronize( c->evFinish[ 3]) != hipSuccess) return SP_ERR_DEVICE;
+	double* ms[ 3] = {count_ms, offsets_ms, place_ms};
+	for (int i=0; i<3; ++i)
+	{
+		float f = 0.0f;
+		if (hipEventElapsedTime( &f, c->evFinish[ i], c->evFinish[ i+1]) != hipSuccess) return SP_ERR_DEVICE;
+		*ms[ i] = (double)f;
+	}
+	return SP_OK;
 }
 
 double sp_matcher_ctx_last_kernel_ms( sp_matcher_ctx_t* c)
