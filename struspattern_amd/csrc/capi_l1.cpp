@@ -1,22 +1,10 @@
 // C-ABI of level 1 (include/strus_pattern_amd.h): lexer compiler handle + GPU lexer context.
 // No CPU fallback: a context cannot be created without a usable HIP device.
-#include "../../include/strus_pattern_amd.h"
 #include "l1_compile.hpp"
 #include "l1_device.h"
-#include "hip_util.hpp"
-#include <hip/hip_runtime_api.h>
-#include <cstdlib>
+#include "capi_util.hpp"
 #include <cstdio>
-#include <cstring>
-#include <new>
-#include <stdexcept>
-#include <string>
-#include <vector>
 
-namespace spa {
-bool l1ScanByLanes( const L1Params& PS, const L1Params& P);
-hipError_t launchL1Lex( const L1Params& PS, const L1Params& PW, const L1Params& P, unsigned nblocks, unsigned nthreads, unsigned laneBlocks, unsigned wordBlocks, unsigned wordWaves, unsigned postWaves, hipStream_t stream, hipEvent_t betweenKernels, hipEvent_t afterWords);
-}
 using namespace spa;
 
 struct sp_lexer
@@ -25,44 +13,32 @@ struct sp_lexer
 	mutable std::string lasterror;
 };
 
-namespace {
-template <class FN>
-int guardedCall1( std::string& err, int errcode, FN fn)
-{
-	try { fn(); return SP_OK; }
-	catch (const std::bad_alloc&) { err = "memory allocation error in strus pattern"; return SP_ERR_NOMEM; }
-	catch (const HipError& e) { err = e.what(); return SP_ERR_DEVICE; }
-	catch (const std::exception& e) { err = e.what(); return errcode; }
-}
-}
-
 struct sp_lexer_ctx
 {
-	const sp_lexer* inst;
-	int device;
+	const sp_lexer* inst = 0;
+	int device = 0;
 	std::string lasterror;
 	DeviceBuffer dByteClass, dClassCtx, dCharMask, dStartMask, dAcceptMask, dShiftDst, dSelfLoop, dExSrc, dExDst, dExCount,
 		dPatterns, dSymbols, dSymbolText, dLiterals, dLiteralText, dLitPats, dTableImage, dWordsImage, dPatOfBit, dApprox, dCharCp, dCharPos, dCpBlocks, dCpPages, dUnitStart, dDocSequential, dNullable,
 		dScanImage, dShapes, dShapePats;
-	uint32_t ldsWords, ldsAccept, ldsStart, ldsShift, ldsSelf, ldsExSrc, ldsExDst; unsigned blockThreads;
-	uint32_t wChar, wAccept, wStart, wShift, wSelf, wExSrc, wExDst, wShapeFp, wWords;	// the words kernel's image: the passes behind the scanned ones + the shape table; offsets biased by what is left out
-	uint32_t imgShapeFp, imgWords, imgAccept, imgStart, imgShift, imgSelf, imgExSrc, imgExDst;	// offsets inside the image of all passes (dTableImage); lds*: inside the image of the scanned passes
-	bool wordsKernel;		// plain tables: literals and word shapes are found by the words kernel
-	DeviceBuffer dArena, dCounters, dText, dDocOffsets, dLexems, dDocRange, dDocStatus, dQueue, dReportCount, dWordQueue, dWordCount;
-	uint32_t queueMul;		// report queue between the two kernels: queueMul/16 reports per text byte (+64 per document)
-	uint32_t queueCap, eventCap;
-	unsigned arenaWaves; uint64_t arenaWords;
-	uint64_t lexemCapacity, minLexemCapacity;
-	unsigned numCUs;
-	hipEvent_t evStart, evMid, evWords, evStop; bool evValid;
+	uint32_t ldsWords = 0, ldsAccept = 0, ldsStart = 0, ldsShift = 0, ldsSelf = 0, ldsExSrc = 0, ldsExDst = 0; unsigned blockThreads = 256;
+	uint32_t wChar = 0, wAccept = 0, wStart = 0, wShift = 0, wSelf = 0, wExSrc = 0, wExDst = 0, wShapeFp = 0, wWords = 0;	// the words kernel's image: the passes behind the scanned ones + the shape table; offsets biased by what is left out
+	uint32_t imgShapeFp = 0, imgWords = 0, imgAccept = 0, imgStart = 0, imgShift = 0, imgSelf = 0, imgExSrc = 0, imgExDst = 0;	// offsets inside the image of all passes (dTableImage); lds*: inside the image of the scanned passes
+	bool wordsKernel = false;	// plain tables: literals and word shapes are found by the words kernel
+	DeviceBuffer dCounters, dText, dDocOffsets, dDocRange, dDocStatus, dQueue, dReportCount, dWordQueue, dWordCount;
+	CountedBuffer arena;		// count: waves of arenaWords words each
+	CountedBuffer lexems;		// count: sp_lexem_t
+	uint32_t queueMul = 8;		// report queue between the two kernels: queueMul/16 reports per text byte (+64 per document)
+	uint32_t queueCap = 4096, eventCap = 32768;
+	uint64_t arenaWords = 0;
+	uint64_t minLexemCapacity = 0;
+	unsigned numCUs = 256;
+	Event evStart, evMid, evWords, evStop; bool evValid = false;
 	char scanKernel[ 48] = "(none)";
 	const char* wordsKernelName = "(none)";
-	hipStream_t lastStream; size_t lastNdocs;
-	hipStream_t own;		// the context's own stream (non-blocking): the host-buffer entry points of different contexts -- one per host thread,
+	hipStream_t lastStream = 0; size_t lastNdocs = 0;
+	Stream own;			// the context's own stream (non-blocking): the host-buffer entry points of different contexts -- one per host thread,
 				// the reference's threading model -- copy and launch side by side instead of queueing on the null stream
-	sp_lexer_ctx() :inst(0),device(0),ldsWords(0),ldsAccept(0),ldsStart(0),ldsShift(0),ldsSelf(0),ldsExSrc(0),ldsExDst(0),blockThreads(256),queueMul(8),queueCap(4096),eventCap(32768),arenaWaves(0),arenaWords(0),lexemCapacity(0),minLexemCapacity(0)
-		,numCUs(256),evStart(0),evMid(0),evWords(0),evStop(0),evValid(false),lastStream(0),lastNdocs(0),own(0)
-		,wChar(0),wAccept(0),wStart(0),wShift(0),wSelf(0),wExSrc(0),wExDst(0),wShapeFp(0),wWords(0),imgShapeFp(0),imgWords(0),imgAccept(0),imgStart(0),imgShift(0),imgSelf(0),imgExSrc(0),imgExDst(0),wordsKernel(false){}
 };
 
 extern "C" {
@@ -71,37 +47,13 @@ sp_lexer_t* sp_lexer_create(void) { try { return new sp_lexer(); } catch (...) {
 void sp_lexer_free( sp_lexer_t* l) { delete l; }
 const char* sp_lexer_last_error( const sp_lexer_t* l) { return l->lasterror.c_str(); }
 
-#define LGUARD( CODE, BODY) return guardedCall1( l->lasterror, CODE, [&]{ BODY; })
+#define LGUARD( CODE, BODY) return guardedCall( l->lasterror, CODE, [&]{ BODY; })
 
 // the compiled lexer as a blob (automaton tables, literal and symbol tables, names) and back: SURVEY.md 8(f).4
 int sp_lexer_serialize( const sp_lexer_t* l, void** blob, size_t* size)
-{
-	*blob = 0; *size = 0;
-	return guardedCall1( l->lasterror, SP_ERR_INVALID, [&]{
-		std::vector<uint8_t> buf;
-		l->compiler.save( buf);
-		*blob = std::malloc( buf.size() ? buf.size() : 1);
-		if (!*blob) throw std::bad_alloc();
-		std::memcpy( *blob, buf.data(), buf.size());
-		*size = buf.size();
-	});
-}
+{ return exportBlob( l->lasterror, blob, size, [&]( std::vector<uint8_t>& buf){ l->compiler.save( buf); }); }
 sp_lexer_t* sp_lexer_deserialize( const void* blob, size_t size, char* err, size_t errsize)
-{
-	sp_lexer* l = 0;
-	try
-	{
-		l = new sp_lexer();
-		l->compiler.load( blob, size);
-		return l;
-	}
-	catch (const std::exception& e)
-	{
-		if (err && errsize) { std::strncpy( err, e.what(), errsize-1); err[ errsize-1] = 0; }
-		delete l;
-		return 0;
-	}
-}
+{ return importBlob<sp_lexer>( err, errsize, [&]( sp_lexer& l){ l.compiler.load( blob, size); }); }
 
 
 int sp_lexer_define_lexem_name( sp_lexer_t* l, uint32_t id, const char* name)
@@ -309,11 +261,8 @@ sp_lexer_ctx_t* sp_lexer_ctx_create( const sp_lexer_t* l, int device)
 		c->dCounters.alloc( L1C_ALLOC*sizeof(uint64_t));
 		uint32_t npat = (uint32_t)T.patterns.size();
 		c->queueCap = 4096 > 2*npat+256 ? 4096 : 2*npat+256;
-		HIP_CHECK( hipStreamCreateWithFlags( &c->own, hipStreamNonBlocking));
-		HIP_CHECK( hipEventCreate( &c->evStart));
-		HIP_CHECK( hipEventCreate( &c->evMid));
-		HIP_CHECK( hipEventCreate( &c->evWords));
-		HIP_CHECK( hipEventCreate( &c->evStop));
+		c->own.create( device);
+		c->evStart.create(); c->evMid.create(); c->evWords.create(); c->evStop.create();
 		return c;
 	}
 	catch (const std::exception& e)
@@ -324,16 +273,7 @@ sp_lexer_ctx_t* sp_lexer_ctx_create( const sp_lexer_t* l, int device)
 	}
 }
 
-void sp_lexer_ctx_free( sp_lexer_ctx_t* c)
-{
-	if (!c) return;
-	if (c->own) { (void)hipSetDevice( c->device); (void)hipStreamSynchronize( c->own); (void)hipStreamDestroy( c->own); }
-	if (c->evStart) (void)hipEventDestroy( c->evStart);
-	if (c->evMid) (void)hipEventDestroy( c->evMid);
-	if (c->evWords) (void)hipEventDestroy( c->evWords);
-	if (c->evStop) (void)hipEventDestroy( c->evStop);
-	delete c;
-}
+void sp_lexer_ctx_free( sp_lexer_ctx_t* c) { delete c; }	// (`own` waits for its work before it goes: Stream)
 const char* sp_lexer_ctx_last_error( const sp_lexer_ctx_t* c) { return c->lasterror.c_str(); }
 int sp_lexer_ctx_reset( sp_lexer_ctx_t*) { return SP_OK; }	// the context keeps no per-document state between calls
 
@@ -356,7 +296,7 @@ int sp_lexer_ctx_grow_arena( sp_lexer_ctx_t* c)
 	if (events)
 	{
 		if (c->eventCap >= (1u<<26)) { c->lasterror = "arena at its maximum size"; return SP_ERR_INVALID; }
-		c->eventCap *= 2; c->arenaWaves = 0;
+		c->eventCap *= 2; c->arena.count = 0;
 	}
 	if (queue)
 	{
@@ -369,11 +309,13 @@ int sp_lexer_ctx_grow_arena( sp_lexer_ctx_t* c)
 } // extern "C"
 
 namespace {
-// a copy on the context's own stream, complete when the call returns
-inline void copySync( sp_lexer_ctx* c, void* dst, const void* src, size_t n, hipMemcpyKind kind)
+// the host arrays of a batch of `ndocs` documents with `nlexems` lexems (sp_lex_batch_free)
+void allocLexBatch( sp_lex_batch_t* out, size_t ndocs, uint64_t nlexems)
 {
-	HIP_CHECK( hipMemcpyAsync( dst, src, n, kind, c->own));
-	HIP_CHECK( hipStreamSynchronize( c->own));
+	out->ndocs = ndocs;
+	out->doc_lexem_offsets = hostArray<uint64_t>( ndocs+1);
+	out->doc_status = hostArray<int32_t>( ndocs+1);
+	out->lexems = hostArray<sp_lexem_t>( nlexems+1);
 }
 enum {SPA_L1_POST_WAVES_PER_EU_DEFAULT=6};
 void launchLex( sp_lexer_ctx* c, const void* d_text, const void* d_doc_offsets, size_t ndocs, size_t nbytes, hipStream_t stream)
@@ -400,23 +342,16 @@ void launchLex( sp_lexer_ctx* c, const void* d_text, const void* d_doc_offsets, 
 	nwaves = (nwaves + 3u) & ~3u;
 	if (nwaves == 0) nwaves = 4;
 	uint64_t perWaveWords = 4ull*c->eventCap;		// the handler's event array (the report queue is per document: dQueue)
+	const ArenaWaves aw = arenaWaves( perWaveWords*4, nwaves, (size_t)c->numCUs*postPerCU, 4);
+	nwaves = aw.run;
+	if (c->arena.count < nwaves || c->arenaWords != perWaveWords)
 	{
-		size_t maxWaves = ((size_t)48 << 30) / (perWaveWords*4);
-		if (maxWaves < 4) maxWaves = 4;
-		if (nwaves > maxWaves) nwaves = (unsigned)(maxWaves & ~(size_t)3);
-	}
-	if (c->arenaWaves < nwaves || c->arenaWords != perWaveWords)
-	{
-		size_t full = (size_t)c->numCUs*postPerCU;
-		if (full * perWaveWords*4 > ((size_t)48 << 30)) full = ((size_t)48 << 30) / (perWaveWords*4);
-		unsigned alloc = (nwaves >= 64 && nwaves < full) ? (unsigned)full : nwaves;		// (single documents, the plugin path: a small arena per context)
-		c->arenaWaves = 0;
-		c->dArena.alloc( (size_t)alloc * perWaveWords * 4);
-		c->arenaWaves = alloc; c->arenaWords = perWaveWords;
+		c->arena.realloc( aw.alloc, perWaveWords*4);
+		c->arenaWords = perWaveWords;
 	}
 	uint64_t want = (uint64_t)nbytes/3 + 4096;
 	if (want < c->minLexemCapacity) want = c->minLexemCapacity;
-	if (c->lexemCapacity < want) { c->lexemCapacity = 0; c->dLexems.alloc( want*sizeof(sp_lexem_t)); c->lexemCapacity = want; }	// (capacity follows the buffer also when the allocation fails)
+	c->lexems.ensure( want, sizeof(sp_lexem_t));
 	c->dDocRange.reserve( (ndocs+1)*2*sizeof(uint64_t));
 	c->dDocStatus.reserve( (ndocs+1)*sizeof(int32_t));
 	c->dReportCount.reserve( (maxUnits+1)*sizeof(uint32_t));
@@ -469,8 +404,8 @@ void launchLex( sp_lexer_ctx* c, const void* d_text, const void* d_doc_offsets, 
 	P.nofPasses = T.nofPasses; P.nofClasses = T.nofClasses; P.maxExceptions = T.maxExceptions ? T.maxExceptions : 1;
 	P.nofPatterns = (uint32_t)T.patterns.size();
 	P.text = (const uint8_t*)d_text; P.docOffsets = (const uint64_t*)d_doc_offsets; P.ndocs = (uint32_t)ndocs;
-	P.arenaBase = (uint32_t*)c->dArena.ptr; P.arenaWords = perWaveWords; P.queueCap = c->queueCap; P.eventCap = c->eventCap;
-	P.counters = (uint64_t*)c->dCounters.ptr; P.lexems = (uint32_t*)c->dLexems.ptr; P.lexemCapacity = c->lexemCapacity;
+	P.arenaBase = (uint32_t*)c->arena.ptr(); P.arenaWords = perWaveWords; P.queueCap = c->queueCap; P.eventCap = c->eventCap;
+	P.counters = (uint64_t*)c->dCounters.ptr; P.lexems = (uint32_t*)c->lexems.ptr(); P.lexemCapacity = c->lexems.count;
 	P.docRange = (uint64_t*)c->dDocRange.ptr; P.docStatus = (int32_t*)c->dDocStatus.ptr;
 	P.reportQueue = (uint32_t*)c->dQueue.ptr; P.reportCount = (uint32_t*)c->dReportCount.ptr; P.queueMul = c->queueMul;
 	P.approx = T.approx.empty() ? 0 : (const DevApproxPattern*)c->dApprox.ptr; P.nofApprox = (uint32_t)T.approx.size();
@@ -533,12 +468,12 @@ extern "C" {
 int sp_lexer_ctx_match_docs_device( sp_lexer_ctx_t* c, const void* d_text, const void* d_doc_offsets,
 				    size_t ndocs, size_t nbytes, void* stream, sp_lex_device_batch_t* out)
 {
-	return guardedCall1( c->lasterror, SP_ERR_INVALID, [&]{
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
 		if (ndocs >= 0xFFFFFFFFull) throw std::runtime_error( "too many documents in one batch");
 		launchLex( c, d_text, d_doc_offsets, ndocs, nbytes, (hipStream_t)stream);
 		if (out)
 		{
-			out->ndocs = ndocs; out->d_lexems = c->dLexems.ptr; out->d_doc_ranges = c->dDocRange.ptr;
+			out->ndocs = ndocs; out->d_lexems = c->lexems.ptr(); out->d_doc_ranges = c->dDocRange.ptr;
 			out->d_doc_status = c->dDocStatus.ptr; out->d_counters = c->dCounters.ptr;
 		}
 	});
@@ -546,11 +481,11 @@ int sp_lexer_ctx_match_docs_device( sp_lexer_ctx_t* c, const void* d_text, const
 
 int sp_lexer_ctx_batch_counters( sp_lexer_ctx_t* c, uint64_t counters[8])
 {
-	return guardedCall1( c->lasterror, SP_ERR_DEVICE, [&]{
+	return guardedCall( c->lasterror, SP_ERR_DEVICE, [&]{
 		HIP_CHECK( hipSetDevice( c->device));
 		HIP_CHECK( hipStreamSynchronize( c->lastStream));
 		uint64_t all[ L1C_ALLOC];
-		copySync( c, all, c->dCounters.ptr, L1C_ALLOC*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		copySync( c->own, all, c->dCounters.ptr, L1C_ALLOC*sizeof(uint64_t), hipMemcpyDeviceToHost);
 		for (int i=0; i<L1C_COUNT; ++i) counters[ i] = all[ i];
 #ifndef SPA_PROF
 		// (the phase profile of a PROF build lives in 4..7) scan units of the batch and documents scanned again in one piece
@@ -559,34 +494,18 @@ int sp_lexer_ctx_batch_counters( sp_lexer_ctx_t* c, uint64_t counters[8])
 	});
 }
 
-int sp_lexer_ctx_batch_status( sp_lexer_ctx_t* c, int32_t* status, size_t ndocs)
-{
-	return guardedCall1( c->lasterror, SP_ERR_DEVICE, [&]{
-		HIP_CHECK( hipSetDevice( c->device));
-		HIP_CHECK( hipStreamSynchronize( c->lastStream));
-		if (ndocs > c->lastNdocs) ndocs = c->lastNdocs;
-		if (ndocs) copySync( c, status, c->dDocStatus.ptr, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
-	});
-}
+int sp_lexer_ctx_batch_status( sp_lexer_ctx_t* c, int32_t* status, size_t ndocs) { return batchStatus( c, c->dDocStatus, status, ndocs); }
 
-double sp_lexer_ctx_last_kernel_ms( sp_lexer_ctx_t* c)
-{
-	if (!c->evValid) return -1.0;
-	float ms = 0.0f;
-	if (hipEventSynchronize( c->evStop) != hipSuccess) return -1.0;
-	if (hipEventElapsedTime( &ms, c->evStart, c->evStop) != hipSuccess) return -1.0;
-	return (double)ms;
-}
+double sp_lexer_ctx_last_kernel_ms( sp_lexer_ctx_t* c) { return lastKernelMs( c); }
 
 int sp_lexer_ctx_last_kernel_ms_split( sp_lexer_ctx_t* c, double* scan_ms, double* post_ms)
 {
 	*scan_ms = -1.0; *post_ms = -1.0;
 	if (!c->evValid) return SP_ERR_INVALID;
-	float a = 0.0f, b = 0.0f;
+	double a = 0.0, b = 0.0;
 	if (hipEventSynchronize( c->evStop) != hipSuccess) return SP_ERR_INVALID;
-	if (hipEventElapsedTime( &a, c->evStart, c->evMid) != hipSuccess) return SP_ERR_INVALID;
-	if (hipEventElapsedTime( &b, c->evMid, c->evStop) != hipSuccess) return SP_ERR_INVALID;
-	*scan_ms = (double)a; *post_ms = (double)b;
+	if (!elapsedMs( c->evStart, c->evMid, a) || !elapsedMs( c->evMid, c->evStop, b)) return SP_ERR_INVALID;
+	*scan_ms = a; *post_ms = b;
 	return SP_OK;
 }
 
@@ -606,19 +525,18 @@ int sp_lexer_ctx_last_kernel_ms_split3( sp_lexer_ctx_t* c, double* scan_ms, doub
 {
 	*scan_ms = -1.0; *words_ms = -1.0; *post_ms = -1.0;
 	if (!c->evValid) return SP_ERR_INVALID;
-	float a = 0.0f, b = 0.0f, d = 0.0f;
+	double a = 0.0, b = 0.0, d = 0.0;
 	if (hipEventSynchronize( c->evStop) != hipSuccess) return SP_ERR_INVALID;
-	if (hipEventElapsedTime( &a, c->evStart, c->evMid) != hipSuccess) return SP_ERR_INVALID;
-	if (hipEventElapsedTime( &b, c->evMid, c->evWords) != hipSuccess) return SP_ERR_INVALID;
-	if (hipEventElapsedTime( &d, c->evWords, c->evStop) != hipSuccess) return SP_ERR_INVALID;
-	*scan_ms = (double)a; *words_ms = (double)b; *post_ms = (double)d;
+	if (!elapsedMs( c->evStart, c->evMid, a) || !elapsedMs( c->evMid, c->evWords, b) || !elapsedMs( c->evWords, c->evStop, d)) return SP_ERR_INVALID;
+	*scan_ms = a; *words_ms = b; *post_ms = d;
 	return SP_OK;
 }
 
 int sp_lexer_ctx_match_docs( sp_lexer_ctx_t* c, const char* text, const uint64_t* doc_offsets, size_t ndocs, sp_lex_batch_t* out)
 {
 	std::memset( out, 0, sizeof(*out));
-	int rc = guardedCall1( c->lasterror, SP_ERR_INVALID, [&]{
+	// (the code of guardedCall as it is: an invalid batch is SP_ERR_INVALID here, SP_ERR_DEVICE from sp_matcher_ctx_match_docs)
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
 		if (ndocs >= 0xFFFFFFFFull) throw std::runtime_error( "too many documents in one batch");
 		HIP_CHECK( hipSetDevice( c->device));
 		size_t nbytes = ndocs ? (size_t)doc_offsets[ ndocs] : 0;
@@ -628,18 +546,18 @@ int sp_lexer_ctx_match_docs( sp_lexer_ctx_t* c, const char* text, const uint64_t
 		}
 		c->dText.reserve( nbytes+16);
 		c->dDocOffsets.reserve( (ndocs+1)*sizeof(uint64_t));
-		if (nbytes) copySync( c, c->dText.ptr, text, nbytes, hipMemcpyHostToDevice);
-		copySync( c, c->dDocOffsets.ptr, doc_offsets, (ndocs+1)*sizeof(uint64_t), hipMemcpyHostToDevice);
+		if (nbytes) copySync( c->own, c->dText.ptr, text, nbytes, hipMemcpyHostToDevice);
+		copySync( c->own, c->dDocOffsets.ptr, doc_offsets, (ndocs+1)*sizeof(uint64_t), hipMemcpyHostToDevice);
 		uint64_t counters[ L1C_COUNT];
 		std::vector<int32_t> st( ndocs+1);
 		for (int attempt=0;; ++attempt)
 		{
 			launchLex( c, c->dText.ptr, c->dDocOffsets.ptr, ndocs, nbytes, c->own);
 			HIP_CHECK( hipStreamSynchronize( c->own));
-			copySync( c, counters, c->dCounters.ptr, sizeof(counters), hipMemcpyDeviceToHost);
-			if (ndocs) copySync( c, st.data(), c->dDocStatus.ptr, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+			copySync( c->own, counters, c->dCounters.ptr, sizeof(counters), hipMemcpyDeviceToHost);
+			if (ndocs) copySync( c->own, st.data(), c->dDocStatus.ptr, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
 			bool grow = false;
-			if (counters[ L1C_LEXEMS] > c->lexemCapacity) { c->minLexemCapacity = counters[ L1C_LEXEMS] + counters[ L1C_LEXEMS]/8 + 1024; grow = true; }
+			if (counters[ L1C_LEXEMS] > c->lexems.count) { c->minLexemCapacity = counters[ L1C_LEXEMS] + counters[ L1C_LEXEMS]/8 + 1024; grow = true; }
 			if (counters[ L1C_FAILED])
 			{
 				bool arena = false;
@@ -649,17 +567,13 @@ int sp_lexer_ctx_match_docs( sp_lexer_ctx_t* c, const char* text, const uint64_t
 			if (!grow || attempt >= 12) break;
 		}
 		std::vector<uint64_t> range( ndocs*2+2);
-		if (ndocs) copySync( c, range.data(), c->dDocRange.ptr, ndocs*2*sizeof(uint64_t), hipMemcpyDeviceToHost);
-		uint64_t nlex = counters[ L1C_LEXEMS] < c->lexemCapacity ? counters[ L1C_LEXEMS] : c->lexemCapacity;
+		if (ndocs) copySync( c->own, range.data(), c->dDocRange.ptr, ndocs*2*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		uint64_t nlex = clampCount( counters[ L1C_LEXEMS], c->lexems.count);
 		std::vector<sp_lexem_t> raw( nlex+1);
-		if (nlex) copySync( c, raw.data(), c->dLexems.ptr, nlex*sizeof(sp_lexem_t), hipMemcpyDeviceToHost);
-		out->ndocs = ndocs;
-		out->doc_lexem_offsets = (uint64_t*)std::malloc( (ndocs+1)*sizeof(uint64_t));
-		out->doc_status = (int32_t*)std::malloc( (ndocs+1)*sizeof(int32_t));
+		if (nlex) copySync( c->own, raw.data(), c->lexems.ptr(), nlex*sizeof(sp_lexem_t), hipMemcpyDeviceToHost);
 		uint64_t total = 0;
 		for (size_t di=0; di<ndocs; ++di) { if (st[ di] != 0) range[ 2*di+1] = 0; total += range[ 2*di+1]; }
-		out->lexems = (sp_lexem_t*)std::malloc( (total+1)*sizeof(sp_lexem_t));
-		if (!out->doc_lexem_offsets || !out->doc_status || !out->lexems) throw std::bad_alloc();
+		allocLexBatch( out, ndocs, total);
 		uint64_t lp = 0;
 		for (size_t di=0; di<ndocs; ++di)
 		{
@@ -677,47 +591,42 @@ int sp_lexer_ctx_match_docs( sp_lexer_ctx_t* c, const char* text, const uint64_t
 			char msg[ 160];
 			snprintf( msg, sizeof(msg), "at least one document failed: document %zu has status %d%s", bad, bad < ndocs ? st[ bad] : -1,
 				(bad < ndocs && st[ bad] == SP_DOC_ERR_LEXEMSIZE) ? " (size of matched term out of range)" : "");
-			throw std::runtime_error( msg);
+			throw DocumentFailed( msg);
 		}
 	});
-	if (rc == SP_OK) return SP_OK;
-	return c->lasterror.find( "document failed") != std::string::npos ? SP_ERR_MATCH : rc;
 }
 
 // host copy of the lexems of the documents [first_doc, first_doc+ndocs) of the last device batch
 int sp_lexer_ctx_batch_fetch_docs( sp_lexer_ctx_t* c, size_t first_doc, size_t ndocs, sp_lex_batch_t* out)
 {
 	std::memset( out, 0, sizeof(*out));
-	return guardedCall1( c->lasterror, SP_ERR_DEVICE, [&]{
+	return guardedCall( c->lasterror, SP_ERR_DEVICE, [&]{
 		HIP_CHECK( hipSetDevice( c->device));
 		HIP_CHECK( hipStreamSynchronize( c->lastStream));
 		if (first_doc > c->lastNdocs || ndocs > c->lastNdocs - first_doc) throw std::runtime_error( "document range outside the last batch");
 		uint64_t counters[ L1C_COUNT];
-		copySync( c, counters, c->dCounters.ptr, sizeof(counters), hipMemcpyDeviceToHost);
-		const uint64_t devLexems = counters[ L1C_LEXEMS] < c->lexemCapacity ? counters[ L1C_LEXEMS] : c->lexemCapacity;
+		copySync( c->own, counters, c->dCounters.ptr, sizeof(counters), hipMemcpyDeviceToHost);
+		const uint64_t devLexems = clampCount( counters[ L1C_LEXEMS], c->lexems.count);
 		std::vector<uint64_t> range( ndocs*2+2);
-		out->ndocs = ndocs;
-		out->doc_lexem_offsets = (uint64_t*)std::malloc( (ndocs+1)*sizeof(uint64_t));
-		out->doc_status = (int32_t*)std::malloc( (ndocs+1)*sizeof(int32_t));
-		if (!out->doc_lexem_offsets || !out->doc_status) throw std::bad_alloc();
+		std::vector<int32_t> st( ndocs+1);
 		if (ndocs)
 		{
-			copySync( c, range.data(), (const uint64_t*)c->dDocRange.ptr + 2*first_doc, ndocs*2*sizeof(uint64_t), hipMemcpyDeviceToHost);
-			copySync( c, out->doc_status, (const int32_t*)c->dDocStatus.ptr + first_doc, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+			copySync( c->own, range.data(), (const uint64_t*)c->dDocRange.ptr + 2*first_doc, ndocs*2*sizeof(uint64_t), hipMemcpyDeviceToHost);
+			copySync( c->own, st.data(), (const int32_t*)c->dDocStatus.ptr + first_doc, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
 		}
 		uint64_t total = 0;
 		for (size_t di=0; di<ndocs; ++di)
 		{
-			if (out->doc_status[ di] != 0 || range[ 2*di] + range[ 2*di+1] > devLexems) range[ 2*di+1] = 0;
+			if (st[ di] != 0 || range[ 2*di] + range[ 2*di+1] > devLexems) range[ 2*di+1] = 0;
 			total += range[ 2*di+1];
 		}
-		out->lexems = (sp_lexem_t*)std::malloc( (total+1)*sizeof(sp_lexem_t));
-		if (!out->lexems) throw std::bad_alloc();
+		allocLexBatch( out, ndocs, total);
+		std::memcpy( out->doc_status, st.data(), ndocs*sizeof(int32_t));
 		uint64_t lp = 0;
 		for (size_t di=0; di<ndocs; ++di)
 		{
 			out->doc_lexem_offsets[ di] = lp;
-			if (range[ 2*di+1]) copySync( c, out->lexems + lp, (const sp_lexem_t*)c->dLexems.ptr + range[ 2*di], range[ 2*di+1]*sizeof(sp_lexem_t), hipMemcpyDeviceToHost);
+			if (range[ 2*di+1]) copySync( c->own, out->lexems + lp, (const sp_lexem_t*)c->lexems.ptr() + range[ 2*di], range[ 2*di+1]*sizeof(sp_lexem_t), hipMemcpyDeviceToHost);
 			lp += range[ 2*di+1];
 		}
 		out->doc_lexem_offsets[ ndocs] = lp;

@@ -1,0 +1,92 @@
+// What the two halves of the C-ABI (capi_l1.cpp, capi_l2.cpp) share: exception -> return code, text and blob export,
+// the entry points that are the same for a lexer and a matcher context.
+#ifndef SPA_CAPI_UTIL_HPP
+#define SPA_CAPI_UTIL_HPP
+#include "../../include/strus_pattern_amd.h"
+#include "hip_util.hpp"
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+namespace spa {
+
+// "at least one document failed": the batch is complete, its doc_status tells which ones (SP_ERR_MATCH)
+struct DocumentFailed :public std::runtime_error
+{
+	explicit DocumentFailed( const std::string& msg) :std::runtime_error( msg){}
+};
+
+template <class FN>
+int guardedCall( std::string& err, int errcode, FN fn)
+{
+	try { fn(); return SP_OK; }
+	catch (const std::bad_alloc&) { err = "memory allocation error in strus pattern"; return SP_ERR_NOMEM; }
+	catch (const HipError& e) { err = e.what(); return SP_ERR_DEVICE; }
+	catch (const DocumentFailed& e) { err = e.what(); return SP_ERR_MATCH; }
+	catch (const std::exception& e) { err = e.what(); return errcode; }
+}
+
+// bounded copy of a message into a caller's buffer (which may be absent)
+inline void copyText( char* dst, size_t dstsize, const char* text)
+{
+	if (dst && dstsize) { std::strncpy( dst, text, dstsize-1); dst[ dstsize-1] = 0; }
+}
+
+// malloc'ed array of n elements for the caller (sp_free, sp_*_batch_free)
+template <class T>
+T* hostArray( uint64_t n)
+{
+	T* p = (T*)std::malloc( (size_t)n * sizeof(T));
+	if (!p) throw std::bad_alloc();
+	return p;
+}
+
+// sp_*_serialize: what `save` writes as a blob for the caller (sp_free)
+template <class FN>
+int exportBlob( std::string& err, void** blob, size_t* size, FN save)
+{
+	*blob = 0; *size = 0;
+	return guardedCall( err, SP_ERR_INVALID, [&]{
+		std::vector<uint8_t> buf;
+		save( buf);
+		*blob = hostArray<uint8_t>( buf.size() ? buf.size() : 1);
+		std::memcpy( *blob, buf.data(), buf.size());
+		*size = buf.size();
+	});
+}
+
+// sp_*_deserialize: a new handle that `load` has filled, or NULL with the message in `err`
+template <class HANDLE, class FN>
+HANDLE* importBlob( char* err, size_t errsize, FN load)
+{
+	HANDLE* h = 0;
+	try { h = new HANDLE(); load( *h); return h; }
+	catch (const std::exception& e) { copyText( err, errsize, e.what()); delete h; return 0; }
+}
+
+// what of a counted output lies inside its buffer
+inline uint64_t clampCount( uint64_t counted, uint64_t capacity) { return counted < capacity ? counted : capacity; }
+
+// ---- sp_*_ctx_batch_status, sp_*_ctx_last_kernel_ms
+template <class CTX>
+int batchStatus( CTX* c, const DeviceBuffer& dDocStatus, int32_t* status, size_t ndocs)
+{
+	return guardedCall( c->lasterror, SP_ERR_DEVICE, [&]{
+		HIP_CHECK( hipSetDevice( c->device));
+		HIP_CHECK( hipStreamSynchronize( c->lastStream));
+		if (ndocs > c->lastNdocs) ndocs = c->lastNdocs;
+		if (ndocs) copySync( c->own, status, dDocStatus.ptr, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+	});
+}
+
+template <class CTX>
+double lastKernelMs( CTX* c)
+{
+	double ms = -1.0;
+	if (!c->evValid || hipEventSynchronize( c->evStop) != hipSuccess || !elapsedMs( c->evStart, c->evStop, ms)) return -1.0;
+	return ms;
+}
+
+} // namespace
+#endif

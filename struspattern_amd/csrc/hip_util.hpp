@@ -1,10 +1,11 @@
-// Small HIP host helpers: error -> exception, RAII device buffer.
+// Small HIP host helpers: error -> exception, RAII device buffer, owned stream and events.
 #ifndef SPA_HIP_UTIL_HPP
 #define SPA_HIP_UTIL_HPP
 #include <hip/hip_runtime_api.h>
 #include <stdexcept>
 #include <string>
 #include <cstddef>
+#include <cstdint>
 #include <cstdlib>
 #include <atomic>
 
@@ -53,6 +54,63 @@ private:
 	DeviceBuffer( const DeviceBuffer&);
 	void operator=( const DeviceBuffer&);
 };
+
+// A buffer of `count` elements.  The count follows the buffer: a failed allocation leaves {NULL, 0}, never {NULL, old count}.
+struct CountedBuffer
+{
+	DeviceBuffer buf;
+	uint64_t count = 0;
+	void* ptr() const { return buf.ptr; }
+	// exact reallocation for n elements
+	void realloc( uint64_t n, size_t elemBytes) { count = 0; buf.alloc( (size_t)n * elemBytes); count = n; }
+	// grow-only
+	void ensure( uint64_t n, size_t elemBytes) { if (count < n) realloc( n, elemBytes); }
+};
+
+// A stream of the context's own (non-blocking), created on demand; synchronised, then destroyed with its owner.
+struct Stream
+{
+	hipStream_t h = 0;
+	int device = 0;
+	Stream() = default;
+	Stream( const Stream&) = delete;
+	~Stream() { if (h) { (void)hipSetDevice( device); (void)hipStreamSynchronize( h); (void)hipStreamDestroy( h); } }
+	void create( int device_) { if (!h) { device = device_; HIP_CHECK( hipStreamCreateWithFlags( &h, hipStreamNonBlocking)); } }
+	operator hipStream_t() const { return h; }
+};
+
+struct Event
+{
+	hipEvent_t h = 0;
+	Event() = default;
+	Event( const Event&) = delete;
+	~Event() { if (h) (void)hipEventDestroy( h); }
+	void create() { if (!h) HIP_CHECK( hipEventCreate( &h)); }
+	operator hipEvent_t() const { return h; }
+};
+
+// milliseconds between two recorded events that have completed
+inline bool elapsedMs( hipEvent_t from, hipEvent_t to, double& ms)
+{
+	float f = 0.0f;
+	if (hipEventElapsedTime( &f, from, to) != hipSuccess) return false;
+	ms = (double)f;
+	return true;
+}
+
+// a copy on `stream`, complete when the call returns
+inline void copySync( hipStream_t stream, void* dst, const void* src, size_t n, hipMemcpyKind kind)
+{
+	HIP_CHECK( hipMemcpyAsync( dst, src, n, kind, stream));
+	HIP_CHECK( hipStreamSynchronize( stream));
+}
+
+// Waves of a per-wave arena of `perWaveBytes` (capi_l2.cpp).  `run`: the waves of this launch, as many as wanted while the arena stays
+// below ~48 GiB (fewer resident waves when documents need a large working set; never fewer than 4, a multiple of `multiple` when cut).
+// `alloc`: the waves to allocate when the arena has to grow: batches of 64 waves and more get the arena of the full machine (`fullSlots`
+// waves) at once; a context that sees single documents (the plugin path: one context per host thread) keeps a small one -- gigabytes less.
+struct ArenaWaves { unsigned run, alloc; };
+ArenaWaves arenaWaves( size_t perWaveBytes, unsigned wanted, size_t fullSlots, unsigned multiple);
 
 } // namespace
 #endif

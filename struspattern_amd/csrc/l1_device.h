@@ -2,6 +2,7 @@
 #ifndef SPA_L1_DEVICE_H
 #define SPA_L1_DEVICE_H
 #include <stdint.h>
+#include <hip/hip_runtime_api.h>
 #include "l1_tables.h"
 
 namespace spa {
@@ -100,6 +101,12 @@ struct L1Params
 	uint32_t ldsChar;		// offset of the character rows in the image (0; the words kernel's image leaves the scanned passes out: biased, as the other offsets)
 	uint32_t postClusters;		// 1: the handler runs a cluster of reports per lane (postDocumentClusters); 0: one report after the other
 };
+
+// ---- host entry points of l1_kernel.hip
+// true when the batch goes through the lane-per-stream scan kernel
+bool l1ScanByLanes( const L1Params& PS, const L1Params& P);
+// enqueue scan, words and post-processing kernels (PS, PW, P: their parameters); the two events are recorded between them
+hipError_t launchL1Lex( const L1Params& PS, const L1Params& PW, const L1Params& P, unsigned nblocks, unsigned nthreads, unsigned laneBlocks, unsigned wordBlocks, unsigned wordWaves, unsigned postWaves, hipStream_t stream, hipEvent_t betweenKernels, hipEvent_t afterWords);
 
 } // namespace
 #endif

@@ -2,6 +2,7 @@
 #ifndef SPA_L2_DEVICE_H
 #define SPA_L2_DEVICE_H
 #include <stdint.h>
+#include <hip/hip_runtime_api.h>
 #include "l2_tables.h"
 #if defined(__HIPCC__)
 #include "wave_scan.h"
@@ -68,6 +69,9 @@ struct L2Params
 	const uint32_t* docList;
 	const uint32_t* docListCount;
 };
+
+// enqueue the general kernel (l2_kernel.hip): one wave per workgroup
+hipError_t launchL2Match( const L2Params& P, unsigned nblocks, hipStream_t stream);
 
 #if defined(__HIPCC__)
 // ---- the per-document prologue and epilogue of the batch contract (IO: L2BatchIO in whatever address space the

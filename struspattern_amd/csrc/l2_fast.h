@@ -14,6 +14,8 @@
 #ifndef SPA_L2_FAST_H
 #define SPA_L2_FAST_H
 #include <stdint.h>
+#include <string>
+#include <vector>
 #include "l2_tables.h"
 #include "l2_device.h"
 
@@ -199,6 +201,18 @@ struct FastParams
 	L2BatchIO io;			// (after the tier's own fields: right behind the tables, the kernel ran 2.5 % slower)
 	uint64_t* prof;			// [8] wave-cycles per phase (make PROF=1 builds), may be NULL
 };
+
+// ---- the kernel instances (l2_fast_kernel.hip): `variant` picks the LDS capacities R, T
+hipError_t launchL2Fast( const FastParams& P, unsigned variant, unsigned nblocks, hipStream_t stream);
+int fastBlocksPerCU( unsigned variant);
+void fastCapacities( unsigned variant, uint32_t& R, uint32_t& T);
+unsigned fastVariantNamed( const char* size);
+const char* fastKernelName( unsigned variant);
+
+// ---- the tables (l2_fast_tables.cpp): the install lines of a flat rule set, or the reason why it is not one; the per-wave layout
+struct FlatTables;
+std::string buildFastTables( const FlatTables& ft, std::vector<FastKeyInst>& out, std::vector<FastStatic>* statics);
+void layoutFast( FastSpillLayout& S, uint32_t bucketMeta[16], uint32_t& expShift, const std::vector<FastKeyInst>& keyinst, uint32_t R, uint32_t T, uint32_t maxRules, uint32_t maxStaged);
 
 } // namespace
 #endif

@@ -19,6 +19,8 @@
 #ifndef SPA_L2_JOIN_H
 #define SPA_L2_JOIN_H
 #include <stdint.h>
+#include <string>
+#include <vector>
 #include "l2_device.h"
 
 namespace spa {
@@ -77,6 +79,12 @@ struct JoinParams
 	L2BatchIO io;
 	uint32_t altRules;		// some rule has a JOIN_ALT_* flag: the look-back goes on behind a taking lexem
 };
+
+// enqueue the join kernel (l2_join_kernel.hip): one wave per document
+hipError_t launchL2Join( const JoinParams& P, unsigned nwaves, hipStream_t stream);
+// the join tables of a rule set (l2_join_tables.cpp), or the reason why it is not eligible
+struct FlatTables;
+std::string buildJoinTables( const FlatTables& ft, std::vector<JoinKey>& keytab, std::vector<JoinRule>& rules, std::vector<uint32_t>& filter, uint32_t& maxRange, uint32_t& delimiter, uint32_t& altPrograms);
 
 } // namespace
 #endif
