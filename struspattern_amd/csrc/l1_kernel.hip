@@ -1197,7 +1197,7 @@ __device__ __forceinline__ void scanDocumentsLanes( const L1Params& P)
 				P.reportCount[ unit] = w.err ? 0u : w.nQueue;
 				if (w.err) P.docStatus[ doc] = (int32_t)w.err;
 				if (w.err == L1D_ERR_ARENA) atomicAdd( (unsigned long long*)&P.counters[ L1C_OVER_QUEUE], 1ull);
-				atomicAdd( (unsigned long long*)&P.counters[ L1C_RAW], (unsigned long long)w.nQueue);
+				atomicAdd( (unsigned long long*)&P.counters[ L1C_RAW], (unsigned long long)(w.err ? 0u : w.nQueue));
 			}
 		}
 	}
@@ -2449,12 +2449,16 @@ __device__ void scanDocuments( const L1Params& P)
 			if (w.err == L1D_CHUNK_UNPROVEN) { P.docSequential[ doc] = 1; P.reportCount[ u0] = 0; }
 			else
 			{
+				// (the re-scan replaces what the proven units of its document left in the first pass: their records leave the count of
+				//  raw reports with them, or the batch would count such a document once per pass)
+				u32 replaced = 0;
+				if (CH && P.sequentialPass) for (u32 u=u0; u<u1; ++u) replaced += P.reportCount[ u];
 				P.reportCount[ u0] = w.err ? 0u : w.nQueue;
 				for (u32 u=u0+1; u<u1; ++u) P.reportCount[ u] = 0;
 				// (the sequential pass decides alone about its document: a chunk of the first pass may have left an error behind)
 				if (w.err || P.sequentialPass) P.docStatus[ doc] = (int32_t)w.err;
 				if (w.err == L1D_ERR_ARENA) atomicAdd( (unsigned long long*)&P.counters[ L1C_OVER_QUEUE], 1ull);
-				atomicAdd( (unsigned long long*)&P.counters[ L1C_RAW], (unsigned long long)w.nQueue);
+				atomicAdd( (unsigned long long*)&P.counters[ L1C_RAW], (unsigned long long)(w.err ? 0u : w.nQueue) - (unsigned long long)replaced);
 			}
 		}
 	}
