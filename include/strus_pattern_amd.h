@@ -315,6 +315,21 @@ int sp_lexer_serialize(const sp_lexer_t* l, void** blob, size_t* size);
 sp_lexer_t* sp_lexer_deserialize(const void* blob, size_t size, char* err, size_t errsize);
 /* compiled automaton tables as a flat u64 array (test hook; layout in csrc/capi_l1.cpp) */
 size_t sp_lexer_dump_tables(const sp_lexer_t* l, uint64_t** out);
+/* one of the table images the kernels read (test hook): which = 0 all passes, 1 the passes the scan kernel runs, 2 the words
+ * kernel's; the eight word offsets {character rows, accept, start, shift, self loop, exception sources, exception targets,
+ * compact shape table}, then the image.  0 when the lexer has no such image (2: a table the words kernel does not take). */
+size_t sp_lexer_dump_image(const sp_lexer_t* l, int which, uint64_t** out);
+/* Which kernels a context on a device of num_cus compute units launches for a batch of ndocs documents and nbytes bytes, and why
+ * -- the lexer's counterpart of sp_matcher_fast_tier; needs no device.  Writes one line of key=value fields separated by blanks:
+ *   route             approx | lanes | passes(N) | none: approximate literal table, lane-per-stream scan kernel, the N-pass scan
+ *                     instance, nothing to scan (literals and word shapes only);  cp=1: the instances for classes by code point
+ *   scan_kernel, words_kernel   what sp_lexer_ctx_scan_kernel_name / _words_kernel_name return after that launch
+ *   scan_grid, scan_threads, scan_lds (bytes, 0 = tables read from global memory), lane_grid, word_grid, word_waves,
+ *   word_lds_words, post_grid, post_waves (before a context bounds them by its arena), chunk_bytes, max_units (bound of the
+ *   scan units), scan_words, post_clusters, image_words, scan_image_words, words_image_words (sizes of the three table images)
+ * The SPA_L1_* switches of the environment count as they do for a context created and launched now.  SP_ERR_INVALID before
+ * compile() or when the line does not fit bufsize. */
+int sp_lexer_launch_plan(const sp_lexer_t* l, unsigned num_cus, size_t ndocs, size_t nbytes, char* buf, size_t bufsize);
 
 /* PatternLexerInstanceInterface::createContext (:1120): an error before compile(); SP_ERR_DEVICE
  * without a usable GPU (no CPU fallback) */

@@ -580,6 +580,24 @@ class PatternLexerInstance:
         self._L.sp_free(p)
         return arr
 
+    def dumpImage(self, which):
+        """(offsets, words) of a table image the kernels read: which = 0 all passes, 1 the scanned passes, 2 the words kernel's
+        (None for a table without one); offsets = [oChar, oAccept, oStart, oShift, oSelf, oExSrc, oExDst, oShapeFp]"""
+        p = ctypes.POINTER(ctypes.c_uint64)()
+        n = self._L.sp_lexer_dump_image(self._h, which, ctypes.byref(p))
+        if n < 8:
+            return None
+        arr = np.ctypeslib.as_array(p, shape=(n,)).copy()
+        self._L.sp_free(p)
+        return [int(x) for x in arr[:8]], arr[8:]
+
+    def launchPlan(self, num_cus, ndocs, nbytes):
+        """what a context on a device of num_cus compute units launches for a batch of ndocs documents and nbytes bytes, as a
+        dict of strings (include/strus_pattern_amd.h, sp_lexer_launch_plan); needs no device"""
+        buf = ctypes.create_string_buffer(1024)
+        self._chk(self._L.sp_lexer_launch_plan(self._h, num_cus, ndocs, nbytes, buf, 1024), "no launch plan")
+        return dict(f.split("=", 1) for f in buf.value.decode().split())
+
     def name(self):
         return "std"
 

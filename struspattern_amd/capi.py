@@ -132,6 +132,8 @@ SIGNATURES = {
     "sp_lexer_define_option": (ctypes.c_int, [c_vp, c_cp, ctypes.c_double]),
     "sp_lexer_compile": (ctypes.c_int, [c_vp]),
     "sp_lexer_dump_tables": (ctypes.c_size_t, [c_vp, P(P(c_u64))]),
+    "sp_lexer_dump_image": (ctypes.c_size_t, [c_vp, ctypes.c_int, P(P(c_u64))]),
+    "sp_lexer_launch_plan": (ctypes.c_int, [c_vp, ctypes.c_uint, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t]),
     "sp_lexer_ctx_create": (c_vp, [c_vp, ctypes.c_int]),
     "sp_lexer_ctx_free": (None, [c_vp]),
     "sp_lexer_ctx_last_error": (c_cp, [c_vp]),

@@ -1,7 +1,8 @@
 // C-ABI of level 1 (include/strus_pattern_amd.h): lexer compiler handle + GPU lexer context.
 // No CPU fallback: a context cannot be created without a usable HIP device.
 #include "l1_compile.hpp"
-#include "l1_device.h"
+#include "l1_image.hpp"
+#include "l1_launch.h"
 #include "capi_util.hpp"
 #include <cstdio>
 
@@ -18,24 +19,20 @@ struct sp_lexer_ctx
 	const sp_lexer* inst = 0;
 	int device = 0;
 	std::string lasterror;
-	DeviceBuffer dByteClass, dClassCtx, dCharMask, dStartMask, dAcceptMask, dShiftDst, dSelfLoop, dExSrc, dExDst, dExCount,
+	DeviceBuffer dByteClass, dClassCtx, dExCount,
 		dPatterns, dSymbols, dSymbolText, dLiterals, dLiteralText, dLitPats, dTableImage, dWordsImage, dPatOfBit, dApprox, dCharCp, dCharPos, dCpBlocks, dCpPages, dUnitStart, dDocSequential, dNullable,
-		dScanImage, dShapes, dShapePats;
-	uint32_t ldsWords = 0, ldsAccept = 0, ldsStart = 0, ldsShift = 0, ldsSelf = 0, ldsExSrc = 0, ldsExDst = 0; unsigned blockThreads = 256;
-	uint32_t wChar = 0, wAccept = 0, wStart = 0, wShift = 0, wSelf = 0, wExSrc = 0, wExDst = 0, wShapeFp = 0, wWords = 0;	// the words kernel's image: the passes behind the scanned ones + the shape table; offsets biased by what is left out
-	uint32_t imgShapeFp = 0, imgWords = 0, imgAccept = 0, imgStart = 0, imgShift = 0, imgSelf = 0, imgExSrc = 0, imgExDst = 0;	// offsets inside the image of all passes (dTableImage); lds*: inside the image of the scanned passes
-	bool wordsKernel = false;	// plain tables: literals and word shapes are found by the words kernel
+		dScanImage, dShapePats;
+	L1Images images;		// the table images behind dTableImage, dScanImage and dWordsImage (l1_image.hpp)
 	DeviceBuffer dCounters, dText, dDocOffsets, dDocRange, dDocStatus, dQueue, dReportCount, dWordQueue, dWordCount;
 	CountedBuffer arena;		// count: waves of arenaWords words each
 	CountedBuffer lexems;		// count: sp_lexem_t
 	uint32_t queueMul = 8;		// report queue between the two kernels: queueMul/16 reports per text byte (+64 per document)
-	uint32_t queueCap = 4096, eventCap = 32768;
+	uint32_t eventCap = 32768;
 	uint64_t arenaWords = 0;
 	uint64_t minLexemCapacity = 0;
 	unsigned numCUs = 256;
 	Event evStart, evMid, evWords, evStop; bool evValid = false;
-	char scanKernel[ 48] = "(none)";
-	const char* wordsKernelName = "(none)";
+	L1LaunchPlan plan;		// of the last launch
 	hipStream_t lastStream = 0; size_t lastNdocs = 0;
 	Stream own;			// the context's own stream (non-blocking): the host-buffer entry points of different contexts -- one per host thread,
 				// the reference's threading model -- copy and launch side by side instead of queueing on the null stream
@@ -128,6 +125,52 @@ size_t sp_lexer_dump_tables( const sp_lexer_t* l, uint64_t** out)
 	return b.size();
 }
 
+// Test dump of a table image (l1_image.hpp): `which` 0 = all passes, 1 = the scanned passes, 2 = the words kernel's; the eight
+// offsets {oChar, oAccept, oStart, oShift, oSelf, oExSrc, oExDst, oShapeFp}, then the words (none: a table without a words kernel has no image 2)
+size_t sp_lexer_dump_image( const sp_lexer_t* l, int which, uint64_t** out)
+{
+	*out = 0;
+	try
+	{
+		if (!l->compiler.compiled() || which < 0 || which > 2) return 0;
+		const L1Images images = buildL1Images( l->compiler.tables(), L1Switches::fromEnv());
+		if (which == 2 && !images.wordsKernel) return 0;
+		const L1Image& img = which == 0 ? images.all : which == 1 ? images.scan : images.words;
+		const uint64_t offsets[ 8] = {img.oChar, img.oAccept, img.oStart, img.oShift, img.oSelf, img.oExSrc, img.oExDst, img.oShapeFp};
+		*out = (uint64_t*)std::malloc( (8 + img.words.size() + 1)*sizeof(uint64_t));
+		if (!*out) return 0;
+		std::memcpy( *out, offsets, sizeof(offsets));
+		if (!img.words.empty()) std::memcpy( *out + 8, img.words.data(), img.words.size()*sizeof(uint64_t));
+		return 8 + img.words.size();
+	}
+	catch (const std::exception& e) { l->lasterror = e.what(); return 0; }
+}
+
+// What a context on a device of `num_cus` compute units would launch for a batch of `ndocs` documents and `nbytes` bytes, without a
+// device: one line of key=value fields (include/strus_pattern_amd.h)
+int sp_lexer_launch_plan( const sp_lexer_t* l, unsigned num_cus, size_t ndocs, size_t nbytes, char* buf, size_t bufsize)
+{
+	if (buf && bufsize) buf[ 0] = 0;
+	return guardedCall( l->lasterror, SP_ERR_INVALID, [&]{
+		if (!l->compiler.compiled()) throw std::runtime_error( "called launch plan without calling 'compile'");
+		if (ndocs >= 0xFFFFFFFFull) throw std::runtime_error( "too many documents in one batch");
+		const LexTables& T = l->compiler.tables();
+		const L1Switches sw = L1Switches::fromEnv();
+		const L1Images images = buildL1Images( T, sw);
+		const L1LaunchPlan p = planL1Launch( T, images, num_cus ? num_cus : 256u, ndocs, nbytes, sw);
+		char route[ 24];
+		if (p.route == L1_ROUTE_PASSES) std::snprintf( route, sizeof(route), "passes(%u)", p.scanPasses);
+		else std::snprintf( route, sizeof(route), "%s", p.route == L1_ROUTE_APPROX ? "approx" : p.route == L1_ROUTE_LANES ? "lanes" : "none");
+		int n = std::snprintf( buf, bufsize, "route=%s cp=%d scan_kernel=%s words_kernel=%s scan_grid=%u scan_threads=%u scan_lds=%zu lane_grid=%u "
+			"word_grid=%u word_waves=%u word_lds_words=%u post_grid=%u post_waves=%u chunk_bytes=%u max_units=%llu scan_words=%u post_clusters=%u "
+			"image_words=%zu scan_image_words=%zu words_image_words=%zu",
+			route, p.cp ? 1 : 0, p.scanKernelName, p.wordsKernelName, p.scanGrid, p.scanThreads, p.scanLdsBytes(), p.laneGrid,
+			p.wordGrid, p.wordWaves, p.wordLdsWords, p.postGrid(), p.postWaves, p.chunkBytes, (unsigned long long)p.maxUnits, p.scanWords, p.postClusters,
+			images.all.words.size(), images.scan.words.size(), images.wordsKernel ? images.words.words.size() : (size_t)0);
+		if (n < 0 || !buf || (size_t)n >= bufsize) throw std::runtime_error( "buffer too small for the launch plan");
+	});
+}
+
 sp_lexer_ctx_t* sp_lexer_ctx_create( const sp_lexer_t* l, int device)
 {
 	sp_lexer_ctx* c = 0;
@@ -152,16 +195,9 @@ sp_lexer_ctx_t* sp_lexer_ctx_create( const sp_lexer_t* l, int device)
 		HIP_CHECK( hipGetDeviceProperties( &prop, device));
 		c->numCUs = prop.multiProcessorCount > 0 ? (unsigned)prop.multiProcessorCount : 256u;
 		const LexTables& T = l->compiler.tables();
-		if (T.nofPasses > 32) throw std::runtime_error( "too many regular expression positions for this version (more than 32 passes of 4096 positions)");
+		c->images = buildL1Images( T, L1Switches::fromEnv());	// (SPA_L1_NO_WORDS_KERNEL is read here; the launch switches at every launch)
 		c->dByteClass.upload( T.byteClass.data(), T.byteClass.size());
 		c->dClassCtx.upload( T.classCtx.data(), T.classCtx.size());
-		c->dCharMask.upload( T.charMask.data(), T.charMask.size()*8);
-		c->dStartMask.upload( T.startMask.data(), T.startMask.size()*8);
-		c->dAcceptMask.upload( T.acceptMask.data(), T.acceptMask.size()*8);
-		c->dShiftDst.upload( T.shiftDst.data(), T.shiftDst.size()*8);
-		c->dSelfLoop.upload( T.selfLoop.data(), T.selfLoop.size()*8);
-		c->dExSrc.upload( T.exSrc.data(), T.exSrc.size()*8);
-		c->dExDst.upload( T.exDst.data(), T.exDst.size()*8);
 		c->dExCount.upload( T.exCount.data(), T.exCount.size()*4);
 		c->dPatOfBit.upload( T.patOfBit.data(), T.patOfBit.size()*4);
 		c->dPatterns.upload( T.patterns.data(), T.patterns.size()*sizeof(DevLexPattern));
@@ -173,94 +209,11 @@ sp_lexer_ctx_t* sp_lexer_ctx_create( const sp_lexer_t* l, int device)
 		if (!T.cpBlocks.empty()) { c->dCpBlocks.upload( T.cpBlocks.data(), T.cpBlocks.size()*2); c->dCpPages.upload( T.cpPages.data(), T.cpPages.size()); }
 		if (!T.nullable.empty()) c->dNullable.upload( T.nullable.data(), T.nullable.size()*sizeof(DevNullable));
 		if (!T.approx.empty()) c->dApprox.upload( T.approx.data(), T.approx.size()*sizeof(DevApproxPattern));
-		c->dShapes.upload( T.shapes.data(), T.shapes.size()*sizeof(DevShape));
 		c->dShapePats.upload( T.shapePats.data(), T.shapePats.size()*4);
-		// literals and word shapes by the words kernel: plain tables (words by ASCII word characters, no classes by code point, no empty matches)
-		c->wordsKernel = T.approx.empty() && !T.ucp && T.cpBlocks.empty() && T.nullable.empty() && !getenv( "SPA_L1_NO_WORDS_KERNEL");
-		if (!c->wordsKernel && T.nofShapes) throw std::runtime_error( "internal: word shapes in a table the words kernel does not take");
-		{
-			// image of all passes: what the kernels that walk an automaton backwards read (global memory)
-			std::vector<uint64_t> img;
-			img.insert( img.end(), T.charMask.begin(), T.charMask.end());
-			c->imgAccept = (uint32_t)img.size(); img.insert( img.end(), T.acceptMask.begin(), T.acceptMask.end());
-			c->imgStart = (uint32_t)img.size(); img.insert( img.end(), T.startMask.begin(), T.startMask.end());
-			c->imgShift = (uint32_t)img.size(); img.insert( img.end(), T.shiftDst.begin(), T.shiftDst.end());
-			c->imgSelf = (uint32_t)img.size(); img.insert( img.end(), T.selfLoop.begin(), T.selfLoop.end());
-			c->imgExSrc = (uint32_t)img.size(); img.insert( img.end(), T.exSrc.begin(), T.exSrc.end());
-			c->imgExDst = (uint32_t)img.size(); img.insert( img.end(), T.exDst.begin(), T.exDst.end());
-			c->imgShapeFp = (uint32_t)img.size(); img.insert( img.end(), T.shapeFp.begin(), T.shapeFp.end());	// (the compact shape table rides along: staged in LDS with the rest)
-			c->dTableImage.upload( img.data(), img.size()*8);
-			c->imgWords = (uint32_t)img.size();
-		}
-		if (c->wordsKernel)
-		{
-			// image of the words kernel: it walks the patterns of the passes BEHIND the scanned ones only, so those passes and the compact
-			// shape table are all it stages in LDS (the 10k set: 101 KB instead of 124: room for 16 waves per workgroup).  The kernel
-			// indexes by absolute pass: the offsets carry the bias (modulo 2^32).
-			const size_t sp = T.scanPasses, mx = T.maxExceptions;
-			auto tail = [&]( std::vector<uint64_t>& img, const std::vector<uint64_t>& v, size_t perPass) -> uint32_t
-			{
-				size_t skip = sp*perPass < v.size() ? sp*perPass : v.size();
-				uint32_t off = (uint32_t)img.size() - (uint32_t)skip;
-				img.insert( img.end(), v.begin() + skip, v.end());
-				return off;
-			};
-			std::vector<uint64_t> img;
-			c->wChar = tail( img, T.charMask, (size_t)T.nofClasses*64);
-			c->wAccept = tail( img, T.acceptMask, (size_t)CTX_COUNT*64);
-			c->wStart = tail( img, T.startMask, (size_t)CTX_COUNT*64);
-			c->wShift = tail( img, T.shiftDst, 64);
-			c->wSelf = tail( img, T.selfLoop, 64);
-			c->wExSrc = tail( img, T.exSrc, mx*64);
-			c->wExDst = tail( img, T.exDst, mx*64);
-			c->wShapeFp = (uint32_t)img.size(); img.insert( img.end(), T.shapeFp.begin(), T.shapeFp.end());
-			if (img.empty()) img.push_back( 0);
-			c->dWordsImage.upload( img.data(), img.size()*8);
-			c->wWords = (uint32_t)img.size();
-		}
-		{
-			// LDS image of the scan kernel: the passes it runs (the word shapes' passes behind them are never scanned), when it fits
-			// (one copy per workgroup; bigger workgroups when the copy is big)
-			const uint32_t sp = c->wordsKernel ? T.scanPasses : T.nofPasses;
-			const size_t maxEx = T.maxExceptions ? T.maxExceptions : 1;
-			std::vector<uint64_t> img;
-			img.insert( img.end(), T.charMask.begin(), T.charMask.begin() + (size_t)sp*T.nofClasses*64);
-			c->ldsAccept = (uint32_t)img.size(); img.insert( img.end(), T.acceptMask.begin(), T.acceptMask.begin() + (size_t)sp*CTX_COUNT*64);
-			c->ldsStart = (uint32_t)img.size(); img.insert( img.end(), T.startMask.begin(), T.startMask.begin() + (size_t)sp*CTX_COUNT*64);
-			c->ldsShift = (uint32_t)img.size(); img.insert( img.end(), T.shiftDst.begin(), T.shiftDst.begin() + (size_t)sp*64);
-			c->ldsSelf = (uint32_t)img.size(); img.insert( img.end(), T.selfLoop.begin(), T.selfLoop.begin() + (size_t)sp*64);
-			c->ldsExSrc = (uint32_t)img.size(); img.insert( img.end(), T.exSrc.begin(), T.exSrc.begin() + (size_t)sp*maxEx*64);
-			c->ldsExDst = (uint32_t)img.size(); img.insert( img.end(), T.exDst.begin(), T.exDst.begin() + (size_t)sp*maxEx*64);
-			if (img.empty()) img.push_back( 0);
-			size_t bytes = img.size()*8;
-			c->dScanImage.upload( img.data(), bytes);
-			if (bytes <= 144*1024 && sp <= 8)
-			{
-				c->ldsWords = (uint32_t)img.size();
-				// as many workgroups per CU as copies of the image fit into the 160 KB of LDS, sharing the waves
-				// the register budget allows (5 per SIMD up to 2 passes, 4 beyond; two 10-wave workgroups of the
-				// 3-pass instance at 96 registers were measured not to share a CU)
-				const unsigned maxWaves = sp <= 2 ? 20u : 16u;
-				unsigned maxCopies = (unsigned)((160*1024 - 1024) / (bytes ? bytes : 1));
-				if (maxCopies < 1) maxCopies = 1;
-				if (maxCopies > 5) maxCopies = 5;
-				// waves per workgroup in multiples of 4 (one per SIMD): workgroups of 6 or 10 waves load the four
-				// SIMDs unevenly and the next workgroup does not fit beside them (measured: 3 x 6 waves of the
-				// 2-pass instance ran at the speed of 10-12 resident waves)
-				unsigned best = 0, wpb = 4;
-				for (unsigned cp=maxCopies; cp>=1; --cp)
-				{
-					unsigned wv = (maxWaves / cp) & ~3u;
-					if (wv > 16) wv = 16;
-					if (wv * cp > best) { best = wv * cp; wpb = wv; }
-				}
-				c->blockThreads = 64 * wpb;
-			}
-			else { c->ldsWords = 0; c->blockThreads = 256; }
-		}
+		c->dTableImage.upload( c->images.all.words.data(), c->images.all.words.size()*8);
+		c->dScanImage.upload( c->images.scan.words.data(), c->images.scan.words.size()*8);
+		if (c->images.wordsKernel) c->dWordsImage.upload( c->images.words.words.data(), c->images.words.words.size()*8);
 		c->dCounters.alloc( L1C_ALLOC*sizeof(uint64_t));
-		uint32_t npat = (uint32_t)T.patterns.size();
-		c->queueCap = 4096 > 2*npat+256 ? 4096 : 2*npat+256;
 		c->own.create( device);
 		c->evStart.create(); c->evMid.create(); c->evWords.create(); c->evStop.create();
 		return c;
@@ -301,7 +254,7 @@ int sp_lexer_ctx_grow_arena( sp_lexer_ctx_t* c)
 	if (queue)
 	{
 		if (c->queueMul >= 4096) { c->lasterror = "report queue at its maximum size (4096 x 1/16 reports per text byte)"; return SP_ERR_INVALID; }
-		c->queueCap *= 2; c->queueMul *= 2;
+		c->queueMul *= 2;
 	}
 	return SP_OK;
 }
@@ -317,34 +270,17 @@ void allocLexBatch( sp_lex_batch_t* out, size_t ndocs, uint64_t nlexems)
 	out->doc_status = hostArray<int32_t>( ndocs+1);
 	out->lexems = hostArray<sp_lexem_t>( nlexems+1);
 }
-enum {SPA_L1_POST_WAVES_PER_EU_DEFAULT=6};
 void launchLex( sp_lexer_ctx* c, const void* d_text, const void* d_doc_offsets, size_t ndocs, size_t nbytes, hipStream_t stream)
 {
 	HIP_CHECK( hipSetDevice( c->device));
 	const LexTables& T = c->inst->compiler.tables();
-	// documents longer than a chunk are scanned as several units (SPA_L1_CHUNK_BYTES: tests)
-	uint32_t chunkBytes = 32768;		// (12288 x 64 KiB documents: scan 102.4 ms unchunked, 95.9 / 95.5 / 97.0 ms at 32 / 16 / 4 KiB chunks)
-	// (an expression that can stay live across blanks -- <[^>]*>, ".*" with DOTALL -- fails the warm-up proof of nearly every chunk:
-	//  such tables are scanned document by document, the chunked pass would only be thrown away)
-	if (!T.lanesOk) chunkBytes = 0xFFFFFFC0u;
-	if (const char* e = getenv( "SPA_L1_CHUNK_BYTES")) { long v = atol( e); if (v >= 64 && v <= (1l << 30)) chunkBytes = (uint32_t)v & ~63u; }
-	const uint64_t maxUnits = (uint64_t)ndocs + (uint64_t)nbytes / chunkBytes + 2;
-	if (maxUnits >= 0xFFFFFFFFull) throw std::runtime_error( "too many scan units in one batch");
-	// scan kernel: one wave per unit up to what the device holds (a wave without a unit leaves at once)
-	unsigned wavesWanted = (unsigned)((maxUnits < (uint64_t)c->numCUs*20) ? maxUnits : (uint64_t)c->numCUs*20);
-	const unsigned wpb = c->blockThreads / 64;
-	unsigned nblocks = (wavesWanted + wpb-1) / wpb;
-	if (nblocks == 0) nblocks = 1;
-	// the post-processing kernel (and the approximate-matching kernel) has its own number of waves: one event array each
-	unsigned postPerCU = 4*SPA_L1_POST_WAVES_PER_EU_DEFAULT;	// (matches the register budget of the kernel, l1_kernel.hip)
-	if (const char* e = getenv( "SPA_L1_POST_WAVES_PER_CU")) { int v = atoi( e); if (v >= 1 && v <= 40) postPerCU = (unsigned)v; }
-	unsigned nwaves = (unsigned)((ndocs < (size_t)c->numCUs*postPerCU) ? ndocs : (size_t)c->numCUs*postPerCU);
-	nwaves = (nwaves + 3u) & ~3u;
-	if (nwaves == 0) nwaves = 4;
+	const bool wordsKernel = c->images.wordsKernel;
+	L1LaunchPlan plan = planL1Launch( T, c->images, c->numCUs, ndocs, nbytes, L1Switches::fromEnv());
+	const uint64_t maxUnits = plan.maxUnits;
 	uint64_t perWaveWords = 4ull*c->eventCap;		// the handler's event array (the report queue is per document: dQueue)
-	const ArenaWaves aw = arenaWaves( perWaveWords*4, nwaves, (size_t)c->numCUs*postPerCU, 4);
-	nwaves = aw.run;
-	if (c->arena.count < nwaves || c->arenaWords != perWaveWords)
+	const ArenaWaves aw = arenaWaves( perWaveWords*4, plan.postWaves, plan.postSlots, 4);
+	plan.postWaves = aw.run;
+	if (c->arena.count < plan.postWaves || c->arenaWords != perWaveWords)
 	{
 		c->arena.realloc( aw.alloc, perWaveWords*4);
 		c->arenaWords = perWaveWords;
@@ -363,8 +299,8 @@ void launchLex( sp_lexer_ctx* c, const void* d_text, const void* d_doc_offsets, 
 		size_t freeB = 0, totalB = 0;
 		if (hipMemGetInfo( &freeB, &totalB) == hipSuccess)
 		{
-			const uint64_t have = (uint64_t)c->dQueue.bytes + (c->wordsKernel ? (uint64_t)c->dWordQueue.bytes : 0);
-			const uint64_t want = qbytes * (c->wordsKernel ? 2 : 1);
+			const uint64_t have = (uint64_t)c->dQueue.bytes + (wordsKernel ? (uint64_t)c->dWordQueue.bytes : 0);
+			const uint64_t want = qbytes * (wordsKernel ? 2 : 1);
 			if (want > have && want - have > (uint64_t)(0.8 * (double)freeB))
 			{
 				char msg[ 200];
@@ -375,7 +311,7 @@ void launchLex( sp_lexer_ctx* c, const void* d_text, const void* d_doc_offsets, 
 		}
 	}
 	c->dQueue.reserve( ((((uint64_t)nbytes * c->queueMul) >> 4) + 64ull*(maxUnits+2)) * 16);
-	if (c->wordsKernel)
+	if (wordsKernel)
 	{
 		c->dWordQueue.reserve( ((((uint64_t)nbytes * c->queueMul) >> 4) + 64ull*(maxUnits+2)) * 16);
 		c->dWordCount.reserve( (maxUnits+1)*sizeof(uint32_t));
@@ -391,9 +327,6 @@ void launchLex( sp_lexer_ctx* c, const void* d_text, const void* d_doc_offsets, 
 	L1Params P;
 	std::memset( &P, 0, sizeof(P));
 	P.byteClass = (const uint8_t*)c->dByteClass.ptr; P.classCtx = (const uint8_t*)c->dClassCtx.ptr;
-	P.charMask = (const uint64_t*)c->dCharMask.ptr; P.startMask = (const uint64_t*)c->dStartMask.ptr;
-	P.acceptMask = (const uint64_t*)c->dAcceptMask.ptr; P.shiftDst = (const uint64_t*)c->dShiftDst.ptr;
-	P.selfLoop = (const uint64_t*)c->dSelfLoop.ptr; P.exSrc = (const uint64_t*)c->dExSrc.ptr; P.exDst = (const uint64_t*)c->dExDst.ptr;
 	P.exCount = (const uint32_t*)c->dExCount.ptr;
 	P.patOfBit = (const uint32_t*)c->dPatOfBit.ptr; P.patterns = (const DevLexPattern*)c->dPatterns.ptr;
 	P.symbols = (const DevSymbol*)c->dSymbols.ptr; P.symbolText = (const uint8_t*)c->dSymbolText.ptr;
@@ -404,7 +337,7 @@ void launchLex( sp_lexer_ctx* c, const void* d_text, const void* d_doc_offsets, 
 	P.nofPasses = T.nofPasses; P.nofClasses = T.nofClasses; P.maxExceptions = T.maxExceptions ? T.maxExceptions : 1;
 	P.nofPatterns = (uint32_t)T.patterns.size();
 	P.text = (const uint8_t*)d_text; P.docOffsets = (const uint64_t*)d_doc_offsets; P.ndocs = (uint32_t)ndocs;
-	P.arenaBase = (uint32_t*)c->arena.ptr(); P.arenaWords = perWaveWords; P.queueCap = c->queueCap; P.eventCap = c->eventCap;
+	P.arenaBase = (uint32_t*)c->arena.ptr(); P.arenaWords = perWaveWords; P.eventCap = c->eventCap;
 	P.counters = (uint64_t*)c->dCounters.ptr; P.lexems = (uint32_t*)c->lexems.ptr(); P.lexemCapacity = c->lexems.count;
 	P.docRange = (uint64_t*)c->dDocRange.ptr; P.docStatus = (int32_t*)c->dDocStatus.ptr;
 	P.reportQueue = (uint32_t*)c->dQueue.ptr; P.reportCount = (uint32_t*)c->dReportCount.ptr; P.queueMul = c->queueMul;
@@ -413,51 +346,36 @@ void launchLex( sp_lexer_ctx* c, const void* d_text, const void* d_doc_offsets, 
 	P.cpBlocks = T.cpBlocks.empty() ? 0 : (const uint16_t*)c->dCpBlocks.ptr; P.cpPages = (const uint8_t*)c->dCpPages.ptr;
 	P.ucp = T.ucp ? 1u : 0u;
 	P.nullable = T.nullable.empty() ? 0 : (const DevNullable*)c->dNullable.ptr; P.nofNullable = (uint32_t)T.nullable.size();
-	P.unitStart = (uint32_t*)c->dUnitStart.ptr; P.chunkBytes = chunkBytes; P.docSequential = (uint32_t*)c->dDocSequential.ptr; P.sequentialPass = 0;
+	P.unitStart = (uint32_t*)c->dUnitStart.ptr; P.chunkBytes = plan.chunkBytes; P.docSequential = (uint32_t*)c->dDocSequential.ptr; P.sequentialPass = 0;
 	P.splitPatterns = (T.patterns.size() != c->inst->compiler.nofDefinitions()) ? 1u : 0u;
-	P.shapes = (const DevShape*)c->dShapes.ptr; P.shapePats = (const uint32_t*)c->dShapePats.ptr; P.shapeMask = (uint32_t)T.shapes.size()-1;
+	P.shapePats = (const uint32_t*)c->dShapePats.ptr; P.shapeMask = (uint32_t)T.shapes.size()-1;
 	P.nofShapeVariants = (uint32_t)T.shapeVariants.size();
 	for (size_t i=0; i<T.shapeVariants.size() && i<SHAPE_MAXVARIANTS; ++i) P.shapeVariants[ i] = T.shapeVariants[ i];
-	P.shapeFpOffset = c->imgShapeFp; P.shapeSalt = T.shapeSalt;
-	P.wordQueue = (uint32_t*)c->dWordQueue.ptr; P.wordCount = (uint32_t*)c->dWordCount.ptr; P.wordsKernel = c->wordsKernel ? 1u : 0u;
+	P.shapeSalt = T.shapeSalt;
+	P.wordQueue = (uint32_t*)c->dWordQueue.ptr; P.wordCount = (uint32_t*)c->dWordCount.ptr; P.wordsKernel = wordsKernel ? 1u : 0u;
 	HIP_CHECK( hipEventRecord( c->evStart, stream));
 	// the post-processing kernel, which walks the scanned patterns backwards, reads the image of all passes from global memory ...
 	P.tableImage = (const uint64_t*)c->dTableImage.ptr; P.ldsWords = 0;
-	P.ldsChar = 0; P.ldsAccept = c->imgAccept; P.ldsStart = c->imgStart; P.ldsShift = c->imgShift; P.ldsSelf = c->imgSelf;
-	P.ldsExSrc = c->imgExSrc; P.ldsExDst = c->imgExDst;
+	c->images.all.apply( P);
+	P.scanWords = plan.scanWords;
 	// ... the scan kernel stages the image of the passes it runs in LDS
 	L1Params PS = P;
-	PS.nofPasses = c->wordsKernel ? T.scanPasses : T.nofPasses;
-	PS.tableImage = (const uint64_t*)c->dScanImage.ptr; PS.ldsWords = c->ldsWords;
-	PS.ldsAccept = c->ldsAccept; PS.ldsStart = c->ldsStart; PS.ldsShift = c->ldsShift; PS.ldsSelf = c->ldsSelf;
-	PS.ldsExSrc = c->ldsExSrc; PS.ldsExDst = c->ldsExDst;
-	if (PS.nofPasses == 0) HIP_CHECK( hipMemsetAsync( c->dReportCount.ptr, 0, (maxUnits+1)*sizeof(uint32_t), stream));
-	// words kernel: a wave per unit, workgroups of 16 (12) waves that share one LDS copy of ITS image -- the passes behind the scanned ones + the shape table -- when it fits
+	PS.nofPasses = plan.scanPasses;
+	PS.tableImage = (const uint64_t*)c->dScanImage.ptr; PS.ldsWords = plan.scanLdsWords;
+	c->images.scan.apply( PS);
+	PS.shapeFpOffset = P.shapeFpOffset;		// (the scan image holds no shape table and the scan kernels read none: the value they have always been passed)
+	if (plan.scanPasses == 0) HIP_CHECK( hipMemsetAsync( c->dReportCount.ptr, 0, (maxUnits+1)*sizeof(uint32_t), stream));
+	// ... the words kernel ITS image -- the passes behind the scanned ones + the shape table -- when it fits
 	L1Params PW = P;
-	// (16 waves per workgroup while the image leaves room for their rings and run ends, else 12; SPA_L1_WORD_WAVES=12: A/B runs)
-	unsigned wordWaves = ((size_t)c->wWords*8 + (size_t)L1_WORD_WAVES_SMALL*L1_WORDS_LDS_PER_WAVE <= 160*1024 && !getenv( "SPA_L1_WORD_WAVES")) ? (unsigned)L1_WORD_WAVES_SMALL : (unsigned)L1_WORD_WAVES;
-	if (c->wordsKernel)
+	if (wordsKernel)
 	{
 		PW.tableImage = (const uint64_t*)c->dWordsImage.ptr;
-		PW.ldsChar = c->wChar; PW.ldsAccept = c->wAccept; PW.ldsStart = c->wStart; PW.ldsShift = c->wShift; PW.ldsSelf = c->wSelf;
-		PW.ldsExSrc = c->wExSrc; PW.ldsExDst = c->wExDst; PW.shapeFpOffset = c->wShapeFp;
+		c->images.words.apply( PW);
 	}
-	PW.ldsWords = ((size_t)c->wWords*8 + (size_t)wordWaves*L1_WORDS_LDS_PER_WAVE <= 160*1024 && T.nofShapes) ? c->wWords : 0u;
-	unsigned wordBlocks = (unsigned)((maxUnits + wordWaves-1) / wordWaves < (uint64_t)c->numCUs ? (maxUnits + wordWaves-1) / wordWaves : (uint64_t)c->numCUs);
-	if (wordBlocks == 0) wordBlocks = 1;
-	// (scanWords = 0 keeps the batch off the lane-per-stream scan kernel: an expression that can stay live across blanks would
-	//  fail the warm-up proof of most pieces, SPA_L1_NO_LANES: tests)
-	P.postClusters = getenv( "SPA_L1_POST_SEQ") ? 0u : 1u;		// (SPA_L1_POST_SEQ: tests and A/B runs, one report after the other)
-	P.scanWords = PS.scanWords = PW.scanWords = (c->wordsKernel && T.lanesOk && !getenv( "SPA_L1_NO_LANES")) ? T.scanWords : 0u;
-	// lane-per-stream scan kernel (a few automaton words left to scan): a wave per unit, workgroups of four waves
-	unsigned laneBlocks = (unsigned)((maxUnits + 3) / 4 < (uint64_t)c->numCUs*4 ? (maxUnits + 3) / 4 : (uint64_t)c->numCUs*4);
-	if (laneBlocks == 0) laneBlocks = 1;
-	HIP_CHECK( launchL1Lex( PS, PW, P, nblocks, c->blockThreads, laneBlocks, wordBlocks, wordWaves, nwaves, stream, c->evMid, c->evWords));
-	c->wordsKernelName = !c->wordsKernel || P.nofApprox ? "(none)" : (wordWaves == (unsigned)L1_WORD_WAVES_SMALL ? "spa_l1_words_kernel_w16" : "spa_l1_words_kernel");
-	if (P.nofApprox) std::snprintf( c->scanKernel, sizeof(c->scanKernel), "spa_l1_approx_kernel");
-	else if (l1ScanByLanes( PS, P)) std::snprintf( c->scanKernel, sizeof(c->scanKernel), "spa_l1_scan_lanes_kernel");
-	else if (PS.nofPasses == 0) std::snprintf( c->scanKernel, sizeof(c->scanKernel), "(none)");
-	else std::snprintf( c->scanKernel, sizeof(c->scanKernel), "spa_l1_scan_kernel_p%u", PS.nofPasses <= 8 ? PS.nofPasses : PS.nofPasses <= 16 ? 16u : 32u);
+	PW.ldsWords = plan.wordLdsWords;
+	P.postClusters = plan.postClusters;
+	HIP_CHECK( launchL1Lex( plan, PS, PW, P, stream, c->evMid, c->evWords));
+	c->plan = plan;
 	HIP_CHECK( hipEventRecord( c->evStop, stream));
 	c->evValid = true; c->lastStream = stream; c->lastNdocs = ndocs;
 }
@@ -512,12 +430,12 @@ int sp_lexer_ctx_last_kernel_ms_split( sp_lexer_ctx_t* c, double* scan_ms, doubl
 // the scan kernel the last launch went through (bench.py prices and names the kernel that ran)
 const char* sp_lexer_ctx_scan_kernel_name( const sp_lexer_ctx_t* c)
 {
-	return c->scanKernel;
+	return c->plan.scanKernelName;
 }
 
 const char* sp_lexer_ctx_words_kernel_name( const sp_lexer_ctx_t* c)
 {
-	return c->wordsKernelName;
+	return c->plan.wordsKernelName;
 }
 
 // the same with the words kernel on its own (round 3: automaton scan | literals + word shapes | start of match + handler + ordinal positions)

@@ -1,8 +1,9 @@
-// Launch parameters of the level-1 lexer kernel (shared by l1_kernel.hip and capi_l1.cpp).
+// Launch parameters of the level-1 lexer kernels (shared by l1_kernel.hip, l1_image.cpp and capi_l1.cpp).  No HIP header: the
+// host-only sources that include it compile without the runtime.
 #ifndef SPA_L1_DEVICE_H
 #define SPA_L1_DEVICE_H
 #include <stdint.h>
-#include <hip/hip_runtime_api.h>
+#include <stddef.h>
 #include "l1_tables.h"
 
 namespace spa {
@@ -14,19 +15,25 @@ enum {L1C_LEXEMS=0, L1C_BYTES=1, L1C_RAW=2, L1C_FAILED=3, L1C_COUNT=8, L1C_CURSO
 
 // words kernel: waves of a workgroup (12, or 16 while its table image leaves room), static LDS per wave (ring + run ends); the image takes the rest of the 160 KB
 enum {L1_WORD_WAVES=12, L1_WORD_WAVES_SMALL=16, L1_WORDS_LDS_PER_WAVE=512*2 + 96*5*4};
+// LDS of a CU; the largest table image the scan kernel stages (the rest is the waves' own); static-LDS limit: a launch with more
+// dynamic LDS than this needs hipFuncSetAttribute first
+enum {L1_CU_LDS_BYTES=160*1024, L1_SCAN_IMAGE_MAX_BYTES=144*1024, L1_STATIC_LDS_LIMIT=65536};
+enum {L1_POST_WAVES=4};		// waves of a workgroup of the post-processing kernel
 
 struct L1Params
 {
 	// compiled tables (read only)
 	const uint8_t* byteClass;	// 256
 	const uint8_t* classCtx;	// nofClasses
-	const uint64_t* charMask;	// [pass][class][64]
-	const uint64_t* startMask;	// [pass][4][64]
-	const uint64_t* acceptMask;	// [pass][4][64]
-	const uint64_t* shiftDst;	// [pass][64]
-	const uint64_t* selfLoop;	// [pass][64]
-	const uint64_t* exSrc;		// [pass][maxExceptions][64]
-	const uint64_t* exDst;
+	// Seven slots nothing reads, left null (once the tables one by one: the kernels read them through tableImage only).  They
+	// keep their place for the same reason as the two layout slots below.
+	const uint64_t* _table0;
+	const uint64_t* _table1;
+	const uint64_t* _table2;
+	const uint64_t* _table3;
+	const uint64_t* _table4;
+	const uint64_t* _table5;
+	const uint64_t* _table6;
 	const uint32_t* exCount;	// [pass]
 	// Two unused slots, kept on purpose: with them the 3-pass instance runs 6% faster (115 vs 122 ms on half a
 	// bench step, same box, three runs) -- the offsets of the fields behind them decide how the compiler groups
@@ -54,7 +61,7 @@ struct L1Params
 	// per-wave working memory
 	uint32_t* arenaBase;
 	uint64_t arenaWords;		// words per wave
-	uint32_t queueCap;		// (unused since the kernels were split)
+	uint32_t _queueCap;		// (nothing reads it since the kernels were split; left 0)
 	uint32_t eventCap;		// event array records (4 words each)
 	// hand-over between the scan kernel and the post-processing kernel: the raw reports of document d, 16 B each,
 	// at reportQueue[ 4*qbase(d) ..) with qbase(d) = (begin(d)*queueMul >> 4) + 64*d -- room for queueMul/16 reports
@@ -89,7 +96,7 @@ struct L1Params
 	// words kernel (round 3): whole-word literals and word shapes (l1_tables.h) are found where runs of word characters end, by a
 	// kernel of its own with a lane per byte; its reports of unit u -- start already known, (end offset, pattern) order, records
 	// of candidates that did not confirm marked L1_DEAD_FLAG -- lie at wordQueue[ 4*queueBase(u) ..), wordCount[u] of them
-	const DevShape* shapes; const uint32_t* shapePats;
+	const DevShape* _shapes /*nothing reads it (the kernel probes the compact table at shapeFpOffset); left null*/; const uint32_t* shapePats;
 	uint32_t shapeMask, nofShapeVariants;
 	uint32_t shapeVariants[ SHAPE_MAXVARIANTS];
 	uint32_t* wordQueue;
@@ -102,11 +109,10 @@ struct L1Params
 	uint32_t postClusters;		// 1: the handler runs a cluster of reports per lane (postDocumentClusters); 0: one report after the other
 };
 
-// ---- host entry points of l1_kernel.hip
-// true when the batch goes through the lane-per-stream scan kernel
-bool l1ScanByLanes( const L1Params& PS, const L1Params& P);
-// enqueue scan, words and post-processing kernels (PS, PW, P: their parameters); the two events are recorded between them
-hipError_t launchL1Lex( const L1Params& PS, const L1Params& PW, const L1Params& P, unsigned nblocks, unsigned nthreads, unsigned laneBlocks, unsigned wordBlocks, unsigned wordWaves, unsigned postWaves, hipStream_t stream, hipEvent_t betweenKernels, hipEvent_t afterWords);
+// The layout is part of the kernels' speed (see the note on the layout slots): no field is added, removed, resized or moved
+// without a measurement.
+static_assert( sizeof(L1Params) == 536, "L1Params changed its size");
+static_assert( offsetof(L1Params,patOfBit) == 96 && offsetof(L1Params,approx) == 336 && offsetof(L1Params,postClusters) == 532, "L1Params changed its layout");
 
 } // namespace
 #endif

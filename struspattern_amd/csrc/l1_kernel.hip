@@ -2590,91 +2590,106 @@ extern "C" __global__ __launch_bounds__(64*POST_WAVES) SPA_L1_POST_OCC4 void spa
 extern "C" __global__ __launch_bounds__(64*POST_WAVES) SPA_L1_POST_OCC4 void spa_l1_post_kernel_ch( L1Params P) { postDocuments<false,false,true>( P); }
 extern "C" __global__ __launch_bounds__(64*POST_WAVES) SPA_L1_POST_OCC void spa_l1_post_kernel_cp( L1Params P) { postDocuments<false,true,true>( P); }
 
+// ---- host part: the launch of a batch, as its plan says (l1_image.hpp)
+#include <cstring>
+#include "l1_launch.h"
+
 namespace spa {
-// PS: the parameters of the scan kernel (its table image holds the scanned passes only; nofPasses = 0: nothing to scan);
-// PW: of the words kernel (the passes it walks + the shape table, in LDS when they fit; offsets biased); P: of the other kernels (all passes, read from global memory)
-bool l1ScanByLanes( const L1Params& PS, const L1Params& P)
+static_assert( (int)POST_WAVES == (int)L1_POST_WAVES, "workgroup size of the post-processing kernel");
+
+namespace {
+typedef const void* L1Kernel;
+// The scan instances: `plain` for batches of whole documents, `ch` for batches with documents scanned in chunks and for the
+// sequential re-scan, `cp` for tables with classes by code point or empty matches.
+struct ScanInstance { unsigned passes; L1Kernel plain, ch, cp; unsigned maxThreads; const char* name; };
+#define SPA_L1_SCAN_INSTANCE( N, T) { N, (L1Kernel)spa_l1_scan_kernel_p##N, (L1Kernel)spa_l1_scan_kernel_p##N##_ch, (L1Kernel)spa_l1_scan_kernel_p##N##_cp, T, "spa_l1_scan_kernel_p" #N }
+const ScanInstance g_scanInstances[] = {
+	SPA_L1_SCAN_INSTANCE( 1, 1024), SPA_L1_SCAN_INSTANCE( 2, 1024), SPA_L1_SCAN_INSTANCE( 3, 1024), SPA_L1_SCAN_INSTANCE( 4, 1024),
+	SPA_L1_SCAN_INSTANCE( 5, 1024), SPA_L1_SCAN_INSTANCE( 6, 1024), SPA_L1_SCAN_INSTANCE( 7, 1024), SPA_L1_SCAN_INSTANCE( 8, 1024),
+	SPA_L1_SCAN_INSTANCE( 16, 256), SPA_L1_SCAN_INSTANCE( 32, 256)};
+#undef SPA_L1_SCAN_INSTANCE
+// the instance that runs `passes` passes (1..32)
+const ScanInstance& scanInstance( unsigned passes) { return g_scanInstances[ passes <= 8 ? passes-1 : passes <= 16 ? 8 : 9]; }
+
+// one launch; more dynamic LDS than the static limit has to be allowed first
+hipError_t launch( L1Kernel kernel, unsigned grid, unsigned threads, size_t lds, hipStream_t stream, const L1Params& params)
 {
-	return PS.nofPasses == 1 && PS.scanWords >= 1 && PS.scanWords <= 4 && PS.reportsOrdered && !P.cpBlocks && !P.nofNullable && PS.ldsWords && (size_t)PS.ldsWords * 8 <= 65536;
+	if (lds > L1_STATIC_LDS_LIMIT)
+	{
+		hipError_t e = hipFuncSetAttribute( kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+		if (e != hipSuccess) return e;
+	}
+	void* args[ 1] = {(void*)&params};
+	return hipLaunchKernel( kernel, dim3( grid), dim3( threads), args, lds, stream);
+}
 }
 
-hipError_t launchL1Lex( const L1Params& PS, const L1Params& PW, const L1Params& P, unsigned nblocks, unsigned nthreads, unsigned laneBlocks, unsigned wordBlocks, unsigned wordWaves, unsigned postWaves, hipStream_t stream, hipEvent_t betweenKernels, hipEvent_t afterWords)
+hipError_t launchL1Lex( const L1LaunchPlan& plan, const L1Params& PS, const L1Params& PW, const L1Params& P, hipStream_t stream, hipEvent_t betweenKernels, hipEvent_t afterWords)
 {
-	if (P.nofApprox)
+	hipError_t e;
+	if (plan.route == L1_ROUTE_APPROX)
 	{
 		// approximate literal table: one kernel, one wave per workgroup
-		hipLaunchKernelGGL( spa_l1_approx_kernel, dim3( postWaves), dim3( 64), 0, stream, P);
-		hipError_t e = hipGetLastError();
+		hipLaunchKernelGGL( spa_l1_approx_kernel, dim3( plan.postWaves), dim3( 64), 0, stream, P);
+		e = hipGetLastError();
 		if (e != hipSuccess) return e;
 		if (betweenKernels) { e = hipEventRecord( betweenKernels, stream); if (e != hipSuccess) return e; }
 		return afterWords ? hipEventRecord( afterWords, stream) : hipSuccess;
 	}
-	const size_t lds = (size_t)PS.ldsWords * 8;
+	const size_t lds = plan.scanLdsBytes();
 	// the units of the batch (chunks of long documents), then BOTH sets of instances: which one a batch needs is known on
 	// the device only (classes by code point: here; chunked documents: after the units kernel) -- the other one leaves at once
 	hipLaunchKernelGGL( spa_l1_units_kernel, dim3( 1), dim3( 64), 0, stream, P);
-	hipError_t e = hipGetLastError();
+	e = hipGetLastError();
 	if (e != hipSuccess) return e;
 	L1Params S = PS;
 	S.sequentialPass = 1;
-#define SPA_L1_LAUNCH_ONE( KERNEL, ARGS) do { \
-	if (lds > 65536) { e = hipFuncSetAttribute( (const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (e != hipSuccess) return e; } \
-	hipLaunchKernelGGL( KERNEL, dim3( nblocks), dim3( nthreads), lds, stream, ARGS); } while (0)
-#define SPA_L1_LAUNCH( N) do { \
-	if (P.cpBlocks || P.nofNullable) { SPA_L1_LAUNCH_ONE( spa_l1_scan_kernel_##N##_cp, PS); SPA_L1_LAUNCH_ONE( spa_l1_scan_kernel_##N##_cp, S); } \
-	else { SPA_L1_LAUNCH_ONE( spa_l1_scan_kernel_##N, PS); SPA_L1_LAUNCH_ONE( spa_l1_scan_kernel_##N##_ch, PS); SPA_L1_LAUNCH_ONE( spa_l1_scan_kernel_##N##_ch, S); } } while (0)
-	// what is left to scan fits four automaton words: a lane per stream (scanUnitLanes); the documents a piece of which could not
-	// be joined go through the sequential pass of the one-pass instance behind it
-	const bool lanes = l1ScanByLanes( PS, P);
-	if (lanes)
+	if (plan.route == L1_ROUTE_LANES)
 	{
-		hipLaunchKernelGGL( spa_l1_scan_lanes_kernel, dim3( laneBlocks), dim3( 256), lds, stream, PS);
-		SPA_L1_LAUNCH_ONE( spa_l1_scan_kernel_p1_ch, S);
+		// a lane per stream (scanUnitLanes); the documents a piece of which could not be joined go through the sequential pass
+		// of the one-pass instance behind it
+		hipLaunchKernelGGL( spa_l1_scan_lanes_kernel, dim3( plan.laneGrid), dim3( 256), lds, stream, PS);
+		e = launch( scanInstance( 1).ch, plan.scanGrid, plan.scanThreads, lds, stream, S);
+		if (e != hipSuccess) return e;
 	}
-	else switch (PS.nofPasses)
+	else if (plan.route == L1_ROUTE_PASSES)
 	{
-		case 0: break;		// (nothing to scan: the caller has cleared the report counts)
-		case 1: SPA_L1_LAUNCH( p1); break;
-		case 2: SPA_L1_LAUNCH( p2); break;
-		case 3: SPA_L1_LAUNCH( p3); break;
-		case 4: SPA_L1_LAUNCH( p4); break;
-		case 5: SPA_L1_LAUNCH( p5); break;
-		case 6: SPA_L1_LAUNCH( p6); break;
-		case 7: SPA_L1_LAUNCH( p7); break;
-		case 8: SPA_L1_LAUNCH( p8); break;
-		default:
-			if (PS.nofPasses <= 16) SPA_L1_LAUNCH( p16);
-			else if (PS.nofPasses <= 32) SPA_L1_LAUNCH( p32);
-			else return hipErrorInvalidValue;
-	}
-	if (e != hipSuccess) return e;
-	e = hipGetLastError();
-	if (e != hipSuccess) return e;
-	if (betweenKernels) { e = hipEventRecord( betweenKernels, stream); if (e != hipSuccess) return e; }
-	if (P.wordsKernel)
-	{
-		// (its own copy of the parameters: its image staged in LDS when it fits, PW.ldsWords; 16 or 12 waves per workgroup by what the image leaves)
-		const size_t wlds = (size_t)PW.ldsWords * 8;
-		if (wordWaves == (unsigned)L1_WORD_WAVES_SMALL)
+		if (plan.scanPasses < 1 || plan.scanPasses > 32) return hipErrorInvalidValue;
+		const ScanInstance& si = scanInstance( plan.scanPasses);
+		// (the name reported is the plan's: the instance launched is the one of that name, or nothing is launched)
+		if (std::strcmp( si.name, plan.scanKernelName) != 0 || plan.scanThreads > si.maxThreads) return hipErrorInvalidValue;
+		if (plan.cp)
 		{
-			if (wlds > 65536) { e = hipFuncSetAttribute( (const void*)spa_l1_words_kernel_w16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds); if (e != hipSuccess) return e; }
-			hipLaunchKernelGGL( spa_l1_words_kernel_w16, dim3( wordBlocks), dim3( 64*L1_WORD_WAVES_SMALL), wlds, stream, PW);
+			if ((e = launch( si.cp, plan.scanGrid, plan.scanThreads, lds, stream, PS)) != hipSuccess) return e;
+			if ((e = launch( si.cp, plan.scanGrid, plan.scanThreads, lds, stream, S)) != hipSuccess) return e;
 		}
 		else
 		{
-			if (wlds > 65536) { e = hipFuncSetAttribute( (const void*)spa_l1_words_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)wlds); if (e != hipSuccess) return e; }
-			hipLaunchKernelGGL( spa_l1_words_kernel, dim3( wordBlocks), dim3( 64*L1_WORD_WAVES), wlds, stream, PW);
+			if ((e = launch( si.plain, plan.scanGrid, plan.scanThreads, lds, stream, PS)) != hipSuccess) return e;
+			if ((e = launch( si.ch, plan.scanGrid, plan.scanThreads, lds, stream, PS)) != hipSuccess) return e;
+			if ((e = launch( si.ch, plan.scanGrid, plan.scanThreads, lds, stream, S)) != hipSuccess) return e;
 		}
+	}
+	// (L1_ROUTE_NONE: nothing to scan, the caller has cleared the report counts)
+	e = hipGetLastError();
+	if (e != hipSuccess) return e;
+	if (betweenKernels) { e = hipEventRecord( betweenKernels, stream); if (e != hipSuccess) return e; }
+	if (plan.wordsKernel)
+	{
+		// (its own copy of the parameters: its image staged in LDS when it fits; 16 or 12 waves per workgroup by what the image leaves)
+		const bool small = plan.wordWaves == (unsigned)L1_WORD_WAVES_SMALL;
+		e = launch( small ? (L1Kernel)spa_l1_words_kernel_w16 : (L1Kernel)spa_l1_words_kernel, plan.wordGrid, 64*plan.wordWaves, (size_t)plan.wordLdsWords * 8, stream, PW);
+		if (e != hipSuccess) return e;
 		e = hipGetLastError();
 		if (e != hipSuccess) return e;
 	}
 	if (afterWords) { e = hipEventRecord( afterWords, stream); if (e != hipSuccess) return e; }
 	// its own number of waves (one event array each), in workgroups of POST_WAVES
-	if (P.cpBlocks || P.nofNullable) hipLaunchKernelGGL( spa_l1_post_kernel_cp, dim3( (postWaves + POST_WAVES-1) / POST_WAVES), dim3( 64*POST_WAVES), 0, stream, P);
+	if (plan.cp) hipLaunchKernelGGL( spa_l1_post_kernel_cp, dim3( plan.postGrid()), dim3( 64*POST_WAVES), 0, stream, P);
 	else
 	{
-		hipLaunchKernelGGL( spa_l1_post_kernel, dim3( (postWaves + POST_WAVES-1) / POST_WAVES), dim3( 64*POST_WAVES), 0, stream, P);
-		hipLaunchKernelGGL( spa_l1_post_kernel_ch, dim3( (postWaves + POST_WAVES-1) / POST_WAVES), dim3( 64*POST_WAVES), 0, stream, P);
+		hipLaunchKernelGGL( spa_l1_post_kernel, dim3( plan.postGrid()), dim3( 64*POST_WAVES), 0, stream, P);
+		hipLaunchKernelGGL( spa_l1_post_kernel_ch, dim3( plan.postGrid()), dim3( 64*POST_WAVES), 0, stream, P);
 	}
 	return hipGetLastError();
 }

@@ -9,7 +9,7 @@ from tests.l1_table_sim import CTX_EDGE, M64
 LANES = 64
 WARM = 256                  # bytes of warm-up before a piece (SPA_L1_LANE_WARM)
 DEFAULT_CHUNK = 32768       # launchLex
-MAX_LANE_WORDS = 4          # l1ScanByLanes
+MAX_LANE_WORDS = 4          # planL1Launch (l1_image.cpp): the lane-per-stream route
 
 
 def scan_words(t):
