@@ -244,7 +244,8 @@ int sp_matcher_ctx_match_lexed_device(sp_matcher_ctx_t* c, const void* d_lexems,
 typedef struct sp_match_finished_batch {
 	size_t ndocs;
 	void* d_results;             /* sp_result_t[]: document 0's results first; inside a document the order the
-	                                engine produced; `exclusive` applied; item_begin indexes d_items below */
+	                                engine produced, or with SP_FINISH_CANONICAL ascending by the tuple T below; `exclusive` applied;
+	                                item_begin indexes d_items below */
 	void* d_items;               /* sp_result_item_t[], in result order, no gaps */
 	void* d_doc_result_offsets;  /* uint64_t[ndocs+1]; a failed document (d_doc_status != 0) has an empty range */
 	void* d_doc_item_offsets;    /* uint64_t[ndocs+1] */
@@ -258,12 +259,36 @@ typedef struct sp_match_finished_batch {
  * context invalidates the finished state (not the buffers: a consumer still reading them orders itself as with any
  * stream work); it works on whatever the last launch sequence left, the reruns of sp_matcher_ctx_match_docs included. */
 int sp_matcher_ctx_batch_finish_device(sp_matcher_ctx_t* c, void* stream, sp_match_finished_batch_t* out);
+/* sp_matcher_ctx_batch_finish_device with flags; 0 is exactly that call, unknown bits return SP_ERR_INVALID.
+ * SP_FINISH_CANONICAL: inside each document the surviving results are ascending by the tuple
+ *   T(r) = ( ordpos, ordend, origseg, origpos, origendseg, origend,    words 1..6 of the record
+ *            handle,                                                   word 0
+ *            item_count,                                               word 8
+ *            result_format[r]                    (matchers with format strings only),
+ *            the 7*item_count words of r's items, in item order,
+ *            the 2*item_count words of item_format for those items     (with format strings only) )
+ * compared lexicographically, every word as an unsigned 32-bit value.  item_begin (word 7) is not part of the key: it is
+ * assigned after the sort, the block start plus the item counts of the results before.  Two results with equal T have
+ * byte-identical finished records, so the finished bytes are a function of the results alone and not of the engine that
+ * produced them: the same from the general, the LDS-resident and the join kernel (result-set mode).  Everything else is
+ * as without the flag: document order, failed documents empty, `exclusive` evaluated on the engine's order (the
+ * survivors are sorted), items gapless in result order, the same offsets and totals.  The working memory of the sort
+ * (24 bytes per result of the batch) belongs to the context and is allocated at the first finish that asks for it. */
+#define SP_FINISH_CANONICAL      1u
+int sp_matcher_ctx_batch_finish_device_ex(sp_matcher_ctx_t* c, void* stream, uint32_t flags, sp_match_finished_batch_t* out);
 /* plain copy of the finished buffers to the host (plus doc_stats and doc_status of the batch): NO regrouping and NO
  * elimination on the host; field for field what sp_matcher_ctx_batch_fetch returns for the same batch.
  * SP_ERR_INVALID when the last batch has not been finished. */
 int sp_matcher_ctx_finished_fetch(sp_matcher_ctx_t* c, sp_match_batch_t* out);
-/* durations of the three passes of the last finish in milliseconds (HIP events on its stream; waits for them) */
+/* durations of the three passes of the last finish in milliseconds (HIP events on its stream; waits for them);
+ * place_ms is the final placement, also after a canonical finish */
 int sp_matcher_ctx_last_finish_ms(sp_matcher_ctx_t* c, double* count_ms, double* offsets_ms, double* place_ms);
+/* duration of the sorting pass of the last finish, between offsets and place (HIP events on its stream); 0.0 after a
+ * finish without SP_FINISH_CANONICAL */
+int sp_matcher_ctx_last_finish_sort_ms(sp_matcher_ctx_t* c, double* sort_ms);
+/* diagnostics and tests: the largest number of results of one document that the canonical sort orders inside one
+ * workgroup's LDS, without a merge pass */
+uint32_t sp_matcher_finish_sort_tile(void);
 /* copies the results of the last device batch to the host, grouped by document (as sp_matcher_ctx_match_docs
  * returns them, `exclusive` elimination included) */
 int sp_matcher_ctx_batch_fetch(sp_matcher_ctx_t* c, sp_match_batch_t* out);

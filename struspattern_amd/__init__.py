@@ -16,6 +16,7 @@ __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", 
            "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
+SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
 SP_ERR_UNAVAILABLE = -6     # include/strus_pattern_amd.h: a value that does not exist for the context
 
 JOIN_OP = {"sequence": 0, "sequence_imm": 1, "sequence_struct": 2, "within": 3, "within_struct": 4, "any": 5, "and": 6}
@@ -165,11 +166,12 @@ class PatternMatcherContext:
             raise PatternError("device batch match failed (%d): %s" % (rc, self._err()))
         return out
 
-    def batchFinishDevice(self, stream=0):
+    def batchFinishDevice(self, stream=0, canonical=False):
         """finish the last batch on the device (asynchronous on `stream`): document order, `exclusive` applied, failed
-        documents empty, items without gaps; returns the device pointers (capi.SpMatchFinishedBatch)."""
+        documents empty, items without gaps; returns the device pointers (capi.SpMatchFinishedBatch).  canonical: the
+        results of a document in the order of SP_FINISH_CANONICAL, the same bytes from every engine."""
         out = capi.SpMatchFinishedBatch()
-        rc = self._L.sp_matcher_ctx_batch_finish_device(self._h, stream or None, ctypes.byref(out))
+        rc = self._L.sp_matcher_ctx_batch_finish_device_ex(self._h, stream or None, SP_FINISH_CANONICAL if canonical else 0, ctypes.byref(out))
         if rc != 0:
             raise PatternError("finishing the batch on the device failed (%d): %s" % (rc, self._err()))
         return out
@@ -184,6 +186,13 @@ class PatternMatcherContext:
         if self._L.sp_matcher_ctx_last_finish_ms(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(d)) != 0:
             raise PatternError("no timed finish")
         return a.value, b.value, d.value
+
+    def lastFinishSortMs(self):
+        """duration of the sorting pass of the last batchFinishDevice in milliseconds (0.0 without canonical=True)"""
+        a = ctypes.c_double(-1.0)
+        if self._L.sp_matcher_ctx_last_finish_sort_ms(self._h, ctypes.byref(a)) != 0:
+            raise PatternError("no timed finish")
+        return a.value
 
     def batchFetch(self, first_doc=None, ndocs=None):
         """host copy of the last device batch, grouped by document; with (first_doc, ndocs) only of

@@ -111,8 +111,11 @@ SIGNATURES = {
     "sp_matcher_ctx_batch_fetch": (ctypes.c_int, [c_vp, P(SpMatchBatch)]),
     "sp_matcher_ctx_batch_fetch_docs": (ctypes.c_int, [c_vp, ctypes.c_size_t, ctypes.c_size_t, P(SpMatchBatch)]),
     "sp_matcher_ctx_batch_finish_device": (ctypes.c_int, [c_vp, c_vp, P(SpMatchFinishedBatch)]),
+    "sp_matcher_ctx_batch_finish_device_ex": (ctypes.c_int, [c_vp, c_vp, c_u32, P(SpMatchFinishedBatch)]),
     "sp_matcher_ctx_finished_fetch": (ctypes.c_int, [c_vp, P(SpMatchBatch)]),
     "sp_matcher_ctx_last_finish_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_double)]),
+    "sp_matcher_ctx_last_finish_sort_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_matcher_finish_sort_tile": (c_u32, []),
     "sp_matcher_ctx_batch_counters": (ctypes.c_int, [c_vp, P(c_u64)]),
     "sp_matcher_ctx_last_kernel_ms": (ctypes.c_double, [c_vp]),
     "sp_matcher_ctx_kernel_kind": (ctypes.c_int, [c_vp]),

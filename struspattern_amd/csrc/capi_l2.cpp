@@ -151,7 +151,10 @@ struct sp_matcher_ctx
 		DeviceBuffer dResults, dItems, dResultFormat, dItemFormat, dDocResultOffsets, dDocItemOffsets, dTotals, dKept, dCovered, dCursor;
 		bool done = false;
 		hipStream_t stream = 0;
-		Event ev[ 4]; bool evValid = false;
+		Event ev[ 5]; bool evValid = false;	// [4]: between the sort and the placement of a canonical finish
+		bool canonical = false;
+		// working memory of the canonical order, allocated at the first finish that asks for it
+		DeviceBuffer dSortKeys[ 2], dSortIdx[ 2], dSortCursor;
 	} fin;
 	// single-document mode
 	struct SingleDoc
@@ -802,10 +805,16 @@ int sp_matcher_ctx_batch_counters( sp_matcher_ctx_t* c, uint64_t counters[8])
 }
 
 // ---- the last device batch finished on the device: document order, `exclusive` applied, items without gaps (l2_finish.h)
-int sp_matcher_ctx_batch_finish_device( sp_matcher_ctx_t* c, void* stream_, sp_match_finished_batch_t* out)
+int sp_matcher_ctx_batch_finish_device( sp_matcher_ctx_t* c, void* stream, sp_match_finished_batch_t* out)
+{ return sp_matcher_ctx_batch_finish_device_ex( c, stream, 0, out); }
+
+// flags: SP_FINISH_CANONICAL orders the results of every document by the tuple T of the header
+int sp_matcher_ctx_batch_finish_device_ex( sp_matcher_ctx_t* c, void* stream_, uint32_t flags, sp_match_finished_batch_t* out)
 {
 	if (out) std::memset( out, 0, sizeof(*out));
 	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (flags & ~(uint32_t)SP_FINISH_CANONICAL) throw std::runtime_error( "unknown finish flags");
+		const bool canonical = (flags & SP_FINISH_CANONICAL) != 0;
 		if (!c->haveBatch) throw std::runtime_error( "no batch to finish: no batch has run on this context");
 		hipStream_t stream = (hipStream_t)stream_;
 		HIP_CHECK( hipSetDevice( c->device));
@@ -829,13 +838,23 @@ int sp_matcher_ctx_batch_finish_device( sp_matcher_ctx_t* c, void* stream_, sp_m
 		if (!c->fin.dTotals.ptr) c->fin.dTotals.alloc( 2*sizeof(uint64_t));
 		if (!c->fin.dCursor.ptr) c->fin.dCursor.alloc( 2*sizeof(uint32_t));
 		if (exclusive) c->fin.dCovered.reserve( devResults+1);
-		hipEvent_t ev[ 4];
-		for (int i=0; i<4; ++i) { c->fin.ev[ i].create(); ev[ i] = c->fin.ev[ i]; }
+		if (canonical)
+		{
+			for (int i=0; i<2; ++i)
+			{
+				c->fin.dSortKeys[ i].reserve( (devResults+1)*sizeof(uint64_t));
+				c->fin.dSortIdx[ i].reserve( (devResults+1)*sizeof(uint32_t));
+			}
+			if (!c->fin.dSortCursor.ptr) c->fin.dSortCursor.alloc( sizeof(uint32_t));
+		}
+		hipEvent_t ev[ 5];
+		for (int i=0; i<5; ++i) { c->fin.ev[ i].create(); ev[ i] = c->fin.ev[ i]; }
 
 		// another stream than the batch's runs behind the batch (evStop closes every launch sequence, reruns included)
 		if (stream != c->lastStream) HIP_CHECK( hipStreamWaitEvent( stream, c->evStop, 0));
 		HIP_CHECK( hipMemsetAsync( c->fin.dCursor.ptr, 0, 2*sizeof(uint32_t), stream));
 		if (exclusive) HIP_CHECK( hipMemsetAsync( c->fin.dCovered.ptr, 0, devResults+1, stream));
+		if (canonical) HIP_CHECK( hipMemsetAsync( c->fin.dSortCursor.ptr, 0, sizeof(uint32_t), stream));
 		FinishParams F;
 		std::memset( &F, 0, sizeof(F));
 		F.results = (const uint32_t*)c->io.results.ptr(); F.items = (const uint32_t*)c->io.items.ptr();
@@ -849,9 +868,15 @@ int sp_matcher_ctx_batch_finish_device( sp_matcher_ctx_t* c, void* stream_, sp_m
 		F.docResultOffsets = (uint64_t*)c->fin.dDocResultOffsets.ptr; F.docItemOffsets = (uint64_t*)c->fin.dDocItemOffsets.ptr;
 		F.outResultFormat = (uint32_t*)c->fin.dResultFormat.ptr; F.outItemFormat = (uint32_t*)c->fin.dItemFormat.ptr;
 		F.totals = (uint64_t*)c->fin.dTotals.ptr;
+		if (canonical)
+		{
+			F.canonical = 1;
+			for (int i=0; i<2; ++i) { F.sortKeys[ i] = (uint64_t*)c->fin.dSortKeys[ i].ptr; F.sortIdx[ i] = (uint32_t*)c->fin.dSortIdx[ i].ptr; }
+			F.sortCursor = (uint32_t*)c->fin.dSortCursor.ptr;
+		}
 		c->fin.evValid = false;
 		HIP_CHECK( launchL2Finish( F, c->numCUs, stream, ev));
-		c->fin.evValid = true; c->fin.done = true; c->fin.stream = stream;
+		c->fin.evValid = true; c->fin.done = true; c->fin.stream = stream; c->fin.canonical = canonical;
 		if (out)
 		{
 			out->ndocs = ndocs;
@@ -898,10 +923,23 @@ int sp_matcher_ctx_last_finish_ms( sp_matcher_ctx_t* c, double* count_ms, double
 	*count_ms = *offsets_ms = *place_ms = -1.0;
 	if (!c->fin.evValid) return SP_ERR_INVALID;
 	if (hipEventSynchronize( c->fin.ev[ 3]) != hipSuccess) return SP_ERR_DEVICE;
-	double* ms[ 3] = {count_ms, offsets_ms, place_ms};
-	for (int i=0; i<3; ++i) if (!elapsedMs( c->fin.ev[ i], c->fin.ev[ i+1], *ms[ i])) return SP_ERR_DEVICE;
+	// (a canonical finish sorts between the offsets and the placement: the placement starts at ev[4] then)
+	if (!elapsedMs( c->fin.ev[ 0], c->fin.ev[ 1], *count_ms) || !elapsedMs( c->fin.ev[ 1], c->fin.ev[ 2], *offsets_ms)
+	||  !elapsedMs( c->fin.ev[ c->fin.canonical ? 4 : 2], c->fin.ev[ 3], *place_ms)) return SP_ERR_DEVICE;
 	return SP_OK;
 }
+
+// duration of the sorting pass of the last finish (0.0 after a finish without SP_FINISH_CANONICAL)
+int sp_matcher_ctx_last_finish_sort_ms( sp_matcher_ctx_t* c, double* sort_ms)
+{
+	*sort_ms = -1.0;
+	if (!c->fin.evValid) return SP_ERR_INVALID;
+	if (!c->fin.canonical) { *sort_ms = 0.0; return SP_OK; }
+	if (hipEventSynchronize( c->fin.ev[ 3]) != hipSuccess) return SP_ERR_DEVICE;
+	return elapsedMs( c->fin.ev[ 2], c->fin.ev[ 4], *sort_ms) ? SP_OK : SP_ERR_DEVICE;
+}
+
+uint32_t sp_matcher_finish_sort_tile(void) { return FINISH_SORT_TILE; }
 
 double sp_matcher_ctx_last_kernel_ms( sp_matcher_ctx_t* c) { return lastKernelMs( c); }
 

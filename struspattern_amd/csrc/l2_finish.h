@@ -5,6 +5,8 @@
 //   A  count   kept results and items of every document (with `exclusive`: the covered flags first)
 //   B  offsets exclusive prefix sums of the two per-document arrays, and the totals
 //   C  place   the survivors and their items (and format words) move to their final place
+// With P.canonical a sorting pass between B and C orders the survivors of every document by the tuple T of
+// include/strus_pattern_amd.h (SP_FINISH_CANONICAL), and C places through the sorted indices.
 // What the passes rely on, as copyOutBatch (capi_l2.cpp) does: the items of one document are ONE block in result order,
 // and every result's item_begin is that block's start plus the item counts of the results before it (all three rule
 // kernels write it so, for results without items too).
@@ -42,9 +44,19 @@ struct FinishParams
 	uint32_t* outResultFormat;
 	uint32_t* outItemFormat;
 	uint64_t* totals;		// results, items
+	// canonical order (SP_FINISH_CANONICAL): working memory of the sort, two buffers of entries parallel to outResults
+	uint32_t canonical;
+	uint64_t* sortKeys[ 2];		// ordpos << 32 | ordend
+	uint32_t* sortIdx[ 2];		// index of the result in its document's raw block
+	uint32_t* sortCursor;		// zeroed
 };
 
-// enqueue the passes; between them the events ev[0..3], if given (timing of the passes)
+// the most results of one document that the sort orders in one workgroup's LDS without a merge pass: 12 bytes an entry,
+// 48 KiB a tile, three workgroups on the 160 KiB of a CU
+enum { FINISH_SORT_TILE = 4096 };
+
+// enqueue the passes; between them the events ev[0..3], if given (timing of the passes); with P.canonical ev[4] between
+// the sort and the placement
 hipError_t launchL2Finish( const FinishParams& P, unsigned numCUs, hipStream_t stream, hipEvent_t* ev);
 
 } // namespace
