@@ -1149,6 +1149,9 @@ static __device__ __forceinline__ void installBatch( LR L, Wave& w, KP P, u32 kb
 					{
 						if ((tInfo[ j] & FTI_INSTALL) && tEv[ j] == pastEvent) fireLocal( sim, tInfo[ j], psord, plex, P.io.withItems);
 					}
+					// a replay that matches (cardinality 1) emits its result with the end of the REPLAYED event (cpp:954-965),
+					// while the batch below stages results that end at the key lexem: the general kernel takes the document
+					if (sim.flags & S_DONE) sim.flags |= S_ODD;
 					// a structure delimiter logged after the replayed event cancels the rule (cpp:1306-1321)
 					bool cancelled = false;
 #pragma unroll
