@@ -13,6 +13,7 @@
 #include <cstring>
 #include <set>
 #include <stdexcept>
+#include <utility>
 
 using namespace spa;
 
@@ -67,6 +68,18 @@ int encodeUtf8( uint32_t cp, unsigned char* b)
 	if (cp < 0x10000) { b[0] = (unsigned char)(0xE0 | (cp >> 12)); b[1] = (unsigned char)(0x80 | ((cp >> 6) & 0x3F)); b[2] = (unsigned char)(0x80 | (cp & 0x3F)); return 3; }
 	b[0] = (unsigned char)(0xF0 | (cp >> 18)); b[1] = (unsigned char)(0x80 | ((cp >> 12) & 0x3F));
 	b[2] = (unsigned char)(0x80 | ((cp >> 6) & 0x3F)); b[3] = (unsigned char)(0x80 | (cp & 0x3F)); return 4;
+}
+// lenient UTF-8 (the approximate-matching kernel's rule): a lead byte with all its continuation bytes is one character,
+// else the byte itself.  Returns the number of bytes taken at s[at]
+unsigned decodeUtf8Lenient( const unsigned char* s, size_t size, size_t at, uint32_t& cp)
+{
+	const unsigned char c = s[ at];
+	const unsigned want = (c >= 0xC2 && c <= 0xDF) ? 2 : (c >= 0xE0 && c <= 0xEF) ? 3 : (c >= 0xF0 && c <= 0xF4) ? 4 : 1;
+	cp = c;
+	if (want == 1 || at + want > size) return 1;
+	uint32_t v = c & (0xFFu >> (want+1));
+	for (unsigned i=1; i<want; ++i) { if ((s[ at+i] & 0xC0) != 0x80) return 1; v = (v << 6) | (s[ at+i] & 0x3F); }
+	cp = v; return want;
 }
 // `glue`: node put between the bytes of one character (empty tree = none)
 void splitUtf8( uint32_t lo, uint32_t hi, std::vector<Tree>& alts, const Tree& glue)
@@ -1008,7 +1021,7 @@ void LexCompiler::defineLexem( uint32_t id, const std::string& expression, uint3
 	if (level > 255) throw std::runtime_error( "level out of range, It must be a positive integer in the range 1..255");
 	if (resultIndex > 255) throw std::runtime_error( "result index out of range, It must be a positive integer in the range 1..255");
 	if (posbind < 0 || posbind > 3) throw std::runtime_error( "unknown position bind value");
-	Def d; d.expression = expression; d.editdist = cutEditDistance( d.expression);
+	LexDef d; d.expression = expression; d.editdist = cutEditDistance( d.expression);
 	if (d.editdist > 255) throw std::runtime_error( "edit distance out of range, It must be a positive integer in the range 1..255");
 	d.id = id; d.resultIndex = resultIndex; d.level = level; d.posbind = posbind;
 	m_defs.push_back( d);
@@ -1046,491 +1059,461 @@ void LexCompiler::defineOption( const std::string& name, double)
 	else throw std::runtime_error( "unknown option '" + name + "'");
 }
 
-// src/patternLexer.cpp:1068-1118 (+ PatternTable::complete :333-412)
-void LexCompiler::compile()
+// ---------------------------------------------------------------- compile(): its switches and its stages, in the order they run
+namespace {
+
+typedef std::map<uint32_t, std::map<std::string,uint32_t> > SymbolTables;
+// What the environment switches of compile(); read once at its top (the launch side has L1Switches::fromEnv)
+struct CompileSwitches
 {
-	LexTables& T = m_tables;
-	T = LexTables();
-
-	// 0. a table with an edit distance expression: every expression takes the approximate route
-	//    (src/patternLexer.cpp:333-352); supported for tables of plain literals
-	bool approxTable = false;
-	for (size_t di=0; di<m_defs.size(); ++di) if (m_defs[ di].editdist) approxTable = true;
-	if (m_options & LEX_BYTECHAR) approxTable = true;		// forceOneByteCharMap (:1055-1058): the same route without an edit distance
-	if (approxTable)
+	bool shapesOff;					// SPA_L1_SHAPES=0 keeps every expression in the scanned passes: tests
+	enum {SHARE_OFF, SHARE_ON, SHARE_FORCE} share;	// SPA_L1_SHARE=on: shared first positions when they save a pass, =force: always; tests
+	bool shareVarSet;				// SPA_L1_SHARE is set to anything
+	// a table compiled with SPA_L1_SHARE set has no word shapes, whatever the value ("off" included)
+	bool noShapes() const { return shapesOff || shareVarSet; }
+	static CompileSwitches fromEnv()
 	{
-		if (m_options & LEX_CASELESS) throw std::runtime_error( "approximate matching (~N) together with CASELESS is not supported by this lexer");
-		if (!m_symbols.empty()) throw std::runtime_error( "approximate matching (~N) together with symbols is not supported by this lexer");
-		if (m_defs.size() > L1_APPROX_MAXPATTERNS) throw std::runtime_error( "too many expressions in a table with approximate matching (~N)");
+		auto env = []( const char* name) -> const char* { return getenv( name); };
+		const char* shapes = env( "SPA_L1_SHAPES"); const char* share = env( "SPA_L1_SHARE");
+		CompileSwitches sw;
+		sw.shapesOff = shapes && shapes[ 0] == '0';
+		sw.shareVarSet = share != 0;
+		sw.share = !share ? SHARE_OFF : !std::strcmp( share, "force") ? SHARE_FORCE : !std::strcmp( share, "on") ? SHARE_ON : SHARE_OFF;
+		return sw;
 	}
+};
 
-	// 1. per pattern automata
-	const bool ucp = (m_options & LEX_UCP) != 0;
-	if (ucp && approxTable) throw std::runtime_error( "approximate matching (~N) together with UCP is not supported by this lexer");
-	std::vector<CpRanges> cpSets;			// code point sets of the leaves with ByteSet::cpRef
+// ---- stage 1, the expressions: one automaton per entry of LexTables::patterns (an empty one where the entry needs no automaton bits)
+struct Expressions
+{
+	bool approxTable, ucp;
+	std::vector<CpRanges> cpSets;					// code point sets of the leaves with ByteSet::cpRef
 	std::vector<Automaton> autos;
-	std::map<std::string,std::vector<uint32_t> > literalWords;
+	std::map<std::string,std::vector<uint32_t> > literalWords;	// whole-word literal -> patterns[] entries, ascending
 	std::vector<std::pair<uint32_t,ShapeKey> > shapeOf;		// (patterns[] entry, key) of the expressions that are word shapes
-	T.patterns.clear();
-	for (size_t di=0; di<m_defs.size(); ++di)
+	std::vector<char> isShape, scanned;				// per patterns[] entry: a word shape / has its bits in the scanned passes
+};
+bool isLiteral( const DevLexPattern& p) { return p.word == L1_WORD_LITERAL; }
+
+void addWithoutAutomaton( const DevLexPattern& dp, Expressions& X, LexTables& T)
+{
+	T.patterns.push_back( dp); X.autos.push_back( Automaton());
+	for (int c=0; c<CTX_COUNT; ++c) { X.autos.back().start[c] = 0; X.autos.back().accept[c] = 0; }
+}
+// an expression of a table with an edit distance (src/patternLexer.cpp:333-352); supported for tables of plain literals
+DevApproxPattern approxPatternOf( const LexDef& d)
+{
+	const bool plain = !d.expression.empty() && d.expression.find_first_of( "\\.[](){}|*+?^$") == std::string::npos && !d.resultIndex;
+	if (!plain) throw std::runtime_error( "failed to compile pattern \"" + d.expression + "\": a table with approximate matching (~N) or option BYTECHAR holds plain literal expressions only in this lexer");
+	DevApproxPattern ap; std::memset( &ap, 0, sizeof(ap));
+	ap.id = d.id; ap.levelBind = (d.level & 0xFF) | ((uint32_t)d.posbind << 8); ap.editdist = d.editdist; ap.byteLen = (uint32_t)d.expression.size();
+	for (size_t at=0; at<d.expression.size();)
 	{
-		const Def& d = m_defs[ di];
-		if (approxTable)
-		{
-			if (d.expression.empty() || d.expression.find_first_of( "\\.[](){}|*+?^$") != std::string::npos || d.resultIndex)
-			{
-				throw std::runtime_error( "failed to compile pattern \"" + d.expression + "\": a table with approximate matching (~N) or option BYTECHAR holds plain literal expressions only in this lexer");
-			}
-			DevApproxPattern ap; std::memset( &ap, 0, sizeof(ap));
-			ap.id = d.id; ap.levelBind = (d.level & 0xFF) | ((uint32_t)d.posbind << 8); ap.editdist = d.editdist; ap.byteLen = (uint32_t)d.expression.size();
-			const unsigned char* s = (const unsigned char*)d.expression.data();
-			for (size_t at=0; at<d.expression.size();)
-			{
-				// lenient UTF-8 (the kernel's rule): a lead byte with all its continuation bytes, else the byte itself
-				unsigned char c = s[ at];
-				unsigned want = (c >= 0xC2 && c <= 0xDF) ? 2 : (c >= 0xE0 && c <= 0xEF) ? 3 : (c >= 0xF0 && c <= 0xF4) ? 4 : 1;
-				uint32_t cp = c; unsigned n = 1;
-				if (want > 1 && at + want <= d.expression.size())
-				{
-					uint32_t v = c & (0xFFu >> (want+1)); bool ok = true;
-					for (unsigned i=1; i<want; ++i) { if ((s[ at+i] & 0xC0) != 0x80) { ok = false; break; } v = (v << 6) | (s[ at+i] & 0x3F); }
-					if (ok) { cp = v; n = want; }
-				}
-				if (ap.len >= L1_APPROX_MAXCHARS) throw std::runtime_error( "failed to compile pattern \"" + d.expression + "\": a literal with approximate matching has at most 24 characters");
-				ap.cp[ ap.len++] = cp; at += n;
-			}
-			if (d.editdist > L1_APPROX_MAXDIST || d.editdist >= ap.len) throw std::runtime_error( "failed to compile pattern \"" + d.expression + "\": the edit distance is at most 3 and below the number of characters");
-			T.approx.push_back( ap);
-			DevLexPattern dp; std::memset( &dp, 0, sizeof(dp));
-			dp.id = d.id; dp.levelBind = ap.levelBind; dp.word = L1_WORD_LITERAL; dp.defIndex = (uint32_t)di;
-			T.patterns.push_back( dp);
-			autos.push_back( Automaton());
-			for (int c=0; c<CTX_COUNT; ++c) { autos.back().start[c] = 0; autos.back().accept[c] = 0; }
-			continue;
-		}
-		const size_t cpSetsBefore = cpSets.size();
-		Syntax syn( d.expression, m_options, &cpSets, false);
-		Tree tree = syn.run();
-		if (ucp && hasWordAssertion( tree))
-		{
-			// \\b / \\B by Unicode word characters: the bytes of one character have to agree on it
-			cpSets.resize( cpSetsBefore);
-			Syntax again( d.expression, m_options, &cpSets, true);
-			tree = again.run();
-		}
+		uint32_t cp;
+		at += decodeUtf8Lenient( (const unsigned char*)d.expression.data(), d.expression.size(), at, cp);
+		if (ap.len >= L1_APPROX_MAXCHARS) throw std::runtime_error( "failed to compile pattern \"" + d.expression + "\": a literal with approximate matching has at most 24 characters");
+		ap.cp[ ap.len++] = cp;
+	}
+	if (d.editdist > L1_APPROX_MAXDIST || d.editdist >= ap.len) throw std::runtime_error( "failed to compile pattern \"" + d.expression + "\": the edit distance is at most 3 and below the number of characters");
+	return ap;
+}
+// one expression of an exact table: its entries of T.patterns (several when it is cut at an alternation) and their automata
+void compileExpression( const LexDef& d, size_t di, unsigned options, const SymbolTables& symbols, Expressions& X, LexTables& T)
+{
+	const size_t cpSetsBefore = X.cpSets.size();
+	Syntax syn( d.expression, options, &X.cpSets, false);
+	Tree tree = syn.run();
+	if (X.ucp && hasWordAssertion( tree))
+	{
+		// \\b / \\B by Unicode word characters: the bytes of one character have to agree on it
+		X.cpSets.resize( cpSetsBefore);
+		Syntax again( d.expression, options, &X.cpSets, true);
+		tree = again.run();
+	}
+	DevLexPattern dp; std::memset( &dp, 0, sizeof(dp));
+	dp.id = d.id; dp.defIndex = (uint32_t)di;
+	dp.levelBind = (d.level & 0xFF) | ((uint32_t)d.posbind << 8);
+	if (d.resultIndex)
+	{
+		int before = 0, after = 0;
+		const bool fixed = d.resultIndex <= syn.groups() && groupContext( tree, d.resultIndex, before, after);
+		if (!fixed) throw std::runtime_error( "failed to compile pattern \"" + d.expression + "\": selecting a sub expression needs fixed-length context around the group in this lexer");
+		dp.prefixLen = (uint32_t)before; dp.suffixLen = (uint32_t)after;
+		dp.levelBind |= (1u << 17);
+	}
+	if (symbols.count( d.id)) dp.levelBind |= (1u << 16);
+	std::vector<std::string> words;
+	if (!d.resultIndex && wholeWordLiterals( tree, words))
+	{
+		dp.word = L1_WORD_LITERAL;
+		for (size_t wi=0; wi<words.size(); ++wi) X.literalWords[ words[ wi]].push_back( (uint32_t)T.patterns.size());
+		addWithoutAutomaton( dp, X, T);
+		return;
+	}
+	std::vector<Automaton> parts;
+	makeAutomata( tree, d.expression, X.ucp, parts);
+	// what Hyperscan answers hs_compile_ext_multi with (the reference hands the message on, patternLexer.cpp:1094-1104)
+	const bool emptyBuffer = !(options & LEX_ALLOWEMPTY) && (parts[ 0].emptyOk & (1u << (CTX_EDGE*CTX_COUNT + CTX_EDGE)));
+	if (emptyBuffer) throw std::runtime_error( "failed to compile pattern \"" + d.expression + "\": Pattern matches empty buffer; use option ALLOWEMPTY to enable support");
+	if ((options & LEX_ALLOWEMPTY) && parts[ 0].emptyOk)
+	{
+		// HS_FLAG_ALLOWEMPTY: the expression also reports its empty matches (one report per offset where nothing longer ends)
+		if (parts.size() > 1) throw std::runtime_error( "failed to compile pattern \"" + d.expression + "\": an expression that matches the empty string must fit one automaton word with ALLOWEMPTY");
+		DevNullable nl; nl.pattern = (uint32_t)T.patterns.size(); nl.emptyOk = parts[ 0].emptyOk; nl._pad[0] = 0; nl._pad[1] = 0;
+		T.nullable.push_back( nl);
+	}
+	ShapeKey sk;
+	if (parts.size() == 1 && !parts[ 0].emptyOk && wordShapeOf( tree, sk)) X.shapeOf.push_back( std::make_pair( (uint32_t)T.patterns.size(), sk));
+	for (size_t k=0; k<parts.size(); ++k) { T.patterns.push_back( dp); X.autos.push_back( parts[ k]); }
+}
+Expressions compileExpressions( const std::vector<LexDef>& defs, unsigned options, const SymbolTables& symbols, LexTables& T)
+{
+	Expressions X;
+	// a table with an edit distance expression: every expression takes the approximate route
+	X.approxTable = (options & LEX_BYTECHAR) != 0;		// forceOneByteCharMap (:1055-1058): the same route without an edit distance
+	for (size_t di=0; di<defs.size(); ++di) if (defs[ di].editdist) X.approxTable = true;
+	if (X.approxTable)
+	{
+		if (options & LEX_CASELESS) throw std::runtime_error( "approximate matching (~N) together with CASELESS is not supported by this lexer");
+		if (!symbols.empty()) throw std::runtime_error( "approximate matching (~N) together with symbols is not supported by this lexer");
+		if (defs.size() > L1_APPROX_MAXPATTERNS) throw std::runtime_error( "too many expressions in a table with approximate matching (~N)");
+	}
+	X.ucp = (options & LEX_UCP) != 0;
+	if (X.ucp && X.approxTable) throw std::runtime_error( "approximate matching (~N) together with UCP is not supported by this lexer");
+	for (size_t di=0; di<defs.size(); ++di)
+	{
+		if (!X.approxTable) { compileExpression( defs[ di], di, options, symbols, X, T); continue; }
+		T.approx.push_back( approxPatternOf( defs[ di]));
 		DevLexPattern dp; std::memset( &dp, 0, sizeof(dp));
-		dp.id = d.id; dp.defIndex = (uint32_t)di;
-		dp.levelBind = (d.level & 0xFF) | ((uint32_t)d.posbind << 8);
-		if (d.resultIndex)
-		{
-			int before = 0, after = 0;
-			if (d.resultIndex > syn.groups() || !groupContext( tree, d.resultIndex, before, after))
-			{
-				throw std::runtime_error( "failed to compile pattern \"" + d.expression + "\": selecting a sub expression needs fixed-length context around the group in this lexer");
-			}
-			dp.prefixLen = (uint32_t)before; dp.suffixLen = (uint32_t)after;
-			dp.levelBind |= (1u << 17);
-		}
-		if (m_symbols.count( d.id)) dp.levelBind |= (1u << 16);
-		std::vector<std::string> words;
-		if (!d.resultIndex && wholeWordLiterals( tree, words))
-		{
-			dp.word = L1_WORD_LITERAL;
-			for (size_t wi=0; wi<words.size(); ++wi) literalWords[ words[ wi]].push_back( (uint32_t)T.patterns.size());
-			T.patterns.push_back( dp);
-			autos.push_back( Automaton());
-			for (int c=0; c<CTX_COUNT; ++c) { autos.back().start[c] = 0; autos.back().accept[c] = 0; }
-			continue;
-		}
-		std::vector<Automaton> parts;
-		makeAutomata( tree, d.expression, ucp, parts);
-		if (!(m_options & LEX_ALLOWEMPTY) && (parts[ 0].emptyOk & (1u << (CTX_EDGE*CTX_COUNT + CTX_EDGE))))
-		{
-			// what Hyperscan answers hs_compile_ext_multi with (the reference hands the message on, patternLexer.cpp:1094-1104)
-			throw std::runtime_error( "failed to compile pattern \"" + d.expression + "\": Pattern matches empty buffer; use option ALLOWEMPTY to enable support");
-		}
-		if ((m_options & LEX_ALLOWEMPTY) && parts[ 0].emptyOk)
-		{
-			// HS_FLAG_ALLOWEMPTY: the expression also reports its empty matches (one report per offset where nothing longer ends)
-			if (parts.size() > 1) throw std::runtime_error( "failed to compile pattern \"" + d.expression + "\": an expression that matches the empty string must fit one automaton word with ALLOWEMPTY");
-			DevNullable nl; nl.pattern = (uint32_t)T.patterns.size(); nl.emptyOk = parts[ 0].emptyOk; nl._pad[0] = 0; nl._pad[1] = 0;
-			T.nullable.push_back( nl);
-		}
-		{
-			ShapeKey sk;
-			if (parts.size() == 1 && !parts[ 0].emptyOk && wordShapeOf( tree, sk)) shapeOf.push_back( std::make_pair( (uint32_t)T.patterns.size(), sk));
-		}
-		for (size_t k=0; k<parts.size(); ++k) { T.patterns.push_back( dp); autos.push_back( parts[ k]); }
+		dp.id = defs[ di].id; dp.levelBind = T.approx.back().levelBind; dp.word = L1_WORD_LITERAL; dp.defIndex = (uint32_t)di;
+		addWithoutAutomaton( dp, X, T);
 	}
-	// word shapes are taken when the table is a plain one: words by ASCII word characters (no UCP), no classes by code point, the
-	// default layout (SPA_L1_SHAPES=0 keeps every expression in the scanned passes: tests)
-	std::vector<char> isShape( autos.size(), 0);
+	return X;
+}
+uint32_t shapeVariantOf( uint32_t tag) { return (tag & 3u) == (uint32_t)SHAPE_PREVWORD ? (uint32_t)SHAPE_PREVWORD : tag; }
+// word shapes are taken when the table is a plain one: words by ASCII word characters (no UCP), no classes by code point, the
+// default layout
+void selectShapes( Expressions& X, const CompileSwitches& sw, unsigned options, const std::vector<DevLexPattern>& patterns)
+{
+	if (sw.noShapes() || X.ucp || !X.cpSets.empty() || X.approxTable || (options & LEX_ALLOWEMPTY)) X.shapeOf.clear();
+	// the lexer probes one key per variant (kind, place, length) at every end of a word: the most populated ones are kept
+	std::map<uint32_t,size_t> population;
+	for (size_t i=0; i<X.shapeOf.size(); ++i) population[ shapeVariantOf( X.shapeOf[ i].second.tag)] += 1;
+	if (population.size() > SHAPE_MAXVARIANTS)
 	{
-		const char* sw = getenv( "SPA_L1_SHAPES");
-		const bool off = (sw && sw[ 0] == '0') || getenv( "SPA_L1_SHARE") || ucp || !cpSets.empty() || approxTable || (m_options & LEX_ALLOWEMPTY);
-		if (off) shapeOf.clear();
-		// the lexer probes one key per variant (kind, place, length) at every end of a word: the most populated ones are kept
-		std::map<uint32_t,size_t> population;
-		auto variantOf = []( const ShapeKey& k) -> uint32_t { return (k.tag & 3u) == (uint32_t)SHAPE_PREVWORD ? (uint32_t)SHAPE_PREVWORD : k.tag; };
-		for (size_t i=0; i<shapeOf.size(); ++i) population[ variantOf( shapeOf[ i].second)] += 1;
-		if (population.size() > SHAPE_MAXVARIANTS)
-		{
-			std::vector<std::pair<size_t,uint32_t> > byPop;
-			for (std::map<uint32_t,size_t>::const_iterator pi=population.begin(); pi!=population.end(); ++pi) byPop.push_back( std::make_pair( pi->second, pi->first));
-			std::sort( byPop.begin(), byPop.end());
-			std::set<uint32_t> dropped;
-			for (size_t i=0; i+SHAPE_MAXVARIANTS<byPop.size(); ++i) dropped.insert( byPop[ i].second);
-			std::vector<std::pair<uint32_t,ShapeKey> > kept;
-			for (size_t i=0; i<shapeOf.size(); ++i) if (!dropped.count( variantOf( shapeOf[ i].second))) kept.push_back( shapeOf[ i]);
-			shapeOf.swap( kept);
-		}
-		for (size_t i=0; i<shapeOf.size(); ++i) isShape[ shapeOf[ i].first] = 1;
+		std::vector<std::pair<size_t,uint32_t> > byPop;
+		for (std::map<uint32_t,size_t>::const_iterator pi=population.begin(); pi!=population.end(); ++pi) byPop.push_back( std::make_pair( pi->second, pi->first));
+		std::sort( byPop.begin(), byPop.end());
+		std::set<uint32_t> dropped;
+		for (size_t i=0; i+SHAPE_MAXVARIANTS<byPop.size(); ++i) dropped.insert( byPop[ i].second);
+		std::vector<std::pair<uint32_t,ShapeKey> > kept;
+		for (size_t i=0; i<X.shapeOf.size(); ++i) if (!dropped.count( shapeVariantOf( X.shapeOf[ i].second.tag))) kept.push_back( X.shapeOf[ i]);
+		X.shapeOf.swap( kept);
 	}
-	if (T.patterns.size() >= (1u << 24)) throw std::runtime_error( "too many patterns");
+	X.isShape.assign( X.autos.size(), 0);
+	for (size_t i=0; i<X.shapeOf.size(); ++i) X.isShape[ X.shapeOf[ i].first] = 1;
+	X.scanned.assign( X.autos.size(), 0);
+	for (size_t pi=0; pi<X.autos.size(); ++pi) X.scanned[ pi] = !isLiteral( patterns[ pi]) && !X.isShape[ pi];
+}
 
-	// 2. layout: a pattern never straddles a 64-bit word.  Patterns in definition order make the report
-	//    order for equal end offsets (ascending pattern index) fall out of the (pass, lane, bit) order;
-	//    but in-order packing leaves ~8% of the bits unused, and when that costs a whole pass (every pass
-	//    is a full unit of work per input byte) the patterns are packed first-fit by decreasing size
-	//    instead and the kernel sorts the (few) reports that share an end offset.
-	std::vector<uint32_t> bitBase( autos.size(), 0);
-	std::vector<uint32_t> wordOf( autos.size(), 0);
-	T.nofPositions = 0;
-	uint32_t word = 0;
+// ---- stage 2, the layout: a pattern never straddles a 64-bit word.  Patterns in definition order make the report
+//      order for equal end offsets (ascending pattern index) fall out of the (pass, lane, bit) order;
+//      but in-order packing leaves ~8% of the bits unused, and when that costs a whole pass (every pass
+//      is a full unit of work per input byte) the patterns are packed first-fit by decreasing size
+//      instead and the kernel sorts the (few) reports that share an end offset.
+struct Layout
+{
+	std::vector<uint32_t> wordOf;			// per patterns[] entry: its word
+	std::vector<std::vector<uint8_t> > bitOf;	// ... and the bit of every position of its automaton inside that word
+	uint32_t words;					// number of words used
+	uint32_t scanWords;				// ... of them by the passes the scan kernel runs
+	uint32_t nofPositions; bool reportsOrdered;
+	explicit Layout( size_t n) :wordOf(n,0),bitOf(n),words(0),scanWords(0),nofPositions(0),reportsOrdered(true){}
+};
+void placeRun( Layout& L, size_t pi, uint32_t word, uint32_t base, size_t n)
+{
+	L.wordOf[ pi] = word; L.bitOf[ pi].resize( n);
+	for (size_t k=0; k<n; ++k) L.bitOf[ pi][ k] = (uint8_t)(base + k);
+}
+// the expressions marked in `which`, in definition order, into the words from `word` on; returns the number of words then in use
+uint32_t layoutInOrder( const std::vector<Automaton>& autos, const std::vector<char>& which, uint32_t word, Layout& L)
+{
+	uint32_t used = 0; bool any = false;
+	for (size_t pi=0; pi<autos.size(); ++pi)
 	{
-		uint32_t used = 0; bool any = false;
-		for (size_t pi=0; pi<autos.size(); ++pi)
-		{
-			uint32_t n = (uint32_t)autos[ pi].pos.size();
-			if (T.patterns[ pi].word == L1_WORD_LITERAL || isShape[ pi]) continue;
-			T.nofPositions += n;
-			if (used + n > 64) { ++word; used = 0; }
-			bitBase[ pi] = used; wordOf[ pi] = word; used += n; any = true;
-		}
-		if (!any) word = 0; else ++word;		// word = number of words used
+		if (!which[ pi]) continue;
+		const uint32_t n = (uint32_t)autos[ pi].pos.size();
+		L.nofPositions += n;
+		if (used + n > 64) { ++word; used = 0; }
+		placeRun( L, pi, word, used, n); used += n; any = true;
 	}
-	T.reportsOrdered = true;
+	return any ? word+1 : L.words;
+}
+// first-fit by decreasing size, taken when it saves a pass over the layout in order
+bool layoutBySize( const Expressions& X, Layout& L)
+{
+	const uint32_t perPass = L1_WORDS_PER_PASS;
+	const uint32_t passesInOrder = (L.words + perPass-1) / perPass;
+	const uint32_t passesMin = (L.nofPositions + 64*perPass-1) / (64*perPass);
+	if (passesInOrder <= passesMin || passesInOrder <= 1) return false;
+	const std::vector<Automaton>& autos = X.autos;
+	std::vector<size_t> bySize;
+	for (size_t pi=0; pi<autos.size(); ++pi) if (X.scanned[ pi]) bySize.push_back( pi);
+	std::stable_sort( bySize.begin(), bySize.end(), [&]( size_t a, size_t b) { return autos[ a].pos.size() > autos[ b].pos.size(); });
+	std::vector<uint32_t> fill, base2( autos.size(), 0), word2( autos.size(), 0);
+	size_t firstOpen = 0;
+	for (size_t k=0; k<bySize.size(); ++k)
 	{
-		const uint32_t perPass = L1_WORDS_PER_PASS;
-		const uint32_t passesInOrder = (word + perPass-1) / perPass;
-		const uint32_t passesMin = (T.nofPositions + 64*perPass-1) / (64*perPass);
-		if (passesInOrder > passesMin && passesInOrder > 1)
-		{
-			std::vector<size_t> bySize;
-			for (size_t pi=0; pi<autos.size(); ++pi) if (T.patterns[ pi].word != L1_WORD_LITERAL && !isShape[ pi]) bySize.push_back( pi);
-			std::stable_sort( bySize.begin(), bySize.end(), [&]( size_t a, size_t b) { return autos[ a].pos.size() > autos[ b].pos.size(); });
-			std::vector<uint32_t> fill;
-			std::vector<uint32_t> base2( autos.size(), 0), word2( autos.size(), 0);
-			size_t firstOpen = 0;
-			for (size_t k=0; k<bySize.size(); ++k)
-			{
-				const size_t pi = bySize[ k];
-				const uint32_t n = (uint32_t)autos[ pi].pos.size();
-				size_t wi = firstOpen;
-				while (wi < fill.size() && fill[ wi] + n > 64) ++wi;
-				if (wi == fill.size()) fill.push_back( 0);
-				base2[ pi] = fill[ wi]; word2[ pi] = (uint32_t)wi; fill[ wi] += n;
-				while (firstOpen < fill.size() && fill[ firstOpen] == 64) ++firstOpen;
-			}
-			const uint32_t passesPacked = ((uint32_t)fill.size() + perPass-1) / perPass;
-			if (passesPacked < passesInOrder)
-			{
-				bitBase.swap( base2); wordOf.swap( word2); word = (uint32_t)fill.size();
-				T.reportsOrdered = false;
-			}
-		}
+		const size_t pi = bySize[ k];
+		const uint32_t n = (uint32_t)autos[ pi].pos.size();
+		size_t wi = firstOpen;
+		while (wi < fill.size() && fill[ wi] + n > 64) ++wi;
+		if (wi == fill.size()) fill.push_back( 0);
+		base2[ pi] = fill[ wi]; word2[ pi] = (uint32_t)wi; fill[ wi] += n;
+		while (firstOpen < fill.size() && fill[ firstOpen] == 64) ++firstOpen;
 	}
-	// the passes the scan kernel runs end here; the word shapes follow in passes of their own (in definition order)
-	T.scanPasses = (word + L1_WORDS_PER_PASS-1) / L1_WORDS_PER_PASS;
-	T.scanWords = word;
-	T.lanesOk = true;
-	for (size_t pi=0; pi<autos.size() && T.lanesOk; ++pi)
+	const uint32_t passesPacked = ((uint32_t)fill.size() + perPass-1) / perPass;
+	if (passesPacked >= passesInOrder) return false;
+	for (size_t k=0; k<bySize.size(); ++k) placeRun( L, bySize[ k], word2[ bySize[ k]], base2[ bySize[ k]], autos[ bySize[ k]].pos.size());
+	L.words = (uint32_t)fill.size(); L.reportsOrdered = false;
+	return true;
+}
+// Shared first position.  Many sets hold families of patterns that begin alike ([a-z]+ing\b,
+// [a-z]+ed\b, ..; \bun\w+, \bup\w+, ..).  When the first position of a pattern is its only start
+// position, is not accepting and has no edge coming back into it, "position 0 is live" means the
+// same for every pattern with an identical position 0 (same bytes, same self loop, same start
+// contexts): such patterns can share that one bit when they sit in the same word -- the edges
+// from the shared bit to each pattern's own positions become one exception row of that word, and
+// the pattern's mask (accept attribution, start-of-match run) is its own bits plus the shared one.
+// Opt-in (CompileSwitches::share): on the 10k-pattern benchmark set it takes the tables from 3 passes to 2
+// but the lexer kernel only from 226 to 219 ms -- the per-byte scalar work and the report handling dominate,
+// not the pass count -- so the default stays the plain layout.
+bool layoutSharedFirstPosition( const std::vector<Automaton>& autos, const std::vector<DevLexPattern>& patterns, const CompileSwitches& sw, Layout& L)
+{
+	if (sw.share == CompileSwitches::SHARE_OFF) return false;
+	std::map<std::string,std::vector<size_t> > groups;
+	std::vector<size_t> singles;
+	for (size_t pi=0; pi<autos.size(); ++pi)
 	{
-		if (T.patterns[ pi].word == L1_WORD_LITERAL || isShape[ pi]) continue;
+		if (isLiteral( patterns[ pi])) continue;
 		const Automaton& a = autos[ pi];
-		const size_t n = a.pos.size();
-		for (size_t k=0; k<n && T.lanesOk; ++k)
-		{
-			if (!a.pos[ k].has( ' ')) continue;
-			// is position k on a cycle?  (reachability over the follow edges, at most 64 positions)
-			uint64_t seen = 0, front = a.follow[ k];
-			while (front & ~seen)
-			{
-				const uint64_t fresh = front & ~seen;
-				seen |= fresh; front = 0;
-				for (size_t q=0; q<n; ++q) if (fresh & (1ull << q)) front |= a.follow[ q];
-			}
-			if (seen & (1ull << k)) T.lanesOk = false;
-		}
+		bool ok = a.pos.size() >= 2;
+		uint64_t anyStart = 0;
+		for (int c=0; c<CTX_COUNT && ok; ++c) { ok = (a.start[ c] & ~1ull) == 0 && (a.accept[ c] & 1ull) == 0; anyStart |= a.start[ c]; }
+		for (size_t k=1; k<a.pos.size() && ok; ++k) ok = (a.follow[ k] & 1ull) == 0;
+		if (!ok || !anyStart) { singles.push_back( pi); continue; }
+		std::string key;
+		for (unsigned c=0; c<256; c+=8) { unsigned char b = 0; for (unsigned x=0; x<8; ++x) if (a.pos[ 0].has( c+x)) b |= (unsigned char)(1u << x); key.push_back( (char)b); }
+		key.push_back( (char)(a.follow[ 0] & 1ull)); key.push_back( (char)(a.pos[ 0].cpRef & 0xFF)); key.push_back( (char)((a.pos[ 0].cpRef >> 8) & 0xFF));
+		for (int c=0; c<CTX_COUNT; ++c) key.push_back( (char)(a.start[ c] & 1ull));
+		groups[ key].push_back( pi);
 	}
-	T.nofShapes = (uint32_t)shapeOf.size();
-	if (!shapeOf.empty())
+	struct Bin { uint32_t used; std::vector<size_t> members; bool shared; };
+	std::vector<Bin> bins;
+	for (std::map<std::string,std::vector<size_t> >::iterator gi=groups.begin(); gi!=groups.end(); ++gi)
 	{
-		uint32_t w2 = T.scanPasses * L1_WORDS_PER_PASS, used = 0;
-		for (size_t pi=0; pi<autos.size(); ++pi)
+		std::vector<size_t>& mem = gi->second;
+		if (mem.size() < 2) { singles.push_back( mem[ 0]); continue; }
+		std::stable_sort( mem.begin(), mem.end(), [&]( size_t a, size_t b) { return autos[ a].pos.size() > autos[ b].pos.size(); });
+		const size_t firstBin = bins.size();
+		for (size_t k=0; k<mem.size(); ++k)
 		{
-			if (!isShape[ pi]) continue;
-			const uint32_t n = (uint32_t)autos[ pi].pos.size();
-			T.nofPositions += n;
-			if (used + n > 64) { ++w2; used = 0; }
-			bitBase[ pi] = used; wordOf[ pi] = w2; used += n;
+			const uint32_t chain = (uint32_t)autos[ mem[ k]].pos.size() - 1;
+			size_t bi = firstBin;
+			while (bi < bins.size() && bins[ bi].used + chain > 64) ++bi;
+			if (bi == bins.size()) { Bin b; b.used = 1; b.shared = true; bins.push_back( b); }
+			bins[ bi].members.push_back( mem[ k]); bins[ bi].used += chain;
 		}
-		word = w2 + 1;
 	}
-	// bit of every position of every pattern inside its word (contiguous in the two layouts above)
-	std::vector<std::vector<uint8_t> > bitOf( autos.size());
-	for (size_t pi=0; pi<autos.size(); ++pi)
+	// everything else first-fit by decreasing size into what is left (a bin opened here has no shared bit)
+	std::sort( singles.begin(), singles.end());
+	std::stable_sort( singles.begin(), singles.end(), [&]( size_t a, size_t b) { return autos[ a].pos.size() > autos[ b].pos.size(); });
+	for (size_t k=0; k<singles.size(); ++k)
 	{
-		if (T.patterns[ pi].word == L1_WORD_LITERAL) continue;
-		for (size_t k=0; k<autos[ pi].pos.size(); ++k) bitOf[ pi].push_back( (uint8_t)(bitBase[ pi] + k));
+		const Automaton& a = autos[ singles[ k]];
+		const uint32_t n = (uint32_t)a.pos.size();
+		// a pattern with exception edges of its own stays out of the words that spend their exception
+		// row on a shared first position (a second row is paid by every word of the pass)
+		bool ownEx = false;
+		for (uint32_t q=0; q<n && !ownEx; ++q) ownEx = (a.follow[ q] & ~(1ull << q) & ~(q+1 < n ? (1ull << (q+1)) : 0ull)) != 0;
+		size_t bi = 0;
+		while (bi < bins.size() && (bins[ bi].used + n > 64 || (ownEx && bins[ bi].shared))) ++bi;
+		if (bi == bins.size()) { Bin b; b.used = 0; b.shared = false; bins.push_back( b); }
+		bins[ bi].members.push_back( singles[ k] | ((size_t)1 << 62)); bins[ bi].used += n;
 	}
-	// 2b. shared first position.  Many sets hold families of patterns that begin alike ([a-z]+ing\b,
-	//     [a-z]+ed\b, ..; \bun\w+, \bup\w+, ..).  When the first position of a pattern is its only start
-	//     position, is not accepting and has no edge coming back into it, "position 0 is live" means the
-	//     same for every pattern with an identical position 0 (same bytes, same self loop, same start
-	//     contexts): such patterns can share that one bit when they sit in the same word -- the edges
-	//     from the shared bit to each pattern's own positions become one exception row of that word, and
-	//     the pattern's mask (accept attribution, start-of-match run) is its own bits plus the shared one.
+	const uint32_t perPass = L1_WORDS_PER_PASS;
+	const uint32_t passesNow = L.words ? (L.words + perPass-1) / perPass : 1;
+	const uint32_t passesShared = bins.empty() ? 1 : ((uint32_t)bins.size() + perPass-1) / perPass;
+	if (bins.empty() || !(passesShared < passesNow || sw.share == CompileSwitches::SHARE_FORCE)) return false;
+	L.nofPositions = 0;
+	for (size_t bi=0; bi<bins.size(); ++bi)
 	{
-		// Opt-in (SPA_L1_SHARE=on: when it saves a pass, =force: always; tests): on the 10k-pattern benchmark set
-		// it takes the tables from 3 passes to 2 but the lexer kernel only from 226 to 219 ms -- the per-byte
-		// scalar work and the report handling dominate, not the pass count -- so the default stays the plain layout.
-		const char* shareEnv = getenv( "SPA_L1_SHARE");
-		const bool shareForce = shareEnv && !std::strcmp( shareEnv, "force");
-		const bool shareOff = !(shareForce || (shareEnv && !std::strcmp( shareEnv, "on")));
-		std::map<std::string,std::vector<size_t> > groups;
-		std::vector<size_t> singles;
-		for (size_t pi=0; pi<autos.size() && !shareOff; ++pi)
+		uint32_t next = bins[ bi].shared ? 1 : 0;
+		L.nofPositions += next;
+		for (size_t k=0; k<bins[ bi].members.size(); ++k)
 		{
-			if (T.patterns[ pi].word == L1_WORD_LITERAL) continue;
-			const Automaton& a = autos[ pi];
-			bool ok = a.pos.size() >= 2;
-			uint64_t anyStart = 0;
-			for (int c=0; c<CTX_COUNT && ok; ++c) { ok = (a.start[ c] & ~1ull) == 0 && (a.accept[ c] & 1ull) == 0; anyStart |= a.start[ c]; }
-			for (size_t k=1; k<a.pos.size() && ok; ++k) ok = (a.follow[ k] & 1ull) == 0;
-			if (!ok || !anyStart) { singles.push_back( pi); continue; }
-			std::string key;
-			for (unsigned c=0; c<256; c+=8) { unsigned char b = 0; for (unsigned x=0; x<8; ++x) if (a.pos[ 0].has( c+x)) b |= (unsigned char)(1u << x); key.push_back( (char)b); }
-			key.push_back( (char)(a.follow[ 0] & 1ull)); key.push_back( (char)(a.pos[ 0].cpRef & 0xFF)); key.push_back( (char)((a.pos[ 0].cpRef >> 8) & 0xFF));
-			for (int c=0; c<CTX_COUNT; ++c) key.push_back( (char)(a.start[ c] & 1ull));
-			groups[ key].push_back( pi);
-		}
-		if (!shareOff)
-		{
-			struct Bin { uint32_t used; std::vector<size_t> members; bool shared; };
-			std::vector<Bin> bins;
-			for (std::map<std::string,std::vector<size_t> >::iterator gi=groups.begin(); gi!=groups.end(); ++gi)
-			{
-				std::vector<size_t>& mem = gi->second;
-				if (mem.size() < 2) { singles.push_back( mem[ 0]); continue; }
-				std::stable_sort( mem.begin(), mem.end(), [&]( size_t a, size_t b) { return autos[ a].pos.size() > autos[ b].pos.size(); });
-				const size_t firstBin = bins.size();
-				for (size_t k=0; k<mem.size(); ++k)
-				{
-					const uint32_t chain = (uint32_t)autos[ mem[ k]].pos.size() - 1;
-					size_t bi = firstBin;
-					while (bi < bins.size() && bins[ bi].used + chain > 64) ++bi;
-					if (bi == bins.size()) { Bin b; b.used = 1; b.shared = true; bins.push_back( b); }
-					bins[ bi].members.push_back( mem[ k]); bins[ bi].used += chain;
-				}
-			}
-			// everything else first-fit by decreasing size into what is left (a bin opened here has no shared bit)
-			std::sort( singles.begin(), singles.end());
-			std::stable_sort( singles.begin(), singles.end(), [&]( size_t a, size_t b) { return autos[ a].pos.size() > autos[ b].pos.size(); });
-			for (size_t k=0; k<singles.size(); ++k)
-			{
-				const Automaton& a = autos[ singles[ k]];
-				const uint32_t n = (uint32_t)a.pos.size();
-				// a pattern with exception edges of its own stays out of the words that spend their exception
-				// row on a shared first position (a second row is paid by every word of the pass)
-				bool ownEx = false;
-				for (uint32_t q=0; q<n && !ownEx; ++q) ownEx = (a.follow[ q] & ~(1ull << q) & ~(q+1 < n ? (1ull << (q+1)) : 0ull)) != 0;
-				size_t bi = 0;
-				while (bi < bins.size() && (bins[ bi].used + n > 64 || (ownEx && bins[ bi].shared))) ++bi;
-				if (bi == bins.size()) { Bin b; b.used = 0; b.shared = false; bins.push_back( b); }
-				bins[ bi].members.push_back( singles[ k] | ((size_t)1 << 62)); bins[ bi].used += n;
-			}
-			const uint32_t perPass = L1_WORDS_PER_PASS;
-			const uint32_t passesNow = word ? (word + perPass-1) / perPass : 1;
-			const uint32_t passesShared = bins.empty() ? 1 : ((uint32_t)bins.size() + perPass-1) / perPass;
-			if (!bins.empty() && (passesShared < passesNow || shareForce))
-			{
-				T.nofPositions = 0;
-				for (size_t bi=0; bi<bins.size(); ++bi)
-				{
-					uint32_t next = bins[ bi].shared ? 1 : 0;
-					T.nofPositions += next;
-					for (size_t k=0; k<bins[ bi].members.size(); ++k)
-					{
-						const bool single = (bins[ bi].members[ k] >> 62) != 0;
-						const size_t pi = bins[ bi].members[ k] & (((size_t)1 << 62) - 1);
-						const size_t n = autos[ pi].pos.size();
-						bitOf[ pi].clear();
-						wordOf[ pi] = (uint32_t)bi;
-						if (!single) bitOf[ pi].push_back( 0);			// the shared first position
-						for (size_t q=single?0:1; q<n; ++q) { bitOf[ pi].push_back( (uint8_t)next++); ++T.nofPositions; }
-					}
-				}
-				word = (uint32_t)bins.size();
-				T.reportsOrdered = false;
-			}
+			const bool single = (bins[ bi].members[ k] >> 62) != 0;
+			const size_t pi = bins[ bi].members[ k] & (((size_t)1 << 62) - 1);
+			const size_t n = autos[ pi].pos.size();
+			L.bitOf[ pi].clear();
+			L.wordOf[ pi] = (uint32_t)bi;
+			if (!single) L.bitOf[ pi].push_back( 0);			// the shared first position
+			for (size_t q=single?0:1; q<n; ++q) { L.bitOf[ pi].push_back( (uint8_t)next++); ++L.nofPositions; }
 		}
 	}
-	T.wordPatBegin.clear(); T.wordPats.clear();
+	L.words = (uint32_t)bins.size(); L.reportsOrdered = false;
+	return true;
+}
+// can the expression stay live across a blank (a position on a cycle takes ' ')?  LexTables::lanesOk
+bool staysLiveAcrossBlank( const Automaton& a)
+{
+	const size_t n = a.pos.size();
+	for (size_t k=0; k<n; ++k)
 	{
-		// patterns of every word (ascending pattern index inside a word)
-		std::vector<std::vector<uint32_t> > perWord( word);
-		for (size_t pi=0; pi<autos.size(); ++pi)
+		if (!a.pos[ k].has( ' ')) continue;
+		// is position k on a cycle?  (reachability over the follow edges, at most 64 positions)
+		uint64_t seen = 0, front = a.follow[ k];
+		while (front & ~seen)
 		{
-			if (T.patterns[ pi].word == L1_WORD_LITERAL) continue;
-			T.patterns[ pi].word = wordOf[ pi];
-			uint64_t mask = 0;
-			for (size_t k=0; k<bitOf[ pi].size(); ++k) mask |= 1ull << bitOf[ pi][ k];
-			T.patterns[ pi].maskLo = (uint32_t)mask; T.patterns[ pi].maskHi = (uint32_t)(mask >> 32);
-			perWord[ wordOf[ pi]].push_back( (uint32_t)pi);
+			const uint64_t fresh = front & ~seen;
+			seen |= fresh; front = 0;
+			for (size_t q=0; q<n; ++q) if (fresh & (1ull << q)) front |= a.follow[ q];
 		}
-		T.wordPatBegin.push_back( 0);
-		for (uint32_t wi=0; wi<word; ++wi)
-		{
-			T.wordPats.insert( T.wordPats.end(), perWord[ wi].begin(), perWord[ wi].end());
-			T.wordPatBegin.push_back( (uint32_t)T.wordPats.size());
-		}
+		if (seen & (1ull << k)) return true;
 	}
-	uint32_t nwords = word;
-	T.nofPasses = (nwords + L1_WORDS_PER_PASS-1) / L1_WORDS_PER_PASS;
-	if (T.nofPasses == 0) T.nofPasses = 1;
+	return false;
+}
+
+// ---- stage 3, the tables from (automata, layout)
+// patterns of every word (ascending pattern index inside a word), the owner of every bit; T.nofPasses
+void wordPatternLists( const std::vector<Automaton>& autos, const Layout& L, LexTables& T)
+{
+	T.nofPasses = std::max( 1u, (L.words + L1_WORDS_PER_PASS-1) / L1_WORDS_PER_PASS);
 	const uint32_t totalWords = T.nofPasses * L1_WORDS_PER_PASS;
-	while (T.wordPatBegin.size() < totalWords+1) T.wordPatBegin.push_back( (uint32_t)T.wordPats.size());
-
 	T.patOfBit.assign( (size_t)totalWords*64, 0);
+	std::vector<std::vector<uint32_t> > perWord( L.words);
 	for (size_t pi=0; pi<autos.size(); ++pi)
 	{
-		if (T.patterns[ pi].word == L1_WORD_LITERAL) continue;
-		for (uint32_t k=0; k<(uint32_t)autos[ pi].pos.size(); ++k) T.patOfBit[ (size_t)T.patterns[ pi].word*64 + bitOf[ pi][ k]] = (uint32_t)pi;	// a shared bit never accepts: any owner will do
+		if (isLiteral( T.patterns[ pi])) continue;
+		T.patterns[ pi].word = L.wordOf[ pi];
+		uint64_t mask = 0;
+		for (size_t k=0; k<L.bitOf[ pi].size(); ++k) mask |= 1ull << L.bitOf[ pi][ k];
+		T.patterns[ pi].maskLo = (uint32_t)mask; T.patterns[ pi].maskHi = (uint32_t)(mask >> 32);
+		perWord[ L.wordOf[ pi]].push_back( (uint32_t)pi);
+		for (size_t k=0; k<L.bitOf[ pi].size(); ++k) T.patOfBit[ (size_t)L.wordOf[ pi]*64 + L.bitOf[ pi][ k]] = (uint32_t)pi;	// a shared bit never accepts: any owner will do
 	}
+	T.wordPatBegin.push_back( 0);
+	for (uint32_t wi=0; wi<L.words; ++wi)
+	{
+		T.wordPats.insert( T.wordPats.end(), perWord[ wi].begin(), perWord[ wi].end());
+		T.wordPatBegin.push_back( (uint32_t)T.wordPats.size());
+	}
+	while (T.wordPatBegin.size() < totalWords+1) T.wordPatBegin.push_back( (uint32_t)T.wordPats.size());
+}
+// The symbols the byte classes are made of: a byte in a context.  With UCP the continuation bytes 80..BF exist twice: as
+// bytes of a character that is not a word character (symbols 128..191, context OTHER) and of one that is (symbols 256..319,
+// context WORD) -- the kernel knows which from the lead byte.
+unsigned symByte( unsigned sym) { return sym < 256 ? sym : 0x80u + (sym - 256u); }
+int symCtx( unsigned sym) { return sym < 256 ? ctxOfByte( sym) : (int)CTX_WORD; }
+// does position k of automaton a take the symbol?  Positions classed by code point take no byte.
+bool takesSymbol( const Automaton& a, size_t k, unsigned sym)
+{
+	const unsigned c = symByte( sym);
+	if (a.pos[ k].cpRef >= 0 || !a.pos[ k].has( c)) return false;
+	return c < 0x80 || a.ctxDef[ k] < 0 || a.ctxDef[ k] == symCtx( sym);
+}
+// does position k of automaton a take the character cp beyond ASCII (context cpCtx), seen at its lead byte?
+bool takesCodePoint( const Automaton& a, size_t k, const std::vector<CpRanges>& cpSets, uint32_t cp, int cpCtx)
+{
+	const ByteSet& b = a.pos[ k];
+	if (a.ctxDef[ k] >= 0 && a.ctxDef[ k] != cpCtx) return false;
+	if (b.cpRef < 0) { unsigned char enc[4]; encodeUtf8( cp, enc); return b.has( enc[0]); }
+	const CpRanges& r = cpSets[ b.cpRef];
+	size_t lo = 0, hi = r.size();
+	while (lo < hi) { size_t mid = (lo+hi)/2; if (r[ mid].second < cp) lo = mid+1; else hi = mid; }
+	return lo < r.size() && r[ lo].first <= cp;
+}
 
-	// 3. byte classes: bytes that no position distinguishes (and that share a context) are one class.  With UCP the
-	//    continuation bytes 80..BF exist twice: as bytes of a character that is not a word character (symbols 128..191,
-	//    context OTHER) and of one that is (symbols 256..319, context WORD) -- the kernel knows which from the lead byte.
+// byte classes: bytes that no position distinguishes (and that share a context) are one class
+void byteClasses( const std::vector<Automaton>& autos, bool ucp, LexTables& T)
+{
 	const unsigned nofSymbols = ucp ? 320u : 256u;
-	auto symByte = []( unsigned sym) -> unsigned { return sym < 256 ? sym : 0x80u + (sym - 256u); };
-	auto symCtx = []( unsigned sym) -> int { return sym < 256 ? ctxOfByte( sym) : (int)CTX_WORD; };
-	// does position k of automaton a take the symbol (a byte in a context)?  Positions classed by code point take no byte.
-	auto takesSymbol = [&]( const Automaton& a, size_t k, unsigned sym) -> bool
+	std::vector<uint64_t> sig( nofSymbols, 1469598103934665603ull);
+	uint32_t gp = 0;
+	for (size_t pi=0; pi<autos.size(); ++pi) for (size_t k=0; k<autos[ pi].pos.size(); ++k, ++gp) for (unsigned c=0; c<nofSymbols; ++c)
 	{
-		const unsigned c = symByte( sym);
-		if (a.pos[ k].cpRef >= 0 || !a.pos[ k].has( c)) return false;
-		return c < 0x80 || a.ctxDef[ k] < 0 || a.ctxDef[ k] == symCtx( sym);
-	};
+		// (a position classed by code point still tells its lead bytes apart from the others: harmless refinement)
+		const bool in = autos[ pi].pos[k].cpRef >= 0 ? (c < 256 && autos[ pi].pos[k].has( c)) : takesSymbol( autos[ pi], k, c);
+		if (in) sig[ c] = (sig[ c] ^ (gp+1)) * 1099511628211ull + 0x9E3779B97F4A7C15ull;
+	}
+	std::map<std::pair<uint64_t,int>,uint32_t> classOf;
+	T.byteClass.assign( nofSymbols, 0);
+	for (unsigned c=0; c<nofSymbols; ++c)
 	{
-		std::vector<uint64_t> sig( nofSymbols, 1469598103934665603ull);
+		std::pair<uint64_t,int> key( sig[ c], symCtx( c));
+		const auto at = classOf.insert( std::make_pair( key, (uint32_t)classOf.size()));
+		if (at.second && at.first->second > 254) throw std::runtime_error( "too many distinct byte classes");
+		if (at.second) T.classCtx.push_back( (uint8_t)key.second);
+		T.byteClass[ c] = (uint8_t)at.first->second;
+	}
+	T.nofClasses = (uint32_t)classOf.size();
+}
+// Classes by code point.  A position with a code point set (ByteSet::cpRef) is entered at the lead byte of a
+// well-formed character and looks at its code point; every other position looks at the lead byte as a byte.
+// Code points that no position tells apart are one class, numbered behind the byte classes.
+// Returns a code point of every such class (class id - number of byte classes -> code point).
+std::vector<uint32_t> codePointClasses( const std::vector<Automaton>& autos, const std::vector<CpRanges>& cpSets, bool ucp, LexTables& T)
+{
+	std::vector<uint32_t> repCpOfClass;
+	if (cpSets.empty() && !ucp) return repCpOfClass;
+	std::vector<uint32_t> cut;
+	for (uint32_t cp=0x80; cp<0x800; cp+=64) cut.push_back( cp);			// one lead byte each
+	for (uint32_t cp=0x800; cp<0x10000; cp=(cp+0x1000) & ~0xFFFu) cut.push_back( cp);
+	for (uint32_t cp=0x10000; cp<0x110000; cp=(cp+0x40000) & ~0x3FFFFu) cut.push_back( cp);
+	cut.push_back( 0x110000);
+	for (size_t i=0; i<cpSets.size(); ++i) for (size_t k=0; k<cpSets[ i].size(); ++k) { cut.push_back( cpSets[ i][ k].first); cut.push_back( cpSets[ i][ k].second+1); }
+	if (ucp)
+	{
+		// the context of a character beyond ASCII: word character or not
+		static const char* cats[2] = {"L", "N"};
+		for (int ci=0; ci<2; ++ci) for (const UcCategory* c=UC_CATEGORIES; c->name; ++c)
+		{
+			if (std::strcmp( c->name, cats[ ci])) continue;
+			for (uint32_t i=0; i<c->count; ++i) { cut.push_back( c->ranges[ i].lo); cut.push_back( c->ranges[ i].hi+1); }
+		}
+	}
+	std::sort( cut.begin(), cut.end()); cut.erase( std::unique( cut.begin(), cut.end()), cut.end());
+	std::vector<uint8_t> flat( 0x110000, 0xFF);
+	std::map<uint64_t,uint32_t> classOfSig;
+	for (size_t ai=0; ai+1<cut.size(); ++ai)
+	{
+		const uint32_t cp = cut[ ai];
+		if (cp < 0x80 || cp >= 0x110000) continue;
+		const int cpCtx = (ucp && ucpWordCp( cp)) ? (int)CTX_WORD : (int)CTX_OTHER;
+		uint64_t sig = 1469598103934665603ull ^ (uint64_t)cpCtx;
 		uint32_t gp = 0;
 		for (size_t pi=0; pi<autos.size(); ++pi) for (size_t k=0; k<autos[ pi].pos.size(); ++k, ++gp)
-		{
-			for (unsigned c=0; c<nofSymbols; ++c)
-			{
-				// (a position classed by code point still tells its lead bytes apart from the others: harmless refinement)
-				const bool in = autos[ pi].pos[k].cpRef >= 0 ? (c < 256 && autos[ pi].pos[k].has( c)) : takesSymbol( autos[ pi], k, c);
-				if (in) sig[ c] = (sig[ c] ^ (gp+1)) * 1099511628211ull + 0x9E3779B97F4A7C15ull;
-			}
-		}
-		std::map<std::pair<uint64_t,int>,uint32_t> classOf;
-		T.byteClass.assign( nofSymbols, 0); T.classCtx.clear();
-		for (unsigned c=0; c<nofSymbols; ++c)
-		{
-			std::pair<uint64_t,int> key( sig[ c], symCtx( c));
-			std::map<std::pair<uint64_t,int>,uint32_t>::const_iterator it = classOf.find( key);
-			uint32_t cls;
-			if (it == classOf.end())
-			{
-				cls = (uint32_t)classOf.size();
-				if (cls > 254) throw std::runtime_error( "too many distinct byte classes");
-				classOf[ key] = cls; T.classCtx.push_back( (uint8_t)key.second);
-			}
-			else cls = it->second;
-			T.byteClass[ c] = (uint8_t)cls;
-		}
-		T.nofClasses = (uint32_t)classOf.size();
+			if (takesCodePoint( autos[ pi], k, cpSets, cp, cpCtx)) sig = (sig ^ (gp+1)) * 1099511628211ull + 0x9E3779B97F4A7C15ull;
+		const auto at = classOfSig.insert( std::make_pair( sig, T.nofClasses));
+		if (at.second && at.first->second > 254) throw std::runtime_error( "too many distinct character classes");
+		if (at.second) { ++T.nofClasses; T.classCtx.push_back( (uint8_t)cpCtx); repCpOfClass.push_back( cp); }
+		for (uint32_t c=cp; c<cut[ ai+1]; ++c) flat[ c] = (uint8_t)at.first->second;
 	}
-
-	// 3b. classes by code point.  A position with a code point set (ByteSet::cpRef) is entered at the lead byte of a
-	//     well-formed character and looks at its code point; every other position looks at the lead byte as a byte.
-	//     Code points that no position tells apart are one class, numbered behind the byte classes.
-	const uint32_t nofByteClasses = T.nofClasses;
-	std::vector<uint32_t> repCpOfClass;		// class id - nofByteClasses -> a code point of the class
-	T.cpBlocks.clear(); T.cpPages.clear();
-	T.ucp = ucp;
-	if (!cpSets.empty() || ucp)
+	std::map<std::string,uint16_t> pageOf;
+	for (uint32_t blk=0; blk<0x110000/64; ++blk)
 	{
-		std::vector<uint32_t> cut;
-		for (uint32_t cp=0x80; cp<0x800; cp+=64) cut.push_back( cp);			// one lead byte each
-		for (uint32_t cp=0x800; cp<0x10000; cp=(cp+0x1000) & ~0xFFFu) cut.push_back( cp);
-		for (uint32_t cp=0x10000; cp<0x110000; cp=(cp+0x40000) & ~0x3FFFFu) cut.push_back( cp);
-		cut.push_back( 0x110000);
-		for (size_t i=0; i<cpSets.size(); ++i) for (size_t k=0; k<cpSets[ i].size(); ++k) { cut.push_back( cpSets[ i][ k].first); cut.push_back( cpSets[ i][ k].second+1); }
-		if (ucp)
-		{
-			// the context of a character beyond ASCII: word character or not
-			static const char* cats[2] = {"L", "N"};
-			for (int ci=0; ci<2; ++ci) for (const UcCategory* c=UC_CATEGORIES; c->name; ++c)
-			{
-				if (std::strcmp( c->name, cats[ ci])) continue;
-				for (uint32_t i=0; i<c->count; ++i) { cut.push_back( c->ranges[ i].lo); cut.push_back( c->ranges[ i].hi+1); }
-			}
-		}
-		std::sort( cut.begin(), cut.end()); cut.erase( std::unique( cut.begin(), cut.end()), cut.end());
-		auto inSet = [&]( int ref, uint32_t cp) -> bool
-		{
-			const CpRanges& r = cpSets[ ref];
-			size_t lo = 0, hi = r.size();
-			while (lo < hi) { size_t mid = (lo+hi)/2; if (r[ mid].second < cp) lo = mid+1; else hi = mid; }
-			return lo < r.size() && r[ lo].first <= cp;
-		};
-		std::vector<uint8_t> flat( 0x110000, 0xFF);
-		std::map<uint64_t,uint32_t> classOfSig;
-		for (size_t ai=0; ai+1<cut.size(); ++ai)
-		{
-			const uint32_t cp = cut[ ai];
-			if (cp < 0x80 || cp >= 0x110000) continue;
-			unsigned char enc[4]; encodeUtf8( cp, enc);
-			const int cpCtx = (ucp && ucpWordCp( cp)) ? (int)CTX_WORD : (int)CTX_OTHER;
-			uint64_t sig = 1469598103934665603ull ^ (uint64_t)cpCtx;
-			uint32_t gp = 0;
-			for (size_t pi=0; pi<autos.size(); ++pi) for (size_t k=0; k<autos[ pi].pos.size(); ++k, ++gp)
-			{
-				const ByteSet& b = autos[ pi].pos[ k];
-				const bool in = (b.cpRef >= 0 ? inSet( b.cpRef, cp) : b.has( enc[0])) && (autos[ pi].ctxDef[ k] < 0 || autos[ pi].ctxDef[ k] == cpCtx);
-				if (in) sig = (sig ^ (gp+1)) * 1099511628211ull + 0x9E3779B97F4A7C15ull;
-			}
-			std::map<uint64_t,uint32_t>::const_iterator it = classOfSig.find( sig);
-			uint32_t cls;
-			if (it == classOfSig.end())
-			{
-				cls = T.nofClasses++;
-				if (cls > 254) throw std::runtime_error( "too many distinct character classes");
-				classOfSig[ sig] = cls; T.classCtx.push_back( (uint8_t)cpCtx); repCpOfClass.push_back( cp);
-			}
-			else cls = it->second;
-			for (uint32_t c=cp; c<cut[ ai+1]; ++c) flat[ c] = (uint8_t)cls;
-		}
-		std::map<std::string,uint16_t> pageOf;
-		for (uint32_t blk=0; blk<0x110000/64; ++blk)
-		{
-			std::string key( (const char*)&flat[ (size_t)blk*64], 64);
-			std::map<std::string,uint16_t>::const_iterator it = pageOf.find( key);
-			uint16_t page;
-			if (it == pageOf.end())
-			{
-				if (pageOf.size() >= 0xFFFF) throw std::runtime_error( "too many distinct character class pages");
-				page = (uint16_t)pageOf.size(); pageOf[ key] = page;
-				T.cpPages.insert( T.cpPages.end(), key.begin(), key.end());
-			}
-			else page = it->second;
-			T.cpBlocks.push_back( page);
-		}
+		std::string key( (const char*)&flat[ (size_t)blk*64], 64);
+		if (!pageOf.count( key) && pageOf.size() >= 0xFFFF) throw std::runtime_error( "too many distinct character class pages");
+		const auto at = pageOf.insert( std::make_pair( key, (uint16_t)pageOf.size()));
+		if (at.second) T.cpPages.insert( T.cpPages.end(), key.begin(), key.end());
+		T.cpBlocks.push_back( at.first->second);
 	}
-
-	// 4. masks
+	return repCpOfClass;
+}
+// the masks of every (pass, lane), and one exception row per distinct destination set of a word
+void masksAndExceptions( const Expressions& X, const Layout& L, uint32_t nofByteClasses, const std::vector<uint32_t>& repCpOfClass, LexTables& T)
+{
+	const uint32_t totalWords = T.nofPasses * L1_WORDS_PER_PASS;
 	T.charMask.assign( (size_t)T.nofPasses * T.nofClasses * 64, 0);
 	T.startMask.assign( (size_t)T.nofPasses * CTX_COUNT * 64, 0);
 	T.acceptMask.assign( (size_t)T.nofPasses * CTX_COUNT * 64, 0);
@@ -1539,13 +1522,13 @@ void LexCompiler::compile()
 	std::vector<std::map<uint64_t,uint64_t> > exBySrc( totalWords);	// src bit -> dst set (edges that are neither self loop nor shift)
 	std::vector<std::map<uint64_t,uint64_t> > exOfWord( totalWords);	// dst set -> src set
 	std::vector<unsigned> repOfClass( T.nofClasses, 0);
-	for (unsigned c=nofSymbols; c-->0;) repOfClass[ T.byteClass[ c]] = c;	// (byte classes by a symbol of theirs; the classes by code point come behind them)
-	for (size_t pi=0; pi<autos.size(); ++pi)
+	for (unsigned c=(X.ucp ? 320u : 256u); c-->0;) repOfClass[ T.byteClass[ c]] = c;	// (byte classes by a symbol of theirs; the classes by code point come behind them)
+	for (size_t pi=0; pi<X.autos.size(); ++pi)
 	{
-		const Automaton& a = autos[ pi];
-		if (T.patterns[ pi].word == L1_WORD_LITERAL) continue;
+		const Automaton& a = X.autos[ pi];
+		if (isLiteral( T.patterns[ pi])) continue;
 		const uint32_t w = T.patterns[ pi].word;
-		const std::vector<uint8_t>& bit = bitOf[ pi];
+		const std::vector<uint8_t>& bit = L.bitOf[ pi];
 		const uint32_t pass = w / 64, lane = w % 64;
 		const uint32_t n = (uint32_t)a.pos.size();
 		auto place = [&]( uint64_t local) -> uint64_t		// pattern-local position set -> bits of the word
@@ -1558,20 +1541,8 @@ void LexCompiler::compile()
 		{
 			for (uint32_t cls=0; cls<T.nofClasses; ++cls)
 			{
-				bool member;
-				if (cls < nofByteClasses) member = takesSymbol( a, k, repOfClass[ cls]);
-				else
-				{
-					const uint32_t cp = repCpOfClass[ cls - nofByteClasses];
-					if (a.pos[k].cpRef >= 0)
-					{
-						const CpRanges& r = cpSets[ a.pos[k].cpRef];
-						member = false;
-						for (size_t q=0; q<r.size() && !member; ++q) member = r[ q].first <= cp && cp <= r[ q].second;
-					}
-					else { unsigned char enc[4]; encodeUtf8( cp, enc); member = a.pos[k].has( enc[0]); }
-					if (member && a.ctxDef[ k] >= 0 && a.ctxDef[ k] != (int)T.classCtx[ cls]) member = false;
-				}
+				const bool member = cls < nofByteClasses ? takesSymbol( a, k, repOfClass[ cls])
+					: takesCodePoint( a, k, X.cpSets, repCpOfClass[ cls - nofByteClasses], (int)T.classCtx[ cls]);
 				if (member) T.charMask[ ((size_t)pass*T.nofClasses + cls)*64 + lane] |= 1ull << bit[ k];
 			}
 			uint64_t f = a.follow[ k];
@@ -1585,15 +1556,11 @@ void LexCompiler::compile()
 			T.acceptMask[ ((size_t)pass*CTX_COUNT + c)*64 + lane] |= place( a.accept[ c]);
 		}
 	}
-	// one exception row per distinct destination set of a word (sources with the same destinations share it)
+	T.maxExceptions = 0; T.exCount.assign( T.nofPasses, 0);
 	for (uint32_t w=0; w<totalWords; ++w)
 	{
+		// sources with the same destinations share a row
 		for (std::map<uint64_t,uint64_t>::const_iterator it=exBySrc[ w].begin(); it!=exBySrc[ w].end(); ++it) exOfWord[ w][ it->second] |= it->first;
-	}
-	T.maxExceptions = 0;
-	T.exCount.assign( T.nofPasses, 0);
-	for (uint32_t w=0; w<totalWords; ++w)
-	{
 		uint32_t n = (uint32_t)exOfWord[ w].size();
 		if (n > T.exCount[ w/64]) T.exCount[ w/64] = n;
 		if (n > T.maxExceptions) T.maxExceptions = n;
@@ -1609,112 +1576,175 @@ void LexCompiler::compile()
 			T.exDst[ at] = it->first; T.exSrc[ at] = it->second;
 		}
 	}
+}
+
+// ---- stage 4, the hash tables the kernels probe: open addressing in a zero-filled table of a power-of-two size >= 2n+1,
+//      linear probing from hash & (size-1); a slot is empty while its member `used` (the hash, the tag) is 0.
+//      Slots depend on the order of insertion: every builder below inserts in the order of its map.
+template <class Entry> void hashTableInit( std::vector<Entry>& table, size_t n)
+{
+	size_t size = 1;
+	while (size < n*2+1) size <<= 1;
+	Entry none; std::memset( &none, 0, sizeof(none));
+	table.assign( size, none);
+}
+template <class Entry> void hashTableInsert( std::vector<Entry>& table, uint32_t Entry::*used, uint32_t hash, const Entry& e)
+{
+	size_t slot = hash & (table.size()-1);
+	while (table[ slot].*used) slot = (slot+1) & (table.size()-1);
+	table[ slot] = e;
+}
+// whole-word literals: keyed by the word
+void literalTable( const std::map<std::string,std::vector<uint32_t> >& literalWords, LexTables& T)
+{
+	hashTableInit( T.literals, literalWords.size());
+	T.nofLiterals = (uint32_t)literalWords.size();
+	for (std::map<std::string,std::vector<uint32_t> >::const_iterator li=literalWords.begin(); li!=literalWords.end(); ++li)
+	{
+		uint32_t h = 0;
+		for (size_t k=0; k<li->first.size(); ++k) h = h * (uint32_t)L1_LITHASH_MUL + (uint32_t)(unsigned char)li->first[k] + 1u;
+		h = literalHashFinish( h); if (!h) h = 1;
+		DevLiteral e; std::memset( &e, 0, sizeof(e));
+		e.hash = h; e.textOffset = (uint32_t)T.literalText.size(); e.len = (uint32_t)li->first.size();
+		e.patBegin = (uint32_t)T.litPats.size(); e.patCount = (uint32_t)li->second.size();
+		T.literalText.insert( T.literalText.end(), li->first.begin(), li->first.end());
+		T.litPats.insert( T.litPats.end(), li->second.begin(), li->second.end());	// definition order = ascending
+		e.pat0 = li->second.front(); e.id0 = T.patterns[ e.pat0].id; e.levelBind0 = T.patterns[ e.pat0].levelBind;
+		for (size_t k=0; k<li->first.size() && k<sizeof(e.text); ++k) e.text[ k] = (uint8_t)li->first[ k];
+		hashTableInsert( T.literals, &DevLiteral::hash, h, e);
+	}
+	for (int pad=0; pad<4; ++pad) T.literalText.push_back( 0);	// (the kernel compares four bytes at a time)
+	if (T.litPats.empty()) T.litPats.push_back( 0);
+}
+// word shapes: keyed by (kind, place, literal bytes) -> expressions, ascending; and the compact form the kernel probes
+void shapeTable( const std::vector<std::pair<uint32_t,ShapeKey> >& shapeOf, LexTables& T)
+{
+	std::map<std::pair<uint32_t,uint32_t>,std::vector<uint32_t> > byKey;
+	for (size_t i=0; i<shapeOf.size(); ++i) byKey[ std::make_pair( shapeOf[ i].second.tag, shapeOf[ i].second.key)].push_back( shapeOf[ i].first);
+	hashTableInit( T.shapes, byKey.size());
+	T.nofShapes = (uint32_t)shapeOf.size();
+	std::set<uint32_t> variants;
+	for (std::map<std::pair<uint32_t,uint32_t>,std::vector<uint32_t> >::iterator ki=byKey.begin(); ki!=byKey.end(); ++ki)
+	{
+		std::sort( ki->second.begin(), ki->second.end());
+		DevShape e; e.tag = ki->first.first; e.key = ki->first.second;
+		e.patBegin = (uint32_t)T.shapePats.size(); e.patCount = (uint32_t)ki->second.size();
+		T.shapePats.insert( T.shapePats.end(), ki->second.begin(), ki->second.end());
+		hashTableInsert( T.shapes, &DevShape::tag, shapeSlotHash( e.tag, e.key), e);
+		variants.insert( shapeVariantOf( e.tag));
+	}
+	// compact form: fingerprints unique among the keys (another salt until they are)
+	T.shapeSalt = 0;
+	for (;; ++T.shapeSalt)
+	{
+		std::set<uint32_t> seen;
+		bool unique = true;
+		for (size_t i=0; i<T.shapes.size() && unique; ++i) if (T.shapes[ i].tag) unique = seen.insert( shapeFingerprint( T.shapes[ i].tag, T.shapes[ i].key, T.shapeSalt)).second;
+		if (unique) break;
+		if (T.shapeSalt > 1000) throw std::runtime_error( "internal: no salt makes the word shape fingerprints unique");
+	}
+	T.shapeFp.assign( T.shapes.size(), 0);
+	for (size_t i=0; i<T.shapes.size(); ++i)
+	{
+		const DevShape& e = T.shapes[ i];
+		if (!e.tag) continue;
+		if (e.patCount > 255 || e.patBegin >= (1u << 24)) throw std::runtime_error( "too many expressions share one word shape key");
+		const uint32_t info = (e.patCount << 24) | (e.patCount == 1 ? T.shapePats[ e.patBegin] : e.patBegin);
+		T.shapeFp[ i] = (uint64_t)shapeFingerprint( e.tag, e.key, T.shapeSalt) | ((uint64_t)info << 32);
+	}
+	T.shapeVariants.assign( variants.begin(), variants.end());
+	if (T.shapeVariants.size() > SHAPE_MAXVARIANTS) throw std::runtime_error( "internal: too many word shape variants");
+	if (T.shapePats.empty()) T.shapePats.push_back( 0);
+}
+// symbols: one table keyed by (lexem id, text)
+void symbolTable( const SymbolTables& symbols, LexTables& T)
+{
+	size_t count = 0;
+	for (SymbolTables::const_iterator t=symbols.begin(); t!=symbols.end(); ++t) count += t->second.size();
+	hashTableInit( T.symbols, count);
+	for (SymbolTables::const_iterator t=symbols.begin(); t!=symbols.end(); ++t)
+	{
+		for (std::map<std::string,uint32_t>::const_iterator s=t->second.begin(); s!=t->second.end(); ++s)
+		{
+			uint32_t h = 2166136261u;
+			for (int b=0; b<4; ++b) h = symbolHashStep( h, (t->first >> (8*b)) & 0xFF);
+			for (size_t k=0; k<s->first.size(); ++k) h = symbolHashStep( h, (unsigned char)s->first[k]);
+			if (!h) h = 1;
+			DevSymbol e; std::memset( &e, 0, sizeof(e));
+			e.hash = h; e.lexemId = t->first; e.textOffset = (uint32_t)T.symbolText.size(); e.len = (uint32_t)s->first.size(); e.symbolId = s->second;
+			T.symbolText.insert( T.symbolText.end(), s->first.begin(), s->first.end());
+			hashTableInsert( T.symbols, &DevSymbol::hash, h, e);
+		}
+	}
+	if (T.symbolText.empty()) T.symbolText.push_back( 0);
+}
+
+// ---- stage 5: do the tables fit together?  What the kernels index by is checked here for the tables of compile() and of load() alike
+bool validateTables( const LexTables& T, size_t nofDefs)
+{
+	if (T.shapeFp.size() != T.shapes.size()) return false;
+	if (T.scanPasses > T.nofPasses || T.scanWords > T.scanPasses*64 || T.shapes.empty() || (T.shapes.size() & (T.shapes.size()-1)) || T.shapeVariants.size() > SHAPE_MAXVARIANTS || T.shapePats.empty()) return false;
+	for (size_t i=0; i<T.shapes.size(); ++i) if (T.shapes[ i].tag && (uint64_t)T.shapes[ i].patBegin + T.shapes[ i].patCount > T.shapePats.size()) return false;
+	for (size_t i=0; i<T.shapePats.size(); ++i) if (T.shapePats[ i] >= T.patterns.size() && !T.patterns.empty()) return false;
+	// the shapes the kernel indexes by must fit together (a blob of another build would fault on the device)
+	if (T.byteClass.size() != (T.ucp ? 320u : 256u) || (T.ucp && T.cpBlocks.empty()) || T.classCtx.size() != T.nofClasses
+	||  T.charMask.size() != (size_t)T.nofPasses*T.nofClasses*64 || T.startMask.size() != (size_t)T.nofPasses*CTX_COUNT*64 || T.acceptMask.size() != T.startMask.size()
+	||  T.shiftDst.size() != (size_t)T.nofPasses*64 || T.selfLoop.size() != T.shiftDst.size() || T.exCount.size() != T.nofPasses
+	||  T.exSrc.size() != (size_t)T.nofPasses*(T.maxExceptions ? T.maxExceptions : 1)*64 || T.exDst.size() != T.exSrc.size()
+	||  T.patOfBit.size() != (size_t)T.nofPasses*64*64
+	||  T.symbols.empty() || (T.symbols.size() & (T.symbols.size()-1)) || T.literals.empty() || (T.literals.size() & (T.literals.size()-1))) return false;
+	for (size_t i=0; i<T.byteClass.size(); ++i) if (T.byteClass[ i] >= T.nofClasses) return false;
+	if (!T.cpBlocks.empty())
+	{
+		if (T.cpBlocks.size() != 0x110000/64 || T.cpPages.size() % 64) return false;
+		for (size_t i=0; i<T.cpBlocks.size(); ++i) if ((size_t)T.cpBlocks[ i]*64 + 64 > T.cpPages.size()) return false;
+		for (size_t i=0; i<T.cpPages.size(); ++i) if (T.cpPages[ i] != 0xFF && T.cpPages[ i] >= T.nofClasses) return false;
+	}
+	if (T.patterns.size() < nofDefs || (!T.approx.empty() && T.approx.size() != nofDefs)) return false;
+	for (size_t i=0; i<T.patterns.size(); ++i) if (T.patterns[ i].defIndex >= nofDefs || (i && T.patterns[ i].defIndex < T.patterns[ i-1].defIndex)) return false;
+	for (size_t i=0; i<T.nullable.size(); ++i) if (T.nullable[ i].pattern >= T.patterns.size() || T.nullable.size() > 64) return false;
+	for (size_t i=0; i<T.approx.size(); ++i)
+		if (T.approx[ i].len == 0 || T.approx[ i].len > L1_APPROX_MAXCHARS || T.approx[ i].editdist > L1_APPROX_MAXDIST || T.approx[ i].editdist >= T.approx[ i].len || T.approx.size() > L1_APPROX_MAXPATTERNS) return false;
+	return true;
+}
+
+} // namespace
+
+// src/patternLexer.cpp:1068-1118 (+ PatternTable::complete :333-412).  Builds into tables of its own: a compile() that throws leaves the object as it was
+void LexCompiler::compile()
+{
+	const CompileSwitches sw = CompileSwitches::fromEnv();
+	LexTables T = LexTables();
+	Expressions X = compileExpressions( m_defs, m_options, m_symbols, T);
+	selectShapes( X, sw, m_options, T.patterns);
+	if (T.patterns.size() >= (1u << 24)) throw std::runtime_error( "too many patterns");
+	Layout L( X.autos.size());
+	L.words = L.scanWords = layoutInOrder( X.autos, X.scanned, 0, L);
+	if (layoutBySize( X, L)) L.scanWords = L.words;
+	// the passes the scan kernel runs end here; the word shapes follow in passes of their own (in definition order)
+	L.words = layoutInOrder( X.autos, X.isShape, (L.scanWords + L1_WORDS_PER_PASS-1) / L1_WORDS_PER_PASS * L1_WORDS_PER_PASS, L);
+	const bool shared = layoutSharedFirstPosition( X.autos, T.patterns, sw, L);
+	T.scanWords = L.scanWords; T.scanPasses = (L.scanWords + L1_WORDS_PER_PASS-1) / L1_WORDS_PER_PASS;
+	T.nofPositions = L.nofPositions; T.reportsOrdered = L.reportsOrdered;
+	T.lanesOk = true;
+	for (size_t pi=0; pi<X.autos.size() && T.lanesOk; ++pi) if (X.scanned[ pi] && staysLiveAcrossBlank( X.autos[ pi])) T.lanesOk = false;
+
+	wordPatternLists( X.autos, L, T);
+	T.ucp = X.ucp;
+	byteClasses( X.autos, X.ucp, T);
+	const uint32_t nofByteClasses = T.nofClasses;
+	const std::vector<uint32_t> repCpOfClass = codePointClasses( X.autos, X.cpSets, X.ucp, T);
+	masksAndExceptions( X, L, nofByteClasses, repCpOfClass, T);
 
 	// (the empty-match reports of ALLOWEMPTY are appended behind the automaton's reports of an offset: sort every offset's group)
 	if (T.nullable.size() > 64) throw std::runtime_error( "too many expressions that match the empty string (ALLOWEMPTY: at most 64)");
 	if (!T.nullable.empty()) T.reportsOrdered = false;
-
-	// 4b. whole-word literals: hash table keyed by the word
-	{
-		size_t size = 1;
-		while (size < literalWords.size()*2+1) size <<= 1;
-		DevLiteral none; std::memset( &none, 0, sizeof(none));
-		T.literals.assign( size, none);
-		T.literalText.clear(); T.litPats.clear();
-		T.nofLiterals = (uint32_t)literalWords.size();
-		for (std::map<std::string,std::vector<uint32_t> >::const_iterator li=literalWords.begin(); li!=literalWords.end(); ++li)
-		{
-			uint32_t h = 0;
-			for (size_t k=0; k<li->first.size(); ++k) h = h * (uint32_t)L1_LITHASH_MUL + (uint32_t)(unsigned char)li->first[k] + 1u;
-			h = literalHashFinish( h);
-			if (!h) h = 1;
-			DevLiteral e; std::memset( &e, 0, sizeof(e));
-			e.hash = h; e.textOffset = (uint32_t)T.literalText.size(); e.len = (uint32_t)li->first.size();
-			e.patBegin = (uint32_t)T.litPats.size(); e.patCount = (uint32_t)li->second.size();
-			T.literalText.insert( T.literalText.end(), li->first.begin(), li->first.end());
-			T.litPats.insert( T.litPats.end(), li->second.begin(), li->second.end());	// definition order = ascending
-			e.pat0 = li->second.front(); e.id0 = T.patterns[ e.pat0].id; e.levelBind0 = T.patterns[ e.pat0].levelBind;
-			for (size_t k=0; k<li->first.size() && k<sizeof(e.text); ++k) e.text[ k] = (uint8_t)li->first[ k];
-			size_t slot = h & (size-1);
-			while (T.literals[ slot].hash) slot = (slot+1) & (size-1);
-			T.literals[ slot] = e;
-		}
-		for (int pad=0; pad<4; ++pad) T.literalText.push_back( 0);	// (the kernel compares four bytes at a time)
-		if (T.litPats.empty()) T.litPats.push_back( 0);
-	}
-
-	// 4c. word shapes: hash table keyed by (kind, place, literal bytes) -> expressions, ascending
-	{
-		std::map<std::pair<uint32_t,uint32_t>,std::vector<uint32_t> > byKey;
-		for (size_t i=0; i<shapeOf.size(); ++i) byKey[ std::make_pair( shapeOf[ i].second.tag, shapeOf[ i].second.key)].push_back( shapeOf[ i].first);
-		size_t size = 1;
-		while (size < byKey.size()*2+1) size <<= 1;
-		DevShape none; std::memset( &none, 0, sizeof(none));
-		T.shapes.assign( size, none);
-		T.shapePats.clear(); T.shapeVariants.clear();
-		std::set<uint32_t> variants;
-		for (std::map<std::pair<uint32_t,uint32_t>,std::vector<uint32_t> >::iterator ki=byKey.begin(); ki!=byKey.end(); ++ki)
-		{
-			std::sort( ki->second.begin(), ki->second.end());
-			DevShape e; e.tag = ki->first.first; e.key = ki->first.second;
-			e.patBegin = (uint32_t)T.shapePats.size(); e.patCount = (uint32_t)ki->second.size();
-			T.shapePats.insert( T.shapePats.end(), ki->second.begin(), ki->second.end());
-			size_t slot = shapeSlotHash( e.tag, e.key) & (size-1);
-			while (T.shapes[ slot].tag) slot = (slot+1) & (size-1);
-			T.shapes[ slot] = e;
-			variants.insert( (e.tag & 3u) == (uint32_t)SHAPE_PREVWORD ? (uint32_t)SHAPE_PREVWORD : e.tag);
-		}
-		// compact form: fingerprints unique among the keys (another salt until they are)
-		T.shapeSalt = 0;
-		for (;; ++T.shapeSalt)
-		{
-			std::set<uint32_t> seen;
-			bool unique = true;
-			for (size_t i=0; i<T.shapes.size() && unique; ++i) if (T.shapes[ i].tag) unique = seen.insert( shapeFingerprint( T.shapes[ i].tag, T.shapes[ i].key, T.shapeSalt)).second;
-			if (unique) break;
-			if (T.shapeSalt > 1000) throw std::runtime_error( "internal: no salt makes the word shape fingerprints unique");
-		}
-		T.shapeFp.assign( T.shapes.size(), 0);
-		for (size_t i=0; i<T.shapes.size(); ++i)
-		{
-			const DevShape& e = T.shapes[ i];
-			if (!e.tag) continue;
-			if (e.patCount > 255 || e.patBegin >= (1u << 24)) throw std::runtime_error( "too many expressions share one word shape key");
-			const uint32_t info = (e.patCount << 24) | (e.patCount == 1 ? T.shapePats[ e.patBegin] : e.patBegin);
-			T.shapeFp[ i] = (uint64_t)shapeFingerprint( e.tag, e.key, T.shapeSalt) | ((uint64_t)info << 32);
-		}
-		T.shapeVariants.assign( variants.begin(), variants.end());
-		if (T.shapeVariants.size() > SHAPE_MAXVARIANTS) throw std::runtime_error( "internal: too many word shape variants");
-		if (T.shapePats.empty()) T.shapePats.push_back( 0);
-	}
-
-	// 5. symbols: one hash table keyed by (lexem id, text)
-	{
-		size_t count = 0;
-		for (std::map<uint32_t, std::map<std::string,uint32_t> >::const_iterator t=m_symbols.begin(); t!=m_symbols.end(); ++t) count += t->second.size();
-		size_t size = 1;
-		while (size < count*2+1) size <<= 1;
-		DevSymbol none; std::memset( &none, 0, sizeof(none));
-		T.symbols.assign( size, none);
-		T.symbolText.clear();
-		for (std::map<uint32_t, std::map<std::string,uint32_t> >::const_iterator t=m_symbols.begin(); t!=m_symbols.end(); ++t)
-		{
-			for (std::map<std::string,uint32_t>::const_iterator s=t->second.begin(); s!=t->second.end(); ++s)
-			{
-				uint32_t h = 2166136261u;
-				for (int b=0; b<4; ++b) h = symbolHashStep( h, (t->first >> (8*b)) & 0xFF);
-				for (size_t k=0; k<s->first.size(); ++k) h = symbolHashStep( h, (unsigned char)s->first[k]);
-				if (!h) h = 1;
-				DevSymbol e; std::memset( &e, 0, sizeof(e));
-				e.hash = h; e.lexemId = t->first; e.textOffset = (uint32_t)T.symbolText.size(); e.len = (uint32_t)s->first.size(); e.symbolId = s->second;
-				T.symbolText.insert( T.symbolText.end(), s->first.begin(), s->first.end());
-				size_t slot = h & (size-1);
-				while (T.symbols[ slot].hash) slot = (slot+1) & (size-1);
-				T.symbols[ slot] = e;
-			}
-		}
-		if (T.symbolText.empty()) T.symbolText.push_back( 0);
-	}
+	literalTable( X.literalWords, T);
+	shapeTable( X.shapeOf, T);
+	symbolTable( m_symbols, T);
+	// (the shared first position leaves scanPasses and scanWords as they were before it: such tables are not checked, and do not load)
+	if (!shared && !validateTables( T, m_defs.size())) throw std::logic_error( "internal: the compiled lexer tables have inconsistent shapes");
+	m_tables = std::move( T);
 	m_compiled = true;
 }
 
@@ -1735,7 +1765,7 @@ void LexCompiler::save( std::vector<uint8_t>& out) const
 	w.u32( (uint32_t)m_defs.size());
 	for (size_t i=0; i<m_defs.size(); ++i)
 	{
-		const Def& d = m_defs[ i];
+		const LexDef& d = m_defs[ i];
 		w.str( d.expression); w.u32( d.id); w.u32( d.resultIndex); w.u32( d.level); w.u32( d.editdist); w.u32( (uint32_t)d.posbind);
 	}
 	w.u32( (uint32_t)m_symbols.size());
@@ -1753,64 +1783,31 @@ void LexCompiler::load( const void* blob, size_t size)
 {
 	BlobReader r( blob, size, L1_MAGIC);
 	LexTables T;
-	m_options = r.u32();
+	const unsigned options = r.u32();
 	T.nofPasses = r.u32(); T.nofClasses = r.u32(); T.maxExceptions = r.u32(); T.nofLiterals = r.u32(); T.nofPositions = r.u32(); T.reportsOrdered = r.u32() != 0; T.ucp = r.u32() != 0;
 	r.vec( T.byteClass); r.vec( T.classCtx); r.vec( T.cpBlocks); r.vec( T.cpPages); r.vec( T.charMask); r.vec( T.startMask); r.vec( T.acceptMask); r.vec( T.shiftDst); r.vec( T.selfLoop);
 	r.vec( T.exCount); r.vec( T.exSrc); r.vec( T.exDst); r.vec( T.wordPatBegin); r.vec( T.wordPats); r.vec( T.patOfBit);
 	r.vec( T.patterns); r.vec( T.symbols); r.vec( T.symbolText); r.vec( T.literals); r.vec( T.literalText); r.vec( T.litPats); r.vec( T.approx); r.vec( T.nullable);
 	T.scanPasses = r.u32(); T.scanWords = r.u32(); T.lanesOk = r.u32() != 0; T.nofShapes = r.u32(); r.vec( T.shapes); r.vec( T.shapePats); r.vec( T.shapeVariants); r.vec( T.shapeFp); T.shapeSalt = r.u32();
-	if (T.shapeFp.size() != T.shapes.size()) throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-	if (T.scanPasses > T.nofPasses || T.scanWords > T.scanPasses*64 || T.shapes.empty() || (T.shapes.size() & (T.shapes.size()-1)) || T.shapeVariants.size() > SHAPE_MAXVARIANTS || T.shapePats.empty())
-	{
-		throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-	}
-	for (size_t i=0; i<T.shapes.size(); ++i) if (T.shapes[ i].tag && (uint64_t)T.shapes[ i].patBegin + T.shapes[ i].patCount > T.shapePats.size()) throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-	for (size_t i=0; i<T.shapePats.size(); ++i) if (T.shapePats[ i] >= T.patterns.size() && !T.patterns.empty()) throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-	// the shapes the kernel indexes by must fit together (a blob of another build would fault on the device)
-	if (T.byteClass.size() != (T.ucp ? 320u : 256u) || (T.ucp && T.cpBlocks.empty()) || T.classCtx.size() != T.nofClasses
-	||  T.charMask.size() != (size_t)T.nofPasses*T.nofClasses*64 || T.startMask.size() != (size_t)T.nofPasses*CTX_COUNT*64 || T.acceptMask.size() != T.startMask.size()
-	||  T.shiftDst.size() != (size_t)T.nofPasses*64 || T.selfLoop.size() != T.shiftDst.size() || T.exCount.size() != T.nofPasses
-	||  T.exSrc.size() != (size_t)T.nofPasses*(T.maxExceptions ? T.maxExceptions : 1)*64 || T.exDst.size() != T.exSrc.size()
-	||  T.patOfBit.size() != (size_t)T.nofPasses*64*64
-	||  T.symbols.empty() || (T.symbols.size() & (T.symbols.size()-1)) || T.literals.empty() || (T.literals.size() & (T.literals.size()-1)))
-	{
-		throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-	}
-	for (size_t i=0; i<T.byteClass.size(); ++i) if (T.byteClass[ i] >= T.nofClasses) throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-	if (!T.cpBlocks.empty())
-	{
-		if (T.cpBlocks.size() != 0x110000/64 || T.cpPages.size() % 64) throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-		for (size_t i=0; i<T.cpBlocks.size(); ++i) if ((size_t)T.cpBlocks[ i]*64 + 64 > T.cpPages.size()) throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-		for (size_t i=0; i<T.cpPages.size(); ++i) if (T.cpPages[ i] != 0xFF && T.cpPages[ i] >= T.nofClasses) throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-	}
-	m_defs.clear(); m_symbols.clear(); m_names.clear();
+	std::vector<LexDef> defs; SymbolTables symbols; std::map<uint32_t,std::string> names;
 	const uint32_t nd = r.u32();
 	for (uint32_t i=0; i<nd; ++i)
 	{
-		Def d; d.expression = r.str(); d.id = r.u32(); d.resultIndex = r.u32(); d.level = r.u32(); d.editdist = r.u32(); d.posbind = (int)r.u32();
-		m_defs.push_back( d);
+		LexDef d; d.expression = r.str(); d.id = r.u32(); d.resultIndex = r.u32(); d.level = r.u32(); d.editdist = r.u32(); d.posbind = (int)r.u32();
+		defs.push_back( d);
 	}
-	if (T.patterns.size() < m_defs.size() || (!T.approx.empty() && T.approx.size() != m_defs.size())) throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-	for (size_t i=0; i<T.patterns.size(); ++i)
-	{
-		if (T.patterns[ i].defIndex >= m_defs.size() || (i && T.patterns[ i].defIndex < T.patterns[ i-1].defIndex)) throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-	}
-	for (size_t i=0; i<T.nullable.size(); ++i) if (T.nullable[ i].pattern >= T.patterns.size() || T.nullable.size() > 64) throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-	for (size_t i=0; i<T.approx.size(); ++i)
-	{
-		if (T.approx[ i].len == 0 || T.approx[ i].len > L1_APPROX_MAXCHARS || T.approx[ i].editdist > L1_APPROX_MAXDIST || T.approx[ i].editdist >= T.approx[ i].len || T.approx.size() > L1_APPROX_MAXPATTERNS)
-			throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
-	}
+	if (!validateTables( T, defs.size())) throw std::runtime_error( "compiled lexer blob has inconsistent table shapes");
 	const uint32_t nt = r.u32();
 	for (uint32_t i=0; i<nt; ++i)
 	{
 		const uint32_t id = r.u32(), n = r.u32();
-		std::map<std::string,uint32_t>& tab = m_symbols[ id];
+		std::map<std::string,uint32_t>& tab = symbols[ id];
 		for (uint32_t k=0; k<n; ++k) { const std::string name = r.str(); tab[ name] = r.u32(); }
 	}
 	const uint32_t nn = r.u32();
-	for (uint32_t i=0; i<nn; ++i) { const uint32_t id = r.u32(); m_names[ id] = r.str(); }
+	for (uint32_t i=0; i<nn; ++i) { const uint32_t id = r.u32(); names[ id] = r.str(); }
 	if (!r.atEnd()) throw std::runtime_error( "compiled lexer blob has trailing data");
-	m_tables = T;
+	m_options = options; m_defs.swap( defs); m_symbols.swap( symbols); m_names.swap( names);
+	m_tables = std::move( T);
 	m_compiled = true;
 }

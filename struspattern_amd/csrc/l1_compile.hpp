@@ -61,6 +61,13 @@ struct LexTables
 	bool reportsOrdered;			// patterns sit in the words in definition order (else the kernel sorts the reports of one end offset)
 };
 
+struct LexDef					// one defineLexem call
+{
+	std::string expression;
+	uint32_t id, resultIndex, level, editdist;
+	int posbind;
+};
+
 class LexCompiler
 {
 public:
@@ -83,13 +90,7 @@ public:
 	void load( const void* blob, size_t size);
 
 private:
-	struct Def
-	{
-		std::string expression;
-		uint32_t id, resultIndex, level, editdist;
-		int posbind;
-	};
-	std::vector<Def> m_defs;
+	std::vector<LexDef> m_defs;
 	std::map<uint32_t, std::map<std::string,uint32_t> > m_symbols;
 	std::map<uint32_t,std::string> m_names;
 	unsigned m_options;

@@ -1,14 +1,13 @@
 """CPU-side tests of the product's regex compiler (no GPU): the compiled bit-parallel tables,
 executed by the pure-Python table interpreter in tests/l1_table_sim.py, must produce the same raw
 report stream (pattern, leftmost start, end) as the CPU oracle and as Python's `re`."""
-import random
 import re
 
 import pytest
 
 import oracle
 import struspattern_amd as spa
-from tests import l1_cases
+from tests import l1_cases, l1_compile_corpus
 from tests.l1_table_sim import Tables
 
 
@@ -42,25 +41,7 @@ def test_golden_patterns_raw_reports():
 
 @pytest.mark.parametrize("seed", range(8))
 def test_random_regex_tables_vs_oracle_and_python_re(seed):
-    rng = random.Random(1000 + seed)
-    for _ in range(25):
-        pats = []
-        while len(pats) < rng.randint(1, 6):
-            p = l1_cases.random_regex(rng)
-            try:
-                re.compile(p)
-            except re.error:
-                continue
-            try:        # documented limit of this version: 64 byte positions per expression
-                one = spa.PatternLexerInstance()
-                one.defineOption("DOTALL")
-                one.defineLexem(1, p, 0, 1, "content")
-                one.compile()
-            except spa.PatternError as e:
-                assert "too complex" in str(e) or "matches empty buffer" in str(e), str(e)
-                continue
-            pats.append(p)
-        text = l1_cases.random_text(rng, rng.randint(0, 30)).encode()
+    for pats, text in l1_compile_corpus.random_regex_sets(seed):
         got = _product_reports(pats, text)
         assert got == _oracle_reports(pats, text), (pats, text)
         for i, p in enumerate(pats):
