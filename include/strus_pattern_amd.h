@@ -141,6 +141,24 @@ int sp_matcher_fast_tier(const sp_matcher_t* m, char* why, size_t whysize);
  * engine, `why` says what disqualifies it (programs of more or fewer than two terms, nested programs, `and`, more than one
  * delimiter, the `exclusive` option -- whose outcome depends on the order of the results). */
 int sp_matcher_result_set_tier(const sp_matcher_t* m, char* why, size_t whysize, uint32_t* alt_programs);
+/* What a context created now with `ctx_flags` (sp_matcher_ctx_create_ex) on a device of num_cus compute units (0 = 256), where
+ * fast_blocks_per_cu workgroups of the LDS-resident kernel fit a compute unit, launches for a batch of ndocs documents and nlexems
+ * lexems, and why -- the decisions of csrc/l2_plan.hpp without a device.  rerun_docs > 0: the partial rerun of that many documents
+ * of the batch; arena_grows: after that many sp_matcher_ctx_grow_arena; min_results, min_items: what sp_matcher_ctx_reserve_output
+ * has reserved.  Writes key=value fields, one per line (the reasons are texts with blanks):
+ *   engine            general | flat | join, kind = what sp_matcher_ctx_kernel_kind returns, kernel = sp_matcher_ctx_kernel_name
+ *   flat_why_not, join_why_not   empty for an engine the rule set can run on; alt_programs as sp_matcher_result_set_tier
+ *   route             general | flat+list | join | rerun-list: the kernels of this launch
+ *   general_blocks, arena_run, arena_alloc, arena_alloc_waves (the waves allocated when the arena has to grow),
+ *   arena_per_wave_bytes, arena_max_rules, arena_scratch_cap, stop_words      the general kernel and its per-wave arena
+ *   fast_blocks, spill_alloc_waves, spill_per_wave_bytes, list_blocks         the LDS-resident kernel, the general one behind it
+ *   join_blocks, want_results, want_items (capacities of the output buffers, which only grow)
+ *   R, T, exp_shift, spill_words, max_rules, max_staged, bucket_caps (16, comma separated)   the LDS-resident kernel's layout
+ * The SPA_L2_* switches of the environment count as they do for a context created now.  SP_ERR_INVALID when the arena cannot
+ * grow that often, for a batch of too many documents or when the text does not fit bufsize. */
+int sp_matcher_launch_plan(const sp_matcher_t* m, uint32_t ctx_flags, unsigned num_cus, unsigned fast_blocks_per_cu,
+                           size_t ndocs, size_t nlexems, size_t rerun_docs, uint32_t arena_grows,
+                           uint64_t min_results, uint64_t min_items, char* buf, size_t bufsize);
 
 /* Compiled-table serialisation (the reference has none -- every process recompiles, and with
  * Hyperscan that takes seconds for 10k patterns, src/patternLexer.cpp:1068-1118): the rule set with its key

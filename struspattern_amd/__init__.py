@@ -362,6 +362,14 @@ class PatternMatcherInstance:
         ok = self._L.sp_matcher_result_set_tier(self._h, buf, 256, ctypes.byref(alt))
         return bool(ok), buf.value.decode(), int(alt.value)
 
+    def launchPlan(self, num_cus, ndocs, nlexems, result_sets=False, fast_blocks_per_cu=16, rerun_docs=0, arena_grows=0, min_results=0, min_items=0):
+        """what a context created now (createContext(result_sets=...)) on a device of num_cus compute units launches for a batch of
+        ndocs documents and nlexems lexems, as a dict of strings (include/strus_pattern_amd.h, sp_matcher_launch_plan); needs no device"""
+        buf = ctypes.create_string_buffer(2048)
+        self._chk(self._L.sp_matcher_launch_plan(self._h, 1 if result_sets else 0, num_cus, fast_blocks_per_cu, ndocs, nlexems, rerun_docs, arena_grows,
+                                                 min_results, min_items, buf, 2048), "no launch plan")
+        return dict(f.split("=", 1) for f in buf.value.decode().split("\n") if f)
+
     def dumpTable(self):
         p = ctypes.POINTER(ctypes.c_uint32)()
         n = self._L.sp_matcher_dump_table(self._h, ctypes.byref(p))

@@ -89,6 +89,7 @@ SIGNATURES = {
     "sp_matcher_dump_table": (ctypes.c_size_t, [c_vp, P(P(c_u32))]),
     "sp_matcher_fast_tier": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_result_set_tier": (ctypes.c_int, [c_vp, ctypes.c_char_p, ctypes.c_size_t, P(c_u32)]),
+    "sp_matcher_launch_plan": (ctypes.c_int, [c_vp, c_u32, ctypes.c_uint, ctypes.c_uint, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t, c_u32, c_u64, c_u64, ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_serialize": (ctypes.c_int, [c_vp, P(c_vp), P(ctypes.c_size_t)]),
     "sp_matcher_deserialize": (c_vp, [c_vp, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t]),
     "sp_lexer_serialize": (ctypes.c_int, [c_vp, P(c_vp), P(ctypes.c_size_t)]),

@@ -3,6 +3,7 @@
 #include "l1_compile.hpp"
 #include "l1_image.hpp"
 #include "l1_launch.h"
+#include "l2_plan.hpp"		// arenaWaves: the policy of a per-wave arena
 #include "capi_util.hpp"
 #include <cstdio>
 

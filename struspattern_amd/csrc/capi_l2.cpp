@@ -1,18 +1,11 @@
 // C-ABI of level 2 (include/strus_pattern_amd.h): rule compiler handle + GPU match context.
 // No CPU fallback: a context cannot be created without a usable HIP device.
-#include "l2_compile.hpp"
-#include "l2_device.h"
-#include "l2_fast.h"
-#include "l2_join.h"
+#include "l2_plan.hpp"
 #include "l2_finish.h"
 #include "capi_util.hpp"
 #include <cstdio>
 
 using namespace spa;
-
-#ifndef SPA_L2_WAVES_PER_CU
-#define SPA_L2_WAVES_PER_CU 12
-#endif
 
 struct sp_matcher
 {
@@ -21,74 +14,37 @@ struct sp_matcher
 	mutable std::string lasterror;
 };
 
-// the one statement of the policy declared in hip_util.hpp
-ArenaWaves spa::arenaWaves( size_t perWaveBytes, unsigned wanted, size_t fullSlots, unsigned multiple)
-{
-	const size_t fit = ((size_t)48 << 30) / perWaveBytes;
-	const size_t maxRun = fit < 4 ? 4 : fit;
-	const size_t full = fullSlots < fit ? fullSlots : fit;
-	ArenaWaves w;
-	w.run = wanted > maxRun ? (unsigned)(maxRun / multiple * multiple) : wanted;
-	w.alloc = (w.run >= 64 && w.run < full) ? (unsigned)full : w.run;
-	return w;
-}
-
 namespace {
 
-uint32_t alignUp( uint32_t v, uint32_t a) { return (v + a-1) / a * a; }
-
-void layoutArena( ArenaLayout& L)
+// which kernel serves the rule set under `flags` and `sw` (l2_plan.hpp), with its tables
+L2Engine engineOf( const sp_matcher* m, uint32_t flags, const L2Switches& sw, FlatTables& ft)
 {
-	uint32_t o = 0;
-	L.oRules = o;	o += L.maxRules*32;			// 128-byte blocks: rule + its 4 trigger slots
-	L.oTrigs = 0; L.oBIdx = 0; L.oTrigFree = 0;		// (unused: triggers live in the rule blocks)
-	L.oBEvent = o;	o += alignUp( 2*16*L.bucketCap, 32);	// {event, trigger id} pairs
-	L.oBSize = o;	o += 16;
-	L.oWindow = o;	o += 64;
-	L.oHeap = o;	o += alignUp( L.maxHeap*2, 4);
-	L.oFollow = o;	o += alignUp( L.maxFollow*12, 4);
-	L.oDispose = o;	o += alignUp( L.maxDispose, 4);
-	L.oStop = o;	o += alignUp( (L.nStop?L.nStop:1)*12, 4);
-	L.oItems = o;	o += alignUp( L.maxItems*12, 4);
-	L.oRefs = o;	o += alignUp( L.maxRefs*2, 4);
-	L.oGStack = o;	o += alignUp( L.maxGStack, 4);
-	L.oStaged = o;	o += alignUp( L.maxStaged*8, 4);
-	L.oRuleFree = o; o += alignUp( L.maxRules, 4);
-	L.oItemFree = o; o += alignUp( L.maxItems, 4);
-	L.oRefFree = o;	o += alignUp( L.maxRefs, 4);
-	// expiry window: lists of up to 8 chunks per position; the pool covers every live rule plus one
-	// partly filled chunk per position
-	L.winChunk = L.winCap/8 < 16 ? 16 : L.winCap/8;
-	L.winChunks = L.maxRules/L.winChunk + 64;
-	L.oWinArr = o;	o += alignUp( L.winChunks*L.winChunk, 4);
-	L.oWinChunk = o; o += 64*8;
-	L.oWinFree = o;	o += alignUp( L.winChunks, 4);
-	L.oScratch = o;	o += alignUp( 16*L.scratchCap, 4);
-	L.totalWords = alignUp( o, 64);
+	m->compiler.flatten( ft);
+	return chooseL2Engine( m->compiler, ft, flags, sw);
 }
 
-ArenaLayout initialArena()
+// the flat tier's kernel instance (l2_fast_kernel.hip) and layout for the rule set
+FlatPlan flatPlanOf( const L2Engine& e, const L2Switches& sw)
 {
-	// small defaults (a document's hot state should stay cache and TLB friendly); every capacity
-	// doubles automatically when a document overflows it (SP_DOC_ERR_ARENA -> grow -> rerun)
-	ArenaLayout a;
-	std::memset( &a, 0, sizeof(a));
-	a.maxRules = 1024; a.maxTrigs = 1024; a.bucketCap = 256; a.maxItems = 2048;
-	a.maxRefs = 1024; a.maxFollow = 256; a.maxDispose = 512; a.maxHeap = 256;
-	a.maxGStack = 64; a.maxStaged = 1024; a.winCap = 128; a.scratchCap = 256;
-	return a;
+	// SPA_L2_FAST_SIZE=s|m|l picks the kernel instance (LDS capacities; t = the tiny one of the tests); the spill area takes what does not fit
+	const char size[ 2] = {sw.fastSize, 0};
+	const unsigned variant = fastVariantNamed( size);
+	uint32_t R = 0, T = 0;
+	fastCapacities( variant, R, T);
+	return planFlat( e.flat, variant, fastKernelName( variant), R, T);
 }
 
-// sp_matcher_*_tier: 1 when `reasonOf` the flat tables of the rule set is empty, else 0 with the reason (or the error) in `why`
-template <class FN>
-int tierOf( const sp_matcher* m, char* why, size_t whysize, FN reasonOf)
+// sp_matcher_*_tier: 1 when the engine chosen without any switch is `kind`, else 0 with the reason (or the error) in `why`
+int tierQuery( const sp_matcher* m, uint32_t flags, L2EngineKind kind, char* why, size_t whysize, uint32_t* altPrograms)
 {
+	if (altPrograms) *altPrograms = 0;
 	try
 	{
 		FlatTables ft;
-		m->compiler.flatten( ft);
-		const std::string reason = reasonOf( ft);
+		const L2Engine e = engineOf( m, flags, L2Switches(), ft);
+		const std::string& reason = kind == L2_JOIN ? e.join.whyNot : e.flat.whyNot;
 		copyText( why, whysize, reason.c_str());
+		if (altPrograms) *altPrograms = e.altPrograms;
 		return reason.empty() ? 1 : 0;
 	}
 	catch (const std::exception& e)
@@ -105,6 +61,8 @@ struct sp_matcher_ctx
 	const sp_matcher* inst = 0;
 	int device = 0;
 	unsigned numCUs = 256;
+	L2Switches sw;			// read when the context is created
+	L2EngineKind kind = L2_GENERAL;
 	std::string lasterror;
 	// the exact engine (l2_kernel.hip): compiled tables, working memory, the documents of a launch in list mode
 	struct Exact
@@ -120,11 +78,9 @@ struct sp_matcher_ctx
 		bool on = false;
 		std::string whyNot;
 		DeviceBuffer dKeyinst, dStatics;
-		std::vector<FastKeyInst> keyinst;
-		FastSpillLayout spillLayout = {}; uint32_t bucketMeta[ 16] = {}; uint32_t expShift = 0;
+		FlatPlan plan;			// kernel instance = LDS capacities (l2_fast_kernel.hip), spill layout
 		CountedBuffer spill;		// count: waves
-		unsigned blocksPerCU = 0, variant = 4;	// variant: kernel instance = LDS capacities (l2_fast_kernel.hip)
-		uint32_t maxRules = 2048, maxStaged = 32768;
+		unsigned blocksPerCU = 0;
 	} flat;
 	// result-set mode (l2_join.h; SP_CTX_RESULT_SETS or SPA_L2_JOIN=1): result multisets without materialised rule instances
 	struct ResultSets
@@ -221,43 +177,47 @@ uint32_t sp_matcher_format_count( const sp_matcher_t* m) { return m->compiler.fo
 const char* sp_matcher_format_string( const sp_matcher_t* m, uint32_t format_handle) { return m->compiler.formatString( format_handle); }
 
 // which kernel the context's batches run on: 0 = general, 1 = LDS-resident (flat rule sets), 2 = join kernel (result-set mode)
-int sp_matcher_ctx_kernel_kind( const sp_matcher_ctx_t* c) { return c->join.on ? 2 : c->flat.on ? 1 : 0; }
-// name of the kernel that does a batch's work (the instance of the LDS-resident kernel is picked by SPA_L2_FAST_SIZE, default n)
-const char* sp_matcher_ctx_kernel_name( const sp_matcher_ctx_t* c)
-{
-	if (c->join.on) return "spa_l2_join_kernel";
-	if (!c->flat.on) return "spa_l2_match_kernel";
-	return fastKernelName( c->flat.variant);
-}
+int sp_matcher_ctx_kernel_kind( const sp_matcher_ctx_t* c) { return c->kind; }
+// name of the kernel that does a batch's work: the launch plan's (the instance of the LDS-resident kernel is picked by SPA_L2_FAST_SIZE, default n)
+const char* sp_matcher_ctx_kernel_name( const sp_matcher_ctx_t* c) { return l2KernelName( c->kind, &c->flat.plan); }
 
 // 1 when the compiled rule set is flat (l2_fast.h) and runs on the LDS-resident kernel, else 0 with the reason
 int sp_matcher_fast_tier( const sp_matcher_t* m, char* why, size_t whysize)
-{
-	return tierOf( m, why, whysize, [&]( const FlatTables& ft){
-		std::vector<FastKeyInst> ki;
-		return buildFastTables( ft, ki, 0);
-	});
-}
+{ return tierQuery( m, 0, L2_FLAT, why, whysize, 0); }
 
-// result-set mode: the join tables of the compiled rule set, or the reason why it stays on the exact engine
-static std::string buildResultSetTables( const sp_matcher* m, const FlatTables& ft, std::vector<JoinKey>& keytab, std::vector<JoinRule>& rules,
-					std::vector<uint32_t>& filter, uint32_t& maxRange, uint32_t& delimiter, uint32_t& altPrograms)
-{
-	altPrograms = 0;
-	// (`exclusive` drops the results covered by another one in a scan that follows the order of the results, copyOutBatch)
-	if (m->compiler.exclusive()) return "the `exclusive` option (its outcome depends on the order of the results)";
-	return buildJoinTables( ft, keytab, rules, filter, maxRange, delimiter, altPrograms);
-}
-
+// result-set mode: 1 when a context that asks for it runs the compiled rule set on the join kernel, else 0 with the reason why it stays on the exact engine
 int sp_matcher_result_set_tier( const sp_matcher_t* m, char* why, size_t whysize, uint32_t* alt_programs)
+{ return tierQuery( m, SP_CTX_RESULT_SETS, L2_JOIN, why, whysize, alt_programs); }
+
+// What a context created now with `ctx_flags` on a device of `num_cus` compute units would launch for a batch, without a device:
+// key=value fields, one per line (include/strus_pattern_amd.h)
+int sp_matcher_launch_plan( const sp_matcher_t* m, uint32_t ctx_flags, unsigned num_cus, unsigned fast_blocks_per_cu, size_t ndocs, size_t nlexems,
+			    size_t rerun_docs, uint32_t arena_grows, uint64_t min_results, uint64_t min_items, char* buf, size_t bufsize)
 {
-	if (alt_programs) *alt_programs = 0;
-	return tierOf( m, why, whysize, [&]( const FlatTables& ft){
-		std::vector<JoinKey> jk; std::vector<JoinRule> jr; std::vector<uint32_t> jf;
-		uint32_t maxRange = 0, delimiter = 0, alt = 0;
-		const std::string reason = buildResultSetTables( m, ft, jk, jr, jf, maxRange, delimiter, alt);
-		if (alt_programs && reason.empty()) *alt_programs = alt;
-		return reason;
+	if (buf && bufsize) buf[ 0] = 0;
+	return guardedCall( m->lasterror, SP_ERR_INVALID, [&]{
+		if (ctx_flags & ~(uint32_t)SP_CTX_RESULT_SETS) throw std::runtime_error( "unknown context flags");
+		const L2Switches sw = L2Switches::fromEnv();
+		FlatTables ft;
+		const L2Engine e = engineOf( m, ctx_flags, sw, ft);
+		const FlatPlan fp = e.flat.on ? flatPlanOf( e, sw) : FlatPlan();
+		ArenaLayout arena = initialArena();
+		arena.nStop = ft.nofStopWords;
+		for (uint32_t i=0; i<arena_grows; ++i) if (!growArena( arena)) throw std::runtime_error( "arena at its maximum size");
+		const L2LaunchPlan p = planL2Launch( e.kind(), rerun_docs != 0, num_cus ? num_cus : 256u, fast_blocks_per_cu, rerun_docs ? rerun_docs : ndocs, ndocs, nlexems,
+							arena, &fp, min_results, min_items);
+		static const char* const engines[] = {"general", "flat", "join"};
+		static const char* const routes[] = {"general", "flat+list", "join", "rerun-list"};
+		int n = std::snprintf( buf, bufsize, "engine=%s\nkind=%d\nflat_why_not=%s\njoin_why_not=%s\nalt_programs=%u\nkernel=%s\nroute=%s\n"
+			"general_blocks=%u\narena_run=%u\narena_alloc=%u\narena_alloc_waves=%u\narena_per_wave_bytes=%zu\narena_max_rules=%u\narena_scratch_cap=%u\nstop_words=%u\n"
+			"fast_blocks=%u\nspill_alloc_waves=%llu\nspill_per_wave_bytes=%zu\nlist_blocks=%u\njoin_blocks=%u\nwant_results=%llu\nwant_items=%llu\n"
+			"R=%u\nT=%u\nexp_shift=%u\nspill_words=%u\nmax_rules=%u\nmax_staged=%u\nbucket_caps=",
+			engines[ e.kind()], (int)e.kind(), e.flat.whyNot.c_str(), e.join.whyNot.c_str(), e.altPrograms, p.kernelName, routes[ p.route],
+			p.generalBlocks, p.arena.run, p.arena.alloc, p.arenaAllocWaves, p.arenaPerWaveBytes, p.layout.maxRules, p.layout.scratchCap, ft.nofStopWords,
+			p.fastBlocks, (unsigned long long)p.spillAllocWaves, p.spillPerWaveBytes, p.listBlocks, p.joinBlocks, (unsigned long long)p.wantResults, (unsigned long long)p.wantItems,
+			fp.R, fp.T, fp.expShift, fp.spill.totalWords, fp.spill.maxRules, fp.spill.maxStaged);
+		for (int b=0; b<16 && n >= 0 && buf && (size_t)n < bufsize; ++b) n += std::snprintf( buf+n, bufsize-n, b ? ",%u" : "%u", fp.bucketMeta[ b] >> 16);
+		if (n < 0 || !buf || (size_t)n >= bufsize) throw std::runtime_error( "buffer too small for the launch plan");
 	});
 }
 
@@ -303,8 +263,10 @@ sp_matcher_ctx_t* sp_matcher_ctx_create_ex( const sp_matcher_t* m, int device, u
 		HIP_CHECK( hipGetDeviceProperties( &prop, device));
 		c->numCUs = prop.multiProcessorCount > 0 ? (unsigned)prop.multiProcessorCount : 256u;
 
+		c->sw = L2Switches::fromEnv();
 		FlatTables ft;
-		m->compiler.flatten( ft);
+		const L2Engine engine = engineOf( m, flags, c->sw, ft);
+		c->kind = engine.kind();
 		c->exact.dPrograms.upload( ft.programs.data(), ft.programs.size()*sizeof(DevProgram));
 		c->exact.dTrigdefs.upload( ft.trigdefs.data(), ft.trigdefs.size()*sizeof(DevTrigDef));
 		c->exact.dKeytab.upload( ft.keytab.data(), ft.keytab.size()*sizeof(DevKeyEntry));
@@ -313,45 +275,24 @@ sp_matcher_ctx_t* sp_matcher_ctx_create_ex( const sp_matcher_t* m, int device, u
 		c->exact.nofStopWords = ft.nofStopWords;
 		c->exact.layout.nStop = ft.nofStopWords;
 		c->io.withFormats = m->compiler.formatCount() != 0;
+		c->flat.on = engine.flat.on; c->flat.whyNot = engine.flat.whyNot;
+		if (c->flat.on)
 		{
-			// fast tier: eligible rule sets get the one-line-per-install table (SPA_L2_FAST=0 keeps everything on the general kernel)
-			std::vector<FastKeyInst> ki;
-			std::vector<FastStatic> ks;
-			c->flat.whyNot = buildFastTables( ft, ki, &ks);
-			const char* sw = getenv( "SPA_L2_FAST");
-			if (sw && sw[0] == '0') c->flat.whyNot = "disabled by SPA_L2_FAST=0";
-			c->flat.on = c->flat.whyNot.empty();
-			if (c->flat.on)
-			{
-				if (ki.empty()) ki.resize( 1);
-				c->flat.dKeyinst.upload( ki.data(), ki.size()*sizeof(FastKeyInst));
-				c->flat.dStatics.upload( ks.data(), ks.size()*sizeof(FastStatic));
-				c->flat.keyinst.swap( ki);
-				// SPA_L2_FAST_SIZE=s|m|l picks the kernel instance (LDS capacities; t = the tiny one of the tests); the spill area takes what does not fit
-				if (const char* e = getenv( "SPA_L2_FAST_SIZE")) c->flat.variant = fastVariantNamed( e);
-				if (const char* e = getenv( "SPA_L2_FAST_MAXRULES")) c->flat.maxRules = (uint32_t)atoi( e);
-				if (const char* e = getenv( "SPA_L2_FAST_MAXSTAGED")) c->flat.maxStaged = (uint32_t)atoi( e);
-				if (c->flat.maxRules > 4095) c->flat.maxRules = 4095;		// trigger ids are 14 bits (rule << 2 | slot)
-			}
-			if (getenv( "SPA_L2_VERBOSE")) fprintf( stderr, "[spa] fast tier: %s\n", c->flat.on ? "on" : c->flat.whyNot.c_str());
+			c->flat.dKeyinst.upload( engine.flat.keyinst.data(), engine.flat.keyinst.size()*sizeof(FastKeyInst));
+			c->flat.dStatics.upload( engine.flat.statics.data(), engine.flat.statics.size()*sizeof(FastStatic));
+			c->flat.plan = flatPlanOf( engine, c->sw);
+			c->flat.blocksPerCU = (unsigned)fastBlocksPerCU( c->flat.plan.variant);
 		}
-		// result-set mode: asked for by the flag, or for every context by SPA_L2_JOIN=1; ineligible rule sets stay on the
-		// exact engine, whose results are a correct multiset too
-		if (const char* e = getenv( "SPA_L2_JOIN")) if (e[0] == '1') flags |= SP_CTX_RESULT_SETS;
-		if (flags & SP_CTX_RESULT_SETS)
+		if (c->sw.verbose) fprintf( stderr, "[spa] fast tier: %s\n", c->flat.on ? "on" : c->flat.whyNot.c_str());
+		c->join.on = engine.join.on; c->join.whyNot = engine.join.whyNot;
+		if (c->join.on)
 		{
-			std::vector<JoinKey> jk; std::vector<JoinRule> jr; std::vector<uint32_t> jf;
-			uint32_t altPrograms = 0;
-			c->join.whyNot = buildResultSetTables( m, ft, jk, jr, jf, c->join.maxRange, c->join.delimiter, altPrograms);
-			c->join.on = c->join.whyNot.empty();
-			if (c->join.on)
-			{
-				c->join.dKeytab.upload( jk.data(), jk.size()*sizeof(JoinKey)); c->join.dRules.upload( jr.data(), jr.size()*sizeof(JoinRule)); c->join.dFilter.upload( jf.data(), jf.size()*sizeof(uint32_t));
-				c->join.keymask = (uint32_t)jk.size()-1;
-				c->join.altRules = altPrograms != 0;
-			}
-			if (getenv( "SPA_L2_VERBOSE")) fprintf( stderr, "[spa] result-set mode: %s\n", c->join.on ? "join kernel" : c->join.whyNot.c_str());
+			const L2Engine::Join& j = engine.join;
+			c->join.dKeytab.upload( j.keytab.data(), j.keytab.size()*sizeof(JoinKey)); c->join.dRules.upload( j.rules.data(), j.rules.size()*sizeof(JoinRule)); c->join.dFilter.upload( j.filter.data(), j.filter.size()*sizeof(uint32_t));
+			c->join.keymask = (uint32_t)j.keytab.size()-1; c->join.maxRange = j.maxRange; c->join.delimiter = j.delimiter;
+			c->join.altRules = engine.altPrograms != 0;
 		}
+		if (c->sw.verbose && engine.join.asked) fprintf( stderr, "[spa] result-set mode: %s\n", c->join.on ? "join kernel" : c->join.whyNot.c_str());
 		c->io.dCursor.alloc( 256);		// u32: [0] fast cursor, [1] general cursor (list mode), [2] hand-over count, [16..31] hand-over reasons, [32..47] phase profile (u64 x 8)
 		c->io.dCounters.alloc( SPC_COUNT*sizeof(uint64_t));
 		c->own.create( device);
@@ -372,11 +313,7 @@ const char* sp_matcher_ctx_last_error( const sp_matcher_ctx_t* c) { return c->la
 int sp_matcher_ctx_set_arena( sp_matcher_ctx_t* c, uint32_t max_rules, uint32_t max_triggers, uint32_t bucket_capacity,
 				uint32_t max_items, uint32_t max_follow)
 {
-	if (max_rules) { c->exact.layout.maxRules = max_rules; c->exact.layout.maxHeap = max_rules; c->exact.layout.maxDispose = max_rules; c->exact.layout.winCap = max_rules/4 < 64 ? 64 : max_rules/4; }
-	if (max_triggers) c->exact.layout.maxTrigs = max_triggers;
-	if (bucket_capacity) c->exact.layout.bucketCap = bucket_capacity;
-	if (max_items) { c->exact.layout.maxItems = max_items; c->exact.layout.maxRefs = max_items; }
-	if (max_follow) { c->exact.layout.maxFollow = max_follow; }
+	setArena( c->exact.layout, max_rules, max_triggers, bucket_capacity, max_items, max_follow);
 	c->exact.arena.count = 0;	// forces re-layout at the next launch
 	return SP_OK;
 }
@@ -555,11 +492,7 @@ int sp_matcher_ctx_batch_status( sp_matcher_ctx_t* c, int32_t* status, size_t nd
 
 int sp_matcher_ctx_grow_arena( sp_matcher_ctx_t* c)
 {
-	if (c->exact.layout.maxRules >= (1u<<20)) { c->lasterror = "arena at its maximum size"; return SP_ERR_INVALID; }
-	c->exact.layout.maxRules *= 2; c->exact.layout.maxTrigs *= 2; c->exact.layout.bucketCap *= 2; c->exact.layout.maxItems *= 2;
-	c->exact.layout.maxRefs *= 2; c->exact.layout.maxFollow *= 2; c->exact.layout.maxDispose *= 2; c->exact.layout.maxHeap *= 2;
-	c->exact.layout.maxStaged *= 2; c->exact.layout.maxGStack *= 2; c->exact.layout.winCap *= 2;
-	if (c->exact.layout.scratchCap < 256) c->exact.layout.scratchCap = 256;
+	if (!growArena( c->exact.layout)) { c->lasterror = "arena at its maximum size"; return SP_ERR_INVALID; }
 	c->exact.arena.count = 0;
 	return SP_OK;
 }
@@ -595,33 +528,23 @@ L2BatchIO batchIO( sp_matcher_ctx* c, const void* d_lexems, const void* d_origse
 
 // ---- one batch on `stream`, step by step (launchBatch below)
 
-// the per-wave arena of the general kernel for `docs` documents to run; returns the waves (= workgroups) of its launch
-unsigned ensureArena( sp_matcher_ctx* c, size_t docs, bool rerun)
+// the per-wave arena of the general kernel
+void ensureArena( sp_matcher_ctx* c, const L2LaunchPlan& plan)
 {
-	// geometry: one wave per workgroup; as many as keep every CU busy, never more waves than documents
-	const size_t waveSlots = (size_t)c->numCUs*SPA_L2_WAVES_PER_CU;
-	unsigned wanted = (unsigned)(docs < waveSlots ? docs : waveSlots);
-	if (wanted == 0) wanted = 1;
-	ArenaLayout& L = c->exact.layout;
-	layoutArena( L);
-	const size_t perWave = (size_t)L.totalWords * sizeof(uint32_t);
-	const ArenaWaves aw = arenaWaves( perWave, wanted, waveSlots, 1);
-	if (c->exact.arena.count < aw.run)
+	if (c->exact.arena.count < plan.arena.run)
 	{
-		if (getenv( "SPA_L2_VERBOSE")) fprintf( stderr, "[spa] arena: rules %u bucket %u items %u refs %u staged %u winCap %u -> %.2f MB per wave, %u waves\n", L.maxRules, L.bucketCap, L.maxItems, L.maxRefs, L.maxStaged, L.winCap, L.totalWords*4/1e6, aw.run);
-		c->exact.arena.realloc( rerun ? aw.run : aw.alloc, perWave);	// (a rerun of some documents: what it runs)
+		const ArenaLayout& L = plan.layout;
+		if (c->sw.verbose) fprintf( stderr, "[spa] arena: rules %u bucket %u items %u refs %u staged %u winCap %u -> %.2f MB per wave, %u waves\n", L.maxRules, L.bucketCap, L.maxItems, L.maxRefs, L.maxStaged, L.winCap, L.totalWords*4/1e6, plan.arena.run);
+		c->exact.arena.realloc( plan.arenaAllocWaves, plan.arenaPerWaveBytes);
 	}
-	return aw.run;
 }
 
 // output capacity: results are bounded by what fits; sized from the input, grown by the caller on SP_DOC_ERR_ARENA
-void ensureOutput( sp_matcher_ctx* c, size_t ndocs, size_t nlexems)
+void ensureOutput( sp_matcher_ctx* c, const L2LaunchPlan& plan, size_t ndocs)
 {
 	sp_matcher_ctx::BatchIO& io = c->io;
-	// item indices in a result record are 32 bit: a batch that needs more fails with SP_DOC_ERR_OUTPUT instead of wrapping
-	auto want = []( uint64_t fromInput, uint64_t reserved) { const uint64_t n = fromInput < reserved ? reserved : fromInput; return n > 0xFFFFFFFFull ? 0xFFFFFFFFull : n; };
-	io.results.ensure( want( (uint64_t)nlexems*2 + 1024, io.minResults), sizeof(sp_result_t));
-	io.items.ensure( want( (uint64_t)nlexems*6 + 1024, io.minItems), sizeof(sp_result_item_t));
+	io.results.ensure( plan.wantResults, sizeof(sp_result_t));
+	io.items.ensure( plan.wantItems, sizeof(sp_result_item_t));
 	if (io.withFormats)
 	{
 		io.dResultFormat.reserve( io.results.count*sizeof(uint32_t));
@@ -639,7 +562,7 @@ void resetCursorAndCounters( sp_matcher_ctx* c, bool rerun, hipStream_t stream)
 	else HIP_CHECK( hipMemsetAsync( (uint64_t*)c->io.dCounters.ptr + SPC_FAILED, 0, sizeof(uint64_t), stream));	// (the other counters continue)
 }
 
-L2Params generalParams( const sp_matcher_ctx* c, const L2BatchIO& io)
+L2Params generalParams( const sp_matcher_ctx* c, const L2BatchIO& io, const L2LaunchPlan& plan)
 {
 	L2Params P;
 	std::memset( &P, 0, sizeof(P));
@@ -649,7 +572,7 @@ L2Params generalParams( const sp_matcher_ctx* c, const L2BatchIO& io)
 	P.keylist = (const DevKeyRef*)c->exact.dKeylist.ptr;
 	P.keymask = c->exact.keymask; P.nofStopWords = c->exact.nofStopWords;
 	P.io = io;
-	P.arenaBase = (uint32_t*)c->exact.arena.ptr(); P.arena = c->exact.layout;
+	P.arenaBase = (uint32_t*)c->exact.arena.ptr(); P.arena = plan.layout;
 	return P;
 }
 
@@ -661,7 +584,7 @@ void listMode( const sp_matcher_ctx* c, L2Params& P)
 }
 
 // `rerun`: only these documents of the batch already in the output buffers run again, with the working set the caller has just grown
-void launchRerun( sp_matcher_ctx* c, L2Params P, unsigned nblocks, const std::vector<uint32_t>& rerun, hipStream_t stream)
+void launchRerun( sp_matcher_ctx* c, L2Params P, const L2LaunchPlan& plan, const std::vector<uint32_t>& rerun, hipStream_t stream)
 {
 	const uint32_t n = (uint32_t)rerun.size();
 	c->exact.dDocList.reserve( ((size_t)P.io.ndocs+1)*sizeof(uint32_t));
@@ -669,11 +592,11 @@ void launchRerun( sp_matcher_ctx* c, L2Params P, unsigned nblocks, const std::ve
 	HIP_CHECK( hipMemcpyAsync( (uint32_t*)c->io.dCursor.ptr + 2, &n, sizeof(uint32_t), hipMemcpyHostToDevice, stream));
 	HIP_CHECK( hipStreamSynchronize( stream));		// (the list and its count are host temporaries)
 	listMode( c, P);
-	HIP_CHECK( launchL2Match( P, nblocks, stream));
+	HIP_CHECK( launchL2Match( P, plan.generalBlocks, stream));
 }
 
 // result-set mode: result multisets by joining positions, nothing installed (l2_join.h)
-void launchJoin( sp_matcher_ctx* c, const L2BatchIO& io, size_t nlexems, hipStream_t stream)
+void launchJoin( sp_matcher_ctx* c, const L2BatchIO& io, const L2LaunchPlan& plan, size_t nlexems, hipStream_t stream)
 {
 	JoinParams J;
 	std::memset( &J, 0, sizeof(J));
@@ -681,27 +604,19 @@ void launchJoin( sp_matcher_ctx* c, const L2BatchIO& io, size_t nlexems, hipStre
 	J.filter = (const uint32_t*)c->join.dFilter.ptr; J.counts = (uint32_t*)c->join.dCounts.ptr; J.countsCapacity = nlexems;
 	J.keytab = (const JoinKey*)c->join.dKeytab.ptr; J.keymask = c->join.keymask; J.rules = (const JoinRule*)c->join.dRules.ptr; J.maxRange = c->join.maxRange; J.delimiter = c->join.delimiter; J.altRules = c->join.altRules ? 1u : 0u;
 	J.io = io;
-	const size_t ndocs = io.ndocs, jslots = (size_t)c->numCUs * 32;		// one wave per document, no LDS, few registers
-	HIP_CHECK( launchL2Join( J, (unsigned)(ndocs < jslots ? (ndocs ? ndocs : 1) : jslots), stream));
+	HIP_CHECK( launchL2Join( J, plan.joinBlocks, stream));
 }
 
 // flat rule set: the LDS-resident kernel first; the documents it hands over (exact.dDocList) go through the
 // general kernel in list mode right behind it on the same stream (an empty list costs one short launch)
-void launchFlat( sp_matcher_ctx* c, L2Params P, unsigned nblocks, hipStream_t stream)
+void launchFlat( sp_matcher_ctx* c, L2Params P, const L2LaunchPlan& plan, hipStream_t stream)
 {
 	sp_matcher_ctx::Flat& f = c->flat;
 	const size_t ndocs = P.io.ndocs;
-	uint32_t fR = 0, fT = 0;
-	fastCapacities( f.variant, fR, fT);
-	layoutFast( f.spillLayout, f.bucketMeta, f.expShift, f.keyinst, fR, fT, f.maxRules, f.maxStaged);
-	if (!f.blocksPerCU) f.blocksPerCU = (unsigned)fastBlocksPerCU( f.variant);
-	const size_t fslots = (size_t)c->numCUs * f.blocksPerCU;
-	unsigned fblocks = (unsigned)(ndocs < fslots ? ndocs : fslots);
-	if (fblocks == 0) fblocks = 1;
-	if (f.spill.count < fblocks)
+	if (f.spill.count < plan.fastBlocks)
 	{
-		f.spill.realloc( fblocks >= 64 ? fslots : fblocks, (size_t)f.spillLayout.totalWords * sizeof(uint32_t));	// (single documents: a small spill area, see the arena)
-		if (getenv( "SPA_L2_VERBOSE")) fprintf( stderr, "[spa] fast tier: %u waves/CU, LDS capacities R %u T %u, spill %.2f MB per wave\n", f.blocksPerCU, fR, fT, f.spillLayout.totalWords*4/1e6);
+		f.spill.realloc( plan.spillAllocWaves, plan.spillPerWaveBytes);
+		if (c->sw.verbose) fprintf( stderr, "[spa] fast tier: %u waves/CU, LDS capacities R %u T %u, spill %.2f MB per wave\n", f.blocksPerCU, f.plan.R, f.plan.T, f.plan.spill.totalWords*4/1e6);
 	}
 	c->exact.dDocList.reserve( (ndocs+1)*sizeof(uint32_t));
 	FastParams F;
@@ -709,14 +624,13 @@ void launchFlat( sp_matcher_ctx* c, L2Params P, unsigned nblocks, hipStream_t st
 	F.keyinst = (const FastKeyInst*)f.dKeyinst.ptr; F.statics = (const FastStatic*)f.dStatics.ptr; F.keytab = (const FastKeyEntry*)c->exact.dKeytab.ptr;
 	F.keymask = c->exact.keymask; F.nofStopWords = c->exact.nofStopWords;
 	F.io = P.io;
-	std::memcpy( F.bucketMeta, f.bucketMeta, sizeof(F.bucketMeta)); F.expShift = f.expShift;
-	F.spill = f.spillLayout; F.spillBase = (uint32_t*)f.spill.ptr();
+	std::memcpy( F.bucketMeta, f.plan.bucketMeta, sizeof(F.bucketMeta)); F.expShift = f.plan.expShift;
+	F.spill = f.plan.spill; F.spillBase = (uint32_t*)f.spill.ptr();
 	F.fallbackList = (uint32_t*)c->exact.dDocList.ptr; F.fallbackCount = (uint32_t*)c->io.dCursor.ptr + 2;
 	F.diag = (uint32_t*)c->io.dCursor.ptr + 16; F.prof = (uint64_t*)((uint32_t*)c->io.dCursor.ptr + 32);
-	HIP_CHECK( launchL2Fast( F, f.variant, fblocks, stream));
+	HIP_CHECK( launchL2Fast( F, f.plan.variant, plan.fastBlocks, stream));
 	listMode( c, P);
-	const unsigned listBlocks = nblocks < 2*c->numCUs ? nblocks : 2*c->numCUs;
-	HIP_CHECK( launchL2Match( P, listBlocks, stream));
+	HIP_CHECK( launchL2Match( P, plan.listBlocks, stream));
 }
 
 // enqueue one batch on `stream`; all inputs are device pointers
@@ -725,17 +639,23 @@ void launchFlat( sp_matcher_ctx* c, L2Params P, unsigned nblocks, hipStream_t st
 void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg, const void* d_doc_offsets,
 		  size_t ndocs, size_t nlexems, hipStream_t stream, const void* d_doc_ranges=0, const std::vector<uint32_t>* rerun=0)
 {
+	// everything the launch decides (l2_plan.hpp); it refuses a batch of too many documents before anything is touched
+	const L2LaunchPlan plan = planL2Launch( c->kind, rerun != 0, c->numCUs, c->flat.blocksPerCU, rerun ? rerun->size() : ndocs, ndocs, nlexems,
+						c->exact.layout, &c->flat.plan, c->io.minResults, c->io.minItems);
 	HIP_CHECK( hipSetDevice( c->device));
 	c->fin.done = false;		// (a new batch: what was finished is of the one before)
-	const unsigned nblocks = ensureArena( c, rerun ? rerun->size() : ndocs, rerun != 0);
-	ensureOutput( c, ndocs, nlexems);
+	ensureArena( c, plan);
+	ensureOutput( c, plan, ndocs);
 	resetCursorAndCounters( c, rerun != 0, stream);
 	const L2BatchIO io = batchIO( c, d_lexems, d_origseg, d_doc_offsets, d_doc_ranges, ndocs);
 	HIP_CHECK( hipEventRecord( c->evStart, stream));
-	if (rerun) launchRerun( c, generalParams( c, io), nblocks, *rerun, stream);
-	else if (c->join.on) launchJoin( c, io, nlexems, stream);
-	else if (c->flat.on) launchFlat( c, generalParams( c, io), nblocks, stream);
-	else HIP_CHECK( launchL2Match( generalParams( c, io), nblocks, stream));
+	switch (plan.route)
+	{
+		case L2_ROUTE_RERUN_LIST: launchRerun( c, generalParams( c, io, plan), plan, *rerun, stream); break;
+		case L2_ROUTE_JOIN: launchJoin( c, io, plan, nlexems, stream); break;
+		case L2_ROUTE_FLAT_LIST: launchFlat( c, generalParams( c, io, plan), plan, stream); break;
+		case L2_ROUTE_GENERAL: HIP_CHECK( launchL2Match( generalParams( c, io, plan), plan.generalBlocks, stream)); break;
+	}
 	HIP_CHECK( hipEventRecord( c->evStop, stream));
 	c->evValid = true; c->lastStream = stream; c->lastNdocs = ndocs; c->haveBatch = true;
 }
@@ -757,7 +677,6 @@ int matchDevice( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg,
 		 size_t ndocs, size_t nlexems, void* stream, sp_match_device_batch_t* out)
 {
 	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
-		if (ndocs >= 0xFFFFFFFFull) throw std::runtime_error( "too many documents in one batch");
 		launchBatch( c, d_lexems, d_origseg, d_doc_offsets, ndocs, nlexems, (hipStream_t)stream, d_doc_ranges);
 		if (out) deviceBatch( c, ndocs, out);
 	});
@@ -781,7 +700,7 @@ int sp_matcher_ctx_batch_counters( sp_matcher_ctx_t* c, uint64_t counters[8])
 		HIP_CHECK( hipSetDevice( c->device));
 		HIP_CHECK( hipStreamSynchronize( c->lastStream));
 		copySync( c->own, counters, c->io.dCounters.ptr, SPC_COUNT*sizeof(uint64_t), hipMemcpyDeviceToHost);
-		if (c->flat.on && getenv( "SPA_L2_VERBOSE"))
+		if (c->flat.on && c->sw.verbose)
 		{
 			uint32_t diag[ 16];
 			copySync( c->own, diag, (const uint32_t*)c->io.dCursor.ptr + 16, sizeof(diag), hipMemcpyDeviceToHost);

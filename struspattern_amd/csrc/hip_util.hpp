@@ -105,12 +105,5 @@ inline void copySync( hipStream_t stream, void* dst, const void* src, size_t n, 
 	HIP_CHECK( hipStreamSynchronize( stream));
 }
 
-// Waves of a per-wave arena of `perWaveBytes` (capi_l2.cpp).  `run`: the waves of this launch, as many as wanted while the arena stays
-// below ~48 GiB (fewer resident waves when documents need a large working set; never fewer than 4, a multiple of `multiple` when cut).
-// `alloc`: the waves to allocate when the arena has to grow: batches of 64 waves and more get the arena of the full machine (`fullSlots`
-// waves) at once; a context that sees single documents (the plugin path: one context per host thread) keeps a small one -- gigabytes less.
-struct ArenaWaves { unsigned run, alloc; };
-ArenaWaves arenaWaves( size_t perWaveBytes, unsigned wanted, size_t fullSlots, unsigned multiple);
-
 } // namespace
 #endif

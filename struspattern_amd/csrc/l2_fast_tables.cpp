@@ -12,7 +12,7 @@ static_assert( sizeof(FastKeyInst) == 64, "one install record per 64-byte line")
 static_assert( sizeof(FastStatic) == 32, "compact static line");
 static_assert( sizeof(FastKeyEntry) == sizeof(DevKeyEntry), "the fast kernel reads the general key table in place");
 
-// Why a rule set is not eligible (diagnostics, SPA_L2_VERBOSE), empty when it is.
+// Why a rule set is not eligible (diagnostics: the caller reports it, chooseL2Engine of l2_plan.hpp), empty when it is.
 std::string buildFastTables( const FlatTables& ft, std::vector<FastKeyInst>& out, std::vector<FastStatic>* statics)
 {
 	out.clear();
