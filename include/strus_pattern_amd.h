@@ -52,7 +52,8 @@ enum sp_position_bind {
 };
 
 /* analyzer::PatternLexem(id, ordpos, Position(seg, ofs), origsize)  (src/patternLexer.cpp:908).
- * 16 bytes; the segment index travels in a parallel optional array (always 0 out of the lexer). */
+ * 16 bytes; the segment index travels in a parallel optional array: 0 for everything out of the lexer, the index of the
+ * segment inside its document after sp_lexer_ctx_stitch_segments_device. */
 typedef struct sp_lexem {
 	uint32_t id;
 	uint32_t ordpos;
@@ -409,6 +410,53 @@ int sp_lexer_ctx_match_docs_device(sp_lexer_ctx_t* c, const void* d_text, const 
 /* host copy of the lexems of the documents [first_doc, first_doc+ndocs) of the last device batch
  * (what PatternLexerContextInterface::match returns for each of them, src/patternLexer.cpp:858) */
 int sp_lexer_ctx_batch_fetch_docs(sp_lexer_ctx_t* c, size_t first_doc, size_t ndocs, sp_lex_batch_t* out);
+/* ---- segmented documents: the "documents" of the last device batch are content segments (the pieces an XML, HTML or JSON
+ * segmenter hands to the lexer one at a time), and document d consists of the segments
+ * [doc_seg_offsets[d], doc_seg_offsets[d+1]) of that batch, in that order.  The stitch does on the device what a segmenting
+ * caller does between lexer and matcher (the loop of the reference's command-line tool, `ordposOffset = lexems.back().ordpos()`;
+ * that tool lives in strusAnalyzer, outside the reference repository, so the rule is this project's definition, unpinned by
+ * a reference vector):
+ *   - the lexems of a document are those of its segments in segment order, lexer order inside a segment;
+ *   - the lexem (id, ordpos, origpos, origsize) of the document's s-th segment (s counts every segment from 0, empty ones
+ *     included) becomes (id, ordpos + base_s, origpos, origsize) with origseg = s; base_0 = 0, base_{s+1} = the stitched ordpos
+ *     of the last lexem of segment s, or base_s when segment s has no lexems; origpos stays relative to the segment;
+ *   - a document fails and is empty when one of its segments failed in the lexer (its status: that of its first failing
+ *     segment), when its segment range ends beyond the lexer batch or descends (SP_DOC_ERR_RANGE), or when a stitched ordpos
+ *     or its lexem count does not fit 32 bits (SP_DOC_ERR_RANGE); a document of no segments is valid and empty.
+ * The segment ranges of different documents are meant to be disjoint, as those of an ascending doc_seg_offsets are; the
+ * stitched lexems then fit the lexer's lexem capacity, which sizes the buffers.  Ranges that share segments are not an
+ * input this call defines lexems for: every access stays inside the buffers, and the documents that would end beyond the
+ * capacity fail with SP_DOC_ERR_OUTPUT.
+ * The stitched batch feeds the matcher as it is:
+ *   sp_matcher_ctx_match_docs_device(mctx, out.d_lexems, out.d_origseg, out.d_doc_offsets, ndocs, nlexems, stream, &mout)
+ * with nlexems = d_totals[0], or any upper bound of it such as the lexer batch's lexem counter.  A document that failed
+ * in the stitch reaches the matcher as an empty document and comes back from it with status 0: the caller combines the two
+ * status arrays. */
+typedef struct sp_lex_stitched_batch {
+	size_t ndocs;
+	void* d_lexems;        /* sp_lexem_t[], document 0 first, segment order inside a document */
+	void* d_origseg;       /* uint32_t[] parallel to d_lexems */
+	void* d_doc_offsets;   /* uint64_t[ndocs+1] -- what sp_matcher_ctx_match_docs_device takes */
+	void* d_doc_status;    /* int32_t[ndocs] */
+	void* d_totals;        /* uint64_t[2]: lexems, failed documents */
+} sp_lex_stitched_batch_t;
+/* Enqueues the stitching passes (count, offsets, place: csrc/l1_stitch.h) for the last device batch of the context on `stream`
+ * and returns without waiting for anything; d_doc_seg_offsets is a device array uint64_t[ndocs+1].  A `stream` other than the
+ * batch's is ordered behind the batch with an event.  SP_ERR_INVALID before any batch has run on the context.  The buffers
+ * belong to the context (allocated at the first stitch, a context that never stitches has none) and are valid until the
+ * next stitch on it; the raw batch stays as it is.  The next lexer batch on the context invalidates the stitched state (not
+ * the buffers).  A batch with segments that failed for lack of room is grown and rerun before it is stitched, as ever. */
+int sp_lexer_ctx_stitch_segments_device(sp_lexer_ctx_t* c, const void* d_doc_seg_offsets, size_t ndocs,
+                                        void* stream, sp_lex_stitched_batch_t* out);
+/* plain copy of the stitched buffers to the host (waits for the stitch): the batch is released with sp_lex_batch_free, *origseg
+ * (parallel to out->lexems; the parameter may be NULL) with sp_free.  SP_ERR_INVALID when the last batch has not been stitched. */
+int sp_lexer_ctx_stitched_fetch(sp_lexer_ctx_t* c, sp_lex_batch_t* out, uint32_t** origseg);
+/* copies the first `ndocs` status words of the stitched batch to the host (waits for the stitch; a caller that feeds the matcher
+ * on the device needs only these); ndocs_stitched, if given, receives the number of documents of the stitch.  SP_ERR_INVALID
+ * when the last batch has not been stitched. */
+int sp_lexer_ctx_stitched_status(sp_lexer_ctx_t* c, int32_t* status, size_t ndocs, size_t* ndocs_stitched);
+/* duration of the three passes of the last stitch in milliseconds (HIP events on its stream; waits for them) */
+int sp_lexer_ctx_last_stitch_ms(sp_lexer_ctx_t* c, double* ms);
 int sp_lexer_ctx_batch_counters(sp_lexer_ctx_t* c, uint64_t counters[8]);
 int sp_lexer_ctx_batch_status(sp_lexer_ctx_t* c, int32_t* status, size_t ndocs);
 double sp_lexer_ctx_last_kernel_ms(sp_lexer_ctx_t* c);

@@ -13,7 +13,7 @@ from . import capi
 from .capi import SpLexem, SpResult, SpResultItem
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
-           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND"]
+           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
@@ -481,6 +481,52 @@ class PatternLexerContext:
             self._L.sp_lex_batch_free(ctypes.byref(b))
         return LexBatch(lex, offs, status)
 
+    def stitchSegmentsDevice(self, d_doc_seg_offsets, ndocs, stream=0):
+        """the "documents" of the last device batch are segments: stitch them to `ndocs` documents on the device (asynchronous
+        on `stream`), document d = the segments [doc_seg_offsets[d], doc_seg_offsets[d+1]) (a device array of ndocs+1 u64):
+        ordinal positions continued from segment to segment, a parallel origseg array; returns the device pointers
+        (capi.SpLexStitchedBatch), which PatternMatcherContext.matchDocsDevice takes as they are."""
+        out = capi.SpLexStitchedBatch()
+        rc = self._L.sp_lexer_ctx_stitch_segments_device(self._h, d_doc_seg_offsets, ndocs, stream or None, ctypes.byref(out))
+        if rc != 0:
+            raise PatternError("stitching the segments on the device failed (%d): %s" % (rc, self._err()))
+        return out
+
+    def stitchedFetch(self):
+        """plain host copy of the batch stitched by stitchSegmentsDevice: (LexBatch, origseg (n,) u32)"""
+        b = capi.SpLexBatch()
+        seg = ctypes.POINTER(ctypes.c_uint32)()
+        rc = self._L.sp_lexer_ctx_stitched_fetch(self._h, ctypes.byref(b), ctypes.byref(seg))
+        try:
+            if rc != 0:
+                raise PatternError("fetching the stitched batch failed (%d): %s" % (rc, self._err()))
+            ndocs = b.ndocs
+            lex = np.ctypeslib.as_array(ctypes.cast(b.lexems, ctypes.POINTER(ctypes.c_uint32)), shape=(b.nlexems * 4 + 1,))[:b.nlexems * 4].reshape(-1, 4).copy()
+            offs = np.ctypeslib.as_array(b.doc_lexem_offsets, shape=(ndocs + 1,)).copy()
+            status = np.ctypeslib.as_array(b.doc_status, shape=(ndocs + 1,))[:ndocs].copy()
+            origseg = np.ctypeslib.as_array(seg, shape=(b.nlexems + 1,))[:b.nlexems].copy()
+        finally:
+            self._L.sp_lex_batch_free(ctypes.byref(b))
+            self._L.sp_free(seg)
+        return LexBatch(lex, offs, status), origseg
+
+    def stitchedStatus(self):
+        """the per-document status words of the last stitchSegmentsDevice (waits for it)"""
+        n = ctypes.c_size_t(0)
+        if self._L.sp_lexer_ctx_stitched_status(self._h, None, 0, ctypes.byref(n)) != 0:
+            raise PatternError("reading the stitch status failed: " + self._err())
+        st = np.zeros(n.value, np.int32)
+        if self._L.sp_lexer_ctx_stitched_status(self._h, st.ctypes.data, n.value, None) != 0:
+            raise PatternError("reading the stitch status failed: " + self._err())
+        return st
+
+    def lastStitchMs(self):
+        """duration of the passes of the last stitchSegmentsDevice in milliseconds"""
+        a = ctypes.c_double(-1.0)
+        if self._L.sp_lexer_ctx_last_stitch_ms(self._h, ctypes.byref(a)) != 0:
+            raise PatternError("no timed stitch")
+        return a.value
+
     def batchCounters(self):
         arr = (ctypes.c_uint64 * 8)()
         if self._L.sp_lexer_ctx_batch_counters(self._h, arr) != 0:
@@ -630,6 +676,42 @@ class PatternLexer:
 
     def name(self):
         return "std"
+
+
+def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets):
+    """Segmented documents, host buffers in and out: `text` holds the segments back to back (seg_offsets: nseg+1 byte
+    offsets), document d consists of the segments [doc_seg_offsets[d], doc_seg_offsets[d+1]).  Lexer -> stitch on the
+    device -> rule matcher -> fetch; only the text goes up and the results come down.  Returns the MatchBatch, whose
+    status of a document is the stitch's where that is not 0 (a failed segment, a bad segment range), else the matcher's."""
+    import torch
+    text = bytes(text)
+    seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
+    doc_seg_offsets = np.ascontiguousarray(doc_seg_offsets, dtype=np.uint64)
+    nseg, ndocs = len(seg_offsets) - 1, len(doc_seg_offsets) - 1
+    d_text = torch.frombuffer(bytearray(text + b"\0" * 16), dtype=torch.uint8).cuda()
+    d_so = torch.from_numpy(seg_offsets.view(np.int64)).cuda()
+    d_dso = torch.from_numpy(doc_seg_offsets.view(np.int64)).cuda()
+    stream = torch.cuda.current_stream().cuda_stream
+    for _ in range(12):
+        lctx.matchDocsDevice(d_text.data_ptr(), d_so.data_ptr(), nseg, len(text), stream)
+        lc = lctx.batchCounters()
+        if not lc["failed_docs"] or not set(int(x) for x in lctx.batchStatus(nseg)) & {2, 9}:
+            break
+        lctx.reserveOutput(int(lc["lexems"] * 1.2) + 1024)      # a segment without room: grow and rerun before stitching
+        lctx.growArena()
+    st = lctx.stitchSegmentsDevice(d_dso.data_ptr(), ndocs, stream)
+    nlexems = int(lc["lexems"])                                 # an upper bound of the stitched total
+    for _ in range(12):
+        mctx.matchDocsDevice(st.d_lexems, st.d_doc_offsets, ndocs, nlexems, stream, d_origseg=st.d_origseg)
+        mc = mctx.batchCounters()
+        if not mc["failed_docs"] or not set(int(x) for x in mctx.batchStatus(ndocs)) & {2, 9}:
+            break
+        mctx.reserveOutput(int(mc["results"] * 1.2) + 1024, int(mc["items"] * 1.2) + 1024)
+        mctx.growArena()
+    mb = mctx.batchFetch()
+    stitch_status = lctx.stitchedStatus()
+    mb.status = np.where(stitch_status != 0, stitch_status, mb.status).astype(np.int32)
+    return mb
 
 
 def device_count():

@@ -50,6 +50,10 @@ class SpLexDeviceBatch(ctypes.Structure):
     _fields_ = [("ndocs", ctypes.c_size_t), ("d_lexems", c_vp), ("d_doc_ranges", c_vp), ("d_doc_status", c_vp), ("d_counters", c_vp)]
 
 
+class SpLexStitchedBatch(ctypes.Structure):
+    _fields_ = [("ndocs", ctypes.c_size_t), ("d_lexems", c_vp), ("d_origseg", c_vp), ("d_doc_offsets", c_vp), ("d_doc_status", c_vp), ("d_totals", c_vp)]
+
+
 class SpMatchDeviceBatch(ctypes.Structure):
     _fields_ = [
         ("ndocs", ctypes.c_size_t), ("d_results", c_vp), ("d_items", c_vp), ("d_doc_result_offsets", c_vp),
@@ -147,6 +151,10 @@ SIGNATURES = {
     "sp_lex_batch_free": (None, [P(SpLexBatch)]),
     "sp_lexer_ctx_match_docs_device": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_size_t, ctypes.c_size_t, c_vp, P(SpLexDeviceBatch)]),
     "sp_lexer_ctx_batch_fetch_docs": (ctypes.c_int, [c_vp, ctypes.c_size_t, ctypes.c_size_t, P(SpLexBatch)]),
+    "sp_lexer_ctx_stitch_segments_device": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, c_vp, P(SpLexStitchedBatch)]),
+    "sp_lexer_ctx_stitched_fetch": (ctypes.c_int, [c_vp, P(SpLexBatch), P(P(c_u32))]),
+    "sp_lexer_ctx_stitched_status": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t, P(ctypes.c_size_t)]),
+    "sp_lexer_ctx_last_stitch_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
     "sp_lexer_ctx_batch_counters": (ctypes.c_int, [c_vp, P(c_u64)]),
     "sp_lexer_ctx_batch_status": (ctypes.c_int, [c_vp, c_vp, ctypes.c_size_t]),
     "sp_lexer_ctx_last_kernel_ms": (ctypes.c_double, [c_vp]),

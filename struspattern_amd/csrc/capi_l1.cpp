@@ -3,6 +3,7 @@
 #include "l1_compile.hpp"
 #include "l1_image.hpp"
 #include "l1_launch.h"
+#include "l1_stitch.h"
 #include "l2_plan.hpp"		// arenaWaves: the policy of a per-wave arena
 #include "capi_util.hpp"
 #include <cstdio>
@@ -35,6 +36,17 @@ struct sp_lexer_ctx
 	Event evStart, evMid, evWords, evStop; bool evValid = false;
 	L1LaunchPlan plan;		// of the last launch
 	hipStream_t lastStream = 0; size_t lastNdocs = 0;
+	// the segments of the last batch stitched to documents on the device (l1_stitch.h); nothing is allocated before the first
+	// sp_lexer_ctx_stitch_segments_device
+	struct Stitched
+	{
+		DeviceBuffer dLexems, dOrigseg, dSegWork, dDocCount, dDocOffsets, dDocStatus, dTotals, dCursor;
+		bool done = false;
+		hipStream_t stream = 0;
+		size_t ndocs = 0;
+		uint64_t capacity = 0;		// records in dLexems and dOrigseg: the lexer's lexem capacity at the stitch
+		Event ev[ 2]; bool evValid = false;
+	} stitched;
 	Stream own;			// the context's own stream (non-blocking): the host-buffer entry points of different contexts -- one per host thread,
 				// the reference's threading model -- copy and launch side by side instead of queueing on the null stream
 };
@@ -274,6 +286,7 @@ void allocLexBatch( sp_lex_batch_t* out, size_t ndocs, uint64_t nlexems)
 void launchLex( sp_lexer_ctx* c, const void* d_text, const void* d_doc_offsets, size_t ndocs, size_t nbytes, hipStream_t stream)
 {
 	HIP_CHECK( hipSetDevice( c->device));
+	c->stitched.done = false;		// (a new batch: what was stitched is of the one before)
 	const LexTables& T = c->inst->compiler.tables();
 	const bool wordsKernel = c->images.wordsKernel;
 	L1LaunchPlan plan = planL1Launch( T, c->images, c->numCUs, ndocs, nbytes, L1Switches::fromEnv());
@@ -551,6 +564,104 @@ int sp_lexer_ctx_batch_fetch_docs( sp_lexer_ctx_t* c, size_t first_doc, size_t n
 		out->doc_lexem_offsets[ ndocs] = lp;
 		out->nlexems = lp;
 	});
+}
+
+// ---- the segments of the last device batch stitched to documents on the device (l1_stitch.h)
+int sp_lexer_ctx_stitch_segments_device( sp_lexer_ctx_t* c, const void* d_doc_seg_offsets, size_t ndocs, void* stream_, sp_lex_stitched_batch_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (!c->evValid) throw std::runtime_error( "no batch to stitch: no batch has run on this context");
+		if (ndocs >= 0xFFFFFFFFull) throw std::runtime_error( "too many documents in one batch");
+		if (!d_doc_seg_offsets) throw std::runtime_error( "no segment offsets");
+		hipStream_t stream = (hipStream_t)stream_;
+		HIP_CHECK( hipSetDevice( c->device));
+		sp_lexer_ctx::Stitched& S = c->stitched;
+		S.done = false;
+		// the stitched lexems are a rearrangement of the batch's: the lexer's capacity holds them, nothing is read back to size them
+		const uint64_t capacity = c->lexems.count;
+		const size_t nseg = c->lastNdocs;
+		S.dLexems.reserve( (capacity+1)*sizeof(sp_lexem_t));
+		S.dOrigseg.reserve( (capacity+1)*sizeof(uint32_t));
+		S.dSegWork.reserve( (nseg+1)*2*sizeof(uint32_t));
+		S.dDocCount.reserve( (ndocs+1)*sizeof(uint32_t));
+		S.dDocOffsets.reserve( (ndocs+1)*sizeof(uint64_t));
+		S.dDocStatus.reserve( (ndocs+1)*sizeof(int32_t));
+		if (!S.dTotals.ptr) S.dTotals.alloc( 2*sizeof(uint64_t));
+		if (!S.dCursor.ptr) S.dCursor.alloc( 2*sizeof(uint32_t));
+		hipEvent_t ev[ 2];
+		for (int i=0; i<2; ++i) { S.ev[ i].create(); ev[ i] = S.ev[ i]; }
+
+		// another stream than the batch's runs behind the batch (evStop closes the launch sequence)
+		if (stream != c->lastStream) HIP_CHECK( hipStreamWaitEvent( stream, c->evStop, 0));
+		HIP_CHECK( hipMemsetAsync( S.dCursor.ptr, 0, 2*sizeof(uint32_t), stream));
+		StitchParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.lexems = (const uint32_t*)c->lexems.ptr(); P.segRange = (const uint64_t*)c->dDocRange.ptr; P.segStatus = (const int32_t*)c->dDocStatus.ptr;
+		P.lexemCounter = (const uint64_t*)c->dCounters.ptr + L1C_LEXEMS; P.lexemCapacity = capacity; P.nseg = (uint32_t)nseg;
+		P.docSegOffsets = (const uint64_t*)d_doc_seg_offsets; P.ndocs = (uint32_t)ndocs;
+		P.segWork = (uint32_t*)S.dSegWork.ptr; P.docCount = (uint32_t*)S.dDocCount.ptr; P.cursor = (uint32_t*)S.dCursor.ptr;
+		P.outLexems = (uint32_t*)S.dLexems.ptr; P.outOrigseg = (uint32_t*)S.dOrigseg.ptr;
+		P.docOffsets = (uint64_t*)S.dDocOffsets.ptr; P.docStatus = (int32_t*)S.dDocStatus.ptr; P.totals = (uint64_t*)S.dTotals.ptr;
+		S.evValid = false;
+		HIP_CHECK( launchL1Stitch( P, c->numCUs, stream, ev));
+		S.evValid = true; S.done = true; S.stream = stream; S.ndocs = ndocs; S.capacity = capacity;
+		if (out)
+		{
+			out->ndocs = ndocs; out->d_lexems = S.dLexems.ptr; out->d_origseg = S.dOrigseg.ptr;
+			out->d_doc_offsets = S.dDocOffsets.ptr; out->d_doc_status = S.dDocStatus.ptr; out->d_totals = S.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the stitched buffers: nothing is renumbered or regrouped on the host
+int sp_lexer_ctx_stitched_fetch( sp_lexer_ctx_t* c, sp_lex_batch_t* out, uint32_t** origseg)
+{
+	std::memset( out, 0, sizeof(*out));
+	if (origseg) *origseg = 0;
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		const sp_lexer_ctx::Stitched& S = c->stitched;
+		if (!S.done) throw std::runtime_error( "the last batch of this context has not been stitched (sp_lexer_ctx_stitch_segments_device)");
+		HIP_CHECK( hipSetDevice( c->device));
+		HIP_CHECK( hipStreamSynchronize( S.stream));
+		uint64_t totals[ 2];
+		copySync( c->own, totals, S.dTotals.ptr, sizeof(totals), hipMemcpyDeviceToHost);
+		const uint64_t nlex = clampCount( totals[ 0], S.capacity);
+		allocLexBatch( out, S.ndocs, nlex);
+		if (nlex) copySync( c->own, out->lexems, S.dLexems.ptr, nlex*sizeof(sp_lexem_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->doc_lexem_offsets, S.dDocOffsets.ptr, (S.ndocs+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		if (S.ndocs) copySync( c->own, out->doc_status, S.dDocStatus.ptr, S.ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+		out->nlexems = nlex;
+		if (origseg)
+		{
+			*origseg = hostArray<uint32_t>( nlex+1);
+			if (nlex) copySync( c->own, *origseg, S.dOrigseg.ptr, nlex*sizeof(uint32_t), hipMemcpyDeviceToHost);
+		}
+	});
+}
+
+int sp_lexer_ctx_stitched_status( sp_lexer_ctx_t* c, int32_t* status, size_t ndocs, size_t* ndocs_stitched)
+{
+	if (ndocs_stitched) *ndocs_stitched = 0;
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		const sp_lexer_ctx::Stitched& S = c->stitched;
+		if (!S.done) throw std::runtime_error( "the last batch of this context has not been stitched (sp_lexer_ctx_stitch_segments_device)");
+		if (ndocs_stitched) *ndocs_stitched = S.ndocs;
+		if (ndocs > S.ndocs) ndocs = S.ndocs;
+		if (!ndocs || !status) return;
+		HIP_CHECK( hipSetDevice( c->device));
+		HIP_CHECK( hipStreamSynchronize( S.stream));
+		copySync( c->own, status, S.dDocStatus.ptr, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+	});
+}
+
+// duration of the three passes of the last stitch in milliseconds (HIP events on its stream; waits for them)
+int sp_lexer_ctx_last_stitch_ms( sp_lexer_ctx_t* c, double* ms)
+{
+	*ms = -1.0;
+	if (!c->stitched.evValid) return SP_ERR_INVALID;
+	if (hipEventSynchronize( c->stitched.ev[ 1]) != hipSuccess) return SP_ERR_DEVICE;
+	return elapsedMs( c->stitched.ev[ 0], c->stitched.ev[ 1], *ms) ? SP_OK : SP_ERR_DEVICE;
 }
 
 void sp_lex_batch_free( sp_lex_batch_t* b)

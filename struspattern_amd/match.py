@@ -2,11 +2,15 @@
 through the MI355X lexer + rule automaton, print tokens (-K) and results in the reference tool's
 listing format (doc/webpage/introduction_struspattern.htm:178-260).
 
-    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] file [file ...]
+    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] file [file ...]
 
-Every file is one document (plain UTF-8 text; the reference tool additionally segments XML, which is
-outside this engine -- pass -o to add the offset of the text inside its original file to the printed
-positions).  All files go to the GPU as one batch.  There is no CPU fallback.
+Every file is one document (plain UTF-8 text; the reference tool segments XML with strusAnalyzer's
+segmenters, which are outside this engine -- pass -o to add the offset of the text inside its original
+file to the printed positions).  With --paragraphs every file is a segmented document: its paragraphs
+(split at runs of empty lines, which belong to no segment) go to the lexer one by one, are stitched to
+the document on the GPU, and positions are printed through the segment position map
+(`segmentposmap[seg] + ofs`, as the reference's printResults does; -o adds on top).  All files go to the
+GPU as one batch.  There is no CPU fallback.
 """
 import argparse
 import sys
@@ -14,7 +18,7 @@ import sys
 import numpy as np
 
 import struspattern_amd as spa
-from struspattern_amd import rulelang
+from struspattern_amd import rulelang, segments
 
 
 def main(argv=None):
@@ -22,6 +26,7 @@ def main(argv=None):
     ap.add_argument("-p", "--program", required=True, help="rule program file")
     ap.add_argument("-K", "--tokens", action="store_true", help="also print the tokens recognized")
     ap.add_argument("-o", "--origin", type=int, default=0, help="offset added to the printed byte positions")
+    ap.add_argument("--paragraphs", action="store_true", help="every file is a document whose segments are its paragraphs")
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("files", nargs="+")
     args = ap.parse_args(argv)
@@ -35,6 +40,8 @@ def main(argv=None):
     for fn in args.files:
         with open(fn, "rb") as f:
             docs.append(f.read())
+    if args.paragraphs:
+        return paragraphs(args, prg, lx, mt, docs)
     text = b"".join(docs)
     offs = np.zeros(len(docs) + 1, np.uint64)
     offs[1:] = np.cumsum([len(d) for d in docs])
@@ -49,6 +56,37 @@ def main(argv=None):
                 print(line)
         res = mb.doc(di)
         for line in rulelang.format_results(doc, res, mb.items, mt.patternName, mt.variableName, origin=args.origin,
+                                            result_format=mb.result_format, item_format=mb.item_format, format_string=mt.formatString,
+                                            first_result=int(mb.doc_offsets[di])):
+            print(line)
+    print("OK done")
+    return 0
+
+
+def paragraphs(args, prg, lx, mt, docs):
+    """--paragraphs: lexer per segment -> stitch on the device -> matcher; the listing through the segment position map"""
+    text, seg_offsets, doc_seg_offsets, posmaps = segments.segmented_batch(docs)
+    lctx = lx.createContext(args.device)
+    mb = spa.matchSegmentedDocs(lctx, mt.createContext(args.device), text, seg_offsets, doc_seg_offsets)
+    if np.any(mb.status != 0):
+        bad = int(np.flatnonzero(mb.status)[0])
+        raise spa.PatternError("at least one document failed: %s has status %d" % (args.files[bad], int(mb.status[bad])))
+    lb, origseg = lctx.stitchedFetch()
+    items = np.zeros((0, 7), np.int64)
+    for di, fn in enumerate(args.files):
+        print("%s:" % fn)
+        doc, posmap = docs[di], posmaps[di]
+        a, b = int(lb.doc_offsets[di]), int(lb.doc_offsets[di + 1])
+        if args.tokens:
+            for line in rulelang.format_tokens(prg, doc, segments.absolute_lexems(lb.lexems[a:b], origseg[a:b], posmap)):
+                print(line)
+        res = segments.absolute_records(mb.doc(di), posmap)
+        if len(res):
+            # (the items of a document are one block in result order)
+            ia, ib = int(res[0, 7]), int(res[-1, 7] + res[-1, 8])
+            items = np.zeros((ib, 7), np.int64)
+            items[ia:ib] = segments.absolute_records(mb.items[ia:ib], posmap)
+        for line in rulelang.format_results(doc, res, items, mt.patternName, mt.variableName, origin=args.origin,
                                             result_format=mb.result_format, item_format=mb.item_format, format_string=mt.formatString,
                                             first_result=int(mb.doc_offsets[di])):
             print(line)
