@@ -106,6 +106,16 @@ int sp_device_count(void);
 void sp_free(void* p);
 /* test hook (tests only): device allocations of at least `bytes` fail like an out-of-memory hipMalloc; 0 switches it off */
 void sp_test_fail_alloc_above(uint64_t bytes);
+/* test hook (tests only, needs no device): what sp_matcher_ctx_batch_fetch_docs(first_doc, ndocs) makes of a batch of batch_ndocs
+ * documents, run over host arrays in the layout the kernels leave on the device: `results` / `items` with the counts that lie
+ * inside the buffers, the optional format handles (both or none), per document a (first, count) range of results in `doc_ranges`
+ * and a status; `exclusive`, `max_result_size`: the matcher's options.  Fills `out` (sp_match_batch_free; doc_stats all 0);
+ * SP_ERR_INVALID with the message in `err` otherwise. */
+struct sp_match_batch;
+int sp_match_batch_regroup(const sp_result_t* results, uint64_t nresults, const sp_result_item_t* items, uint64_t nitems,
+	const uint32_t* result_format, const uint32_t* item_format, const uint64_t* doc_ranges, const int32_t* doc_status,
+	size_t batch_ndocs, size_t first_doc, size_t ndocs, int exclusive, uint32_t max_result_size,
+	struct sp_match_batch* out, char* err, size_t errsize);
 
 /* ==== level 2: token pattern matcher ==== */
 

@@ -48,12 +48,24 @@ class MatchBatch:
         return self.results[self.doc_offsets[i]:self.doc_offsets[i + 1]]
 
 
+def _rows(ptr, n, k, ctype=ctypes.c_uint32):
+    """n rows of k columns of `ctype` behind the ctypes pointer `ptr` (to records of any type), copied: shape (n, k), or (n,) for k = 0"""
+    if not n or not ptr:
+        return np.zeros((n, k) if k else n, ctype)
+    a = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=(n * max(k, 1),)).copy()
+    return a.reshape(n, k) if k else a
+
+
 def _formats_of(b):
     if not b.result_format:
         return None, None
-    rf = np.ctypeslib.as_array(b.result_format, shape=(b.nresults + 1,))[:b.nresults].copy()
-    itf = np.ctypeslib.as_array(b.item_format, shape=(b.nitems * 2 + 2,))[:b.nitems * 2].reshape(-1, 2).copy()
-    return rf, itf
+    return _rows(b.result_format, b.nresults, 0), _rows(b.item_format, b.nitems, 2)
+
+
+def _match_batch_of(b):
+    """the MatchBatch of a capi.SpMatchBatch (copies)"""
+    return MatchBatch(_rows(b.results, b.nresults, 9), _rows(b.items, b.nitems, 7), _rows(b.doc_result_offsets, b.ndocs + 1, 0, ctypes.c_uint64),
+                      _rows(b.doc_stats, b.ndocs, 4, ctypes.c_uint64), _rows(b.doc_status, b.ndocs, 0, ctypes.c_int32), *_formats_of(b))
 
 
 class PatternMatcherContext:
@@ -96,8 +108,7 @@ class PatternMatcherContext:
         if rc != 0:
             raise PatternError("failed to fetch pattern match result: " + self._err())
         try:
-            r = np.ctypeslib.as_array(ctypes.cast(res, ctypes.POINTER(ctypes.c_uint32)), shape=(nres.value * 9 + 1,))[:nres.value * 9].reshape(-1, 9).copy()
-            it = np.ctypeslib.as_array(ctypes.cast(items, ctypes.POINTER(ctypes.c_uint32)), shape=(nitems.value * 7 + 1,))[:nitems.value * 7].reshape(-1, 7).copy()
+            r, it = _rows(res, nres.value, 9), _rows(items, nitems.value, 7)
         finally:
             self._L.sp_free(res)
             self._L.sp_free(items)
@@ -110,9 +121,7 @@ class PatternMatcherContext:
         self._L.sp_matcher_ctx_fetch_formats(self._h, ctypes.byref(rf), ctypes.byref(itf))
         if not rf and not self._inst.formatCount():
             return None, None
-        r = np.ctypeslib.as_array(rf, shape=(nresults + 1,))[:nresults].copy() if nresults else np.zeros(0, np.uint32)
-        i = np.ctypeslib.as_array(itf, shape=(nitems * 2 + 2,))[:nitems * 2].reshape(-1, 2).copy() if nitems else np.zeros((0, 2), np.uint32)
-        return r, i
+        return _rows(rf, nresults, 0), _rows(itf, nitems, 2)
 
     def getStatistics(self):
         """the statistics of the last fetch; None in result-set mode on the join kernel, which installs nothing"""
@@ -139,16 +148,9 @@ class PatternMatcherContext:
         try:
             if rc != 0 and (rc != -5 or check):
                 raise PatternError("batch match failed (%d): %s" % (rc, self._err()))
-            u32p = ctypes.POINTER(ctypes.c_uint32)
-            res = np.ctypeslib.as_array(ctypes.cast(b.results, u32p), shape=(b.nresults * 9 + 1,))[:b.nresults * 9].reshape(-1, 9).copy()
-            items = np.ctypeslib.as_array(ctypes.cast(b.items, u32p), shape=(b.nitems * 7 + 1,))[:b.nitems * 7].reshape(-1, 7).copy()
-            offs = np.ctypeslib.as_array(b.doc_result_offsets, shape=(ndocs + 1,)).copy()
-            stats = np.ctypeslib.as_array(b.doc_stats, shape=(ndocs * 4 + 1,))[:ndocs * 4].reshape(-1, 4).copy()
-            status = np.ctypeslib.as_array(b.doc_status, shape=(ndocs + 1,))[:ndocs].copy()
-            rfmt, ifmt = _formats_of(b)
+            return _match_batch_of(b)
         finally:
             self._L.sp_match_batch_free(ctypes.byref(b))
-        return MatchBatch(res, items, offs, stats, status, rfmt, ifmt)
 
     # -- batch mode (device-resident buffers; pointers are raw device addresses, e.g. torch data_ptr())
     def matchDocsDevice(self, d_lexems, d_doc_offsets, ndocs, nlexems, stream=0, d_origseg=0):
@@ -207,17 +209,9 @@ class PatternMatcherContext:
         try:
             if rc != 0:
                 raise PatternError("fetching the batch failed (%d): %s" % (rc, self._err()))
-            ndocs = b.ndocs
-            u32p = ctypes.POINTER(ctypes.c_uint32)
-            res = np.ctypeslib.as_array(ctypes.cast(b.results, u32p), shape=(b.nresults * 9 + 1,))[:b.nresults * 9].reshape(-1, 9).copy()
-            items = np.ctypeslib.as_array(ctypes.cast(b.items, u32p), shape=(b.nitems * 7 + 1,))[:b.nitems * 7].reshape(-1, 7).copy()
-            offs = np.ctypeslib.as_array(b.doc_result_offsets, shape=(ndocs + 1,)).copy()
-            stats = np.ctypeslib.as_array(b.doc_stats, shape=(ndocs * 4 + 1,))[:ndocs * 4].reshape(-1, 4).copy()
-            status = np.ctypeslib.as_array(b.doc_status, shape=(ndocs + 1,))[:ndocs].copy()
-            rfmt, ifmt = _formats_of(b)
+            return _match_batch_of(b)
         finally:
             self._L.sp_match_batch_free(ctypes.byref(b))
-        return MatchBatch(res, items, offs, stats, status, rfmt, ifmt)
 
     def batchCounters(self):
         arr = (ctypes.c_uint64 * 8)()
@@ -407,6 +401,11 @@ class LexBatch:
         return self.lexems[self.doc_offsets[i]:self.doc_offsets[i + 1]]
 
 
+def _lex_batch_of(b):
+    """the LexBatch of a capi.SpLexBatch (copies)"""
+    return LexBatch(_rows(b.lexems, b.nlexems, 4), _rows(b.doc_lexem_offsets, b.ndocs + 1, 0, ctypes.c_uint64), _rows(b.doc_status, b.ndocs, 0, ctypes.c_int32))
+
+
 class PatternLexerContext:
     """PatternLexerContextInterface (src/patternLexer.cpp:681-959) + batch mode."""
 
@@ -436,10 +435,9 @@ class PatternLexerContext:
         if rc != 0:
             raise PatternError("failed to run pattern matching terms with regular expressions: " + self._err())
         try:
-            arr = np.ctypeslib.as_array(ctypes.cast(lex, ctypes.POINTER(ctypes.c_uint32)), shape=(n.value * 4 + 1,))[:n.value * 4].reshape(-1, 4).copy()
+            return _rows(lex, n.value, 4)
         finally:
             self._L.sp_free(lex)
-        return arr
 
     def reset(self):
         self._L.sp_lexer_ctx_reset(self._h)
@@ -453,12 +451,9 @@ class PatternLexerContext:
         try:
             if rc != 0 and (rc != -5 or check):
                 raise PatternError("batch lexer run failed (%d): %s" % (rc, self._err()))
-            lex = np.ctypeslib.as_array(ctypes.cast(b.lexems, ctypes.POINTER(ctypes.c_uint32)), shape=(b.nlexems * 4 + 1,))[:b.nlexems * 4].reshape(-1, 4).copy()
-            offs = np.ctypeslib.as_array(b.doc_lexem_offsets, shape=(ndocs + 1,)).copy()
-            status = np.ctypeslib.as_array(b.doc_status, shape=(ndocs + 1,))[:ndocs].copy()
+            return _lex_batch_of(b)
         finally:
             self._L.sp_lex_batch_free(ctypes.byref(b))
-        return LexBatch(lex, offs, status)
 
     def matchDocsDevice(self, d_text, d_doc_offsets, ndocs, nbytes, stream=0):
         out = capi.SpLexDeviceBatch()
@@ -474,12 +469,9 @@ class PatternLexerContext:
         try:
             if rc != 0:
                 raise PatternError("fetching the lexer batch failed (%d): %s" % (rc, self._err()))
-            lex = np.ctypeslib.as_array(ctypes.cast(b.lexems, ctypes.POINTER(ctypes.c_uint32)), shape=(b.nlexems * 4 + 1,))[:b.nlexems * 4].reshape(-1, 4).copy()
-            offs = np.ctypeslib.as_array(b.doc_lexem_offsets, shape=(ndocs + 1,)).copy()
-            status = np.ctypeslib.as_array(b.doc_status, shape=(ndocs + 1,))[:ndocs].copy()
+            return _lex_batch_of(b)
         finally:
             self._L.sp_lex_batch_free(ctypes.byref(b))
-        return LexBatch(lex, offs, status)
 
     def stitchSegmentsDevice(self, d_doc_seg_offsets, ndocs, stream=0):
         """the "documents" of the last device batch are segments: stitch them to `ndocs` documents on the device (asynchronous
@@ -500,15 +492,10 @@ class PatternLexerContext:
         try:
             if rc != 0:
                 raise PatternError("fetching the stitched batch failed (%d): %s" % (rc, self._err()))
-            ndocs = b.ndocs
-            lex = np.ctypeslib.as_array(ctypes.cast(b.lexems, ctypes.POINTER(ctypes.c_uint32)), shape=(b.nlexems * 4 + 1,))[:b.nlexems * 4].reshape(-1, 4).copy()
-            offs = np.ctypeslib.as_array(b.doc_lexem_offsets, shape=(ndocs + 1,)).copy()
-            status = np.ctypeslib.as_array(b.doc_status, shape=(ndocs + 1,))[:ndocs].copy()
-            origseg = np.ctypeslib.as_array(seg, shape=(b.nlexems + 1,))[:b.nlexems].copy()
+            return _lex_batch_of(b), _rows(seg, b.nlexems, 0)
         finally:
             self._L.sp_lex_batch_free(ctypes.byref(b))
             self._L.sp_free(seg)
-        return LexBatch(lex, offs, status), origseg
 
     def stitchedStatus(self):
         """the per-document status words of the last stitchSegmentsDevice (waits for it)"""

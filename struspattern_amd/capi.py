@@ -75,6 +75,8 @@ SIGNATURES = {
     "sp_device_count": (ctypes.c_int, []),
     "sp_free": (None, [c_vp]),
     "sp_test_fail_alloc_above": (None, [c_u64]),
+    "sp_match_batch_regroup": (ctypes.c_int, [c_vp, c_u64, c_vp, c_u64, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, ctypes.c_size_t, ctypes.c_size_t,
+                                              ctypes.c_int, c_u32, P(SpMatchBatch), ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_create": (c_vp, []),
     "sp_matcher_free": (None, [c_vp]),
     "sp_matcher_last_error": (c_cp, [c_vp]),

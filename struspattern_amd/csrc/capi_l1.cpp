@@ -275,13 +275,15 @@ int sp_lexer_ctx_grow_arena( sp_lexer_ctx_t* c)
 } // extern "C"
 
 namespace {
-// the host arrays of a batch of `ndocs` documents with `nlexems` lexems (sp_lex_batch_free)
-void allocLexBatch( sp_lex_batch_t* out, size_t ndocs, uint64_t nlexems)
+// Host copy of the lexems of the documents [firstDoc, firstDoc+ndocs) of the last launch, grouped by document (batch_fetch.hpp);
+// `counters`: of that launch; bulk: the whole batch in one copy, else a copy per document
+void copyOutLexBatch( sp_lexer_ctx* c, size_t firstDoc, size_t ndocs, const uint64_t* counters, bool bulk, sp_lex_batch_t* out)
 {
-	out->ndocs = ndocs;
-	out->doc_lexem_offsets = hostArray<uint64_t>( ndocs+1);
-	out->doc_status = hostArray<int32_t>( ndocs+1);
-	out->lexems = hostArray<sp_lexem_t>( nlexems+1);
+	LexBatchSource src;
+	src.lexems = (const sp_lexem_t*)c->lexems.ptr(); src.nlexems = clampCount( counters[ L1C_LEXEMS], c->lexems.count);
+	src.docRange = (const uint64_t*)c->dDocRange.ptr; src.docStatus = (const int32_t*)c->dDocStatus.ptr;
+	src.ndocs = c->lastNdocs;
+	fetchLexBatch( src, firstDoc, ndocs, bulk, deviceToHost( c->own), out);
 }
 void launchLex( sp_lexer_ctx* c, const void* d_text, const void* d_doc_offsets, size_t ndocs, size_t nbytes, hipStream_t stream)
 {
@@ -498,24 +500,7 @@ int sp_lexer_ctx_match_docs( sp_lexer_ctx_t* c, const char* text, const uint64_t
 			}
 			if (!grow || attempt >= 12) break;
 		}
-		std::vector<uint64_t> range( ndocs*2+2);
-		if (ndocs) copySync( c->own, range.data(), c->dDocRange.ptr, ndocs*2*sizeof(uint64_t), hipMemcpyDeviceToHost);
-		uint64_t nlex = clampCount( counters[ L1C_LEXEMS], c->lexems.count);
-		std::vector<sp_lexem_t> raw( nlex+1);
-		if (nlex) copySync( c->own, raw.data(), c->lexems.ptr(), nlex*sizeof(sp_lexem_t), hipMemcpyDeviceToHost);
-		uint64_t total = 0;
-		for (size_t di=0; di<ndocs; ++di) { if (st[ di] != 0) range[ 2*di+1] = 0; total += range[ 2*di+1]; }
-		allocLexBatch( out, ndocs, total);
-		uint64_t lp = 0;
-		for (size_t di=0; di<ndocs; ++di)
-		{
-			out->doc_lexem_offsets[ di] = lp;
-			out->doc_status[ di] = st[ di];
-			if (range[ 2*di+1]) std::memcpy( out->lexems + lp, raw.data() + range[ 2*di], range[ 2*di+1]*sizeof(sp_lexem_t));
-			lp += range[ 2*di+1];
-		}
-		out->doc_lexem_offsets[ ndocs] = lp;
-		out->nlexems = lp;
+		copyOutLexBatch( c, 0, ndocs, counters, true, out);
 		if (counters[ L1C_FAILED])
 		{
 			size_t bad = 0;
@@ -535,34 +520,9 @@ int sp_lexer_ctx_batch_fetch_docs( sp_lexer_ctx_t* c, size_t first_doc, size_t n
 	return guardedCall( c->lasterror, SP_ERR_DEVICE, [&]{
 		HIP_CHECK( hipSetDevice( c->device));
 		HIP_CHECK( hipStreamSynchronize( c->lastStream));
-		if (first_doc > c->lastNdocs || ndocs > c->lastNdocs - first_doc) throw std::runtime_error( "document range outside the last batch");
 		uint64_t counters[ L1C_COUNT];
 		copySync( c->own, counters, c->dCounters.ptr, sizeof(counters), hipMemcpyDeviceToHost);
-		const uint64_t devLexems = clampCount( counters[ L1C_LEXEMS], c->lexems.count);
-		std::vector<uint64_t> range( ndocs*2+2);
-		std::vector<int32_t> st( ndocs+1);
-		if (ndocs)
-		{
-			copySync( c->own, range.data(), (const uint64_t*)c->dDocRange.ptr + 2*first_doc, ndocs*2*sizeof(uint64_t), hipMemcpyDeviceToHost);
-			copySync( c->own, st.data(), (const int32_t*)c->dDocStatus.ptr + first_doc, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
-		}
-		uint64_t total = 0;
-		for (size_t di=0; di<ndocs; ++di)
-		{
-			if (st[ di] != 0 || range[ 2*di] + range[ 2*di+1] > devLexems) range[ 2*di+1] = 0;
-			total += range[ 2*di+1];
-		}
-		allocLexBatch( out, ndocs, total);
-		std::memcpy( out->doc_status, st.data(), ndocs*sizeof(int32_t));
-		uint64_t lp = 0;
-		for (size_t di=0; di<ndocs; ++di)
-		{
-			out->doc_lexem_offsets[ di] = lp;
-			if (range[ 2*di+1]) copySync( c->own, out->lexems + lp, (const sp_lexem_t*)c->lexems.ptr() + range[ 2*di], range[ 2*di+1]*sizeof(sp_lexem_t), hipMemcpyDeviceToHost);
-			lp += range[ 2*di+1];
-		}
-		out->doc_lexem_offsets[ ndocs] = lp;
-		out->nlexems = lp;
+		copyOutLexBatch( c, first_doc, ndocs, counters, false, out);
 	});
 }
 

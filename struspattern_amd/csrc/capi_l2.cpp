@@ -333,140 +333,19 @@ BatchCounts readCounts( sp_matcher_ctx* c)
 	return b;
 }
 
-// the host arrays of a batch of `ndocs` documents with room for `nresults` results and `nitems` items (sp_match_batch_free)
-void allocMatchBatch( sp_match_batch_t* out, size_t ndocs, uint64_t nresults, uint64_t nitems, bool withFormats)
-{
-	out->ndocs = ndocs; out->nresults = (size_t)nresults; out->nitems = (size_t)nitems;
-	out->doc_stats = hostArray<uint64_t>( ndocs*4+1);
-	out->doc_status = hostArray<int32_t>( ndocs+1);
-	out->doc_result_offsets = hostArray<uint64_t>( ndocs+1);
-	out->results = hostArray<sp_result_t>( nresults+1);
-	out->items = hostArray<sp_result_item_t>( nitems+1);
-	if (withFormats)
-	{
-		out->result_format = hostArray<uint32_t>( nresults+1);
-		out->item_format = hostArray<uint32_t>( (nitems+1)*2);
-	}
-}
-
-// Host copy of the device results of the last launch for the documents [firstDoc, firstDoc+ndocs), regrouped
-// by document (the device appends whole documents in completion order), with the `exclusive`
-// elimination of fetchResults applied on the way.  The whole batch is copied in bulk; a sub-range
-// copies only the result and item blocks of its own documents.
+// Host copy of the device results of the last launch for the documents [firstDoc, firstDoc+ndocs), regrouped by document with
+// the `exclusive` elimination of fetchResults applied on the way: the plan, the copy segments and the regroup of batch_fetch.hpp
 void copyOutBatch( sp_matcher_ctx* c, size_t firstDoc, size_t ndocs, const BatchCounts& counts, sp_match_batch_t* out)
 {
-	const bool whole = (firstDoc == 0 && ndocs == c->lastNdocs);
-	std::vector<uint64_t> range( ndocs*2+2);
-	std::vector<int32_t> status( ndocs+1);
-	if (ndocs)
-	{
-		copySync( c->own, range.data(), (const uint64_t*)c->io.dDocRange.ptr + 2*firstDoc, ndocs*2*sizeof(uint64_t), hipMemcpyDeviceToHost);
-		copySync( c->own, status.data(), (const int32_t*)c->io.dDocStatus.ptr + firstDoc, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
-	}
-	const uint64_t devResults = counts.results, devItems = counts.items;
-	std::vector<sp_result_t> raw;
-	std::vector<sp_result_item_t> rawitems;
-	std::vector<uint32_t> rawrf, rawif;
-	if (whole)
-	{
-		raw.resize( devResults+1); rawitems.resize( devItems+1);
-		if (devResults) copySync( c->own, raw.data(), c->io.results.ptr(), devResults*sizeof(sp_result_t), hipMemcpyDeviceToHost);
-		if (devItems) copySync( c->own, rawitems.data(), c->io.items.ptr(), devItems*sizeof(sp_result_item_t), hipMemcpyDeviceToHost);
-		if (c->io.withFormats)
-		{
-			rawrf.resize( devResults+1); rawif.resize( 2*devItems+2);
-			if (devResults) copySync( c->own, rawrf.data(), c->io.dResultFormat.ptr, devResults*sizeof(uint32_t), hipMemcpyDeviceToHost);
-			if (devItems) copySync( c->own, rawif.data(), c->io.dItemFormat.ptr, 2*devItems*sizeof(uint32_t), hipMemcpyDeviceToHost);
-		}
-	}
-	else
-	{
-		// the blocks of the wanted documents only, packed one after the other; ranges and item indices are rebased
-		uint64_t nres = 0;
-		for (size_t di=0; di<ndocs; ++di) if (status[ di] == 0 && range[ 2*di] + range[ 2*di+1] <= devResults) nres += range[ 2*di+1];
-		raw.resize( nres+1);
-		if (c->io.withFormats) rawrf.resize( nres+1);
-		uint64_t rp0 = 0;
-		for (size_t di=0; di<ndocs; ++di)
-		{
-			const uint64_t b = range[ 2*di], n = range[ 2*di+1];
-			if (status[ di] != 0 || b + n > devResults) { range[ 2*di+1] = 0; continue; }
-			if (n) copySync( c->own, raw.data() + rp0, (const sp_result_t*)c->io.results.ptr() + b, n*sizeof(sp_result_t), hipMemcpyDeviceToHost);
-			if (n && c->io.withFormats) copySync( c->own, rawrf.data() + rp0, (const uint32_t*)c->io.dResultFormat.ptr + b, n*sizeof(uint32_t), hipMemcpyDeviceToHost);
-			range[ 2*di] = rp0; rp0 += n;
-		}
-		uint64_t nitems = 0;
-		for (uint64_t ri=0; ri<nres; ++ri) nitems += raw[ ri].item_count;
-		rawitems.resize( nitems+1);
-		if (c->io.withFormats) rawif.resize( 2*nitems+2);
-		uint64_t ip0 = 0;
-		for (size_t di=0; di<ndocs; ++di)
-		{
-			// the items of one document are one block, in result order
-			const uint64_t b = range[ 2*di], n = range[ 2*di+1];
-			uint64_t first = 0, cnt = 0;
-			for (uint64_t ri=0; ri<n; ++ri) if (raw[ b+ri].item_count) { if (!cnt) first = raw[ b+ri].item_begin; cnt += raw[ b+ri].item_count; }
-			if (!cnt) continue;
-			if (first + cnt > devItems) throw std::runtime_error( "item block of a document lies outside the device buffer");
-			copySync( c->own, rawitems.data() + ip0, (const sp_result_item_t*)c->io.items.ptr() + first, cnt*sizeof(sp_result_item_t), hipMemcpyDeviceToHost);
-			if (c->io.withFormats) copySync( c->own, rawif.data() + 2*ip0, (const uint32_t*)c->io.dItemFormat.ptr + 2*first, 2*cnt*sizeof(uint32_t), hipMemcpyDeviceToHost);
-			for (uint64_t ri=0; ri<n; ++ri) if (raw[ b+ri].item_count) raw[ b+ri].item_begin = (uint32_t)(raw[ b+ri].item_begin - first + ip0);
-			ip0 += cnt;
-		}
-	}
-	// regroup by document (the device appends whole documents in completion order)
-	uint64_t total = 0, totalItems = 0;
-	for (size_t di=0; di<ndocs; ++di)
-	{
-		if (status[ di] != 0) { range[ 2*di+1] = 0; continue; }
-		total += range[ 2*di+1];
-		for (uint64_t ri=0; ri<range[ 2*di+1]; ++ri) totalItems += raw[ range[ 2*di]+ri].item_count;
-	}
-	allocMatchBatch( out, ndocs, total, totalItems, c->io.withFormats);	// (`exclusive` may keep fewer: nresults, nitems below)
-	std::memcpy( out->doc_status, status.data(), ndocs*sizeof(int32_t));
-	if (ndocs) copySync( c->own, out->doc_stats, (const uint64_t*)c->io.dDocStats.ptr + 4*firstDoc, ndocs*4*sizeof(uint64_t), hipMemcpyDeviceToHost);
-	uint64_t rp = 0, ip = 0;
-	// `exclusive` option: covered results are dropped on the way out (src/patternMatcher.cpp:192-246, :278-289)
-	const bool exclusive = c->inst->compiler.exclusive();
-	const uint32_t maxResultSize = c->inst->compiler.maxResultSize();
-	std::vector<char> covered;
-	for (size_t di=0; di<ndocs; ++di)
-	{
-		out->doc_result_offsets[ di] = rp;
-		const uint64_t b = range[ 2*di], n = range[ 2*di+1];
-		if (exclusive)
-		{
-			covered.assign( n, 0);
-			for (uint64_t ai=0; ai<n; ++ai)
-			{
-				const sp_result_t& r = raw[ b+ai];
-				for (uint64_t ni=ai; ni<n; ++ni)
-				{
-					const sp_result_t& f = raw[ b+ni];
-					if (f.origseg > r.origendseg || f.origpos >= r.origend + maxResultSize) break;
-					bool differ = (f.origendseg != r.origendseg || f.origend != r.origend || f.origseg != r.origseg || f.origpos != r.origpos);
-					if (f.origseg <= r.origseg && f.origpos <= r.origpos && f.origendseg >= r.origendseg && f.origend >= r.origend && differ) covered[ ai] = 1;
-					if (f.origseg >= r.origseg && f.origpos >= r.origpos && f.origendseg <= r.origendseg && f.origend <= r.origend && differ) covered[ ni] = 1;
-				}
-			}
-		}
-		for (uint64_t ri=0; ri<n; ++ri)
-		{
-			if (exclusive && covered[ ri]) continue;
-			sp_result_t r = raw[ b+ri];
-			uint32_t ib = r.item_begin, ic = r.item_count;
-			r.item_begin = (uint32_t)ip;
-			if (c->io.withFormats)
-			{
-				out->result_format[ rp] = rawrf[ b+ri];
-				for (uint32_t k=0; k<ic; ++k) { out->item_format[ 2*(ip+k)] = rawif[ 2*(ib+k)]; out->item_format[ 2*(ip+k)+1] = rawif[ 2*(ib+k)+1]; }
-			}
-			for (uint32_t k=0; k<ic; ++k) out->items[ ip++] = rawitems[ ib+k];
-			out->results[ rp++] = r;
-		}
-	}
-	out->doc_result_offsets[ ndocs] = rp;
-	out->nresults = rp; out->nitems = ip;
+	MatchBatchSource src;
+	src.results = (const sp_result_t*)c->io.results.ptr(); src.nresults = counts.results;
+	src.items = (const sp_result_item_t*)c->io.items.ptr(); src.nitems = counts.items;
+	src.resultFormat = c->io.withFormats ? (const uint32_t*)c->io.dResultFormat.ptr : 0;
+	src.itemFormat = c->io.withFormats ? (const uint32_t*)c->io.dItemFormat.ptr : 0;
+	src.docRange = (const uint64_t*)c->io.dDocRange.ptr; src.docStatus = (const int32_t*)c->io.dDocStatus.ptr;
+	src.docStats = (const uint64_t*)c->io.dDocStats.ptr;
+	src.ndocs = c->lastNdocs;
+	fetchMatchBatch( src, firstDoc, ndocs, c->inst->compiler.exclusive(), c->inst->compiler.maxResultSize(), deviceToHost( c->own), out);
 }
 
 } // namespace
@@ -480,7 +359,6 @@ int sp_matcher_ctx_batch_fetch_docs( sp_matcher_ctx_t* c, size_t first_doc, size
 	return guardedCall( c->lasterror, SP_ERR_DEVICE, [&]{
 		HIP_CHECK( hipSetDevice( c->device));
 		HIP_CHECK( hipStreamSynchronize( c->lastStream));
-		if (first_doc > c->lastNdocs || ndocs > c->lastNdocs - first_doc) throw std::runtime_error( "document range outside the last batch");
 		copyOutBatch( c, first_doc, ndocs, readCounts( c), out);
 	});
 }

@@ -4,6 +4,7 @@
 #define SPA_CAPI_UTIL_HPP
 #include "../../include/strus_pattern_amd.h"
 #include "hip_util.hpp"
+#include "batch_fetch.hpp"
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -33,15 +34,6 @@ inline void copyText( char* dst, size_t dstsize, const char* text)
 	if (dst && dstsize) { std::strncpy( dst, text, dstsize-1); dst[ dstsize-1] = 0; }
 }
 
-// malloc'ed array of n elements for the caller (sp_free, sp_*_batch_free)
-template <class T>
-T* hostArray( uint64_t n)
-{
-	T* p = (T*)std::malloc( (size_t)n * sizeof(T));
-	if (!p) throw std::bad_alloc();
-	return p;
-}
-
 // sp_*_serialize: what `save` writes as a blob for the caller (sp_free)
 template <class FN>
 int exportBlob( std::string& err, void** blob, size_t* size, FN save)
@@ -67,6 +59,12 @@ HANDLE* importBlob( char* err, size_t errsize, FN load)
 
 // what of a counted output lies inside its buffer
 inline uint64_t clampCount( uint64_t counted, uint64_t capacity) { return counted < capacity ? counted : capacity; }
+
+// the copies of a batch fetch (batch_fetch.hpp) from the device, on `stream`
+inline auto deviceToHost( hipStream_t stream)
+{
+	return [stream]( void* dst, const void* src, size_t n){ copySync( stream, dst, src, n, hipMemcpyDeviceToHost); };
+}
 
 // ---- sp_*_ctx_batch_status, sp_*_ctx_last_kernel_ms
 template <class CTX>

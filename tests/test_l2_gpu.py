@@ -314,3 +314,52 @@ def test_failed_allocation_leaves_no_stale_capacity():
     finally:
         capi.lib().sp_test_fail_alloc_above(0)
     _compare(ctx.matchDocs(lex, offs), ref, 20)           # reallocated: same results as before
+
+
+@pytest.mark.parametrize("exclusive", [False, True])
+@pytest.mark.parametrize("formats", [False, True])
+def test_batch_fetch_of_a_document_range_is_the_slice_of_the_whole_batch(exclusive, formats):
+    """batchFetch(first_doc, ndocs) copies only the blocks of its documents (csrc/batch_fetch.hpp): it must return what
+    batchFetch() returns for them, items and format handles re-based, a failed document inside the range included."""
+    import random
+    from .test_formats import _apply, _random_program
+    rng = random.Random(9300)
+    calls = [c for _ in range(3) for c in _random_program(rng, 6)]         # 42 rules, later ones refer to earlier ones
+    if not formats:
+        calls = [(c[0], c[1], "", c[3]) if c[0] == "definePattern" else c for c in calls]
+    m = spa.PatternMatcherInstance()
+    if exclusive:
+        m.defineOption("exclusive")
+        m.defineOption("maxResultSize", 30)
+    _apply(m, calls)
+    assert (m.formatCount() != 0) == formats
+    lex, offs = synth.random_documents(12, 60, 6, seed=77)
+    lex = lex.copy()
+    ndocs, failed = 12, 6
+    a = int(offs[failed])
+    lex[a + 10, 1], lex[a + 11, 1] = lex[a + 11, 1] + 5, lex[a + 10, 1]    # document 6: positions descend, a data error
+    ctx = m.createContext()
+    host = ctx.matchDocs(lex, offs, check=False)
+    whole = ctx.batchFetch()
+    assert [int(x) for x in whole.status] == [1 if d == failed else 0 for d in range(ndocs)]
+    assert len(whole.doc(failed)) == 0 and len(whole.results) > 50 and len(whole.items) > 0
+    for f in ("results", "items", "doc_offsets", "stats", "status"):
+        assert np.array_equal(getattr(whole, f), getattr(host, f)), f
+    assert (whole.result_format is not None) == formats
+    for first, n in [(0, 0), (0, 1), (5, 3), (ndocs - 1, 1), (ndocs, 0)]:
+        sub = ctx.batchFetch(first, n)
+        lo, hi = int(whole.doc_offsets[first]), int(whole.doc_offsets[first + n])
+        ilo = int(whole.results[:lo, 8].sum())
+        ihi = ilo + int(whole.results[lo:hi, 8].sum())
+        want = whole.results[lo:hi].copy()
+        want[:, 7] -= ilo
+        assert np.array_equal(sub.results, want)
+        assert np.array_equal(sub.items, whole.items[ilo:ihi])
+        assert np.array_equal(sub.doc_offsets, whole.doc_offsets[first:first + n + 1] - whole.doc_offsets[first])
+        assert np.array_equal(sub.stats, whole.stats[first:first + n]) and np.array_equal(sub.status, whole.status[first:first + n])
+        if formats:
+            assert np.array_equal(sub.result_format, whole.result_format[lo:hi]) and np.array_equal(sub.item_format, whole.item_format[ilo:ihi])
+        else:
+            assert sub.result_format is None and sub.item_format is None
+    with pytest.raises(spa.PatternError, match="document range outside the last batch"):
+        ctx.batchFetch(ndocs + 1, 0)
