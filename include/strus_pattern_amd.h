@@ -318,6 +318,80 @@ int sp_matcher_ctx_last_finish_sort_ms(sp_matcher_ctx_t* c, double* sort_ms);
 /* diagnostics and tests: the largest number of results of one document that the canonical sort orders inside one
  * workgroup's LDS, without a merge pass */
 uint32_t sp_matcher_finish_sort_tile(void);
+
+/* ---- matched text: the bytes that the results and items of a finished batch cover, gathered on the device
+ * (csrc/l2_text.h) or, for a batch already fetched, on the host (csrc/span_text.hpp).  The rule is the project's own,
+ * unpinned by a reference vector (the reference has no such call; its tools slice the source on the host,
+ * tests/utils/testUtils.cpp:125-150).  The text is the one the lexer batch ran on, all segments back to back;
+ * seg_offsets[nseg+1] is the array given to sp_lexer_ctx_match_docs_device, doc_seg_offsets[ndocs+1] the one given to
+ * sp_lexer_ctx_stitch_segments_device, or NULL: document d is segment d then, and nseg must be ndocs (SP_ERR_INVALID).
+ * Words 3..6 of a result or item record are (origseg, origpos, origendseg, origend).  For a span of document d,
+ *   s0 = doc_seg_offsets[d] + origseg, s1 = doc_seg_offsets[d] + origendseg,
+ *   bytes = text[ seg_offsets[s0] + origpos, seg_offsets[s1] + origend )
+ * -- ONE contiguous range also when the span crosses segments: the tail of its first segment, the whole segments between
+ * and the head of its last; bytes that a segmenter removed between segments are not part of it.  A span is valid when
+ *   doc_seg_offsets[d] <= doc_seg_offsets[d+1] <= nseg,   origseg <= origendseg < doc_seg_offsets[d+1] - doc_seg_offsets[d],
+ *   origpos <= len(s0), origend <= len(s1),   begin <= end <= nbytes,   and the seg_offsets used ascend.
+ * A document with an invalid span in a requested family, or whose spans of one family add up to 2^32 bytes or more, has
+ * text status SP_DOC_ERR_RANGE and ALL its spans are empty (the stitch's rule: it fails and is empty); the other documents
+ * are not affected.  A document without spans (one the matcher failed among them) has text status 0.  No byte outside
+ * [0, nbytes) of the text is read and none outside the output buffers written, whatever the records hold. */
+#define SP_TEXT_RESULTS 1u
+#define SP_TEXT_ITEMS   2u
+typedef struct sp_text_source {
+	const void* d_text;            /* device: uint8_t[nbytes] */
+	uint64_t nbytes;
+	const void* d_seg_offsets;     /* device: uint64_t[nseg+1] */
+	size_t nseg;
+	const void* d_doc_seg_offsets; /* device: uint64_t[ndocs+1]; may be NULL */
+} sp_text_source_t;
+typedef struct sp_match_text_batch {
+	size_t ndocs;
+	void* d_result_text;           /* uint8_t[]: the text of result 0 of the finished d_results first */
+	void* d_result_text_offsets;   /* uint64_t[nresults+1], parallel to the finished d_results; the spans of a failed
+	                                  document all sit on the document's offset */
+	void* d_item_text;             /* the same, parallel to the finished d_items */
+	void* d_item_text_offsets;
+	void* d_doc_text_status;       /* int32_t[ndocs]: 0 or SP_DOC_ERR_RANGE */
+	void* d_totals;                /* uint64_t[2]: result bytes, item bytes */
+} sp_match_text_batch_t;
+/* host copy of a text batch (sp_match_text_free); a family that was not asked for has NULL pointers and a total of 0 */
+typedef struct sp_match_text {
+	size_t ndocs;
+	size_t nresults;
+	size_t nitems;
+	char* result_text;
+	uint64_t* result_text_offsets; /* nresults+1 */
+	char* item_text;
+	uint64_t* item_text_offsets;   /* nitems+1 */
+	int32_t* doc_text_status;      /* ndocs */
+	uint64_t totals[2];            /* result bytes, item bytes */
+} sp_match_text_t;
+/* Gathers the text of the batch finished last on this context (sp_matcher_ctx_batch_finish_device[_ex], either order; the
+ * text follows the finished order).  flags: SP_TEXT_RESULTS | SP_TEXT_ITEMS; a family that is not requested has NULL
+ * pointers in `out`.  Three passes per family on `stream` (count, offsets, place: csrc/l2_text.h); the call enqueues count
+ * and offsets, waits for them to read the totals, sizes the buffers and enqueues the placement, which it does not wait
+ * for.  The buffers belong to the context, are allocated at the first call, only grow, and are valid until the next text
+ * call; the next batch or finish invalidates the state, not the buffers.  A `stream` other than the finish's is ordered
+ * behind it with an event.  SP_ERR_INVALID when the last batch is not finished, for flags 0 or unknown bits, and for a
+ * NULL source; SP_ERR_NOMEM when a buffer cannot be allocated (the context stays usable). */
+int sp_matcher_ctx_finished_text_device(sp_matcher_ctx_t* c, const sp_text_source_t* src, uint32_t flags, void* stream, sp_match_text_batch_t* out);
+/* plain copy of the buffers of the last sp_matcher_ctx_finished_text_device to the host (waits for it) */
+int sp_matcher_ctx_finished_text_fetch(sp_matcher_ctx_t* c, sp_match_text_t* out);
+void sp_match_text_free(sp_match_text_t* t);
+/* duration of all passes of the last text call in milliseconds (HIP events on its stream round them; waits for them; the
+ * host's wait for the totals between offsets and place lies inside) */
+int sp_matcher_ctx_last_text_ms(sp_matcher_ctx_t* c, double* ms);
+/* diagnostics and tests: spans of at least this many bytes are copied by their whole wave in a loop of their own */
+uint32_t sp_matcher_text_long_span(void);
+/* The same rule over host arrays, needs no device: the text of a batch already fetched (sp_matcher_ctx_finished_fetch,
+ * sp_matcher_ctx_batch_fetch, sp_matcher_ctx_match_docs), and the yardstick of the device passes.  The items of document d
+ * are taken to follow those of document d-1 without gaps, in result order.  Fills `out` (sp_match_text_free);
+ * SP_ERR_INVALID with the message in `err` for flags 0 or unknown bits, a NULL source, nseg != ndocs without
+ * doc_seg_offsets, and a batch whose offsets and item counts do not cover its results and items. */
+int sp_match_batch_text(const sp_match_batch_t* mb, const char* text, uint64_t nbytes, const uint64_t* seg_offsets,
+                        size_t nseg, const uint64_t* doc_seg_offsets, uint32_t flags,
+                        sp_match_text_t* out, char* err, size_t errsize);
 /* copies the results of the last device batch to the host, grouped by document (as sp_matcher_ctx_match_docs
  * returns them, `exclusive` elimination included) */
 int sp_matcher_ctx_batch_fetch(sp_matcher_ctx_t* c, sp_match_batch_t* out);

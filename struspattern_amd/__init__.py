@@ -13,10 +13,11 @@ from . import capi
 from .capi import SpLexem, SpResult, SpResultItem
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
-           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs"]
+           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
+SP_TEXT_RESULTS, SP_TEXT_ITEMS = 1, 2   # include/strus_pattern_amd.h: the families of spans of a text call
 SP_ERR_UNAVAILABLE = -6     # include/strus_pattern_amd.h: a value that does not exist for the context
 
 JOIN_OP = {"sequence": 0, "sequence_imm": 1, "sequence_struct": 2, "within": 3, "within_struct": 4, "any": 5, "and": 6}
@@ -66,6 +67,65 @@ def _match_batch_of(b):
     """the MatchBatch of a capi.SpMatchBatch (copies)"""
     return MatchBatch(_rows(b.results, b.nresults, 9), _rows(b.items, b.nitems, 7), _rows(b.doc_result_offsets, b.ndocs + 1, 0, ctypes.c_uint64),
                       _rows(b.doc_stats, b.ndocs, 4, ctypes.c_uint64), _rows(b.doc_status, b.ndocs, 0, ctypes.c_int32), *_formats_of(b))
+
+
+class MatchText:
+    """The text that the results and items of a finished batch cover (host copies): the bytes of span i of a family are
+    text[offsets[i]:offsets[i+1]], parallel to the results / items of the batch.  A family that was not asked for is None."""
+
+    def __init__(self, result_text, result_offsets, item_text, item_offsets, status):
+        self.result_text = result_text        # bytes
+        self.result_offsets = result_offsets  # (nresults+1,) u64
+        self.item_text = item_text
+        self.item_offsets = item_offsets      # (nitems+1,) u64
+        self.status = status                  # (ndocs,) i32: 0, or 5 for a document with a span outside the text (all its spans empty)
+
+    def result(self, i):
+        return self.result_text[int(self.result_offsets[i]):int(self.result_offsets[i + 1])]
+
+    def item(self, i):
+        return self.item_text[int(self.item_offsets[i]):int(self.item_offsets[i + 1])]
+
+
+def _match_text_of(t):
+    """the MatchText of a capi.SpMatchText (copies)"""
+    def family(text, offsets, n, total):
+        if not offsets:
+            return None, None
+        return (ctypes.string_at(text, total) if total else b""), _rows(offsets, n + 1, 0, ctypes.c_uint64)
+    rt, ro = family(t.result_text, t.result_text_offsets, t.nresults, t.totals[0])
+    it, io = family(t.item_text, t.item_text_offsets, t.nitems, t.totals[1])
+    return MatchText(rt, ro, it, io, _rows(t.doc_text_status, t.ndocs, 0, ctypes.c_int32))
+
+
+def batchText(mb, text, seg_offsets, doc_seg_offsets=None, results=True, items=True):
+    """The text of a batch already on the host (a MatchBatch in document order with items without gaps: finishedFetch,
+    batchFetch, matchDocs), by the rule of the device call (include/strus_pattern_amd.h "matched text"), without a device:
+    `text` holds the segments back to back (seg_offsets: nseg+1 byte offsets), document d is the segments
+    [doc_seg_offsets[d], doc_seg_offsets[d+1]), or segment d without doc_seg_offsets.  Returns a MatchText."""
+    L = capi.lib()
+    text = bytes(text)
+    seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
+    dso = None if doc_seg_offsets is None else np.ascontiguousarray(doc_seg_offsets, dtype=np.uint64)
+    res = np.ascontiguousarray(mb.results, dtype=np.uint32).reshape(-1, 9)
+    its = np.ascontiguousarray(mb.items, dtype=np.uint32).reshape(-1, 7)
+    offs = np.ascontiguousarray(mb.doc_offsets, dtype=np.uint64)
+    b = capi.SpMatchBatch()
+    b.ndocs, b.nresults, b.nitems = len(offs) - 1, len(res), len(its)
+    b.results = ctypes.cast(res.ctypes.data, ctypes.POINTER(SpResult))
+    b.items = ctypes.cast(its.ctypes.data, ctypes.POINTER(SpResultItem))
+    b.doc_result_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
+    t = capi.SpMatchText()
+    err = ctypes.create_string_buffer(256)
+    flags = (SP_TEXT_RESULTS if results else 0) | (SP_TEXT_ITEMS if items else 0)
+    rc = L.sp_match_batch_text(ctypes.byref(b), text, len(text), seg_offsets.ctypes.data, len(seg_offsets) - 1,
+                               dso.ctypes.data if dso is not None else None, flags, ctypes.byref(t), err, 256)
+    try:
+        if rc != 0:
+            raise PatternError("no text of the batch (%d): %s" % (rc, err.value.decode()))
+        return _match_text_of(t)
+    finally:
+        L.sp_match_text_free(ctypes.byref(t))
 
 
 class PatternMatcherContext:
@@ -194,6 +254,37 @@ class PatternMatcherContext:
         a = ctypes.c_double(-1.0)
         if self._L.sp_matcher_ctx_last_finish_sort_ms(self._h, ctypes.byref(a)) != 0:
             raise PatternError("no timed finish")
+        return a.value
+
+    def finishedTextDevice(self, d_text, nbytes, d_seg_offsets, nseg, d_doc_seg_offsets=0, results=True, items=True, stream=0):
+        """gather the text that the results and / or items of the batch finished by batchFinishDevice cover, on the device
+        (the placement is asynchronous on `stream`): d_text is the text the lexer batch ran on, d_seg_offsets the nseg+1
+        offsets given to the lexer, d_doc_seg_offsets the ndocs+1 offsets given to the stitch (0: document d is segment d).
+        Returns the device pointers (capi.SpMatchTextBatch), valid until the next call."""
+        src = capi.SpTextSource(d_text or None, nbytes, d_seg_offsets or None, nseg, d_doc_seg_offsets or None)
+        out = capi.SpMatchTextBatch()
+        flags = (SP_TEXT_RESULTS if results else 0) | (SP_TEXT_ITEMS if items else 0)
+        rc = self._L.sp_matcher_ctx_finished_text_device(self._h, ctypes.byref(src), flags, stream or None, ctypes.byref(out))
+        if rc != 0:
+            raise PatternError("gathering the text of the batch on the device failed (%d): %s" % (rc, self._err()))
+        return out
+
+    def finishedTextFetch(self):
+        """plain host copy of the text gathered by finishedTextDevice: a MatchText"""
+        t = capi.SpMatchText()
+        rc = self._L.sp_matcher_ctx_finished_text_fetch(self._h, ctypes.byref(t))
+        try:
+            if rc != 0:
+                raise PatternError("fetching the text of the batch failed (%d): %s" % (rc, self._err()))
+            return _match_text_of(t)
+        finally:
+            self._L.sp_match_text_free(ctypes.byref(t))
+
+    def lastTextMs(self):
+        """duration of the passes of the last finishedTextDevice in milliseconds"""
+        a = ctypes.c_double(-1.0)
+        if self._L.sp_matcher_ctx_last_text_ms(self._h, ctypes.byref(a)) != 0:
+            raise PatternError("no timed text call")
         return a.value
 
     def batchFetch(self, first_doc=None, ndocs=None):
@@ -665,11 +756,13 @@ class PatternLexer:
         return "std"
 
 
-def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets):
+def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False):
     """Segmented documents, host buffers in and out: `text` holds the segments back to back (seg_offsets: nseg+1 byte
     offsets), document d consists of the segments [doc_seg_offsets[d], doc_seg_offsets[d+1]).  Lexer -> stitch on the
     device -> rule matcher -> fetch; only the text goes up and the results come down.  Returns the MatchBatch, whose
-    status of a document is the stitch's where that is not 0 (a failed segment, a bad segment range), else the matcher's."""
+    status of a document is the stitch's where that is not 0 (a failed segment, a bad segment range), else the matcher's.
+    with_text: the batch is finished on the device and the text its results and items cover gathered there; returns
+    (MatchBatch, MatchText)."""
     import torch
     text = bytes(text)
     seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
@@ -695,10 +788,16 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets):
             break
         mctx.reserveOutput(int(mc["results"] * 1.2) + 1024, int(mc["items"] * 1.2) + 1024)
         mctx.growArena()
-    mb = mctx.batchFetch()
+    mt = None
+    if with_text:
+        mctx.batchFinishDevice(stream)
+        mctx.finishedTextDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), nseg, d_dso.data_ptr(), stream=stream)
+        mb, mt = mctx.finishedFetch(), mctx.finishedTextFetch()
+    else:
+        mb = mctx.batchFetch()
     stitch_status = lctx.stitchedStatus()
     mb.status = np.where(stitch_status != 0, stitch_status, mb.status).astype(np.int32)
-    return mb
+    return (mb, mt) if with_text else mb
 
 
 def device_count():

@@ -69,6 +69,25 @@ class SpMatchFinishedBatch(ctypes.Structure):
     ]
 
 
+class SpTextSource(ctypes.Structure):
+    _fields_ = [("d_text", c_vp), ("nbytes", c_u64), ("d_seg_offsets", c_vp), ("nseg", ctypes.c_size_t), ("d_doc_seg_offsets", c_vp)]
+
+
+class SpMatchTextBatch(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("d_result_text", c_vp), ("d_result_text_offsets", c_vp), ("d_item_text", c_vp),
+        ("d_item_text_offsets", c_vp), ("d_doc_text_status", c_vp), ("d_totals", c_vp),
+    ]
+
+
+class SpMatchText(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("nresults", ctypes.c_size_t), ("nitems", ctypes.c_size_t),
+        ("result_text", P(ctypes.c_uint8)), ("result_text_offsets", P(c_u64)), ("item_text", P(ctypes.c_uint8)), ("item_text_offsets", P(c_u64)),
+        ("doc_text_status", P(ctypes.c_int32)), ("totals", c_u64 * 2),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/strus_pattern_amd.h
 SIGNATURES = {
     "sp_version": (c_cp, []),
@@ -123,6 +142,12 @@ SIGNATURES = {
     "sp_matcher_ctx_last_finish_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double), P(ctypes.c_double), P(ctypes.c_double)]),
     "sp_matcher_ctx_last_finish_sort_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
     "sp_matcher_finish_sort_tile": (c_u32, []),
+    "sp_matcher_ctx_finished_text_device": (ctypes.c_int, [c_vp, P(SpTextSource), c_u32, c_vp, P(SpMatchTextBatch)]),
+    "sp_matcher_ctx_finished_text_fetch": (ctypes.c_int, [c_vp, P(SpMatchText)]),
+    "sp_match_text_free": (None, [P(SpMatchText)]),
+    "sp_matcher_ctx_last_text_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_matcher_text_long_span": (c_u32, []),
+    "sp_match_batch_text": (ctypes.c_int, [P(SpMatchBatch), c_vp, c_u64, c_vp, ctypes.c_size_t, c_vp, c_u32, P(SpMatchText), ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_ctx_batch_counters": (ctypes.c_int, [c_vp, P(c_u64)]),
     "sp_matcher_ctx_last_kernel_ms": (ctypes.c_double, [c_vp]),
     "sp_matcher_ctx_kernel_kind": (ctypes.c_int, [c_vp]),

@@ -2,6 +2,8 @@
 // No CPU fallback: a context cannot be created without a usable HIP device.
 #include "l2_plan.hpp"
 #include "l2_finish.h"
+#include "l2_text.h"
+#include "span_text.hpp"
 #include "capi_util.hpp"
 #include <cstdio>
 
@@ -112,6 +114,18 @@ struct sp_matcher_ctx
 		// working memory of the canonical order, allocated at the first finish that asks for it
 		DeviceBuffer dSortKeys[ 2], dSortIdx[ 2], dSortCursor;
 	} fin;
+	// the matched text of the last finished batch (l2_text.h); nothing is allocated before the first sp_matcher_ctx_finished_text_device
+	struct Text
+	{
+		DeviceBuffer dText[ 2], dSpanOffsets[ 2], dSpanWork[ 2], dDocBytes[ 2], dDocTextOffsets[ 2];	// [0] results, [1] items
+		DeviceBuffer dStatus, dTotals, dCursor;
+		bool done = false;
+		uint32_t flags = 0;
+		hipStream_t stream = 0;
+		size_t ndocs = 0;
+		uint64_t nrecords[ 2] = {0, 0}, totals[ 2] = {0, 0};
+		Event ev[ 2]; bool evValid = false;
+	} txt;
 	// single-document mode
 	struct SingleDoc
 	{
@@ -521,7 +535,7 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 	const L2LaunchPlan plan = planL2Launch( c->kind, rerun != 0, c->numCUs, c->flat.blocksPerCU, rerun ? rerun->size() : ndocs, ndocs, nlexems,
 						c->exact.layout, &c->flat.plan, c->io.minResults, c->io.minItems);
 	HIP_CHECK( hipSetDevice( c->device));
-	c->fin.done = false;		// (a new batch: what was finished is of the one before)
+	c->fin.done = false; c->txt.done = false;	// (a new batch: what was finished is of the one before)
 	ensureArena( c, plan);
 	ensureOutput( c, plan, ndocs);
 	resetCursorAndCounters( c, rerun != 0, stream);
@@ -615,7 +629,7 @@ int sp_matcher_ctx_batch_finish_device_ex( sp_matcher_ctx_t* c, void* stream_, u
 		if (!c->haveBatch) throw std::runtime_error( "no batch to finish: no batch has run on this context");
 		hipStream_t stream = (hipStream_t)stream_;
 		HIP_CHECK( hipSetDevice( c->device));
-		c->fin.done = false;
+		c->fin.done = false; c->txt.done = false;
 		// the buffers are sized from what the batch counted: this read waits for the batch, the passes below do not
 		HIP_CHECK( hipStreamSynchronize( c->lastStream));
 		const BatchCounts counts = readCounts( c);
@@ -737,6 +751,127 @@ int sp_matcher_ctx_last_finish_sort_ms( sp_matcher_ctx_t* c, double* sort_ms)
 }
 
 uint32_t sp_matcher_finish_sort_tile(void) { return FINISH_SORT_TILE; }
+
+// ---- the text that the results and items of the finished batch cover, gathered on the device (l2_text.h)
+namespace {
+// grow-only, a failure is SP_ERR_NOMEM (the buffer is left empty, the context usable)
+void reserveOrNoMem( DeviceBuffer& buf, size_t n)
+{
+	try { buf.reserve( n); }
+	catch (const HipError&) { (void)hipGetLastError(); throw std::bad_alloc(); }
+}
+}
+
+int sp_matcher_ctx_finished_text_device( sp_matcher_ctx_t* c, const sp_text_source_t* src, uint32_t flags, void* stream_, sp_match_text_batch_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (!flags || (flags & ~(uint32_t)(SP_TEXT_RESULTS | SP_TEXT_ITEMS))) throw std::runtime_error( "unknown or no text flags");
+		if (!src || !src->d_seg_offsets || (!src->d_text && src->nbytes)) throw std::runtime_error( "no text source");
+		if (!c->fin.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
+		const size_t ndocs = c->lastNdocs;
+		if (!src->d_doc_seg_offsets && src->nseg != ndocs) throw std::runtime_error( "without document segment offsets every document is one segment: nseg must be ndocs");
+		sp_matcher_ctx::Text& t = c->txt;
+		hipStream_t stream = (hipStream_t)stream_;
+		HIP_CHECK( hipSetDevice( c->device));
+		t.done = false; t.evValid = false;
+		// the span arrays are sized from the totals of the finish: this read waits for it
+		HIP_CHECK( hipStreamSynchronize( c->fin.stream));
+		uint64_t records[ 2];
+		copySync( c->own, records, c->fin.dTotals.ptr, sizeof(records), hipMemcpyDeviceToHost);
+		for (int f=0; f<2; ++f) if (flags & (1u << f))
+		{
+			reserveOrNoMem( t.dSpanWork[ f], (records[ f]+1)*sizeof(uint32_t));
+			reserveOrNoMem( t.dSpanOffsets[ f], (records[ f]+1)*sizeof(uint64_t));
+			reserveOrNoMem( t.dDocBytes[ f], (ndocs+1)*sizeof(uint64_t));
+			reserveOrNoMem( t.dDocTextOffsets[ f], (ndocs+1)*sizeof(uint64_t));
+		}
+		reserveOrNoMem( t.dStatus, (ndocs+1)*sizeof(int32_t));
+		reserveOrNoMem( t.dTotals, 2*sizeof(uint64_t));
+		reserveOrNoMem( t.dCursor, 4*sizeof(uint32_t));
+		for (int i=0; i<2; ++i) t.ev[ i].create();
+
+		// another stream than the finish's runs behind the finish
+		if (stream != c->fin.stream) HIP_CHECK( hipStreamWaitEvent( stream, c->fin.ev[ 3], 0));
+		HIP_CHECK( hipMemsetAsync( t.dCursor.ptr, 0, 4*sizeof(uint32_t), stream));
+		HIP_CHECK( hipMemsetAsync( t.dTotals.ptr, 0, 2*sizeof(uint64_t), stream));
+		HIP_CHECK( hipMemsetAsync( t.dStatus.ptr, 0, (ndocs+1)*sizeof(int32_t), stream));
+		TextParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.text = (const uint8_t*)src->d_text; P.nbytes = src->nbytes;
+		P.segOffsets = (const uint64_t*)src->d_seg_offsets; P.nseg = src->nseg;
+		P.docSegOffsets = (const uint64_t*)src->d_doc_seg_offsets;
+		P.ndocs = (uint32_t)ndocs; P.docStatus = (int32_t*)t.dStatus.ptr; P.families = flags;
+		for (int f=0; f<2; ++f) if (flags & (1u << f))
+		{
+			TextFamily& F = P.family[ f];
+			F.records = (const uint32_t*)(f ? c->fin.dItems.ptr : c->fin.dResults.ptr);
+			F.docOffsets = (const uint64_t*)(f ? c->fin.dDocItemOffsets.ptr : c->fin.dDocResultOffsets.ptr);
+			F.nrecords = records[ f];
+			F.spanWork = (uint32_t*)t.dSpanWork[ f].ptr; F.docBytes = (uint64_t*)t.dDocBytes[ f].ptr;
+			F.docTextOffsets = (uint64_t*)t.dDocTextOffsets[ f].ptr; F.spanOffsets = (uint64_t*)t.dSpanOffsets[ f].ptr;
+			F.total = (uint64_t*)t.dTotals.ptr + f; F.cursor = (uint32_t*)t.dCursor.ptr + 2*f;
+		}
+		HIP_CHECK( hipEventRecord( t.ev[ 0], stream));
+		HIP_CHECK( launchL2TextCount( P, c->numCUs, stream));
+		// the text buffers are sized from what the passes counted: this read waits for them, the placement below is not waited for
+		HIP_CHECK( hipStreamSynchronize( stream));
+		uint64_t totals[ 2];
+		copySync( c->own, totals, t.dTotals.ptr, sizeof(totals), hipMemcpyDeviceToHost);
+		for (int f=0; f<2; ++f) if (flags & (1u << f))
+		{
+			reserveOrNoMem( t.dText[ f], totals[ f] + 16);
+			P.family[ f].outText = (uint8_t*)t.dText[ f].ptr; P.family[ f].outCapacity = totals[ f];
+		}
+		HIP_CHECK( launchL2TextPlace( P, c->numCUs, stream));
+		HIP_CHECK( hipEventRecord( t.ev[ 1], stream));
+		t.evValid = true; t.done = true; t.flags = flags; t.stream = stream; t.ndocs = ndocs;
+		for (int f=0; f<2; ++f) { t.nrecords[ f] = records[ f]; t.totals[ f] = (flags & (1u << f)) ? totals[ f] : 0; }
+		if (out)
+		{
+			out->ndocs = ndocs;
+			if (flags & SP_TEXT_RESULTS) { out->d_result_text = t.dText[ 0].ptr; out->d_result_text_offsets = t.dSpanOffsets[ 0].ptr; }
+			if (flags & SP_TEXT_ITEMS) { out->d_item_text = t.dText[ 1].ptr; out->d_item_text_offsets = t.dSpanOffsets[ 1].ptr; }
+			out->d_doc_text_status = t.dStatus.ptr; out->d_totals = t.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the text buffers
+int sp_matcher_ctx_finished_text_fetch( sp_matcher_ctx_t* c, sp_match_text_t* out)
+{
+	std::memset( out, 0, sizeof(*out));
+	const int rc = guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		const sp_matcher_ctx::Text& t = c->txt;
+		if (!t.done) throw std::runtime_error( "no text of the last batch of this context (sp_matcher_ctx_finished_text_device)");
+		HIP_CHECK( hipSetDevice( c->device));
+		HIP_CHECK( hipStreamSynchronize( t.stream));
+		allocMatchText( out, t.ndocs, t.nrecords[ 0], t.nrecords[ 1], t.flags);
+		out->totals[ 0] = t.totals[ 0]; out->totals[ 1] = t.totals[ 1];
+		allocMatchTextBytes( out, t.flags);
+		if (t.ndocs) copySync( c->own, out->doc_text_status, t.dStatus.ptr, t.ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+		char* const text[ 2] = {out->result_text, out->item_text};
+		uint64_t* const offsets[ 2] = {out->result_text_offsets, out->item_text_offsets};
+		for (int f=0; f<2; ++f) if (t.flags & (1u << f))
+		{
+			copySync( c->own, offsets[ f], t.dSpanOffsets[ f].ptr, (t.nrecords[ f]+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+			if (t.totals[ f]) copySync( c->own, text[ f], t.dText[ f].ptr, t.totals[ f], hipMemcpyDeviceToHost);
+		}
+	});
+	if (rc != SP_OK) sp_match_text_free( out);
+	return rc;
+}
+
+// duration of the passes of the last text call in milliseconds (HIP events on its stream)
+int sp_matcher_ctx_last_text_ms( sp_matcher_ctx_t* c, double* ms)
+{
+	*ms = -1.0;
+	if (!c->txt.evValid) return SP_ERR_INVALID;
+	if (hipEventSynchronize( c->txt.ev[ 1]) != hipSuccess) return SP_ERR_DEVICE;
+	return elapsedMs( c->txt.ev[ 0], c->txt.ev[ 1], *ms) ? SP_OK : SP_ERR_DEVICE;
+}
+
+uint32_t sp_matcher_text_long_span(void) { return TEXT_LONG_SPAN; }
 
 double sp_matcher_ctx_last_kernel_ms( sp_matcher_ctx_t* c) { return lastKernelMs( c); }
 
