@@ -40,12 +40,10 @@ struct sp_lexer_ctx
 	// sp_lexer_ctx_stitch_segments_device
 	struct Stitched
 	{
+		PassRun<2> run;
 		DeviceBuffer dLexems, dOrigseg, dSegWork, dDocCount, dDocOffsets, dDocStatus, dTotals, dCursor;
-		bool done = false;
-		hipStream_t stream = 0;
 		size_t ndocs = 0;
 		uint64_t capacity = 0;		// records in dLexems and dOrigseg: the lexer's lexem capacity at the stitch
-		Event ev[ 2]; bool evValid = false;
 	} stitched;
 	Stream own;			// the context's own stream (non-blocking): the host-buffer entry points of different contexts -- one per host thread,
 				// the reference's threading model -- copy and launch side by side instead of queueing on the null stream
@@ -288,7 +286,7 @@ void copyOutLexBatch( sp_lexer_ctx* c, size_t firstDoc, size_t ndocs, const uint
 void launchLex( sp_lexer_ctx* c, const void* d_text, const void* d_doc_offsets, size_t ndocs, size_t nbytes, hipStream_t stream)
 {
 	HIP_CHECK( hipSetDevice( c->device));
-	c->stitched.done = false;		// (a new batch: what was stitched is of the one before)
+	c->stitched.run.done = false;		// (a new batch: what was stitched is of the one before)
 	const LexTables& T = c->inst->compiler.tables();
 	const bool wordsKernel = c->images.wordsKernel;
 	L1LaunchPlan plan = planL1Launch( T, c->images, c->numCUs, ndocs, nbytes, L1Switches::fromEnv());
@@ -537,7 +535,7 @@ int sp_lexer_ctx_stitch_segments_device( sp_lexer_ctx_t* c, const void* d_doc_se
 		hipStream_t stream = (hipStream_t)stream_;
 		HIP_CHECK( hipSetDevice( c->device));
 		sp_lexer_ctx::Stitched& S = c->stitched;
-		S.done = false;
+		S.run.done = false;
 		// the stitched lexems are a rearrangement of the batch's: the lexer's capacity holds them, nothing is read back to size them
 		const uint64_t capacity = c->lexems.count;
 		const size_t nseg = c->lastNdocs;
@@ -549,11 +547,10 @@ int sp_lexer_ctx_stitch_segments_device( sp_lexer_ctx_t* c, const void* d_doc_se
 		S.dDocStatus.reserve( (ndocs+1)*sizeof(int32_t));
 		if (!S.dTotals.ptr) S.dTotals.alloc( 2*sizeof(uint64_t));
 		if (!S.dCursor.ptr) S.dCursor.alloc( 2*sizeof(uint32_t));
-		hipEvent_t ev[ 2];
-		for (int i=0; i<2; ++i) { S.ev[ i].create(); ev[ i] = S.ev[ i]; }
-
 		// another stream than the batch's runs behind the batch (evStop closes the launch sequence)
-		if (stream != c->lastStream) HIP_CHECK( hipStreamWaitEvent( stream, c->evStop, 0));
+		S.run.begin( stream, c->lastStream, c->evStop);
+		hipEvent_t ev[ 2];
+		S.run.events( ev);
 		HIP_CHECK( hipMemsetAsync( S.dCursor.ptr, 0, 2*sizeof(uint32_t), stream));
 		StitchParams P;
 		std::memset( &P, 0, sizeof(P));
@@ -563,9 +560,8 @@ int sp_lexer_ctx_stitch_segments_device( sp_lexer_ctx_t* c, const void* d_doc_se
 		P.segWork = (uint32_t*)S.dSegWork.ptr; P.docCount = (uint32_t*)S.dDocCount.ptr; P.cursor = (uint32_t*)S.dCursor.ptr;
 		P.outLexems = (uint32_t*)S.dLexems.ptr; P.outOrigseg = (uint32_t*)S.dOrigseg.ptr;
 		P.docOffsets = (uint64_t*)S.dDocOffsets.ptr; P.docStatus = (int32_t*)S.dDocStatus.ptr; P.totals = (uint64_t*)S.dTotals.ptr;
-		S.evValid = false;
 		HIP_CHECK( launchL1Stitch( P, c->numCUs, stream, ev));
-		S.evValid = true; S.done = true; S.stream = stream; S.ndocs = ndocs; S.capacity = capacity;
+		S.run.completed( stream); S.ndocs = ndocs; S.capacity = capacity;
 		if (out)
 		{
 			out->ndocs = ndocs; out->d_lexems = S.dLexems.ptr; out->d_origseg = S.dOrigseg.ptr;
@@ -581,9 +577,9 @@ int sp_lexer_ctx_stitched_fetch( sp_lexer_ctx_t* c, sp_lex_batch_t* out, uint32_
 	if (origseg) *origseg = 0;
 	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
 		const sp_lexer_ctx::Stitched& S = c->stitched;
-		if (!S.done) throw std::runtime_error( "the last batch of this context has not been stitched (sp_lexer_ctx_stitch_segments_device)");
+		if (!S.run.done) throw std::runtime_error( "the last batch of this context has not been stitched (sp_lexer_ctx_stitch_segments_device)");
 		HIP_CHECK( hipSetDevice( c->device));
-		HIP_CHECK( hipStreamSynchronize( S.stream));
+		HIP_CHECK( hipStreamSynchronize( S.run.stream));
 		uint64_t totals[ 2];
 		copySync( c->own, totals, S.dTotals.ptr, sizeof(totals), hipMemcpyDeviceToHost);
 		const uint64_t nlex = clampCount( totals[ 0], S.capacity);
@@ -605,24 +601,18 @@ int sp_lexer_ctx_stitched_status( sp_lexer_ctx_t* c, int32_t* status, size_t ndo
 	if (ndocs_stitched) *ndocs_stitched = 0;
 	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
 		const sp_lexer_ctx::Stitched& S = c->stitched;
-		if (!S.done) throw std::runtime_error( "the last batch of this context has not been stitched (sp_lexer_ctx_stitch_segments_device)");
+		if (!S.run.done) throw std::runtime_error( "the last batch of this context has not been stitched (sp_lexer_ctx_stitch_segments_device)");
 		if (ndocs_stitched) *ndocs_stitched = S.ndocs;
 		if (ndocs > S.ndocs) ndocs = S.ndocs;
 		if (!ndocs || !status) return;
 		HIP_CHECK( hipSetDevice( c->device));
-		HIP_CHECK( hipStreamSynchronize( S.stream));
+		HIP_CHECK( hipStreamSynchronize( S.run.stream));
 		copySync( c->own, status, S.dDocStatus.ptr, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
 	});
 }
 
 // duration of the three passes of the last stitch in milliseconds (HIP events on its stream; waits for them)
-int sp_lexer_ctx_last_stitch_ms( sp_lexer_ctx_t* c, double* ms)
-{
-	*ms = -1.0;
-	if (!c->stitched.evValid) return SP_ERR_INVALID;
-	if (hipEventSynchronize( c->stitched.ev[ 1]) != hipSuccess) return SP_ERR_DEVICE;
-	return elapsedMs( c->stitched.ev[ 0], c->stitched.ev[ 1], *ms) ? SP_OK : SP_ERR_DEVICE;
-}
+int sp_lexer_ctx_last_stitch_ms( sp_lexer_ctx_t* c, double* ms) { return c->stitched.run.ms( 0, 1, ms); }
 
 void sp_lex_batch_free( sp_lex_batch_t* b)
 {

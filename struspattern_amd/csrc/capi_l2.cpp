@@ -106,10 +106,8 @@ struct sp_matcher_ctx
 	// the last batch finished on the device (l2_finish.h); nothing is allocated before the first sp_matcher_ctx_batch_finish_device
 	struct Finished
 	{
+		PassRun<5> run;		// ev[4]: between the sort and the placement of a canonical finish
 		DeviceBuffer dResults, dItems, dResultFormat, dItemFormat, dDocResultOffsets, dDocItemOffsets, dTotals, dKept, dCovered, dCursor;
-		bool done = false;
-		hipStream_t stream = 0;
-		Event ev[ 5]; bool evValid = false;	// [4]: between the sort and the placement of a canonical finish
 		bool canonical = false;
 		// working memory of the canonical order, allocated at the first finish that asks for it
 		DeviceBuffer dSortKeys[ 2], dSortIdx[ 2], dSortCursor;
@@ -117,14 +115,12 @@ struct sp_matcher_ctx
 	// the matched text of the last finished batch (l2_text.h); nothing is allocated before the first sp_matcher_ctx_finished_text_device
 	struct Text
 	{
+		PassRun<2> run;
 		DeviceBuffer dText[ 2], dSpanOffsets[ 2], dSpanWork[ 2], dDocBytes[ 2], dDocTextOffsets[ 2];	// [0] results, [1] items
 		DeviceBuffer dStatus, dTotals, dCursor;
-		bool done = false;
 		uint32_t flags = 0;
-		hipStream_t stream = 0;
 		size_t ndocs = 0;
 		uint64_t nrecords[ 2] = {0, 0}, totals[ 2] = {0, 0};
-		Event ev[ 2]; bool evValid = false;
 	} txt;
 	// single-document mode
 	struct SingleDoc
@@ -535,7 +531,7 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 	const L2LaunchPlan plan = planL2Launch( c->kind, rerun != 0, c->numCUs, c->flat.blocksPerCU, rerun ? rerun->size() : ndocs, ndocs, nlexems,
 						c->exact.layout, &c->flat.plan, c->io.minResults, c->io.minItems);
 	HIP_CHECK( hipSetDevice( c->device));
-	c->fin.done = false; c->txt.done = false;	// (a new batch: what was finished is of the one before)
+	c->fin.run.done = false; c->txt.run.done = false;	// (a new batch: what was finished is of the one before)
 	ensureArena( c, plan);
 	ensureOutput( c, plan, ndocs);
 	resetCursorAndCounters( c, rerun != 0, stream);
@@ -629,7 +625,7 @@ int sp_matcher_ctx_batch_finish_device_ex( sp_matcher_ctx_t* c, void* stream_, u
 		if (!c->haveBatch) throw std::runtime_error( "no batch to finish: no batch has run on this context");
 		hipStream_t stream = (hipStream_t)stream_;
 		HIP_CHECK( hipSetDevice( c->device));
-		c->fin.done = false; c->txt.done = false;
+		c->fin.run.done = false; c->txt.run.done = false;
 		// the buffers are sized from what the batch counted: this read waits for the batch, the passes below do not
 		HIP_CHECK( hipStreamSynchronize( c->lastStream));
 		const BatchCounts counts = readCounts( c);
@@ -658,11 +654,10 @@ int sp_matcher_ctx_batch_finish_device_ex( sp_matcher_ctx_t* c, void* stream_, u
 			}
 			if (!c->fin.dSortCursor.ptr) c->fin.dSortCursor.alloc( sizeof(uint32_t));
 		}
-		hipEvent_t ev[ 5];
-		for (int i=0; i<5; ++i) { c->fin.ev[ i].create(); ev[ i] = c->fin.ev[ i]; }
-
 		// another stream than the batch's runs behind the batch (evStop closes every launch sequence, reruns included)
-		if (stream != c->lastStream) HIP_CHECK( hipStreamWaitEvent( stream, c->evStop, 0));
+		c->fin.run.begin( stream, c->lastStream, c->evStop);
+		hipEvent_t ev[ 5];
+		c->fin.run.events( ev);
 		HIP_CHECK( hipMemsetAsync( c->fin.dCursor.ptr, 0, 2*sizeof(uint32_t), stream));
 		if (exclusive) HIP_CHECK( hipMemsetAsync( c->fin.dCovered.ptr, 0, devResults+1, stream));
 		if (canonical) HIP_CHECK( hipMemsetAsync( c->fin.dSortCursor.ptr, 0, sizeof(uint32_t), stream));
@@ -685,9 +680,8 @@ int sp_matcher_ctx_batch_finish_device_ex( sp_matcher_ctx_t* c, void* stream_, u
 			for (int i=0; i<2; ++i) { F.sortKeys[ i] = (uint64_t*)c->fin.dSortKeys[ i].ptr; F.sortIdx[ i] = (uint32_t*)c->fin.dSortIdx[ i].ptr; }
 			F.sortCursor = (uint32_t*)c->fin.dSortCursor.ptr;
 		}
-		c->fin.evValid = false;
 		HIP_CHECK( launchL2Finish( F, c->numCUs, stream, ev));
-		c->fin.evValid = true; c->fin.done = true; c->fin.stream = stream; c->fin.canonical = canonical;
+		c->fin.run.completed( stream); c->fin.canonical = canonical;
 		if (out)
 		{
 			out->ndocs = ndocs;
@@ -705,9 +699,9 @@ int sp_matcher_ctx_finished_fetch( sp_matcher_ctx_t* c, sp_match_batch_t* out)
 {
 	std::memset( out, 0, sizeof(*out));
 	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
-		if (!c->fin.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
+		if (!c->fin.run.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
 		HIP_CHECK( hipSetDevice( c->device));
-		HIP_CHECK( hipStreamSynchronize( c->fin.stream));
+		HIP_CHECK( hipStreamSynchronize( c->fin.run.stream));
 		const size_t ndocs = c->lastNdocs;
 		uint64_t totals[ 2];
 		copySync( c->own, totals, c->fin.dTotals.ptr, sizeof(totals), hipMemcpyDeviceToHost);
@@ -731,23 +725,19 @@ int sp_matcher_ctx_finished_fetch( sp_matcher_ctx_t* c, sp_match_batch_t* out)
 // durations of the three passes of the last finish in milliseconds (HIP events on its stream)
 int sp_matcher_ctx_last_finish_ms( sp_matcher_ctx_t* c, double* count_ms, double* offsets_ms, double* place_ms)
 {
-	*count_ms = *offsets_ms = *place_ms = -1.0;
-	if (!c->fin.evValid) return SP_ERR_INVALID;
-	if (hipEventSynchronize( c->fin.ev[ 3]) != hipSuccess) return SP_ERR_DEVICE;
+	*offsets_ms = *place_ms = -1.0;
 	// (a canonical finish sorts between the offsets and the placement: the placement starts at ev[4] then)
-	if (!elapsedMs( c->fin.ev[ 0], c->fin.ev[ 1], *count_ms) || !elapsedMs( c->fin.ev[ 1], c->fin.ev[ 2], *offsets_ms)
-	||  !elapsedMs( c->fin.ev[ c->fin.canonical ? 4 : 2], c->fin.ev[ 3], *place_ms)) return SP_ERR_DEVICE;
-	return SP_OK;
+	int rc = c->fin.run.ms( 0, 1, count_ms);
+	if (rc == SP_OK) rc = c->fin.run.ms( 1, 2, offsets_ms);
+	if (rc == SP_OK) rc = c->fin.run.ms( c->fin.canonical ? 4 : 2, 3, place_ms);
+	return rc;
 }
 
 // duration of the sorting pass of the last finish (0.0 after a finish without SP_FINISH_CANONICAL)
 int sp_matcher_ctx_last_finish_sort_ms( sp_matcher_ctx_t* c, double* sort_ms)
 {
-	*sort_ms = -1.0;
-	if (!c->fin.evValid) return SP_ERR_INVALID;
-	if (!c->fin.canonical) { *sort_ms = 0.0; return SP_OK; }
-	if (hipEventSynchronize( c->fin.ev[ 3]) != hipSuccess) return SP_ERR_DEVICE;
-	return elapsedMs( c->fin.ev[ 2], c->fin.ev[ 4], *sort_ms) ? SP_OK : SP_ERR_DEVICE;
+	if (c->fin.run.evValid && !c->fin.canonical) { *sort_ms = 0.0; return SP_OK; }
+	return c->fin.run.ms( 2, 4, sort_ms);
 }
 
 uint32_t sp_matcher_finish_sort_tile(void) { return FINISH_SORT_TILE; }
@@ -768,15 +758,15 @@ int sp_matcher_ctx_finished_text_device( sp_matcher_ctx_t* c, const sp_text_sour
 	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
 		if (!flags || (flags & ~(uint32_t)(SP_TEXT_RESULTS | SP_TEXT_ITEMS))) throw std::runtime_error( "unknown or no text flags");
 		if (!src || !src->d_seg_offsets || (!src->d_text && src->nbytes)) throw std::runtime_error( "no text source");
-		if (!c->fin.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
+		if (!c->fin.run.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
 		const size_t ndocs = c->lastNdocs;
 		if (!src->d_doc_seg_offsets && src->nseg != ndocs) throw std::runtime_error( "without document segment offsets every document is one segment: nseg must be ndocs");
 		sp_matcher_ctx::Text& t = c->txt;
 		hipStream_t stream = (hipStream_t)stream_;
 		HIP_CHECK( hipSetDevice( c->device));
-		t.done = false; t.evValid = false;
+		t.run.done = t.run.evValid = false;
 		// the span arrays are sized from the totals of the finish: this read waits for it
-		HIP_CHECK( hipStreamSynchronize( c->fin.stream));
+		HIP_CHECK( hipStreamSynchronize( c->fin.run.stream));
 		uint64_t records[ 2];
 		copySync( c->own, records, c->fin.dTotals.ptr, sizeof(records), hipMemcpyDeviceToHost);
 		for (int f=0; f<2; ++f) if (flags & (1u << f))
@@ -789,10 +779,9 @@ int sp_matcher_ctx_finished_text_device( sp_matcher_ctx_t* c, const sp_text_sour
 		reserveOrNoMem( t.dStatus, (ndocs+1)*sizeof(int32_t));
 		reserveOrNoMem( t.dTotals, 2*sizeof(uint64_t));
 		reserveOrNoMem( t.dCursor, 4*sizeof(uint32_t));
-		for (int i=0; i<2; ++i) t.ev[ i].create();
 
 		// another stream than the finish's runs behind the finish
-		if (stream != c->fin.stream) HIP_CHECK( hipStreamWaitEvent( stream, c->fin.ev[ 3], 0));
+		t.run.begin( stream, c->fin.run.stream, c->fin.run.ev[ 3]);
 		HIP_CHECK( hipMemsetAsync( t.dCursor.ptr, 0, 4*sizeof(uint32_t), stream));
 		HIP_CHECK( hipMemsetAsync( t.dTotals.ptr, 0, 2*sizeof(uint64_t), stream));
 		HIP_CHECK( hipMemsetAsync( t.dStatus.ptr, 0, (ndocs+1)*sizeof(int32_t), stream));
@@ -812,7 +801,7 @@ int sp_matcher_ctx_finished_text_device( sp_matcher_ctx_t* c, const sp_text_sour
 			F.docTextOffsets = (uint64_t*)t.dDocTextOffsets[ f].ptr; F.spanOffsets = (uint64_t*)t.dSpanOffsets[ f].ptr;
 			F.total = (uint64_t*)t.dTotals.ptr + f; F.cursor = (uint32_t*)t.dCursor.ptr + 2*f;
 		}
-		HIP_CHECK( hipEventRecord( t.ev[ 0], stream));
+		HIP_CHECK( hipEventRecord( t.run.ev[ 0], stream));
 		HIP_CHECK( launchL2TextCount( P, c->numCUs, stream));
 		// the text buffers are sized from what the passes counted: this read waits for them, the placement below is not waited for
 		HIP_CHECK( hipStreamSynchronize( stream));
@@ -824,8 +813,8 @@ int sp_matcher_ctx_finished_text_device( sp_matcher_ctx_t* c, const sp_text_sour
 			P.family[ f].outText = (uint8_t*)t.dText[ f].ptr; P.family[ f].outCapacity = totals[ f];
 		}
 		HIP_CHECK( launchL2TextPlace( P, c->numCUs, stream));
-		HIP_CHECK( hipEventRecord( t.ev[ 1], stream));
-		t.evValid = true; t.done = true; t.flags = flags; t.stream = stream; t.ndocs = ndocs;
+		HIP_CHECK( hipEventRecord( t.run.ev[ 1], stream));
+		t.run.completed( stream); t.flags = flags; t.ndocs = ndocs;
 		for (int f=0; f<2; ++f) { t.nrecords[ f] = records[ f]; t.totals[ f] = (flags & (1u << f)) ? totals[ f] : 0; }
 		if (out)
 		{
@@ -843,9 +832,9 @@ int sp_matcher_ctx_finished_text_fetch( sp_matcher_ctx_t* c, sp_match_text_t* ou
 	std::memset( out, 0, sizeof(*out));
 	const int rc = guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
 		const sp_matcher_ctx::Text& t = c->txt;
-		if (!t.done) throw std::runtime_error( "no text of the last batch of this context (sp_matcher_ctx_finished_text_device)");
+		if (!t.run.done) throw std::runtime_error( "no text of the last batch of this context (sp_matcher_ctx_finished_text_device)");
 		HIP_CHECK( hipSetDevice( c->device));
-		HIP_CHECK( hipStreamSynchronize( t.stream));
+		HIP_CHECK( hipStreamSynchronize( t.run.stream));
 		allocMatchText( out, t.ndocs, t.nrecords[ 0], t.nrecords[ 1], t.flags);
 		out->totals[ 0] = t.totals[ 0]; out->totals[ 1] = t.totals[ 1];
 		allocMatchTextBytes( out, t.flags);
@@ -863,13 +852,7 @@ int sp_matcher_ctx_finished_text_fetch( sp_matcher_ctx_t* c, sp_match_text_t* ou
 }
 
 // duration of the passes of the last text call in milliseconds (HIP events on its stream)
-int sp_matcher_ctx_last_text_ms( sp_matcher_ctx_t* c, double* ms)
-{
-	*ms = -1.0;
-	if (!c->txt.evValid) return SP_ERR_INVALID;
-	if (hipEventSynchronize( c->txt.ev[ 1]) != hipSuccess) return SP_ERR_DEVICE;
-	return elapsedMs( c->txt.ev[ 0], c->txt.ev[ 1], *ms) ? SP_OK : SP_ERR_DEVICE;
-}
+int sp_matcher_ctx_last_text_ms( sp_matcher_ctx_t* c, double* ms) { return c->txt.run.ms( 0, 1, ms); }
 
 uint32_t sp_matcher_text_long_span(void) { return TEXT_LONG_SPAN; }
 

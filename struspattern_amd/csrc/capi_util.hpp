@@ -66,6 +66,36 @@ inline auto deviceToHost( hipStream_t stream)
 	return [stream]( void* dst, const void* src, size_t n){ copySync( stream, dst, src, n, hipMemcpyDeviceToHost); };
 }
 
+// ---- a pass sequence that runs behind the stage before it (the finish behind its batch, the text behind the finish, the
+// stitch behind the lexer's batch): whether its output stands, the stream it ran on, and the N events between its passes
+template <int N>
+struct PassRun
+{
+	bool done = false;
+	hipStream_t stream = 0;
+	Event ev[ N]; bool evValid = false;
+
+	// a run on `on`: another stream than the previous stage's runs behind the event that closes that stage
+	void begin( hipStream_t on, hipStream_t prevStream, hipEvent_t prevEvent)
+	{
+		done = evValid = false;
+		for (int i=0; i<N; ++i) ev[ i].create();
+		if (on != prevStream) HIP_CHECK( hipStreamWaitEvent( on, prevEvent, 0));
+	}
+	// the events as the launch functions take them
+	void events( hipEvent_t (&out)[ N]) const { for (int i=0; i<N; ++i) out[ i] = ev[ i]; }
+	// every pass is launched and every event recorded
+	void completed( hipStream_t on) { stream = on; done = evValid = true; }
+	// milliseconds from event i to event j of the last run (waits for j): behind every sp_*_last_*_ms
+	int ms( int i, int j, double* out) const
+	{
+		*out = -1.0;
+		if (!evValid) return SP_ERR_INVALID;
+		if (hipEventSynchronize( ev[ j]) != hipSuccess) return SP_ERR_DEVICE;
+		return elapsedMs( ev[ i], ev[ j], *out) ? SP_OK : SP_ERR_DEVICE;
+	}
+};
+
 // ---- sp_*_ctx_batch_status, sp_*_ctx_last_kernel_ms
 template <class CTX>
 int batchStatus( CTX* c, const DeviceBuffer& dDocStatus, int32_t* status, size_t ndocs)

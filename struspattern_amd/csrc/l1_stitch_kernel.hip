@@ -1,6 +1,6 @@
 // Stitching passes of a segmented lexer batch (l1_stitch.h): count, offsets, place.
 #include <hip/hip_runtime.h>
-#include "wave_scan.h"
+#include "doc_passes.h"
 #include "l1_stitch.h"
 
 using namespace spa;
@@ -8,27 +8,6 @@ using namespace spa;
 namespace {
 
 enum {STITCH_ERR_RANGE=5, STITCH_ERR_OUTPUT=9};		// SP_DOC_ERR_RANGE, SP_DOC_ERR_OUTPUT (include/strus_pattern_amd.h)
-const u64 MAX32 = 0xFFFFFFFFull;
-
-__device__ __forceinline__ u64 uni64( u64 v) { return ((u64)uni( (u32)(v >> 32)) << 32) | uni( (u32)v); }
-
-// inclusive prefix sum of 64 values of 32 bits in 64 bits: the two 16-bit halves cannot overflow the 32-bit scans
-__device__ __forceinline__ u64 waveScanAdd64( u32 v) { return ((u64)waveScanAdd( v >> 16) << 16) + waveScanAdd( v & 0xFFFFu); }
-// lane 63's value (the sum of an inclusive scan), wave-uniform
-__device__ __forceinline__ u64 waveLast64( u64 v)
-{
-	return ((u64)uni( (u32)__shfl( (int)(u32)(v >> 32), 63)) << 32) | uni( (u32)__shfl( (int)(u32)v, 63));
-}
-
-// the next document of a wave, from the device cursor (the barriers: see nextDocument of l2_finish_kernel.hip)
-__device__ __forceinline__ u32 nextDocument( u32* cursor)
-{
-	__builtin_amdgcn_wave_barrier();
-	u32 doc = 0;
-	if (LANE == 0) doc = atomicAdd( cursor, 1u);
-	__builtin_amdgcn_wave_barrier();
-	return uni( doc);
-}
 
 // what of the lexer batch's output lies inside its buffer
 __device__ __forceinline__ u64 deviceLexems( const StitchParams& P)
@@ -79,46 +58,32 @@ __device__ void countDocuments( const StitchParams& P)
 				P.segWork[ 2*seg] = (u32)(total + ci - cnt);
 				P.segWork[ 2*seg+1] = (u32)(base + oi - last);
 			}
-			total += waveLast64( ci); base += waveLast64( oi);
+			total += waveLane64( ci, 63); base += waveLane64( oi, 63);
 		}
 		if (!status && (wide || total > MAX32 || base > MAX32)) status = STITCH_ERR_RANGE;
 		if (LANE == 0) { P.docCount[ doc] = status ? 0u : (u32)total; P.docStatus[ doc] = (int32_t)status; }
 	}
 }
 
-// ---- pass B: exclusive prefix sum over the documents; one workgroup of 16 waves, a tile of 1024 documents per round.
+// ---- pass B: the offsets of the documents' lexems (doc_passes.h), with the capacity rule applied where they are stored.
 // The sum of the counts cannot exceed the lexem capacity when the segment ranges of the documents are disjoint (an
 // ascending docSegOffsets); with ranges that share segments it can, and the documents that end beyond the capacity --
 // from the first such on, all that have lexems -- fail with STITCH_ERR_OUTPUT and are empty, at the end of what fits.
 __device__ void scanDocuments( const StitchParams& P)
 {
-	__shared__ u64 waveSum[ 16];
 	__shared__ unsigned long long sFit;
 	__shared__ u32 sFailed, sOver;
-	const u32 wave = threadIdx.x >> 6;
 	const u64 NOWHERE = ~0ull;
 	if (threadIdx.x == 0) { sFit = 0; sFailed = 0; sOver = 0; }
 	__syncthreads();
-	u64 ubase = 0, fit = 0;
+	u64 fit = 0;
 	u32 failed = 0;
 	bool over = false;
-	for (u64 t0=0; t0<P.ndocs; t0+=1024)
-	{
-		const u64 d = t0 + threadIdx.x;
-		const u32 k = d < P.ndocs ? P.docCount[ d] : 0u;
-		const u64 ki = waveScanAdd64( k);
-		if (LANE == 63) waveSum[ wave] = ki;
-		__syncthreads();
-		u64 before = 0, tile = 0;
-		for (u32 w=0; w<16; ++w)
-		{
-			const u64 a = waveSum[ w];
-			if (w < wave) before += a;
-			tile += a;
-		}
-		if (d < P.ndocs)
-		{
-			const u64 at = ubase + before + (ki - k);
+	scanDocumentCounts<u64, 1>( P.ndocs,
+		[&]( u64 d) { return DocCounts<1>{{ P.docCount[ d]}}; },
+		[&]( u64 d, const DocCounts<1>& count, const DocSums<1>& offset) {
+			const u32 k = count.v[ 0];
+			const u64 at = offset.v[ 0];
 			int32_t st = P.docStatus[ d];
 			if (at + k <= P.lexemCapacity)
 			{
@@ -131,10 +96,7 @@ __device__ void scanDocuments( const StitchParams& P)
 				if (k) { st = STITCH_ERR_OUTPUT; P.docStatus[ d] = st; P.docCount[ d] = 0; }
 			}
 			if (st != 0) ++failed;
-		}
-		ubase += tile;
-		__syncthreads();
-	}
+		});
 	atomicMax( &sFit, (unsigned long long)fit);
 	atomicAdd( &sFailed, failed);
 	if (over) sOver = 1;
@@ -193,16 +155,14 @@ extern "C" __global__ __launch_bounds__(256) void spa_l1_stitch_place_kernel( St
 namespace spa {
 hipError_t launchL1Stitch( const StitchParams& P, unsigned numCUs, hipStream_t stream, hipEvent_t* ev)
 {
-	// a wave per document, 16 waves per CU (l2_finish_kernel.hip: enough 16-byte accesses in flight for the copy)
-	const size_t slots = (size_t)numCUs * 16;
-	const unsigned waves = (unsigned)(P.ndocs < slots ? (P.ndocs ? P.ndocs : 1) : slots);
+	const dim3 perDocument( wavePerDocumentBlocks( P.ndocs, numCUs));
 	hipError_t e;
 	if (ev && (e = hipEventRecord( ev[ 0], stream)) != hipSuccess) return e;
-	hipLaunchKernelGGL( spa_l1_stitch_count_kernel, dim3( (waves + 3) / 4), dim3( 256), 0, stream, P);
+	hipLaunchKernelGGL( spa_l1_stitch_count_kernel, perDocument, dim3( 256), 0, stream, P);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
 	hipLaunchKernelGGL( spa_l1_stitch_offsets_kernel, dim3( 1), dim3( 1024), 0, stream, P);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
-	hipLaunchKernelGGL( spa_l1_stitch_place_kernel, dim3( (waves + 3) / 4), dim3( 256), 0, stream, P);
+	hipLaunchKernelGGL( spa_l1_stitch_place_kernel, perDocument, dim3( 256), 0, stream, P);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
 	if (ev && (e = hipEventRecord( ev[ 1], stream)) != hipSuccess) return e;
 	return hipSuccess;

@@ -1,26 +1,12 @@
 // Finishing passes of a device batch (l2_finish.h): count, offsets, place; for the canonical order a sort before place.
 #include <hip/hip_runtime.h>
 #include "l2_device.h"
+#include "doc_passes.h"
 #include "l2_finish.h"
 
 using namespace spa;
 
 namespace {
-
-typedef u32x4 u32x4u __attribute__((aligned(4)));	// a 16-byte load from a 4-byte aligned address (records are 36 and 28 bytes)
-
-__device__ __forceinline__ u64 uni64( u64 v) { return ((u64)uni( (u32)(v >> 32)) << 32) | uni( (u32)v); }
-
-// The next document of a wave, from the device cursor.  The wave barriers keep the lane-0 branch here apart from a lane-0
-// branch at the end of the caller's loop body: merged with it, the other lanes would go round without a new document.
-__device__ __forceinline__ u32 nextDocument( u32* cursor)
-{
-	__builtin_amdgcn_wave_barrier();
-	u32 doc = 0;
-	if (LANE == 0) doc = atomicAdd( cursor, 1u);
-	__builtin_amdgcn_wave_barrier();
-	return uni( doc);
-}
 
 // The raw blocks of document d: results [first, first+count), items [itemFirst, itemFirst+itemCount).  False when the
 // document counts as empty: it failed, its range does not fit the buffer (the two conditions of copyOutBatch), or it has no results.
@@ -100,36 +86,17 @@ __device__ void markDocuments( const FinishParams& P)
 	}
 }
 
-// ---- pass B: exclusive prefix sums over the documents; one workgroup of 16 waves, a tile of 1024 documents per round.
-// (The sums of a batch fit 32 bits, as the buffers hold at most 2^32-1 records; the offsets are 64 bit by contract.)
+// ---- pass B: the offsets of the kept results and of the kept items of every document, in one trip (doc_passes.h).
+// The sums inside a tile are 32 bit: the kept records are a subset of the batch's, and its buffers hold at most 2^32-1.
 __device__ void scanDocuments( const FinishParams& P)
 {
-	__shared__ u32 waveSum[ 2][ 16];
-	const u32 wave = threadIdx.x >> 6;
-	u64 rbase = 0, ibase = 0;
-	for (u64 t0=0; t0<P.ndocs; t0+=1024)
-	{
-		const u64 d = t0 + threadIdx.x;
-		u32 k = 0, it = 0;
-		if (d < P.ndocs) { const uint2 v = ((const uint2*)P.kept)[ d]; k = v.x; it = v.y; }
-		const u32 ki = waveScanAdd( k), ii = waveScanAdd( it);
-		if (LANE == 63) { waveSum[ 0][ wave] = ki; waveSum[ 1][ wave] = ii; }
-		__syncthreads();
-		u32 kb = 0, ib = 0, kt = 0, itot = 0;
-		for (u32 w=0; w<16; ++w)
-		{
-			const u32 a = waveSum[ 0][ w], b = waveSum[ 1][ w];
-			if (w < wave) { kb += a; ib += b; }
-			kt += a; itot += b;
-		}
-		if (d < P.ndocs) { P.docResultOffsets[ d] = rbase + kb + (ki - k); P.docItemOffsets[ d] = ibase + ib + (ii - it); }
-		rbase += kt; ibase += itot;
-		__syncthreads();
-	}
+	const DocSums<2> total = scanDocumentCounts<u32, 2>( P.ndocs,
+		[&]( u64 d) { const uint2 v = ((const uint2*)P.kept)[ d]; return DocCounts<2>{{ v.x, v.y}}; },
+		[&]( u64 d, const DocCounts<2>&, const DocSums<2>& at) { P.docResultOffsets[ d] = at.v[ 0]; P.docItemOffsets[ d] = at.v[ 1]; });
 	if (threadIdx.x == 0)
 	{
-		P.docResultOffsets[ P.ndocs] = rbase; P.docItemOffsets[ P.ndocs] = ibase;
-		P.totals[ 0] = rbase; P.totals[ 1] = ibase;
+		P.docResultOffsets[ P.ndocs] = total.v[ 0]; P.docItemOffsets[ P.ndocs] = total.v[ 1];
+		P.totals[ 0] = total.v[ 0]; P.totals[ 1] = total.v[ 1];
 	}
 }
 
@@ -181,6 +148,23 @@ __device__ __forceinline__ void copyWords( u32* dst, const u32* src, u64 n, u32 
 	}
 }
 
+// A surviving result by its lane: the record r, result `src` of the batch, becomes result `mine` of the output, and its
+// ic items from item ib on the items from myItems on; with formats, their format words go with them.
+__device__ __forceinline__ void placeResult( const FinishParams& P, const u32* r, u64 src, u64 mine, u32 ib, u32 ic, u64 myItems)
+{
+	u32* o = P.outResults + 9*mine;
+	for (u32 k=0; k<7; ++k) o[ k] = r[ k];
+	o[ 7] = (u32)myItems; o[ 8] = ic;
+	const u32* si = P.items + 7*(u64)ib;
+	u32* di = P.outItems + 7*myItems;
+	for (u32 k=0; k<7*ic; ++k) di[ k] = si[ k];
+	if (P.withFormats)
+	{
+		P.outResultFormat[ mine] = P.resultFormat[ src];
+		for (u32 k=0; k<2*ic; ++k) P.outItemFormat[ 2*myItems + k] = P.itemFormat[ 2*(u64)ib + k];
+	}
+}
+
 __device__ void placeDocuments( const FinishParams& P)
 {
 	for (;;)
@@ -223,17 +207,7 @@ __device__ void placeDocuments( const FinishParams& P)
 				{
 					const u64 mine = rat + (u32)__popcll( mask & ((1ull << LANE) - 1ull));
 					const u64 myItems = iat + (iincl - ic);
-					u32* o = P.outResults + 9*mine;
-					for (u32 k=0; k<7; ++k) o[ k] = r[ k];
-					o[ 7] = (u32)myItems; o[ 8] = ic;
-					const u32* si = P.items + 7*(u64)ib;
-					u32* di = P.outItems + 7*myItems;
-					for (u32 k=0; k<7*ic; ++k) di[ k] = si[ k];
-					if (P.withFormats)
-					{
-						P.outResultFormat[ mine] = P.resultFormat[ first + ri];
-						for (u32 k=0; k<2*ic; ++k) P.outItemFormat[ 2*myItems + k] = P.itemFormat[ 2*(u64)ib + k];
-					}
+					placeResult( P, r, first + ri, mine, ib, ic, myItems);
 				}
 				rat += (u32)__popcll( mask);
 				iat += uni( (u32)__shfl( (int)iincl, 63));
@@ -493,20 +467,7 @@ __device__ void placeSorted( const FinishParams& P)
 			const u32 ib = ok ? r[ 7] : 0u, ic = ok ? r[ 8] : 0u;
 			const u32 iincl = waveScanAdd( ic);
 			const u64 myItems = iat + (iincl - ic);
-			if (ok && myItems + ic <= ip + nki && (u64)ib + ic <= P.nofItems)
-			{
-				u32* o = P.outResults + 9*(rp + e);
-				for (u32 k=0; k<7; ++k) o[ k] = r[ k];
-				o[ 7] = (u32)myItems; o[ 8] = ic;
-				const u32* si = P.items + 7*(u64)ib;
-				u32* di = P.outItems + 7*myItems;
-				for (u32 k=0; k<7*ic; ++k) di[ k] = si[ k];
-				if (P.withFormats)
-				{
-					P.outResultFormat[ rp + e] = P.resultFormat[ first + ri];
-					for (u32 k=0; k<2*ic; ++k) P.outItemFormat[ 2*myItems + k] = P.itemFormat[ 2*(u64)ib + k];
-				}
-			}
+			if (ok && myItems + ic <= ip + nki && (u64)ib + ic <= P.nofItems) placeResult( P, r, first + ri, rp + e, ib, ic, myItems);
 			iat += uni( (u32)__shfl( (int)iincl, 63));
 		}
 	}
@@ -524,12 +485,10 @@ extern "C" __global__ __launch_bounds__(256) void spa_l2_finish_place_sorted_ker
 namespace spa {
 hipError_t launchL2Finish( const FinishParams& P, unsigned numCUs, hipStream_t stream, hipEvent_t* ev)
 {
-	// a wave per document in the passes that walk results; 16 waves per CU keep enough 16-byte accesses in flight for the copy
-	const size_t slots = (size_t)numCUs * 16;
-	const unsigned waves = (unsigned)(P.ndocs < slots ? (P.ndocs ? P.ndocs : 1) : slots);
+	const dim3 perDocument( wavePerDocumentBlocks( P.ndocs, numCUs));	// the passes that walk results
 	hipError_t e;
 	if (ev && (e = hipEventRecord( ev[ 0], stream)) != hipSuccess) return e;
-	if (P.exclusive) hipLaunchKernelGGL( spa_l2_finish_mark_kernel, dim3( (waves + 3) / 4), dim3( 256), 0, stream, P);
+	if (P.exclusive) hipLaunchKernelGGL( spa_l2_finish_mark_kernel, perDocument, dim3( 256), 0, stream, P);
 	else
 	{
 		unsigned blocks = P.ndocs / 256 + 1;		// a thread per document, grid-stride beyond 1024 workgroups
@@ -548,9 +507,9 @@ hipError_t launchL2Finish( const FinishParams& P, unsigned numCUs, hipStream_t s
 		hipLaunchKernelGGL( spa_l2_finish_sort_kernel, dim3( (unsigned)(P.ndocs < groups ? (P.ndocs ? P.ndocs : 1) : groups)), dim3( SORT_THREADS), 0, stream, P);
 		if ((e = hipGetLastError()) != hipSuccess) return e;
 		if (ev && (e = hipEventRecord( ev[ 4], stream)) != hipSuccess) return e;
-		hipLaunchKernelGGL( spa_l2_finish_place_sorted_kernel, dim3( (waves + 3) / 4), dim3( 256), 0, stream, P);
+		hipLaunchKernelGGL( spa_l2_finish_place_sorted_kernel, perDocument, dim3( 256), 0, stream, P);
 	}
-	else hipLaunchKernelGGL( spa_l2_finish_place_kernel, dim3( (waves + 3) / 4), dim3( 256), 0, stream, P);
+	else hipLaunchKernelGGL( spa_l2_finish_place_kernel, perDocument, dim3( 256), 0, stream, P);
 	if ((e = hipGetLastError()) != hipSuccess) return e;
 	if (ev && (e = hipEventRecord( ev[ 3], stream)) != hipSuccess) return e;
 	return hipSuccess;

@@ -1,6 +1,6 @@
 // Text passes of a finished device batch (l2_text.h): count, offsets, place, per family of spans.
 #include <hip/hip_runtime.h>
-#include "wave_scan.h"
+#include "doc_passes.h"
 #include "l2_text.h"
 
 using namespace spa;
@@ -9,28 +9,7 @@ namespace {
 
 enum {TEXT_ERR_RANGE=5};		// SP_DOC_ERR_RANGE (include/strus_pattern_amd.h)
 enum {TEXT_RESULTS=1, TEXT_ITEMS=2};	// SP_TEXT_RESULTS, SP_TEXT_ITEMS
-const u64 MAX32 = 0xFFFFFFFFull;
-
-typedef u32x4 u32x4u __attribute__((aligned(4)));	// a 16-byte load from a 4-byte aligned address (records are 36 and 28 bytes)
 typedef u32 u32b __attribute__((aligned(1)));		// a 4-byte load from any address of the text
-
-__device__ __forceinline__ u64 uni64( u64 v) { return ((u64)uni( (u32)(v >> 32)) << 32) | uni( (u32)v); }
-// inclusive prefix sum of 64 values of 32 bits in 64 bits, and its sum (l1_stitch_kernel.hip)
-__device__ __forceinline__ u64 waveScanAdd64( u32 v) { return ((u64)waveScanAdd( v >> 16) << 16) + waveScanAdd( v & 0xFFFFu); }
-__device__ __forceinline__ u64 shfl64( u64 v, int lane)
-{
-	return ((u64)uni( (u32)__shfl( (int)(u32)(v >> 32), lane)) << 32) | uni( (u32)__shfl( (int)(u32)v, lane));
-}
-
-// the next document of a wave, from the device cursor (the barriers: see nextDocument of l2_finish_kernel.hip)
-__device__ __forceinline__ u32 nextDocument( u32* cursor)
-{
-	__builtin_amdgcn_wave_barrier();
-	u32 doc = 0;
-	if (LANE == 0) doc = atomicAdd( cursor, 1u);
-	__builtin_amdgcn_wave_barrier();
-	return uni( doc);
-}
 
 // what one lane wrote to LDS is read by the other lanes of its wave (and the other way round) only across this
 __device__ __forceinline__ void waveLdsSync()
@@ -94,7 +73,7 @@ __device__ void countSpans( const TextParams& P, const TextFamily& F)
 				const u32 len = (u32)length;
 				const u64 ci = waveScanAdd64( len);
 				if (active) F.spanWork[ i] = (u32)(total + ci - len);
-				total += shfl64( ci, 63);
+				total += waveLane64( ci, 63);
 				if (total > MAX32) { failed = true; break; }
 			}
 		}
@@ -106,37 +85,16 @@ __device__ void countSpans( const TextParams& P, const TextFamily& F)
 	}
 }
 
-// ---- pass B: exclusive prefix sum over the documents; one workgroup of 16 waves, a tile of 1024 documents per round
-// (l1_stitch_kernel.hip).  A document that failed, in this family or the other, counts 0.
+// ---- pass B: the offsets of the documents' bytes (doc_passes.h).  A document that failed, in this family or the other, counts 0.
 __device__ void scanDocuments( const TextParams& P, const TextFamily& F)
 {
-	__shared__ u64 waveSum[ 16];
-	const u32 wave = threadIdx.x >> 6;
-	u64 base = 0;
-	for (u64 t0=0; t0<P.ndocs; t0+=1024)
-	{
-		const u64 d = t0 + threadIdx.x;
-		u32 k = 0;
-		if (d < P.ndocs && P.docStatus[ d] == 0)
-		{
-			const u64 b = F.docBytes[ d];
-			k = b <= MAX32 ? (u32)b : 0u;
-		}
-		const u64 ki = waveScanAdd64( k);
-		if (LANE == 63) waveSum[ wave] = ki;
-		__syncthreads();
-		u64 before = 0, tile = 0;
-		for (u32 w=0; w<16; ++w)
-		{
-			const u64 a = waveSum[ w];
-			if (w < wave) before += a;
-			tile += a;
-		}
-		if (d < P.ndocs) F.docTextOffsets[ d] = base + before + (ki - k);
-		base += tile;
-		__syncthreads();
-	}
-	if (threadIdx.x == 0) { F.docTextOffsets[ P.ndocs] = base; F.spanOffsets[ F.nrecords] = base; *F.total = base; }
+	const u64 total = scanDocumentCounts<u64, 1>( P.ndocs,
+		[&]( u64 d) {
+			const u64 b = P.docStatus[ d] == 0 ? F.docBytes[ d] : 0;
+			return DocCounts<1>{{ b <= MAX32 ? (u32)b : 0u}};
+		},
+		[&]( u64 d, const DocCounts<1>&, const DocSums<1>& at) { F.docTextOffsets[ d] = at.v[ 0]; }).v[ 0];
+	if (threadIdx.x == 0) { F.docTextOffsets[ P.ndocs] = total; F.spanOffsets[ F.nrecords] = total; *F.total = total; }
 }
 
 // ---- pass C
@@ -246,7 +204,7 @@ __device__ void placeSpans( const TextParams& P, const TextFamily& F, u32* sOff,
 				const int j = __ffsll( (unsigned long long)longSpans) - 1;
 				longSpans &= longSpans - 1;
 				const u32 oj = uni( (u32)__shfl( (int)w, j)), lj = uni( (u32)__shfl( (int)len, j));
-				const u64 sj = shfl64( begin, j);
+				const u64 sj = waveLane64( begin, j);
 				copyRange<true>( P, F, at, cur, oj, sOff, sSrc, 0, 0);
 				copyRange<false>( P, F, at, oj, oj + lj, sOff, sSrc, oj, sj);
 				if (oj + lj > cur) cur = oj + lj;
@@ -276,17 +234,9 @@ extern "C" __global__ __launch_bounds__(256) void spa_l2_text_place_items_kernel
 
 namespace spa {
 
-// a wave per document, 16 waves per CU (l1_stitch_kernel.hip)
-static unsigned textBlocks( const TextParams& P, unsigned numCUs)
-{
-	const size_t slots = (size_t)numCUs * 16;
-	const unsigned waves = (unsigned)(P.ndocs < slots ? (P.ndocs ? P.ndocs : 1) : slots);
-	return (waves + 3) / 4;
-}
-
 hipError_t launchL2TextCount( const TextParams& P, unsigned numCUs, hipStream_t stream)
 {
-	const dim3 grid( textBlocks( P, numCUs));
+	const dim3 grid( wavePerDocumentBlocks( P.ndocs, numCUs));
 	hipError_t e;
 	if (P.families & TEXT_RESULTS)
 	{
@@ -308,7 +258,7 @@ hipError_t launchL2TextCount( const TextParams& P, unsigned numCUs, hipStream_t 
 
 hipError_t launchL2TextPlace( const TextParams& P, unsigned numCUs, hipStream_t stream)
 {
-	const dim3 grid( textBlocks( P, numCUs));
+	const dim3 grid( wavePerDocumentBlocks( P.ndocs, numCUs));
 	hipError_t e;
 	if (P.families & TEXT_RESULTS)
 	{

@@ -12,6 +12,7 @@ import oracle
 import struspattern_amd as spa
 from struspattern_amd import capi, synth
 
+from .canonical_order import sorted_batch
 from .test_formats import _apply, _random_program
 from .test_result_set_model import _docs
 
@@ -271,6 +272,72 @@ def test_a_failed_document_is_empty_and_its_neighbours_are_intact():
         mi = got.items[int(mine[0, 7]):int(mine[-1, 7]) + int(mine[-1, 8])]
         ti = ref.items[int(theirs[0, 7]):int(theirs[-1, 7]) + int(theirs[-1, 8])]
         assert np.array_equal(mi, ti)
+
+
+# ---- the offsets pass scans the documents in tiles of 1024: batches around the tile boundary and into a third tile
+TILE_RULES = [("seq_12", "sequence", 1, [1, 2]), ("seq_23", "sequence", 1, [2, 3]), ("seq_24", "sequence", 2, [2, 4]), ("seq_123", "sequence", 2, [1, 2, 3])]
+TILE_FAILING = 1000                 # the document whose lexems are out of order
+_TILE_DOCS = []
+
+
+def _tile_documents():
+    """2049 documents of 0..3 lexems (terms 1..4 at the positions 1, 2, 3); document 1024, the first of the second tile, is
+    1 2 3 between empty ones; document TILE_FAILING is 1 2 3 with descending positions"""
+    if not _TILE_DOCS:
+        rng = np.random.default_rng(77)
+        sizes = rng.integers(1, 4, 2049)
+        sizes[rng.random(2049) < 0.1] = 0
+        sizes[[3, 1021, 1023, 1025, 1027, 2047]] = 0
+        sizes[[TILE_FAILING, 1024]] = 3
+        offs = np.zeros(2050, np.uint64)
+        offs[1:] = np.cumsum(sizes)
+        lex = np.zeros((int(offs[-1]), 4), np.uint32)
+        for d, n in enumerate(sizes):
+            b = int(offs[d])
+            # half of the documents that can hold it are 1 2 (3): they have results, two of the three rules or all of them
+            ids = [1, 2, 3][:n] if rng.random() < 0.5 or d == 1024 else rng.integers(1, 5, n)
+            for k in range(n):
+                lex[b + k] = (ids[k], k + 1, k, 1)
+        b = int(offs[TILE_FAILING])
+        lex[b:b + 3, 0] = (1, 2, 3)
+        lex[b:b + 3, 1] = (3, 2, 1)
+        _TILE_DOCS.append((lex, offs))
+    return _TILE_DOCS[0]
+
+
+@pytest.mark.parametrize("ndocs,exclusive,canonical", [(1023, False, False), (1024, False, False), (1025, False, False), (2049, False, False),
+                                                       (2049, True, False), (1025, False, True)])
+def test_document_counts_around_the_tile_of_the_offsets_pass(ndocs, exclusive, canonical):
+    lex, offs = _tile_documents()
+    lex, offs = lex[:int(offs[ndocs])], offs[:ndocs + 1]
+    m = spa.PatternMatcherInstance()
+    if exclusive:
+        m.defineOption("exclusive")
+        m.defineOption("maxResultSize", 30)
+    synth.apply_rules(m, TILE_RULES)
+    up = _Uploaded(lex, offs)
+    ctx = m.createContext()
+    ctx.reserveOutput(4 * ndocs, 12 * ndocs)             # (at most 3 results of at most 3 items per document: the only failure is the order)
+    up.run(ctx)
+    ref = ctx.batchFetch()
+    assert np.flatnonzero(ref.status).tolist() == [TILE_FAILING] and int(ref.status[TILE_FAILING]) == 1
+    per_doc = np.diff(ref.doc_offsets.astype(np.int64))
+    items_before = np.concatenate([[0], np.cumsum(ref.results[:, 8].astype(np.int64))])
+    items_per_doc = np.diff(items_before[ref.doc_offsets.astype(np.int64)])
+    # what the batch is there for: 0 to 3 results per document (`exclusive` drops the two that seq_123 covers), item counts
+    # that are no multiple of them, results behind the first tile
+    assert set(per_doc.tolist()) == ({0, 1, 2} if exclusive else {0, 1, 2, 3}) and per_doc[TILE_FAILING] == 0
+    assert len(set((items_per_doc[per_doc > 0] / per_doc[per_doc > 0]).tolist())) > 1
+    assert ndocs <= 1024 or per_doc[1024] > 0
+    if canonical:
+        want = sorted_batch(ref)
+        fin = ctx.batchFinishDevice(_stream(), canonical=True)
+        got = ctx.finishedFetch()
+        assert np.array_equal(got.doc_offsets, want.doc_offsets) and np.array_equal(got.results, want.results)
+        assert np.array_equal(got.items, want.items) and np.array_equal(got.status, ref.status)
+        _assert_layout(fin, got)
+    else:
+        _finish_and_compare(ctx)
 
 
 def test_a_batch_whose_output_did_not_fit_is_finished_as_it_is():

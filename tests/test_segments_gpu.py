@@ -170,6 +170,76 @@ def test_stitch_on_another_stream_than_the_batch():
     _assert_stitched(lctx, b.model(dso)[1])
 
 
+# the offsets pass scans the documents in tiles of 1024: batches around the tile boundary and into a third tile
+_TILE = []
+
+
+def _tile_batch():
+    """the lexer's batch of the segments of 2049 documents of 0..2 segments of 0..3 lexems each; document 1024, the first of
+    the second tile, has two segments with lexems between documents without segments"""
+    if not _TILE:
+        rng = np.random.default_rng(14)
+        nsegs = rng.integers(0, 3, 2049)
+        nsegs[[0, 1022, 1023, 1025, 2047]] = 0
+        nsegs[[1021, 1024, 2048]] = 2
+        counts = [int(x) for x in rng.integers(0, 4, int(nsegs.sum()))]
+        dso = np.concatenate([[0], np.cumsum(nsegs)]).astype(np.uint64)
+        counts[int(dso[1024])] = counts[int(dso[1024]) + 1] = 2
+        b = _Batch(_lexer().createContext(), [_segment_text(rng, c) for c in counts])
+        b.lex()
+        _TILE.append((b, dso, counts))
+    return _TILE[0]
+
+
+@pytest.mark.parametrize("ndocs", [1023, 1024, 1025, 2049])
+def test_stitch_parity_around_the_tile_of_the_offsets_pass(ndocs):
+    b, dso, counts = _tile_batch()
+    dso = dso[:ndocs + 1]                           # (the segments behind are in no document)
+    out = b.stitch(dso)
+    raw, want = b.model(dso)
+    assert np.array_equal(np.diff(raw.doc_offsets.astype(np.int64)), counts) and not raw.status.any()
+    assert out.ndocs == ndocs and not want[3].any()
+    lb, origseg = _assert_stitched(b.lctx, want)
+    sizes = np.diff(lb.doc_offsets.astype(np.int64))
+    assert sizes.tolist() == [sum(counts[int(dso[d]):int(dso[d + 1])]) for d in range(ndocs)]
+    assert sizes[1022] == 0 and (ndocs <= 1024 or sizes[1024] == 4) and (ndocs <= 1025 or sizes[1025:].sum() > 0)
+
+
+def test_documents_beyond_the_capacity_in_the_second_tile_of_the_offsets_pass():
+    """2100 documents over the same four segments, 3 lexems per document on average: the running sum passes the lexer's lexem
+    capacity (for a small text 4096 + a third of its bytes, see test_a_segment_failed_by_the_lexer_fails_its_document) at a
+    document of the second tile.  Documents can share segments only where the segment offsets descend, and the document
+    across the descent fails with SP_DOC_ERR_RANGE and has no lexems: here every fifth one."""
+    rng = np.random.default_rng(15)
+    counts = [5, 5, 5, 0]
+    ndocs = 2100
+    lctx = _lexer().createContext()
+    b = _Batch(lctx, [_segment_text(rng, c) for c in counts])
+    b.lex()
+    dso = np.array([d % 5 for d in range(ndocs + 1)], np.uint64)    # [0,1) [1,2) [2,3) [3,4): no lexems, [4,0): descends
+    assert b.stitch(dso).ndocs == ndocs
+    raw, (lex, seg, offs, status) = b.model(dso)                    # (the model knows no capacity)
+    assert np.array_equal(np.diff(raw.doc_offsets.astype(np.int64)), counts)
+    sizes = np.diff(offs.astype(np.int64))
+    assert sizes.tolist() == [(5, 5, 5, 0, 0)[d % 5] for d in range(ndocs)]
+    assert status.tolist() == [(0, 0, 0, 0, SP_DOC_ERR_RANGE)[d % 5] for d in range(ndocs)]
+    lb, origseg = lctx.stitchedFetch()
+    assert np.array_equal(lctx.stitchedStatus(), lb.status)
+    # the statuses: the model's up to the first document that does not fit; from there on SP_DOC_ERR_OUTPUT for every
+    # document with lexems, the model's for the others
+    failed = np.flatnonzero(lb.status == SP_DOC_ERR_OUTPUT)
+    first = int(failed[0])
+    assert 1024 < first < ndocs                     # (behind the first tile: what the test is there for)
+    assert np.array_equal(lb.status[:first], status[:first])
+    assert np.array_equal(lb.status[first:], np.where(sizes[first:] > 0, SP_DOC_ERR_OUTPUT, status[first:]))
+    # every document of the prefix is the model's
+    end = int(offs[first])
+    assert np.array_equal(lb.doc_offsets[:first + 1], offs[:first + 1])
+    assert np.array_equal(lb.lexems, lex[:end]) and np.array_equal(origseg, seg[:end])
+    # every document from there on is empty, at the end of what fits
+    assert np.all(lb.doc_offsets[first:] == end)
+
+
 # ---- 2. failure paths
 def test_bad_segment_ranges_fail_their_documents_only():
     rng = np.random.default_rng(21)

@@ -248,6 +248,40 @@ def test_invalid_span_empties_its_document_only(bad):
     _assert_chosen(src, mb, got, want[:1])
 
 
+@pytest.mark.parametrize("ndocs", [1025, 2049])
+def test_document_counts_beyond_the_tile_of_the_offsets_pass(ndocs):
+    """the offsets pass scans the documents in tiles of 1024: documents of 0..2 spans into the second and the third tile, one
+    of the second tile with an invalid span (it counts 0 there, in both families)"""
+    rng = np.random.default_rng(5)
+    bad = 1030 if ndocs > 1030 else 1024
+    docs = []
+    for d in range(ndocs):
+        spans = []
+        for _ in range(int(rng.integers(0, 3))):
+            pos = int(rng.integers(0, 12))
+            spans.append((0, pos, 0, pos + int(rng.integers(0, 9))))
+        docs.append(spans)
+    docs[1022], docs[-1] = [], [(0, 0, 0, 20)]
+    docs[bad - 1] = [(0, 2, 0, 9)]
+    docs[bad] = [(0, 1, 0, 5), (0, 10, 0, 21)]             # origend beyond its segment
+    seglens = [[20]] * ndocs
+    src = Source([_random_text(rng, 20) for _ in docs])
+    lex, seg, offs, want = _pairs(docs, seglens)
+    ctx = _ctx()
+    Run(ctx, lex, seg, offs)
+    out = src.gather(ctx)
+    mb, got = _assert_text(ctx, src, out)
+    assert np.flatnonzero(got.status).tolist() == [bad] and int(got.status[bad]) == 5
+    assert np.diff(mb.doc_offsets.astype(np.int64)).tolist() == [len(s) for s in docs]
+    _assert_chosen(src, mb, got, want[:bad])
+    # what lies behind the failed document follows the document before it; the last span ends the text
+    r0, r1 = int(mb.doc_offsets[bad]), int(mb.doc_offsets[bad + 1])
+    assert np.all(got.result_offsets[r0:r1 + 1] == got.result_offsets[r0]) and got.result(r0 - 1) == _slice(src, bad - 1, (0, 2, 0, 9))
+    assert len(got.item_text) == len(got.result_text) == sum(s[3] - s[1] for d, spans in enumerate(docs) if d != bad for s in spans)
+    if bad < ndocs - 1:
+        assert got.result(len(mb.results) - 1) == src.text[-20:]
+
+
 # ---- 3. the documented example end to end: lexer -> matcher -> finish -> text
 def _example():
     with open(os.path.join(HERE, "golden", "doc_example.json")) as f:
