@@ -33,7 +33,8 @@ extern "C" {
 #define SP_DOC_ERR_ARENA         2   /* per-document working set exceeded the arena (retry with a larger arena) */
 #define SP_DOC_ERR_KEYTRIGGERS   3   /* >32 identical key events in one pattern (src/ruleMatcherAutomaton.cpp:1213-1216) */
 #define SP_DOC_ERR_PASTFOLLOW    4   /* "encountered past trigger with follow" (src/ruleMatcherAutomaton.cpp:1328-1332) */
-#define SP_DOC_ERR_RANGE         5   /* origsize/origpos out of range    (src/patternMatcher.cpp:144-155) */
+#define SP_DOC_ERR_RANGE         5   /* origsize/origpos out of range    (src/patternMatcher.cpp:144-155); in result-set mode
+                                       (SP_CTX_RESULT_SETS on the join kernel) also: more than 32 767 matches end at one lexem */
 #define SP_DOC_ERR_DATAREF       6   /* "illegal free of event data reference" (src/ruleMatcherAutomaton.cpp:726-731) */
 #define SP_DOC_ERR_LEXEMSIZE     7   /* matched lexem >= 65535 bytes    (src/patternLexer.cpp:727-730) */
 #define SP_DOC_ERR_INTERNAL      8   /* a list walk exceeded its bound: corrupted per-document state (bug) */
@@ -201,6 +202,8 @@ sp_matcher_ctx_t* sp_matcher_ctx_create(const sp_matcher_t* m, int device);
  * with their items -- not the reference's order of the results inside a document, and no statistics
  * (sp_matcher_ctx_statistics returns SP_ERR_UNAVAILABLE).  An eligible rule set (sp_matcher_result_set_tier) runs on the
  * join kernel (sp_matcher_ctx_kernel_kind 2), any other on the exact engine, whose results are a correct multiset too.
+ * The join kernel has one limit the exact engine has not: a document in which ONE lexem completes more than 32 767 matches
+ * fails with SP_DOC_ERR_RANGE and is empty (the other documents of the batch are not affected; csrc/l2_join.h).
  * The environment variable SPA_L2_JOIN=1 at context creation sets this flag on every context (sp_matcher_ctx_create too). */
 #define SP_CTX_RESULT_SETS       1u
 sp_matcher_ctx_t* sp_matcher_ctx_create_ex(const sp_matcher_t* m, int device, uint32_t flags);

@@ -32,6 +32,13 @@ struct JoinKey			// 16 B, open addressing by joinHash( first, second), first==0 
 	uint32_t begin;		// rules[begin .. begin+count), definition order
 	uint32_t count;
 };
+// THE LIMIT of this mode: the counting pass hands every lexem's count to the writing pass as matches | items << 16
+// (JoinParams::counts), so at most JOIN_COUNT_MAX = 32 767 matches may END AT ONE LEXEM (two items per match at most: 65 534
+// fit the high half).  The count saturates: a document in which one lexem completes more fails with SP_DOC_ERR_RANGE, reserves
+// nothing and writes nothing; the other documents of the batch are not affected.  The exact engine has no such limit.
+// The sums of a document are 32 bit as well: a document of 2^32 results or items fails in the same way.
+enum {JOIN_COUNT_MAX=0x7FFF};
+enum {JOIN_COUNT_OVERFLOW=0xFFFFFFFFu};	// what the counting pass returns for a lexem beyond the limit (no valid count: its low half exceeds JOIN_COUNT_MAX)
 enum {JOIN_FILTER_WORDS=4096};		// 16 KB = 131072 bits
 enum {JOIN_SELF=0xFFFFFFFFu};		// `first` of the entries for any( .. ): the lexem alone is the match
 enum {JOIN_STRUCT=1u};			// JoinRule::flags: no delimiter lexem may lie between the two terms (*_struct);

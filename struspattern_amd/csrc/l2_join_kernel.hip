@@ -72,7 +72,17 @@ __device__ __forceinline__ u32 altMatches( const JoinParams& P, const uint4* lex
 	return m;
 }
 
-// returns matches | items << 16
+// `times` more matches of `ni` items each: the count stops at JOIN_COUNT_MAX + 1, so it cannot wrap whatever the rule set and
+// the document hold (below that the items are at most twice the matches: they fit the high half); no branch per match
+__device__ __forceinline__ void countMatches( u32& cnt, u32& icnt, u32 times, u32 ni)
+{
+	const u32 lim = (u32)JOIN_COUNT_MAX + 1u, t = times < lim ? times : lim;
+	cnt = cnt + t < lim ? cnt + t : lim; icnt += ni*t;
+}
+
+// returns matches | items << 16 -- or, counting, JOIN_COUNT_OVERFLOW when the matches exceed JOIN_COUNT_MAX (the count
+// saturates there: the low half never carries into the item half, and two items per match at most fit the high one).  The
+// writing instantiation is entered only with a count the counting one has returned, so it stores exactly that many records.
 template <bool WRITE>
 __device__ __forceinline__ u32 matchesEndingAt( const JoinParams& P, const uint4* lex, const u32* seg, u32 j, uint4 lj, u32* out, u32* fmtOut, u64 itemAt)
 {
@@ -104,7 +114,7 @@ __device__ __forceinline__ u32 matchesEndingAt( const JoinParams& P, const uint4
 						if (vj) putItem( P, itemAt + icnt, vj, lj, sj);
 						if (vi) putItem( P, itemAt + icnt + (vj ? 1u : 0u), vi, lj, sj);
 					}
-					++cnt; icnt += ni;
+					countMatches( cnt, icnt, 1, ni);
 				}
 				break;
 			}
@@ -138,17 +148,15 @@ __device__ __forceinline__ u32 matchesEndingAt( const JoinParams& P, const uint4
 						// captured items, latest first (as the reference lists them): the completing lexem's, then the first one's
 						const u32 vi = P.io.withItems ? (rule.flags >> 8) & 0xFFu : 0u, vj = P.io.withItems ? (rule.flags >> 16) & 0xFFu : 0u;
 						const u32 ni = (vi ? 1u : 0u) + (vj ? 1u : 0u);
-						for (u32 t=0; t<times; ++t)
+						if (!WRITE) countMatches( cnt, icnt, times, ni);
+						else for (u32 t=0; t<times; ++t)
 						{
-							if (WRITE)
-							{
-								u32* o = out + 9*(u64)cnt;
-								const u32 si = seg ? seg[ i] : 0u, sj = seg ? seg[ j] : 0u;
-								st4( o, rule.resultHandle, li.y, lj.y + 1u, si); st4( o+4, li.z, sj, lj.z + lj.w, P.io.withItems ? (u32)(itemAt + icnt) : 0u); o[8] = ni;
-								if (fmtOut) fmtOut[ cnt] = rule.formatHandle;
-								if (vj) putItem( P, itemAt + icnt, vj, lj, sj);
-								if (vi) putItem( P, itemAt + icnt + (vj ? 1u : 0u), vi, li, si);
-							}
+							u32* o = out + 9*(u64)cnt;
+							const u32 si = seg ? seg[ i] : 0u, sj = seg ? seg[ j] : 0u;
+							st4( o, rule.resultHandle, li.y, lj.y + 1u, si); st4( o+4, li.z, sj, lj.z + lj.w, P.io.withItems ? (u32)(itemAt + icnt) : 0u); o[8] = ni;
+							if (fmtOut) fmtOut[ cnt] = rule.formatHandle;
+							if (vj) putItem( P, itemAt + icnt, vj, lj, sj);
+							if (vi) putItem( P, itemAt + icnt + (vj ? 1u : 0u), vi, li, si);
 							++cnt; icnt += ni;
 						}
 					}
@@ -160,6 +168,7 @@ __device__ __forceinline__ u32 matchesEndingAt( const JoinParams& P, const uint4
 		if (li.x == e && li.y > takenPos) takenPos = li.y;
 		if (P.delimiter && li.x == P.delimiter) delimited = true;
 	}
+	if (!WRITE && cnt > (u32)JOIN_COUNT_MAX) return JOIN_COUNT_OVERFLOW;
 	return cnt | (icnt << 16);
 }
 
@@ -188,7 +197,11 @@ __device__ void joinDocuments( const JoinParams& P)
 		u32 total = 0, itotal = 0;
 		if (!err)
 		{
-			bool bad = false, order = false;
+			// the first offending lexem decides the status, as in a sequential feed: a descending position shows at the later
+			// lexem and before that lexem's own range checks; the origpos / origsize checks sit in the else-if chain behind the
+			// position compares, so they see only a lexem that stays on the current position (0 before the first lexem)
+			u32 firstBad = ~0u, firstOrder = ~0u;		// (lane-private: the lexem index)
+			bool wrapped = false;
 			for (u32 base=0; base<n; base+=64)
 			{
 				const u32 j = base + LANE;
@@ -196,21 +209,35 @@ __device__ void joinDocuments( const JoinParams& P)
 				if (j < n)
 				{
 					const uint4 lj = lex[ j];
-					if (lj.x >= (1u<<29) || lj.z >= 0x7FFFFFFFu || lj.w >= 0x7FFFFFFFu) bad = true;
-					if (j + 1 < n && lex[ j+1].y < lj.y) order = true;
+					bool bad = lj.x >= (1u<<29);
+					if ((lj.z >= 0x7FFFFFFFu || lj.w >= 0x7FFFFFFFu) && (j ? lex[ j-1].y : 0u) == lj.y) bad = true;
+					if (j + 1 < n && lex[ j+1].y < lj.y && firstOrder == ~0u) firstOrder = j + 1;
 					c = matchesEndingAt<false>( P, lex, seg, j, lj, 0, 0, 0);
-					if ((c & 0xFFFFu) > 0x7FFFu) bad = true;		// (two items per match at most: both halves fit 16 bits)
+					if (c == (u32)JOIN_COUNT_OVERFLOW) { bad = true; c = 0; }	// more than JOIN_COUNT_MAX matches end at this lexem
+					if (bad && firstBad == ~0u) firstBad = j;
 					if (stored) P.counts[ beg + j] = c;
 				}
 				const u32 incl = waveScanAdd( c & 0xFFFFu), iincl = waveScanAdd( c >> 16);
-				total += uni( (u32)__shfl( (int)incl, 63));
-				itotal += uni( (u32)__shfl( (int)iincl, 63));
+				// (a chunk adds at most 64 x 0x7FFF matches and twice as many items: a sum that wrapped is smaller than what was added)
+				const u32 add = uni( (u32)__shfl( (int)incl, 63)), iadd = uni( (u32)__shfl( (int)iincl, 63));
+				total += add; itotal += iadd;
+				if (total < add || itotal < iadd) wrapped = true;
 			}
-			if (__ballot( order)) err = SPD_ERR_ORDER; else if (__ballot( bad)) err = SPD_ERR_RANGE;
+			if (__ballot( (firstOrder & firstBad) != ~0u))
+			{
+				const u32 o = ~uni( (u32)__shfl( (int)waveScanMax( ~firstOrder), 63)), b = ~uni( (u32)__shfl( (int)waveScanMax( ~firstBad), 63));
+				err = o <= b ? SPD_ERR_ORDER : SPD_ERR_RANGE;
+			}
+			else if (wrapped) err = SPD_ERR_RANGE;		// 2^32 results or items in one document: its sums are 32 bit
 		}
+		// both reservations are made even when the first one does not fit: the counters say what the whole batch needs
 		u64 resBase = 0, itemBase = 0;
-		if (!err && total && !reserveOutput( P.io, SPC_RESULTS, total, resBase)) { err = SPD_ERR_OUTPUT; total = 0; }
-		if (!err && total && itotal && !reserveOutput( P.io, SPC_ITEMS, itotal, itemBase)) { err = SPD_ERR_OUTPUT; total = 0; }
+		if (!err && total)
+		{
+			bool fits = reserveOutput( P.io, SPC_RESULTS, total, resBase);
+			if (itotal && !reserveOutput( P.io, SPC_ITEMS, itotal, itemBase)) fits = false;
+			if (!fits) { err = SPD_ERR_OUTPUT; total = 0; }
+		}
 		if (!err && total)
 		{
 			u32 at = 0, iat = 0;

@@ -1,8 +1,10 @@
-"""The opt-in join prototype of the rule automaton (csrc/l2_join.h, SPA_L2_JOIN=1): two-term rule sets (sequence, within,
-sequence_struct, within_struct, any: the operators of the reference's randomTokenPatternMatch) evaluated without
-materialised rule instances.  It reproduces the reference's result SETS per document, not the order
-of the results inside a document and not the statistics -- so this test compares sorted result tuples with the
-oracle (unoptimized automaton), and checks that the default engine is untouched by the switch."""
+"""The join kernel of result-set mode (csrc/l2_join.h) behind the environment switch SPA_L2_JOIN=1, on rule sets as
+defined (not compile()d): two-term rule sets (sequence, within, sequence_struct, within_struct, any: the operators of the
+reference's randomTokenPatternMatch) evaluated without materialised rule instances.  The mode reproduces the reference's
+result MULTISETS per document, not the order of the results inside a document and not the statistics -- so this test
+compares sorted result tuples with the oracle, and checks that the default engine is untouched by the switch.  Compiled
+rule sets, whose moved keys the kernel follows too, are in tests/test_result_sets_gpu.py; the edges of the kernel's own
+mechanics in tests/test_l2_join_edges_gpu.py."""
 import numpy as np
 import pytest
 
