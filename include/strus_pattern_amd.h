@@ -395,6 +395,79 @@ uint32_t sp_matcher_text_long_span(void);
 int sp_match_batch_text(const sp_match_batch_t* mb, const char* text, uint64_t nbytes, const uint64_t* seg_offsets,
                         size_t nseg, const uint64_t* doc_seg_offsets, uint32_t flags,
                         sp_match_text_t* out, char* err, size_t errsize);
+
+/* ---- pattern frequencies: per document, which patterns matched, how often and where first and last -- the feature
+ * frequency an index, a tagger or a classifier takes from a document -- and over the batch the document and collection
+ * frequency per pattern; summed on the device (csrc/l2_freq.h) or, for a batch already fetched, on the host
+ * (csrc/pattern_freq.hpp).  The rule is the project's own, unpinned by a reference vector (the reference has no such call).
+ * Handles are the pattern handles of the rule set: valid ones run from 1 to the number of pattern names np, the handle
+ * bound is np + 1 (sp_matcher_handle_bound).  For the batch finished last, `exclusive` already applied, every document d:
+ *   - if every result of d has 1 <= handle < handle_bound: one record per distinct handle, ascending by handle, with
+ *       count         the number of results of d with that handle,
+ *       first_ordpos  the minimum of their ordpos,
+ *       last_ordend   the maximum of their ordend                       (all values unsigned);
+ *   - otherwise d has frequency status SP_DOC_ERR_RANGE and no records (the stitch's and the text's rule: it fails and is
+ *     empty); the other documents are not affected.
+ * A document that the matcher failed, or that has no results, has no records and status 0.  Over the batch:
+ *   doc_offsets[ndocs+1]          the record range of every document,       totals[0]  the number of records,
+ *   handle_results[handle_bound]  the sum of `count` over all records with that handle (collection frequency),
+ *   handle_docs[handle_bound]     the number of records with that handle (document frequency);
+ * index 0 of both stays 0, and a document with a range status contributes nothing.  Nothing depends on the order of a
+ * document's results: the bytes are the same after a plain finish, after a canonical one and from result-set mode.  No byte
+ * outside the output buffers is written and no record at or beyond the finished total read, whatever the records hold. */
+typedef struct sp_pattern_freq {
+	uint32_t handle;
+	uint32_t count;
+	uint32_t first_ordpos;
+	uint32_t last_ordend;
+} sp_pattern_freq_t;
+typedef struct sp_pattern_freq_device {
+	size_t ndocs;
+	uint32_t handle_bound;
+	void* d_records;             /* sp_pattern_freq_t[]: document 0's records first, ascending by handle inside a document */
+	void* d_doc_offsets;         /* uint64_t[ndocs+1] */
+	void* d_doc_freq_status;     /* int32_t[ndocs]: 0 or SP_DOC_ERR_RANGE */
+	void* d_handle_results;      /* uint64_t[handle_bound] */
+	void* d_handle_docs;         /* uint32_t[handle_bound] */
+	void* d_totals;              /* uint64_t[1]: records */
+} sp_pattern_freq_device_t;
+/* host copy of a frequency batch (sp_pattern_freq_batch_free) */
+typedef struct sp_pattern_freq_batch {
+	size_t ndocs;
+	size_t nrecords;
+	uint32_t handle_bound;
+	sp_pattern_freq_t* records;
+	uint64_t* doc_offsets;        /* ndocs+1 */
+	int32_t* doc_freq_status;     /* ndocs */
+	uint64_t* handle_results;     /* handle_bound */
+	uint32_t* handle_docs;        /* handle_bound */
+	uint64_t totals[1];           /* records */
+} sp_pattern_freq_batch_t;
+/* np + 1: one more than the number of pattern names of the rule set; every result handle lies in [1, handle_bound) */
+uint32_t sp_matcher_handle_bound(const sp_matcher_t* m);
+/* Sums the frequencies of the batch finished last on this context (sp_matcher_ctx_batch_finish_device[_ex], either order).
+ * Passes on `stream` (count, offsets, place, totals: csrc/l2_freq.h); the call enqueues count and offsets, waits for them
+ * only to read the total, sizes the buffers, enqueues the rest and returns.  The buffers belong to the context, are
+ * allocated at the first call, only grow, and are valid until the next frequency call; the next batch or finish
+ * invalidates the state, not the buffers.  A `stream` other than the finish's is ordered behind it with an event.
+ * SP_ERR_INVALID when the last batch is not finished; SP_ERR_NOMEM when a buffer cannot be allocated (the context stays
+ * usable). */
+int sp_matcher_ctx_finished_pattern_freq_device(sp_matcher_ctx_t* c, void* stream, sp_pattern_freq_device_t* out);
+/* plain copy of the buffers of the last sp_matcher_ctx_finished_pattern_freq_device to the host (waits for it) */
+int sp_matcher_ctx_finished_pattern_freq_fetch(sp_matcher_ctx_t* c, sp_pattern_freq_batch_t* out);
+void sp_pattern_freq_batch_free(sp_pattern_freq_batch_t* b);
+/* duration of all passes of the last frequency call in milliseconds (HIP events on its stream round them; waits for them;
+ * the host's wait for the total between offsets and place lies inside) */
+int sp_matcher_ctx_last_pattern_freq_ms(sp_matcher_ctx_t* c, double* ms);
+/* diagnostics and tests: the handles that the device passes cover with one sweep of a document's results (the window of
+ * their per-wave bitmap); a document whose handles span several windows is swept once per occupied window */
+uint32_t sp_matcher_pattern_freq_window(void);
+/* The same rule over host arrays, needs no device: the frequencies of a batch already fetched (results, doc_result_offsets
+ * and, if given, doc_status: a document with a status has no records), and the yardstick of the device passes.  Fills `out`
+ * (sp_pattern_freq_batch_free); SP_ERR_INVALID with the message in `err` for a bound of 0 and for offsets that do not
+ * ascend or do not cover nresults. */
+int sp_match_batch_pattern_freq(const sp_match_batch_t* mb, uint32_t handle_bound, sp_pattern_freq_batch_t* out,
+                                char* err, size_t errsize);
 /* copies the results of the last device batch to the host, grouped by document (as sp_matcher_ctx_match_docs
  * returns them, `exclusive` elimination included) */
 int sp_matcher_ctx_batch_fetch(sp_matcher_ctx_t* c, sp_match_batch_t* out);

@@ -13,7 +13,7 @@ from . import capi
 from .capi import SpLexem, SpResult, SpResultItem
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
-           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText"]
+           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "PatternFreq", "batchPatternFreq"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
@@ -126,6 +126,53 @@ def batchText(mb, text, seg_offsets, doc_seg_offsets=None, results=True, items=T
         return _match_text_of(t)
     finally:
         L.sp_match_text_free(ctypes.byref(t))
+
+
+class PatternFreq:
+    """The pattern frequencies of a finished batch (host copies): per document one record per distinct handle, ascending by
+    handle, and per handle the sums over the batch (include/strus_pattern_amd.h "pattern frequencies")."""
+
+    def __init__(self, records, doc_offsets, status, handle_results, handle_docs):
+        self.records = records                # (n, 4) u32: handle, count, first_ordpos, last_ordend
+        self.doc_offsets = doc_offsets        # (ndocs+1,) u64
+        self.status = status                  # (ndocs,) i32: 0, or 5 for a document with a handle outside the bound (no records)
+        self.handle_results = handle_results  # (handle_bound,) u64: results per handle over the batch (collection frequency)
+        self.handle_docs = handle_docs        # (handle_bound,) u32: documents per handle (document frequency)
+
+    def doc(self, i):
+        return self.records[int(self.doc_offsets[i]):int(self.doc_offsets[i + 1])]
+
+
+def _pattern_freq_of(b):
+    """the PatternFreq of a capi.SpPatternFreqBatch (copies)"""
+    return PatternFreq(_rows(b.records, b.nrecords, 4), _rows(b.doc_offsets, b.ndocs + 1, 0, ctypes.c_uint64),
+                       _rows(b.doc_freq_status, b.ndocs, 0, ctypes.c_int32), _rows(b.handle_results, b.handle_bound, 0, ctypes.c_uint64),
+                       _rows(b.handle_docs, b.handle_bound, 0))
+
+
+def batchPatternFreq(mb, handle_bound):
+    """The pattern frequencies of a batch already on the host (a MatchBatch in document order: finishedFetch, batchFetch,
+    matchDocs), by the rule of the device call, without a device.  handle_bound: PatternMatcherInstance.handleBound().
+    Returns a PatternFreq."""
+    L = capi.lib()
+    res = np.ascontiguousarray(mb.results, dtype=np.uint32).reshape(-1, 9)
+    offs = np.ascontiguousarray(mb.doc_offsets, dtype=np.uint64)
+    status = None if mb.status is None else np.ascontiguousarray(mb.status, dtype=np.int32)
+    b = capi.SpMatchBatch()
+    b.ndocs, b.nresults = len(offs) - 1, len(res)
+    b.results = ctypes.cast(res.ctypes.data, ctypes.POINTER(SpResult))
+    b.doc_result_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
+    if status is not None:
+        b.doc_status = ctypes.cast(status.ctypes.data, ctypes.POINTER(ctypes.c_int32))
+    f = capi.SpPatternFreqBatch()
+    err = ctypes.create_string_buffer(256)
+    rc = L.sp_match_batch_pattern_freq(ctypes.byref(b), handle_bound, ctypes.byref(f), err, 256)
+    try:
+        if rc != 0:
+            raise PatternError("no pattern frequencies of the batch (%d): %s" % (rc, err.value.decode()))
+        return _pattern_freq_of(f)
+    finally:
+        L.sp_pattern_freq_batch_free(ctypes.byref(f))
 
 
 class PatternMatcherContext:
@@ -287,6 +334,34 @@ class PatternMatcherContext:
             raise PatternError("no timed text call")
         return a.value
 
+    def finishedPatternFreqDevice(self, stream=0):
+        """sum the pattern frequencies of the batch finished by batchFinishDevice on the device (the placement is
+        asynchronous on `stream`): per document one record per distinct handle, per handle the sums over the batch.
+        Returns the device pointers (capi.SpPatternFreqDevice), valid until the next call."""
+        out = capi.SpPatternFreqDevice()
+        rc = self._L.sp_matcher_ctx_finished_pattern_freq_device(self._h, stream or None, ctypes.byref(out))
+        if rc != 0:
+            raise PatternError("summing the pattern frequencies of the batch on the device failed (%d): %s" % (rc, self._err()))
+        return out
+
+    def finishedPatternFreqFetch(self):
+        """plain host copy of the frequencies summed by finishedPatternFreqDevice: a PatternFreq"""
+        f = capi.SpPatternFreqBatch()
+        rc = self._L.sp_matcher_ctx_finished_pattern_freq_fetch(self._h, ctypes.byref(f))
+        try:
+            if rc != 0:
+                raise PatternError("fetching the pattern frequencies of the batch failed (%d): %s" % (rc, self._err()))
+            return _pattern_freq_of(f)
+        finally:
+            self._L.sp_pattern_freq_batch_free(ctypes.byref(f))
+
+    def lastPatternFreqMs(self):
+        """duration of the passes of the last finishedPatternFreqDevice in milliseconds"""
+        a = ctypes.c_double(-1.0)
+        if self._L.sp_matcher_ctx_last_pattern_freq_ms(self._h, ctypes.byref(a)) != 0:
+            raise PatternError("no timed pattern frequency call")
+        return a.value
+
     def batchFetch(self, first_doc=None, ndocs=None):
         """host copy of the last device batch, grouped by document; with (first_doc, ndocs) only of
         that range of documents."""
@@ -411,6 +486,10 @@ class PatternMatcherInstance:
         inside the document and no statistics (getStatistics() is None) -- on the join kernel when resultSetTier() says
         the rule set is eligible, else on the exact engine (include/strus_pattern_amd.h, SP_CTX_RESULT_SETS)."""
         return PatternMatcherContext(self, device, result_sets)
+
+    def handleBound(self):
+        """one more than the number of pattern names: every result handle lies in [1, handleBound())"""
+        return self._L.sp_matcher_handle_bound(self._h)
 
     def patternId(self, name):
         return self._L.sp_matcher_pattern_id(self._h, name.encode())

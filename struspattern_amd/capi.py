@@ -88,6 +88,25 @@ class SpMatchText(ctypes.Structure):
     ]
 
 
+class SpPatternFreq(ctypes.Structure):
+    _fields_ = [(n, c_u32) for n in ("handle", "count", "first_ordpos", "last_ordend")]
+
+
+class SpPatternFreqDevice(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("handle_bound", c_u32), ("d_records", c_vp), ("d_doc_offsets", c_vp), ("d_doc_freq_status", c_vp),
+        ("d_handle_results", c_vp), ("d_handle_docs", c_vp), ("d_totals", c_vp),
+    ]
+
+
+class SpPatternFreqBatch(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("nrecords", ctypes.c_size_t), ("handle_bound", c_u32),
+        ("records", P(SpPatternFreq)), ("doc_offsets", P(c_u64)), ("doc_freq_status", P(ctypes.c_int32)),
+        ("handle_results", P(c_u64)), ("handle_docs", P(c_u32)), ("totals", c_u64 * 1),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/strus_pattern_amd.h
 SIGNATURES = {
     "sp_version": (c_cp, []),
@@ -148,6 +167,13 @@ SIGNATURES = {
     "sp_matcher_ctx_last_text_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
     "sp_matcher_text_long_span": (c_u32, []),
     "sp_match_batch_text": (ctypes.c_int, [P(SpMatchBatch), c_vp, c_u64, c_vp, ctypes.c_size_t, c_vp, c_u32, P(SpMatchText), ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_matcher_handle_bound": (c_u32, [c_vp]),
+    "sp_matcher_ctx_finished_pattern_freq_device": (ctypes.c_int, [c_vp, c_vp, P(SpPatternFreqDevice)]),
+    "sp_matcher_ctx_finished_pattern_freq_fetch": (ctypes.c_int, [c_vp, P(SpPatternFreqBatch)]),
+    "sp_pattern_freq_batch_free": (None, [P(SpPatternFreqBatch)]),
+    "sp_matcher_ctx_last_pattern_freq_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_matcher_pattern_freq_window": (c_u32, []),
+    "sp_match_batch_pattern_freq": (ctypes.c_int, [P(SpMatchBatch), c_u32, P(SpPatternFreqBatch), ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_ctx_batch_counters": (ctypes.c_int, [c_vp, P(c_u64)]),
     "sp_matcher_ctx_last_kernel_ms": (ctypes.c_double, [c_vp]),
     "sp_matcher_ctx_kernel_kind": (ctypes.c_int, [c_vp]),

@@ -3,7 +3,9 @@
 #include "l2_plan.hpp"
 #include "l2_finish.h"
 #include "l2_text.h"
+#include "l2_freq.h"
 #include "span_text.hpp"
+#include "pattern_freq.hpp"
 #include "capi_util.hpp"
 #include <cstdio>
 
@@ -122,6 +124,15 @@ struct sp_matcher_ctx
 		size_t ndocs = 0;
 		uint64_t nrecords[ 2] = {0, 0}, totals[ 2] = {0, 0};
 	} txt;
+	// the pattern frequencies of the last finished batch (l2_freq.h); nothing is allocated before the first sp_matcher_ctx_finished_pattern_freq_device
+	struct Freq
+	{
+		PassRun<2> run;
+		DeviceBuffer dRecords, dDocOffsets, dStatus, dHandleResults, dHandleDocs, dTotals, dDocCount, dDocMeta, dCursor;
+		size_t ndocs = 0;
+		uint32_t handleBound = 0;
+		uint64_t total = 0;
+	} frq;
 	// single-document mode
 	struct SingleDoc
 	{
@@ -182,6 +193,9 @@ uint32_t sp_matcher_pattern_id( const sp_matcher_t* m, const char* name) { retur
 const char* sp_matcher_pattern_name( const sp_matcher_t* m, uint32_t handle) { return m->compiler.patterns().key( handle); }
 uint32_t sp_matcher_variable_id( const sp_matcher_t* m, const char* name) { return m->compiler.variables().get( name); }
 const char* sp_matcher_variable_name( const sp_matcher_t* m, uint32_t variable) { return m->compiler.variables().key( variable); }
+
+// np + 1: every result handle of the rule set lies in [1, handle bound)
+uint32_t sp_matcher_handle_bound( const sp_matcher_t* m) { return (uint32_t)m->compiler.patterns().names().size() + 1; }
 
 uint32_t sp_matcher_format_count( const sp_matcher_t* m) { return m->compiler.formatCount(); }
 const char* sp_matcher_format_string( const sp_matcher_t* m, uint32_t format_handle) { return m->compiler.formatString( format_handle); }
@@ -531,7 +545,7 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 	const L2LaunchPlan plan = planL2Launch( c->kind, rerun != 0, c->numCUs, c->flat.blocksPerCU, rerun ? rerun->size() : ndocs, ndocs, nlexems,
 						c->exact.layout, &c->flat.plan, c->io.minResults, c->io.minItems);
 	HIP_CHECK( hipSetDevice( c->device));
-	c->fin.run.done = false; c->txt.run.done = false;	// (a new batch: what was finished is of the one before)
+	c->fin.run.done = false; c->txt.run.done = false; c->frq.run.done = false;	// (a new batch: what was finished is of the one before)
 	ensureArena( c, plan);
 	ensureOutput( c, plan, ndocs);
 	resetCursorAndCounters( c, rerun != 0, stream);
@@ -625,7 +639,7 @@ int sp_matcher_ctx_batch_finish_device_ex( sp_matcher_ctx_t* c, void* stream_, u
 		if (!c->haveBatch) throw std::runtime_error( "no batch to finish: no batch has run on this context");
 		hipStream_t stream = (hipStream_t)stream_;
 		HIP_CHECK( hipSetDevice( c->device));
-		c->fin.run.done = false; c->txt.run.done = false;
+		c->fin.run.done = false; c->txt.run.done = false; c->frq.run.done = false;
 		// the buffers are sized from what the batch counted: this read waits for the batch, the passes below do not
 		HIP_CHECK( hipStreamSynchronize( c->lastStream));
 		const BatchCounts counts = readCounts( c);
@@ -855,6 +869,92 @@ int sp_matcher_ctx_finished_text_fetch( sp_matcher_ctx_t* c, sp_match_text_t* ou
 int sp_matcher_ctx_last_text_ms( sp_matcher_ctx_t* c, double* ms) { return c->txt.run.ms( 0, 1, ms); }
 
 uint32_t sp_matcher_text_long_span(void) { return TEXT_LONG_SPAN; }
+
+// ---- the pattern frequencies of the finished batch, summed on the device (l2_freq.h)
+int sp_matcher_ctx_finished_pattern_freq_device( sp_matcher_ctx_t* c, void* stream_, sp_pattern_freq_device_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (!c->fin.run.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
+		const size_t ndocs = c->lastNdocs;
+		const uint32_t bound = sp_matcher_handle_bound( c->inst);
+		sp_matcher_ctx::Freq& q = c->frq;
+		hipStream_t stream = (hipStream_t)stream_;
+		HIP_CHECK( hipSetDevice( c->device));
+		q.run.done = q.run.evValid = false;
+		// every result index is checked against the total of the finish: this read waits for it
+		HIP_CHECK( hipStreamSynchronize( c->fin.run.stream));
+		uint64_t finished[ 2];
+		copySync( c->own, finished, c->fin.dTotals.ptr, sizeof(finished), hipMemcpyDeviceToHost);
+		reserveOrNoMem( q.dDocCount, (ndocs+1)*sizeof(uint32_t));
+		reserveOrNoMem( q.dDocMeta, (ndocs+1)*4*sizeof(uint32_t));
+		reserveOrNoMem( q.dStatus, (ndocs+1)*sizeof(int32_t));
+		reserveOrNoMem( q.dDocOffsets, (ndocs+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dHandleResults, (size_t)bound*sizeof(uint64_t));
+		reserveOrNoMem( q.dHandleDocs, (size_t)bound*sizeof(uint32_t));
+		reserveOrNoMem( q.dTotals, sizeof(uint64_t));
+		reserveOrNoMem( q.dCursor, 2*sizeof(uint32_t));
+
+		// another stream than the finish's runs behind the finish
+		q.run.begin( stream, c->fin.run.stream, c->fin.run.ev[ 3]);
+		HIP_CHECK( hipMemsetAsync( q.dCursor.ptr, 0, 2*sizeof(uint32_t), stream));
+		HIP_CHECK( hipMemsetAsync( q.dTotals.ptr, 0, sizeof(uint64_t), stream));
+		HIP_CHECK( hipMemsetAsync( q.dStatus.ptr, 0, (ndocs+1)*sizeof(int32_t), stream));
+		HIP_CHECK( hipMemsetAsync( q.dHandleResults.ptr, 0, (size_t)bound*sizeof(uint64_t), stream));
+		HIP_CHECK( hipMemsetAsync( q.dHandleDocs.ptr, 0, (size_t)bound*sizeof(uint32_t), stream));
+		FreqParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.results = (const uint32_t*)c->fin.dResults.ptr; P.docOffsets = (const uint64_t*)c->fin.dDocResultOffsets.ptr;
+		P.nresults = finished[ 0]; P.ndocs = (uint32_t)ndocs; P.handleBound = bound;
+		P.docCount = (uint32_t*)q.dDocCount.ptr; P.docMeta = (uint32_t*)q.dDocMeta.ptr; P.cursor = (uint32_t*)q.dCursor.ptr;
+		P.docStatus = (int32_t*)q.dStatus.ptr; P.docFreqOffsets = (uint64_t*)q.dDocOffsets.ptr; P.total = (uint64_t*)q.dTotals.ptr;
+		P.handleResults = (uint64_t*)q.dHandleResults.ptr; P.handleDocs = (uint32_t*)q.dHandleDocs.ptr;
+		HIP_CHECK( hipEventRecord( q.run.ev[ 0], stream));
+		HIP_CHECK( launchL2FreqCount( P, c->numCUs, stream));
+		// the records are sized from what the passes counted: this read waits for them, the passes below are not waited for
+		HIP_CHECK( hipStreamSynchronize( stream));
+		uint64_t total = 0;
+		copySync( c->own, &total, q.dTotals.ptr, sizeof(total), hipMemcpyDeviceToHost);
+		reserveOrNoMem( q.dRecords, (total+1)*sizeof(sp_pattern_freq_t));
+		P.records = (uint32_t*)q.dRecords.ptr; P.capacity = total;
+		if (total) HIP_CHECK( hipMemsetAsync( q.dRecords.ptr, 0, total*sizeof(sp_pattern_freq_t), stream));
+		HIP_CHECK( launchL2FreqPlace( P, c->numCUs, stream));
+		HIP_CHECK( hipEventRecord( q.run.ev[ 1], stream));
+		q.run.completed( stream); q.ndocs = ndocs; q.handleBound = bound; q.total = total;
+		if (out)
+		{
+			out->ndocs = ndocs; out->handle_bound = bound;
+			out->d_records = q.dRecords.ptr; out->d_doc_offsets = q.dDocOffsets.ptr; out->d_doc_freq_status = q.dStatus.ptr;
+			out->d_handle_results = q.dHandleResults.ptr; out->d_handle_docs = q.dHandleDocs.ptr; out->d_totals = q.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the frequency buffers
+int sp_matcher_ctx_finished_pattern_freq_fetch( sp_matcher_ctx_t* c, sp_pattern_freq_batch_t* out)
+{
+	std::memset( out, 0, sizeof(*out));
+	const int rc = guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		const sp_matcher_ctx::Freq& q = c->frq;
+		if (!q.run.done) throw std::runtime_error( "no pattern frequencies of the last batch of this context (sp_matcher_ctx_finished_pattern_freq_device)");
+		HIP_CHECK( hipSetDevice( c->device));
+		HIP_CHECK( hipStreamSynchronize( q.run.stream));
+		allocPatternFreq( out, q.ndocs, q.handleBound);
+		allocPatternFreqRecords( out, q.total);
+		if (q.total) copySync( c->own, out->records, q.dRecords.ptr, q.total*sizeof(sp_pattern_freq_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->doc_offsets, q.dDocOffsets.ptr, (q.ndocs+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		if (q.ndocs) copySync( c->own, out->doc_freq_status, q.dStatus.ptr, q.ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->handle_results, q.dHandleResults.ptr, (size_t)q.handleBound*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->handle_docs, q.dHandleDocs.ptr, (size_t)q.handleBound*sizeof(uint32_t), hipMemcpyDeviceToHost);
+	});
+	if (rc != SP_OK) sp_pattern_freq_batch_free( out);
+	return rc;
+}
+
+// duration of the passes of the last frequency call in milliseconds (HIP events on its stream)
+int sp_matcher_ctx_last_pattern_freq_ms( sp_matcher_ctx_t* c, double* ms) { return c->frq.run.ms( 0, 1, ms); }
+
+uint32_t sp_matcher_pattern_freq_window(void) { return FREQ_WINDOW; }
 
 double sp_matcher_ctx_last_kernel_ms( sp_matcher_ctx_t* c) { return lastKernelMs( c); }
 

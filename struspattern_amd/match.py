@@ -2,14 +2,17 @@
 through the MI355X lexer + rule automaton, print tokens (-K) and results in the reference tool's
 listing format (doc/webpage/introduction_struspattern.htm:178-260).
 
-    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] file [file ...]
+    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] file [file ...]
 
 Every file is one document (plain UTF-8 text; the reference tool segments XML with strusAnalyzer's
 segmenters, which are outside this engine -- pass -o to add the offset of the text inside its original
 file to the printed positions).  With --paragraphs every file is a segmented document: its paragraphs
 (split at runs of empty lines, which belong to no segment) go to the lexer one by one, are stitched to
 the document on the GPU, and positions are printed through the segment position map
-(`segmentposmap[seg] + ofs`, as the reference's printResults does; -o adds on top).  All files go to the
+(`segmentposmap[seg] + ofs`, as the reference's printResults does; -o adds on top).  With --frequencies the
+listing of a file is followed by one line per pattern that matched in it, ascending by pattern handle:
+`frequency NAME: count N first ORDPOS last ORDEND` -- how often, the first ordinal position a match starts at
+and the last one a match ends at, summed on the GPU (finishedPatternFreqDevice).  All files go to the
 GPU as one batch.  There is no CPU fallback.
 """
 import argparse
@@ -27,6 +30,7 @@ def main(argv=None):
     ap.add_argument("-K", "--tokens", action="store_true", help="also print the tokens recognized")
     ap.add_argument("-o", "--origin", type=int, default=0, help="offset added to the printed byte positions")
     ap.add_argument("--paragraphs", action="store_true", help="every file is a document whose segments are its paragraphs")
+    ap.add_argument("--frequencies", action="store_true", help="after the listing of a file, one line per pattern that matched in it")
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("files", nargs="+")
     args = ap.parse_args(argv)
@@ -47,7 +51,9 @@ def main(argv=None):
     offs[1:] = np.cumsum([len(d) for d in docs])
 
     lb = lx.createContext(args.device).matchDocs(text, offs)
-    mb = mt.createContext(args.device).matchDocs(lb.lexems, lb.doc_offsets)
+    mctx = mt.createContext(args.device)
+    mb = mctx.matchDocs(lb.lexems, lb.doc_offsets)
+    freq = frequencies(mctx) if args.frequencies else None
     for di, fn in enumerate(args.files):
         print("%s:" % fn)
         doc = docs[di]
@@ -59,18 +65,37 @@ def main(argv=None):
                                             result_format=mb.result_format, item_format=mb.item_format, format_string=mt.formatString,
                                             first_result=int(mb.doc_offsets[di])):
             print(line)
+        print_frequencies(freq, di, mt)
     print("OK done")
     return 0
+
+
+def frequencies(mctx):
+    """--frequencies: the last batch of the context finished on the device and its pattern frequencies summed there"""
+    mctx.batchFinishDevice()
+    mctx.finishedPatternFreqDevice()
+    return mctx.finishedPatternFreqFetch()
+
+
+def print_frequencies(freq, di, mt):
+    if freq is None:
+        return
+    if int(freq.status[di]) != 0:
+        raise spa.PatternError("no pattern frequencies of document %d: status %d" % (di, int(freq.status[di])))
+    for handle, count, first, last in freq.doc(di):
+        print("frequency %s: count %d first %d last %d" % (mt.patternName(int(handle)), count, first, last))
 
 
 def paragraphs(args, prg, lx, mt, docs):
     """--paragraphs: lexer per segment -> stitch on the device -> matcher; the listing through the segment position map"""
     text, seg_offsets, doc_seg_offsets, posmaps = segments.segmented_batch(docs)
     lctx = lx.createContext(args.device)
-    mb = spa.matchSegmentedDocs(lctx, mt.createContext(args.device), text, seg_offsets, doc_seg_offsets)
+    mctx = mt.createContext(args.device)
+    mb = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets)
     if np.any(mb.status != 0):
         bad = int(np.flatnonzero(mb.status)[0])
         raise spa.PatternError("at least one document failed: %s has status %d" % (args.files[bad], int(mb.status[bad])))
+    freq = frequencies(mctx) if args.frequencies else None
     lb, origseg = lctx.stitchedFetch()
     items = np.zeros((0, 7), np.int64)
     for di, fn in enumerate(args.files):
@@ -90,6 +115,7 @@ def paragraphs(args, prg, lx, mt, docs):
                                             result_format=mb.result_format, item_format=mb.item_format, format_string=mt.formatString,
                                             first_result=int(mb.doc_offsets[di])):
             print(line)
+        print_frequencies(freq, di, mt)
     print("OK done")
     return 0
 
