@@ -1235,7 +1235,7 @@ __device__ __forceinline__ u32 runStartBefore( const L1Params& P, const unsigned
 }
 
 // The backward walk of leftmostStart for a candidate of the words kernel: class and context of the bytes it visits come from the
-// wave's ring in LDS (the last 128 bytes of the text, written a tile at a time), the automaton's rows from the LDS image -- two
+// wave's ring in LDS (the last 512 bytes of the text, written a tile at a time), the automaton's rows from the LDS image -- two
 // LDS round trips per byte instead of four dependent global loads.  A walk that leaves the ring goes on with leftmostStart.
 enum {WORD_RING=512, WORD_ENDS=96, WORD_ENDWORDS=5};
 // (per wave: a ring of class | context << 8 of the last 512 bytes, wordRing, and wordEnds -- both declared in wordsDocuments, one pair
@@ -1249,7 +1249,7 @@ template <bool LDS>
 __device__ __forceinline__ u32 confirmWalk( const unsigned char* doc, u32 docLen, const L1Params& P, const LexTab<LDS>& T, const unsigned short* ring, u32 ringLo,
 					    u32 word, u64 mask, u32 to)
 {
-	// ring[ q & 127] = class | context << 8 of byte q for ringLo <= q < ringLo + 128
+	// ring[ q & (WORD_RING-1)] = class | context << 8 of byte q for ringLo <= q < ringLo + WORD_RING
 	const u32 pass = word >> 6, ln = word & 63u;
 	const u32 ccLast = ring[ (to-1u) & (WORD_RING-1)];
 	const u32 nextctx = to < docLen ? ((u32)ring[ to & (WORD_RING-1)] >> 8) : (u32)CTX_EDGE;
