@@ -182,7 +182,8 @@ int sp_matcher_serialize(const sp_matcher_t* m, void** blob, size_t* size);
 sp_matcher_t* sp_matcher_deserialize(const void* blob, size_t size, char* err, size_t errsize);
 
 /* ---- result format strings (definePattern's formatstring, src/patternMatcher.cpp:561-566, :172-181, :253-262).
- * The device does not build strings: it reports which format applies and what its arguments are.
+ * The matcher kernels do not build strings: they report which format applies and what its arguments are; the device
+ * builds the strings on request, from a finished batch (see "result values" below).
  *   - a result with a format handle: its item list holds the ARGUMENTS of the format string; the
  *     reference returns such a result with a value and an empty item list (:253-262).
  *   - an item with a format handle (a variable bound to a sub-pattern that has a format string): the
@@ -395,6 +396,92 @@ uint32_t sp_matcher_text_long_span(void);
 int sp_match_batch_text(const sp_match_batch_t* mb, const char* text, uint64_t nbytes, const uint64_t* seg_offsets,
                         size_t nseg, const uint64_t* doc_seg_offsets, uint32_t flags,
                         sp_match_text_t* out, char* err, size_t errsize);
+
+/* ---- result values: the values of the format strings of a finished batch -- what an index stores as a feature beside the
+ * pattern name ("3'645 Eur" -> "EUR 3'645") -- built on the device (csrc/l2_values.h) or, for a batch already fetched, on the
+ * host (csrc/result_values.hpp).  The rule is the project's own restatement of resultformat.Formatter and of the host shim,
+ * unpinned by a reference vector beyond the one example of the reference's web page (PatternResultFormat lives in
+ * strusAnalyzer).
+ * The format table is built on the host at every sp_matcher_compile (a loaded rule set rebuilds it from its format strings;
+ * the blob is unchanged; without a compile, or when format strings or variable names were added since, the first values call
+ * that finds the counts changed builds it).  A context uploads the table it finds at its FIRST values call and keeps it:
+ * create the contexts that build values after the last definition of the rule set, as for the rule tables themselves.  For every format handle f in 1..sp_matcher_format_count() it holds the parts of the string:
+ *   - "\x" is the literal byte x (a backslash at the end stands for itself);
+ *   - "{var}" and "{var|sep}" are variable parts: the name without its bytes <= 32 at both ends, the separator one blank by
+ *     default and empty for an empty text behind '|'; the part holds the variable handle of the rule set for that name, or
+ *     0 when the rule set has no such variable -- such a part matches no argument;
+ *   - everything else is literal bytes.  Literals and separators live in one byte pool.
+ * A format string that does not parse (no '}' behind a '{', an empty variable name) is no error of definePattern; it makes
+ * the values calls below fail with SP_ERR_INVALID and a message that names the format.
+ * A list is a range [b, e) of the finished item records.  Its top-level records are found by walking i = b: with
+ * (fmt_i, nsub_i) = item_format[i], the arguments of a record with fmt_i != 0 are [i+1, i+1+nsub_i) and the next top-level
+ * record is i+1+nsub_i; behind a record without a format it is i+1.  eval( f, [b,e) ) concatenates the parts of f: a literal
+ * part gives its bytes; a variable part v gives, for every top-level record of the list whose word 0 is v, in list order,
+ * joined by the part's separator: eval( fmt_i, its arguments ) if fmt_i != 0, else the bytes of its span under the
+ * matched-text rule above (words 3..6, seg_offsets, doc_seg_offsets), unchanged.
+ *   SP_VALUE_RESULTS  result r has a value iff result_format[r] != 0: eval( result_format[r], [item_begin, item_begin+item_count) )
+ *   SP_VALUE_ITEMS    item record i has a value iff item_format[i][0] != 0: eval over its nsub records; for every such
+ *                     record, the nested ones included
+ * A record without a format has an empty value range; the format arrays tell an empty value from no value.
+ * A document fails -- value status SP_DOC_ERR_RANGE, ALL its value ranges of both families empty, the other documents not
+ * affected -- when the evaluation of a requested value meets one of these: a span that it uses is invalid under the text
+ * rule; a format handle (of the value's record or of a top-level record of a list it walks for a variable part) exceeds the
+ * format count; such a record's nsub runs beyond the list (for the value's own record: beyond the items of the document, as
+ * a result's item range does); more than sp_matcher_value_max_depth() formats are under evaluation inside each other (8: the
+ * value itself is level 1; the device keeps the walk's stack of 5 words per level and lane in LDS, 40 KB per workgroup);
+ * the document has 2^32 items or more; or the values of one family add up to 2^32 bytes or more.  Records and spans that no
+ * requested value uses are not looked at.  A document the matcher failed, or one without formatted records, has status 0; a
+ * matcher without format strings yields all-empty ranges and status 0.  No byte outside [0, nbytes) of the text is read,
+ * none outside the outputs written and no record at or beyond the finished totals read, whatever the records hold. */
+#define SP_VALUE_RESULTS 1u
+#define SP_VALUE_ITEMS   2u
+typedef struct sp_match_values_batch {
+	size_t ndocs;
+	void* d_result_values;         /* uint8_t[]: the value of result 0 of the finished d_results first */
+	void* d_result_value_offsets;  /* uint64_t[nresults+1], parallel to the finished d_results; the values of a failed
+	                                  document all sit on the document's offset */
+	void* d_item_values;           /* the same, parallel to the finished d_items */
+	void* d_item_value_offsets;
+	void* d_doc_value_status;      /* int32_t[ndocs]: 0 or SP_DOC_ERR_RANGE */
+	void* d_totals;                /* uint64_t[2]: result bytes, item bytes */
+} sp_match_values_batch_t;
+/* host copy of a values batch (sp_match_values_free); a family that was not asked for has NULL pointers and a total of 0 */
+typedef struct sp_match_values {
+	size_t ndocs;
+	size_t nresults;
+	size_t nitems;
+	char* result_values;
+	uint64_t* result_value_offsets; /* nresults+1 */
+	char* item_values;
+	uint64_t* item_value_offsets;   /* nitems+1 */
+	int32_t* doc_value_status;      /* ndocs */
+	uint64_t totals[2];             /* result bytes, item bytes */
+} sp_match_values_t;
+/* Builds the values of the batch finished last on this context (sp_matcher_ctx_batch_finish_device[_ex], either order; the
+ * values follow the finished order).  flags: SP_VALUE_RESULTS | SP_VALUE_ITEMS; a family that is not requested has NULL
+ * pointers in `out`.  Three passes per family on `stream` (count, offsets, place: csrc/l2_values.h); the call enqueues count
+ * and offsets, waits for them to read the totals, sizes the buffers and enqueues the placement, which it does not wait
+ * for.  The buffers belong to the context, are allocated at the first call, only grow, and are valid until the next values
+ * call; the format table is uploaded once per context, at the first call; the next batch or finish invalidates the state,
+ * not the buffers.  A `stream` other than the finish's is ordered behind it with an event.  SP_ERR_INVALID when the last
+ * batch is not finished, for flags 0 or unknown bits, for a NULL source and for a format string that does not parse;
+ * SP_ERR_NOMEM when a buffer cannot be allocated (the context stays usable). */
+int sp_matcher_ctx_finished_values_device(sp_matcher_ctx_t* c, const sp_text_source_t* src, uint32_t flags, void* stream, sp_match_values_batch_t* out);
+/* plain copy of the buffers of the last sp_matcher_ctx_finished_values_device to the host (waits for it) */
+int sp_matcher_ctx_finished_values_fetch(sp_matcher_ctx_t* c, sp_match_values_t* out);
+void sp_match_values_free(sp_match_values_t* v);
+/* duration of all passes of the last values call in milliseconds (HIP events on its stream round them; waits for them; the
+ * host's wait for the totals between offsets and place lies inside) */
+int sp_matcher_ctx_last_values_ms(sp_matcher_ctx_t* c, double* ms);
+/* the number of formats that may be under evaluation inside each other (a compile-time constant) */
+uint32_t sp_matcher_value_max_depth(void);
+/* The same rule over host arrays, needs no device: the values of a batch already fetched (sp_matcher_ctx_finished_fetch,
+ * sp_matcher_ctx_batch_fetch, sp_matcher_ctx_match_docs) of matcher `m`, and the yardstick of the device passes.  The items of
+ * document d are taken to follow those of document d-1 without gaps, in result order.  Fills `out` (sp_match_values_free);
+ * SP_ERR_INVALID with the message in `err` under the rules of sp_match_batch_text, and for a format string that does not parse. */
+int sp_match_batch_values(const sp_matcher_t* m, const sp_match_batch_t* mb, const char* text, uint64_t nbytes,
+                          const uint64_t* seg_offsets, size_t nseg, const uint64_t* doc_seg_offsets, uint32_t flags,
+                          sp_match_values_t* out, char* err, size_t errsize);
 
 /* ---- pattern frequencies: per document, which patterns matched, how often and where first and last -- the feature
  * frequency an index, a tagger or a classifier takes from a document -- and over the batch the document and collection

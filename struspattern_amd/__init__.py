@@ -13,11 +13,12 @@ from . import capi
 from .capi import SpLexem, SpResult, SpResultItem
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
-           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "PatternFreq", "batchPatternFreq"]
+           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
 SP_TEXT_RESULTS, SP_TEXT_ITEMS = 1, 2   # include/strus_pattern_amd.h: the families of spans of a text call
+SP_VALUE_RESULTS, SP_VALUE_ITEMS = 1, 2  # include/strus_pattern_amd.h: the families of records of a values call
 SP_ERR_UNAVAILABLE = -6     # include/strus_pattern_amd.h: a value that does not exist for the context
 
 JOIN_OP = {"sequence": 0, "sequence_imm": 1, "sequence_struct": 2, "within": 3, "within_struct": 4, "any": 5, "and": 6}
@@ -126,6 +127,72 @@ def batchText(mb, text, seg_offsets, doc_seg_offsets=None, results=True, items=T
         return _match_text_of(t)
     finally:
         L.sp_match_text_free(ctypes.byref(t))
+
+
+class MatchValues:
+    """The values of the format strings of a finished batch (host copies): the value of record i of a family is
+    values[offsets[i]:offsets[i+1]], parallel to the results / items of the batch; a record without a format has an empty
+    range (the format arrays of the batch tell an empty value from no value).  A family that was not asked for is None."""
+
+    def __init__(self, result_values, result_offsets, item_values, item_offsets, status):
+        self.result_values = result_values    # bytes
+        self.result_offsets = result_offsets  # (nresults+1,) u64
+        self.item_values = item_values
+        self.item_offsets = item_offsets
+        self.status = status                  # (ndocs,) i32: 0, or 5 for a document whose values cannot be built (all of them empty)
+
+    def result(self, i):
+        return self.result_values[int(self.result_offsets[i]):int(self.result_offsets[i + 1])]
+
+    def item(self, i):
+        return self.item_values[int(self.item_offsets[i]):int(self.item_offsets[i + 1])]
+
+
+def _match_values_of(v):
+    """the MatchValues of a capi.SpMatchValues (copies)"""
+    def family(values, offsets, n, total):
+        if not offsets:
+            return None, None
+        return (ctypes.string_at(values, total) if total else b""), _rows(offsets, n + 1, 0, ctypes.c_uint64)
+    rv, ro = family(v.result_values, v.result_value_offsets, v.nresults, v.totals[0])
+    iv, io = family(v.item_values, v.item_value_offsets, v.nitems, v.totals[1])
+    return MatchValues(rv, ro, iv, io, _rows(v.doc_value_status, v.ndocs, 0, ctypes.c_int32))
+
+
+def batchValues(matcher, mb, text, seg_offsets, doc_seg_offsets=None, flags=SP_VALUE_RESULTS | SP_VALUE_ITEMS):
+    """The values of the format strings of a batch already on the host (a MatchBatch of `matcher`, a PatternMatcherInstance,
+    in document order with items without gaps: finishedFetch, batchFetch, matchDocs), by the rule of the device call
+    (include/strus_pattern_amd.h "result values"), without a device.  The text source is that of batchText.  Returns a
+    MatchValues."""
+    L = capi.lib()
+    text = bytes(text)
+    seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
+    dso = None if doc_seg_offsets is None else np.ascontiguousarray(doc_seg_offsets, dtype=np.uint64)
+    res = np.ascontiguousarray(mb.results, dtype=np.uint32).reshape(-1, 9)
+    its = np.ascontiguousarray(mb.items, dtype=np.uint32).reshape(-1, 7)
+    offs = np.ascontiguousarray(mb.doc_offsets, dtype=np.uint64)
+    b = capi.SpMatchBatch()
+    b.ndocs, b.nresults, b.nitems = len(offs) - 1, len(res), len(its)
+    b.results = ctypes.cast(res.ctypes.data, ctypes.POINTER(SpResult))
+    b.items = ctypes.cast(its.ctypes.data, ctypes.POINTER(SpResultItem))
+    b.doc_result_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
+    if mb.result_format is not None and mb.item_format is not None:
+        rf = np.ascontiguousarray(mb.result_format, dtype=np.uint32).reshape(-1)
+        itf = np.ascontiguousarray(mb.item_format, dtype=np.uint32).reshape(-1, 2)
+        if len(rf) != len(res) or len(itf) != len(its):
+            raise PatternError("format arrays of the batch are not parallel to its results and items")
+        b.result_format = ctypes.cast(rf.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
+        b.item_format = ctypes.cast(itf.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
+    v = capi.SpMatchValues()
+    err = ctypes.create_string_buffer(512)
+    rc = L.sp_match_batch_values(matcher._h, ctypes.byref(b), text, len(text), seg_offsets.ctypes.data, len(seg_offsets) - 1,
+                                 dso.ctypes.data if dso is not None else None, flags, ctypes.byref(v), err, 512)
+    try:
+        if rc != 0:
+            raise PatternError("no values of the batch (%d): %s" % (rc, err.value.decode(errors="replace")))
+        return _match_values_of(v)
+    finally:
+        L.sp_match_values_free(ctypes.byref(v))
 
 
 class PatternFreq:
@@ -332,6 +399,35 @@ class PatternMatcherContext:
         a = ctypes.c_double(-1.0)
         if self._L.sp_matcher_ctx_last_text_ms(self._h, ctypes.byref(a)) != 0:
             raise PatternError("no timed text call")
+        return a.value
+
+    def finishedValuesDevice(self, d_text, nbytes, d_seg_offsets, nseg, d_doc_seg_offsets=0, flags=SP_VALUE_RESULTS | SP_VALUE_ITEMS, stream=0):
+        """build the values of the format strings of the results and / or items of the batch finished by batchFinishDevice,
+        on the device (the placement is asynchronous on `stream`); the text source is that of finishedTextDevice.
+        Returns the device pointers (capi.SpMatchValuesBatch), valid until the next call."""
+        src = capi.SpTextSource(d_text or None, nbytes, d_seg_offsets or None, nseg, d_doc_seg_offsets or None)
+        out = capi.SpMatchValuesBatch()
+        rc = self._L.sp_matcher_ctx_finished_values_device(self._h, ctypes.byref(src), flags, stream or None, ctypes.byref(out))
+        if rc != 0:
+            raise PatternError("building the values of the batch on the device failed (%d): %s" % (rc, self._err()))
+        return out
+
+    def finishedValuesFetch(self):
+        """plain host copy of the values built by finishedValuesDevice: a MatchValues"""
+        v = capi.SpMatchValues()
+        rc = self._L.sp_matcher_ctx_finished_values_fetch(self._h, ctypes.byref(v))
+        try:
+            if rc != 0:
+                raise PatternError("fetching the values of the batch failed (%d): %s" % (rc, self._err()))
+            return _match_values_of(v)
+        finally:
+            self._L.sp_match_values_free(ctypes.byref(v))
+
+    def lastValuesMs(self):
+        """duration of the passes of the last finishedValuesDevice in milliseconds"""
+        a = ctypes.c_double()
+        if self._L.sp_matcher_ctx_last_values_ms(self._h, ctypes.byref(a)) != 0:
+            raise PatternError("no timed values call")
         return a.value
 
     def finishedPatternFreqDevice(self, stream=0):
@@ -835,13 +931,14 @@ class PatternLexer:
         return "std"
 
 
-def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False):
+def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False):
     """Segmented documents, host buffers in and out: `text` holds the segments back to back (seg_offsets: nseg+1 byte
     offsets), document d consists of the segments [doc_seg_offsets[d], doc_seg_offsets[d+1]).  Lexer -> stitch on the
     device -> rule matcher -> fetch; only the text goes up and the results come down.  Returns the MatchBatch, whose
     status of a document is the stitch's where that is not 0 (a failed segment, a bad segment range), else the matcher's.
     with_text: the batch is finished on the device and the text its results and items cover gathered there; returns
-    (MatchBatch, MatchText)."""
+    (MatchBatch, MatchText).  with_values: the values of the format strings are built there too; returns
+    (MatchBatch, MatchValues), or (MatchBatch, MatchText, MatchValues) with both."""
     import torch
     text = bytes(text)
     seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
@@ -867,16 +964,22 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
             break
         mctx.reserveOutput(int(mc["results"] * 1.2) + 1024, int(mc["items"] * 1.2) + 1024)
         mctx.growArena()
-    mt = None
-    if with_text:
+    mt = mv = None
+    if with_text or with_values:
         mctx.batchFinishDevice(stream)
-        mctx.finishedTextDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), nseg, d_dso.data_ptr(), stream=stream)
-        mb, mt = mctx.finishedFetch(), mctx.finishedTextFetch()
+        if with_text:
+            mctx.finishedTextDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), nseg, d_dso.data_ptr(), stream=stream)
+        if with_values:
+            mctx.finishedValuesDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), nseg, d_dso.data_ptr(), stream=stream)
+        mb = mctx.finishedFetch()
+        mt = mctx.finishedTextFetch() if with_text else None
+        mv = mctx.finishedValuesFetch() if with_values else None
     else:
         mb = mctx.batchFetch()
     stitch_status = lctx.stitchedStatus()
     mb.status = np.where(stitch_status != 0, stitch_status, mb.status).astype(np.int32)
-    return (mb, mt) if with_text else mb
+    out = (mb,) + ((mt,) if with_text else ()) + ((mv,) if with_values else ())
+    return out if len(out) > 1 else mb
 
 
 def device_count():

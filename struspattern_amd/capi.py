@@ -88,6 +88,21 @@ class SpMatchText(ctypes.Structure):
     ]
 
 
+class SpMatchValuesBatch(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("d_result_values", c_vp), ("d_result_value_offsets", c_vp), ("d_item_values", c_vp),
+        ("d_item_value_offsets", c_vp), ("d_doc_value_status", c_vp), ("d_totals", c_vp),
+    ]
+
+
+class SpMatchValues(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("nresults", ctypes.c_size_t), ("nitems", ctypes.c_size_t),
+        ("result_values", P(ctypes.c_uint8)), ("result_value_offsets", P(c_u64)), ("item_values", P(ctypes.c_uint8)), ("item_value_offsets", P(c_u64)),
+        ("doc_value_status", P(ctypes.c_int32)), ("totals", c_u64 * 2),
+    ]
+
+
 class SpPatternFreq(ctypes.Structure):
     _fields_ = [(n, c_u32) for n in ("handle", "count", "first_ordpos", "last_ordend")]
 
@@ -166,6 +181,12 @@ SIGNATURES = {
     "sp_match_text_free": (None, [P(SpMatchText)]),
     "sp_matcher_ctx_last_text_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
     "sp_matcher_text_long_span": (c_u32, []),
+    "sp_matcher_ctx_finished_values_device": (ctypes.c_int, [c_vp, P(SpTextSource), c_u32, c_vp, P(SpMatchValuesBatch)]),
+    "sp_matcher_ctx_finished_values_fetch": (ctypes.c_int, [c_vp, P(SpMatchValues)]),
+    "sp_match_values_free": (None, [P(SpMatchValues)]),
+    "sp_matcher_ctx_last_values_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_matcher_value_max_depth": (c_u32, []),
+    "sp_match_batch_values": (ctypes.c_int, [c_vp, P(SpMatchBatch), c_vp, c_u64, c_vp, ctypes.c_size_t, c_vp, c_u32, P(SpMatchValues), ctypes.c_char_p, ctypes.c_size_t]),
     "sp_match_batch_text": (ctypes.c_int, [P(SpMatchBatch), c_vp, c_u64, c_vp, ctypes.c_size_t, c_vp, c_u32, P(SpMatchText), ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_handle_bound": (c_u32, [c_vp]),
     "sp_matcher_ctx_finished_pattern_freq_device": (ctypes.c_int, [c_vp, c_vp, P(SpPatternFreqDevice)]),

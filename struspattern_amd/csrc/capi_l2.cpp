@@ -4,10 +4,13 @@
 #include "l2_finish.h"
 #include "l2_text.h"
 #include "l2_freq.h"
+#include "l2_values.h"
 #include "span_text.hpp"
+#include "result_values.hpp"
 #include "pattern_freq.hpp"
 #include "capi_util.hpp"
 #include <cstdio>
+#include <mutex>
 
 using namespace spa;
 
@@ -16,6 +19,27 @@ struct sp_matcher
 	RuleCompiler compiler;
 	bool compiled = false;	// compile() is optional for the matcher (reference: tests/randomTokenPatternMatch :317-320)
 	mutable std::string lasterror;
+	// the parts of the format strings (result_values.hpp): built when the rule set compiles or is loaded, else at the first values call
+	mutable std::mutex formatMutex;
+	mutable FormatTable formatTable;
+	mutable bool haveFormatTable = false;
+	mutable size_t formatTableVariables = 0;	// the variable names the table was resolved against
+
+	// rebuild = true (every compile, every load): the definitions may have changed under the same counts
+	const FormatTable& formats( bool rebuild = false) const
+	{
+		std::lock_guard<std::mutex> lock( formatMutex);
+		const size_t nvariables = compiler.variables().names().size();
+		if (rebuild || !haveFormatTable || formatTable.count != compiler.formatCount() || formatTableVariables != nvariables)
+		{
+			formatTableVariables = nvariables;
+			formatTable = buildFormatTable( compiler.formatCount(),
+				[this]( uint32_t f) { return compiler.formatString( f); },
+				[this]( const std::string& name) { return compiler.variables().get( name); });
+			haveFormatTable = true;
+		}
+		return formatTable;
+	}
 };
 
 namespace {
@@ -124,6 +148,19 @@ struct sp_matcher_ctx
 		size_t ndocs = 0;
 		uint64_t nrecords[ 2] = {0, 0}, totals[ 2] = {0, 0};
 	} txt;
+	// the values of the format strings of the last finished batch (l2_values.h); nothing is allocated before the first sp_matcher_ctx_finished_values_device
+	struct Values
+	{
+		PassRun<2> run;
+		DeviceBuffer dFmtParts, dParts, dPool;		// the format table, uploaded at the first call
+		bool uploaded = false;
+		uint32_t poolBytes = 0;
+		DeviceBuffer dValues[ 2], dValueOffsets[ 2], dValueWork[ 2], dDocBytes[ 2], dDocValueOffsets[ 2];	// [0] results, [1] items
+		DeviceBuffer dStatus, dTotals, dCursor;
+		uint32_t flags = 0;
+		size_t ndocs = 0;
+		uint64_t nrecords[ 2] = {0, 0}, totals[ 2] = {0, 0};
+	} val;
 	// the pattern frequencies of the last finished batch (l2_freq.h); nothing is allocated before the first sp_matcher_ctx_finished_pattern_freq_device
 	struct Freq
 	{
@@ -187,7 +224,7 @@ int sp_matcher_define_pattern( sp_matcher_t* m, const char* name, const char* fo
 int sp_matcher_define_option( sp_matcher_t* m, const char* name, double value)
 { MGUARD( SP_ERR_INVALID, m->compiler.defineOption( name ? name : "", value)); }
 int sp_matcher_compile( sp_matcher_t* m)
-{ MGUARD( SP_ERR_COMPILE, m->compiler.compile(); m->compiled = true); }
+{ MGUARD( SP_ERR_COMPILE, m->compiler.compile(); m->compiled = true; m->formats( true)); }
 
 uint32_t sp_matcher_pattern_id( const sp_matcher_t* m, const char* name) { return m->compiler.patterns().get( name); }
 const char* sp_matcher_pattern_name( const sp_matcher_t* m, uint32_t handle) { return m->compiler.patterns().key( handle); }
@@ -249,7 +286,7 @@ int sp_matcher_launch_plan( const sp_matcher_t* m, uint32_t ctx_flags, unsigned 
 int sp_matcher_serialize( const sp_matcher_t* m, void** blob, size_t* size)
 { return exportBlob( m->lasterror, blob, size, [&]( std::vector<uint8_t>& buf){ m->compiler.save( buf, m->compiled); }); }
 sp_matcher_t* sp_matcher_deserialize( const void* blob, size_t size, char* err, size_t errsize)
-{ return importBlob<sp_matcher>( err, errsize, [&]( sp_matcher& m){ m.compiled = m.compiler.load( blob, size); }); }
+{ return importBlob<sp_matcher>( err, errsize, [&]( sp_matcher& m){ m.compiled = m.compiler.load( blob, size); m.formats( true); }); }
 
 size_t sp_matcher_dump_table( const sp_matcher_t* m, uint32_t** out)
 {
@@ -545,7 +582,7 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 	const L2LaunchPlan plan = planL2Launch( c->kind, rerun != 0, c->numCUs, c->flat.blocksPerCU, rerun ? rerun->size() : ndocs, ndocs, nlexems,
 						c->exact.layout, &c->flat.plan, c->io.minResults, c->io.minItems);
 	HIP_CHECK( hipSetDevice( c->device));
-	c->fin.run.done = false; c->txt.run.done = false; c->frq.run.done = false;	// (a new batch: what was finished is of the one before)
+	c->fin.run.done = false; c->txt.run.done = false; c->val.run.done = false; c->frq.run.done = false;	// (a new batch: what was finished is of the one before)
 	ensureArena( c, plan);
 	ensureOutput( c, plan, ndocs);
 	resetCursorAndCounters( c, rerun != 0, stream);
@@ -639,7 +676,7 @@ int sp_matcher_ctx_batch_finish_device_ex( sp_matcher_ctx_t* c, void* stream_, u
 		if (!c->haveBatch) throw std::runtime_error( "no batch to finish: no batch has run on this context");
 		hipStream_t stream = (hipStream_t)stream_;
 		HIP_CHECK( hipSetDevice( c->device));
-		c->fin.run.done = false; c->txt.run.done = false; c->frq.run.done = false;
+		c->fin.run.done = false; c->txt.run.done = false; c->val.run.done = false; c->frq.run.done = false;
 		// the buffers are sized from what the batch counted: this read waits for the batch, the passes below do not
 		HIP_CHECK( hipStreamSynchronize( c->lastStream));
 		const BatchCounts counts = readCounts( c);
@@ -869,6 +906,159 @@ int sp_matcher_ctx_finished_text_fetch( sp_matcher_ctx_t* c, sp_match_text_t* ou
 int sp_matcher_ctx_last_text_ms( sp_matcher_ctx_t* c, double* ms) { return c->txt.run.ms( 0, 1, ms); }
 
 uint32_t sp_matcher_text_long_span(void) { return TEXT_LONG_SPAN; }
+
+// ---- the values of the format strings of the finished batch, built on the device (l2_values.h)
+int sp_matcher_ctx_finished_values_device( sp_matcher_ctx_t* c, const sp_text_source_t* src, uint32_t flags, void* stream_, sp_match_values_batch_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (!flags || (flags & ~(uint32_t)(SP_VALUE_RESULTS | SP_VALUE_ITEMS))) throw std::runtime_error( "unknown or no value flags");
+		if (!src || !src->d_seg_offsets || (!src->d_text && src->nbytes)) throw std::runtime_error( "no text source");
+		if (!c->fin.run.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
+		const size_t ndocs = c->lastNdocs;
+		if (!src->d_doc_seg_offsets && src->nseg != ndocs) throw std::runtime_error( "without document segment offsets every document is one segment: nseg must be ndocs");
+		const FormatTable& table = c->inst->formats();
+		if (!table.error.empty()) throw std::runtime_error( table.error);
+		sp_matcher_ctx::Values& v = c->val;
+		hipStream_t stream = (hipStream_t)stream_;
+		HIP_CHECK( hipSetDevice( c->device));
+		v.run.done = v.run.evValid = false;
+		if (!v.uploaded)
+		{
+			// the format table: once per context
+			reserveOrNoMem( v.dFmtParts, (table.fmtParts.size()+1)*sizeof(uint32_t));
+			reserveOrNoMem( v.dParts, (table.parts.size()+1)*sizeof(uint32_t));
+			reserveOrNoMem( v.dPool, table.pool.size()+16);
+			copySync( c->own, v.dFmtParts.ptr, table.fmtParts.data(), table.fmtParts.size()*sizeof(uint32_t), hipMemcpyHostToDevice);
+			if (!table.parts.empty()) copySync( c->own, v.dParts.ptr, table.parts.data(), table.parts.size()*sizeof(uint32_t), hipMemcpyHostToDevice);
+			if (!table.pool.empty()) copySync( c->own, v.dPool.ptr, table.pool.data(), table.pool.size(), hipMemcpyHostToDevice);
+			v.poolBytes = (uint32_t)table.pool.size();
+			v.uploaded = true;
+		}
+		// the value arrays are sized from the totals of the finish: this read waits for it
+		HIP_CHECK( hipStreamSynchronize( c->fin.run.stream));
+		uint64_t records[ 2];
+		copySync( c->own, records, c->fin.dTotals.ptr, sizeof(records), hipMemcpyDeviceToHost);
+		for (int f=0; f<2; ++f) if (flags & (1u << f))
+		{
+			reserveOrNoMem( v.dValueWork[ f], (records[ f]+1)*sizeof(uint32_t));
+			reserveOrNoMem( v.dValueOffsets[ f], (records[ f]+1)*sizeof(uint64_t));
+			reserveOrNoMem( v.dDocBytes[ f], (ndocs+1)*sizeof(uint64_t));
+			reserveOrNoMem( v.dDocValueOffsets[ f], (ndocs+1)*sizeof(uint64_t));
+		}
+		reserveOrNoMem( v.dStatus, (ndocs+1)*sizeof(int32_t));
+		reserveOrNoMem( v.dTotals, 2*sizeof(uint64_t));
+		reserveOrNoMem( v.dCursor, 4*sizeof(uint32_t));
+
+		// another stream than the finish's runs behind the finish
+		v.run.begin( stream, c->fin.run.stream, c->fin.run.ev[ 3]);
+		HIP_CHECK( hipMemsetAsync( v.dCursor.ptr, 0, 4*sizeof(uint32_t), stream));
+		HIP_CHECK( hipMemsetAsync( v.dTotals.ptr, 0, 2*sizeof(uint64_t), stream));
+		HIP_CHECK( hipMemsetAsync( v.dStatus.ptr, 0, (ndocs+1)*sizeof(int32_t), stream));
+		// a matcher without format strings has no format arrays: every value is empty, the passes only lay out the offsets
+		const bool withFormats = c->io.withFormats && table.count;
+		for (int f=0; f<2; ++f) if ((flags & (1u << f)) && !withFormats)
+		{
+			HIP_CHECK( hipMemsetAsync( v.dValueOffsets[ f].ptr, 0, (records[ f]+1)*sizeof(uint64_t), stream));
+		}
+		ValuesParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.text = (const uint8_t*)src->d_text; P.nbytes = src->nbytes;
+		P.segOffsets = (const uint64_t*)src->d_seg_offsets; P.nseg = src->nseg;
+		P.docSegOffsets = (const uint64_t*)src->d_doc_seg_offsets;
+		P.fmtParts = (const uint32_t*)v.dFmtParts.ptr; P.parts = (const uint32_t*)v.dParts.ptr; P.pool = (const uint8_t*)v.dPool.ptr;
+		P.formatCount = table.count; P.poolBytes = v.poolBytes;
+		P.items = (const uint32_t*)c->fin.dItems.ptr; P.itemFormat = (const uint32_t*)c->fin.dItemFormat.ptr;
+		P.docItemOffsets = (const uint64_t*)c->fin.dDocItemOffsets.ptr; P.nitems = records[ 1];
+		P.ndocs = (uint32_t)ndocs; P.docStatus = (int32_t*)v.dStatus.ptr; P.families = withFormats ? flags : 0;
+		for (int f=0; f<2; ++f) if (flags & (1u << f))
+		{
+			ValuesFamily& F = P.family[ f];
+			F.records = (const uint32_t*)(f ? c->fin.dItems.ptr : c->fin.dResults.ptr);
+			F.format = (const uint32_t*)(f ? c->fin.dItemFormat.ptr : c->fin.dResultFormat.ptr);
+			F.docOffsets = (const uint64_t*)(f ? c->fin.dDocItemOffsets.ptr : c->fin.dDocResultOffsets.ptr);
+			F.nrecords = records[ f];
+			F.valueWork = (uint32_t*)v.dValueWork[ f].ptr; F.docBytes = (uint64_t*)v.dDocBytes[ f].ptr;
+			F.docValueOffsets = (uint64_t*)v.dDocValueOffsets[ f].ptr; F.valueOffsets = (uint64_t*)v.dValueOffsets[ f].ptr;
+			F.total = (uint64_t*)v.dTotals.ptr + f; F.cursor = (uint32_t*)v.dCursor.ptr + 2*f;
+		}
+		HIP_CHECK( hipEventRecord( v.run.ev[ 0], stream));
+		HIP_CHECK( launchL2ValuesCount( P, c->numCUs, stream));
+		// the value buffers are sized from what the passes counted: this read waits for them, the placement below is not waited for
+		HIP_CHECK( hipStreamSynchronize( stream));
+		uint64_t totals[ 2];
+		copySync( c->own, totals, v.dTotals.ptr, sizeof(totals), hipMemcpyDeviceToHost);
+		for (int f=0; f<2; ++f) if (flags & (1u << f))
+		{
+			reserveOrNoMem( v.dValues[ f], totals[ f] + 16);
+			P.family[ f].outValues = (uint8_t*)v.dValues[ f].ptr; P.family[ f].outCapacity = totals[ f];
+		}
+		HIP_CHECK( launchL2ValuesPlace( P, c->numCUs, stream));
+		HIP_CHECK( hipEventRecord( v.run.ev[ 1], stream));
+		v.run.completed( stream); v.flags = flags; v.ndocs = ndocs;
+		for (int f=0; f<2; ++f) { v.nrecords[ f] = records[ f]; v.totals[ f] = (flags & (1u << f)) ? totals[ f] : 0; }
+		if (out)
+		{
+			out->ndocs = ndocs;
+			if (flags & SP_VALUE_RESULTS) { out->d_result_values = v.dValues[ 0].ptr; out->d_result_value_offsets = v.dValueOffsets[ 0].ptr; }
+			if (flags & SP_VALUE_ITEMS) { out->d_item_values = v.dValues[ 1].ptr; out->d_item_value_offsets = v.dValueOffsets[ 1].ptr; }
+			out->d_doc_value_status = v.dStatus.ptr; out->d_totals = v.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the value buffers
+int sp_matcher_ctx_finished_values_fetch( sp_matcher_ctx_t* c, sp_match_values_t* out)
+{
+	std::memset( out, 0, sizeof(*out));
+	const int rc = guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		const sp_matcher_ctx::Values& v = c->val;
+		if (!v.run.done) throw std::runtime_error( "no values of the last batch of this context (sp_matcher_ctx_finished_values_device)");
+		HIP_CHECK( hipSetDevice( c->device));
+		HIP_CHECK( hipStreamSynchronize( v.run.stream));
+		allocMatchValues( out, v.ndocs, v.nrecords[ 0], v.nrecords[ 1], v.flags);
+		out->totals[ 0] = v.totals[ 0]; out->totals[ 1] = v.totals[ 1];
+		allocMatchValuesBytes( out, v.flags);
+		if (v.ndocs) copySync( c->own, out->doc_value_status, v.dStatus.ptr, v.ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+		char* const bytes[ 2] = {out->result_values, out->item_values};
+		uint64_t* const offsets[ 2] = {out->result_value_offsets, out->item_value_offsets};
+		for (int f=0; f<2; ++f) if (v.flags & (1u << f))
+		{
+			copySync( c->own, offsets[ f], v.dValueOffsets[ f].ptr, (v.nrecords[ f]+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+			if (v.totals[ f]) copySync( c->own, bytes[ f], v.dValues[ f].ptr, v.totals[ f], hipMemcpyDeviceToHost);
+		}
+	});
+	if (rc != SP_OK) sp_match_values_free( out);
+	return rc;
+}
+
+// duration of the passes of the last values call in milliseconds (HIP events on its stream)
+int sp_matcher_ctx_last_values_ms( sp_matcher_ctx_t* c, double* ms) { return c->val.run.ms( 0, 1, ms); }
+
+uint32_t sp_matcher_value_max_depth(void) { return VALUE_MAX_DEPTH; }
+
+// the same rule over host arrays (result_values.hpp)
+int sp_match_batch_values( const sp_matcher_t* m, const sp_match_batch_t* mb, const char* text, uint64_t nbytes, const uint64_t* seg_offsets,
+			   size_t nseg, const uint64_t* doc_seg_offsets, uint32_t flags, sp_match_values_t* out, char* err, size_t errsize)
+{
+	std::memset( out, 0, sizeof(*out));
+	copyText( err, errsize, "");
+	try
+	{
+		if (!m) throw std::runtime_error( "no matcher");
+		if (!mb) throw std::runtime_error( "no batch");
+		const TextSource S = { text, nbytes, seg_offsets, nseg, doc_seg_offsets };
+		matchBatchValues( m->formats(), *mb, S, flags, out);
+		return SP_OK;
+	}
+	catch (const std::bad_alloc&) { sp_match_values_free( out); return SP_ERR_NOMEM; }
+	catch (const std::exception& e)
+	{
+		sp_match_values_free( out);
+		copyText( err, errsize, e.what());
+		return SP_ERR_INVALID;
+	}
+}
 
 // ---- the pattern frequencies of the finished batch, summed on the device (l2_freq.h)
 int sp_matcher_ctx_finished_pattern_freq_device( sp_matcher_ctx_t* c, void* stream_, sp_pattern_freq_device_t* out)

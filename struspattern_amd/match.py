@@ -2,7 +2,7 @@
 through the MI355X lexer + rule automaton, print tokens (-K) and results in the reference tool's
 listing format (doc/webpage/introduction_struspattern.htm:178-260).
 
-    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] file [file ...]
+    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] file [file ...]
 
 Every file is one document (plain UTF-8 text; the reference tool segments XML with strusAnalyzer's
 segmenters, which are outside this engine -- pass -o to add the offset of the text inside its original
@@ -12,7 +12,9 @@ the document on the GPU, and positions are printed through the segment position 
 (`segmentposmap[seg] + ofs`, as the reference's printResults does; -o adds on top).  With --frequencies the
 listing of a file is followed by one line per pattern that matched in it, ascending by pattern handle:
 `frequency NAME: count N first ORDPOS last ORDEND` -- how often, the first ordinal position a match starts at
-and the last one a match ends at, summed on the GPU (finishedPatternFreqDevice).  All files go to the
+and the last one a match ends at, summed on the GPU (finishedPatternFreqDevice).  With --device-values the values of
+the format strings in the listing are built on the GPU (finishedValuesDevice) instead of resultformat.Formatter; the listing
+is the same.  All files go to the
 GPU as one batch.  There is no CPU fallback.
 """
 import argparse
@@ -31,6 +33,7 @@ def main(argv=None):
     ap.add_argument("-o", "--origin", type=int, default=0, help="offset added to the printed byte positions")
     ap.add_argument("--paragraphs", action="store_true", help="every file is a document whose segments are its paragraphs")
     ap.add_argument("--frequencies", action="store_true", help="after the listing of a file, one line per pattern that matched in it")
+    ap.add_argument("--device-values", action="store_true", help="the values of the format strings are built on the device")
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("files", nargs="+")
     args = ap.parse_args(argv)
@@ -53,6 +56,7 @@ def main(argv=None):
     lb = lx.createContext(args.device).matchDocs(text, offs)
     mctx = mt.createContext(args.device)
     mb = mctx.matchDocs(lb.lexems, lb.doc_offsets)
+    values = device_values(mctx, text, offs) if args.device_values else None
     freq = frequencies(mctx) if args.frequencies else None
     for di, fn in enumerate(args.files):
         print("%s:" % fn)
@@ -63,11 +67,25 @@ def main(argv=None):
         res = mb.doc(di)
         for line in rulelang.format_results(doc, res, mb.items, mt.patternName, mt.variableName, origin=args.origin,
                                             result_format=mb.result_format, item_format=mb.item_format, format_string=mt.formatString,
-                                            first_result=int(mb.doc_offsets[di])):
+                                            first_result=int(mb.doc_offsets[di]), values=values):
             print(line)
         print_frequencies(freq, di, mt)
     print("OK done")
     return 0
+
+
+def device_values(mctx, text, offs):
+    """--device-values: the last batch of the context finished on the device and the values of its format strings built
+    there; every document is one segment of `text`"""
+    import torch
+    d_text = torch.frombuffer(bytearray(text + b"\0" * 16), dtype=torch.uint8).cuda()
+    d_so = torch.from_numpy(np.ascontiguousarray(offs, dtype=np.uint64).view(np.int64)).cuda()
+    mctx.batchFinishDevice()
+    mctx.finishedValuesDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), len(offs) - 1)
+    values = mctx.finishedValuesFetch()
+    if np.any(values.status != 0):
+        raise spa.PatternError("no values of document %d: status %d" % (int(np.flatnonzero(values.status)[0]), int(values.status.max())))
+    return values
 
 
 def frequencies(mctx):
@@ -91,7 +109,11 @@ def paragraphs(args, prg, lx, mt, docs):
     text, seg_offsets, doc_seg_offsets, posmaps = segments.segmented_batch(docs)
     lctx = lx.createContext(args.device)
     mctx = mt.createContext(args.device)
-    mb = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets)
+    values = None
+    if args.device_values:
+        mb, values = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_values=True)
+    else:
+        mb = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets)
     if np.any(mb.status != 0):
         bad = int(np.flatnonzero(mb.status)[0])
         raise spa.PatternError("at least one document failed: %s has status %d" % (args.files[bad], int(mb.status[bad])))
@@ -113,7 +135,7 @@ def paragraphs(args, prg, lx, mt, docs):
             items[ia:ib] = segments.absolute_records(mb.items[ia:ib], posmap)
         for line in rulelang.format_results(doc, res, items, mt.patternName, mt.variableName, origin=args.origin,
                                             result_format=mb.result_format, item_format=mb.item_format, format_string=mt.formatString,
-                                            first_result=int(mb.doc_offsets[di])):
+                                            first_result=int(mb.doc_offsets[di]), values=values):
             print(line)
         print_frequencies(freq, di, mt)
     print("OK done")

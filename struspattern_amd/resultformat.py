@@ -122,3 +122,32 @@ class Formatter:
             else:
                 out.append(Result(self.pattern_name(int(r[0])), None, r[1:7], lst))
         return out
+
+
+class DeviceValues(Formatter):
+    """Formatter whose values are not evaluated here but taken from a MatchValues of the batch (built on the device by
+    finishedValuesDevice, or by batchValues): `items` / `item_format` are the whole arrays of the batch, `results` its rows
+    first_result.. ."""
+
+    def __init__(self, pattern_name, variable_name, values, first_result=0):
+        Formatter.__init__(self, pattern_name, variable_name, None)
+        self.values, self.first_result = values, first_result
+
+    def gather(self, items, item_format, begin, end, src):
+        out, i = [], begin
+        while i < end:
+            fmt, nsub = int(item_format[i][0]), int(item_format[i][1])
+            value = self.values.item(i).decode("utf-8", "replace") if fmt else None
+            out.append(Item(self.variable_name(int(items[i][0])), value, items[i][1:7]))
+            i += 1 + (nsub if fmt else 0)
+        return out
+
+    def results(self, results, items, result_format, item_format, src):
+        out = []
+        for ri, r in enumerate(results):
+            ib, ic = int(r[7]), int(r[8])
+            if int(result_format[ri]):
+                out.append(Result(self.pattern_name(int(r[0])), self.values.result(self.first_result + ri).decode("utf-8", "replace"), r[1:7], []))
+            else:
+                out.append(Result(self.pattern_name(int(r[0])), None, r[1:7], self.gather(items, item_format, ib, ib + ic, src)))
+        return out

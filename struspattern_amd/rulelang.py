@@ -295,13 +295,14 @@ def format_tokens(prg, text, lexems, origin=0):
     return out
 
 
-def format_results(text, results, items, pattern_name, variable_name, origin=0, result_format=None, item_format=None, format_string=None, first_result=0):
+def format_results(text, results, items, pattern_name, variable_name, origin=0, result_format=None, item_format=None, format_string=None, first_result=0, values=None):
     """The result listing of strusPatternMatch: "Name [ordpos, origpos]: var [ordpos, origpos, size] 'text' ...".
     With format strings (result_format / item_format of the batch, `results` = rows first_result.. of it) a
-    result or item that has a value prints it instead of the text it covers."""
+    result or item that has a value prints it instead of the text it covers; `values` (a MatchValues of the batch) gives
+    the values instead of resultformat.Formatter."""
     if result_format is not None:
         from . import resultformat
-        fm = resultformat.Formatter(pattern_name, variable_name, format_string)
+        fm = resultformat.Formatter(pattern_name, variable_name, format_string) if values is None else resultformat.DeviceValues(pattern_name, variable_name, values, first_result)
         out = []
         for r in fm.results(results, items, result_format[first_result:first_result + len(results)], item_format, text):
             parts = ["%s [%d, %d, %d] '%s'" % (i.name, i.ordpos, i.origpos + origin, i.origend - i.origpos, i.value if i.value is not None else i.text(text)) for i in r.items]
