@@ -555,6 +555,109 @@ uint32_t sp_matcher_pattern_freq_window(void);
  * ascend or do not cover nresults. */
 int sp_match_batch_pattern_freq(const sp_match_batch_t* mb, uint32_t handle_bound, sp_pattern_freq_batch_t* out,
                                 char* err, size_t errsize);
+
+/* ---- index terms: per document the distinct pairs (pattern, value) of its results -- the entries an inverted index stores
+ * for a document, with the term frequency and the first position, and the way from every occurrence to its term; grouped on
+ * the device (csrc/l2_terms.h) or, for a batch already fetched, on the host (csrc/match_terms.hpp).  The rule is the project's
+ * own, unpinned by a reference vector (the reference has no such call).
+ * The input is the batch finished last on a context, `exclusive` applied, in finished order (plain or canonical).  Every
+ * result r has a TERM VALUE, chosen by `flags`:
+ *   SP_TERM_VALUES  the bytes [result_value_offsets[r], result_value_offsets[r+1]) of the values batch built on this context
+ *                   for this finished batch with SP_VALUE_RESULTS; an unformatted result has the empty value;
+ *   SP_TERM_TEXT    the result's range [result_text_offsets[r], result_text_offsets[r+1]) of the text batch built on this
+ *                   context for this finished batch with SP_TEXT_RESULTS;
+ *   both            the value where result_format[r] != 0, else the text (a batch without format arrays: the text).
+ * Two results of a document are the SAME TERM iff their handles are equal and their term values are equal byte strings: the
+ * same length and the same bytes.  An empty value is a value; the same bytes under two handles are two terms.  Valid handles
+ * are those of the frequency rule above: 1 <= handle < handle_bound.
+ * A document d FAILS -- term status SP_DOC_ERR_RANGE, no records, all its result_term entries 0xFFFFFFFF, the other documents
+ * not affected -- when a source that `flags` selects (both of them with both flags) has a non-zero value or text status for
+ * d, or when one of its results has a handle outside [1, handle_bound).  A document that the matcher failed, or one without
+ * results, has no records and term status 0 (results that a hand-made batch gives to a document with a matcher status keep
+ * the result_term 0xFFFFFFFF).  Every other document has one record per distinct term:
+ *   handle, count (its results with this term), first_ordpos (the minimum of their ordpos, unsigned), last_ordend (the
+ *   maximum of their ordend), first_result (the smallest index, counted from the start of d's finished block, of a result
+ *   with this term: the range of THAT result in the selected source is the term's bytes -- a term owns no bytes of its
+ *   own), value_bytes (the length of the term value).
+ * The records of d are ascending by handle, then by first_result; the terms of one handle are contiguous.  INVARIANT: the
+ * sum of `count`, the minimum of `first_ordpos` and the maximum of `last_ordend` over the terms of a handle are that
+ * handle's sp_pattern_freq_t of the same document, and the handles that occur are the same.
+ *   doc_term_offsets[ndocs+1]  the record range of every document,          totals[0]  the number of records,
+ *   result_term[nresults]      parallel to the finished results: the index of the result's term inside its document's
+ *                              block of records (a posting list is a gather through it),
+ *   doc_term_status[ndocs]     0 or SP_DOC_ERR_RANGE.
+ * count, first_ordpos, last_ordend and value_bytes depend on the results only; first_result, result_term and the order
+ * inside a handle follow the finished order.  After a canonical finish the whole batch is a function of the results alone:
+ * the exact engines and result-set mode leave the same bytes.  A hash only chooses where the device looks for a term; two
+ * results are one term only after their bytes were compared (sp_test_term_hash_bits).  No byte outside the outputs is written,
+ * no record at or beyond the finished total and no source byte outside the source's total read, whatever the records hold.
+ * The dictionary of the whole batch (the distinct terms across documents with their document frequency) is NOT built: the
+ * per-handle sums of the frequency pass stay what the batch offers. */
+#define SP_TERM_VALUES 1u
+#define SP_TERM_TEXT   2u
+typedef struct sp_match_term {
+	uint32_t handle;
+	uint32_t count;         /* results of d with this term */
+	uint32_t first_ordpos;  /* minimum of their ordpos, unsigned */
+	uint32_t last_ordend;   /* maximum of their ordend */
+	uint32_t first_result;  /* smallest index, inside d's finished block, of a result with this term:
+	                           its value range in the selected source IS the term's bytes */
+	uint32_t value_bytes;   /* length of the term value */
+} sp_match_term_t;
+typedef struct sp_match_terms_device {
+	size_t ndocs;
+	uint32_t handle_bound;
+	uint32_t flags;
+	void* d_records;             /* sp_match_term_t[]: document 0's records first */
+	void* d_doc_term_offsets;    /* uint64_t[ndocs+1] */
+	void* d_result_term;         /* uint32_t[nresults], parallel to the finished d_results */
+	void* d_doc_term_status;     /* int32_t[ndocs]: 0 or SP_DOC_ERR_RANGE */
+	void* d_totals;              /* uint64_t[1]: records */
+} sp_match_terms_device_t;
+/* host copy of a terms batch (sp_match_terms_free) */
+typedef struct sp_match_terms {
+	size_t ndocs;
+	size_t nresults;
+	size_t nrecords;
+	uint32_t handle_bound;
+	uint32_t flags;
+	sp_match_term_t* records;
+	uint64_t* doc_term_offsets;   /* ndocs+1 */
+	uint32_t* result_term;        /* nresults */
+	int32_t* doc_term_status;     /* ndocs */
+	uint64_t totals[1];           /* records */
+} sp_match_terms_t;
+/* Groups the results of the batch finished last on this context into terms.  flags: SP_TERM_VALUES | SP_TERM_TEXT; a source
+ * that is selected must have been built on this context since that finish WITH its results family
+ * (sp_matcher_ctx_finished_values_device with SP_VALUE_RESULTS, sp_matcher_ctx_finished_text_device with SP_TEXT_RESULTS): the
+ * terms point into its buffers, so they are valid as long as those are.  Passes on `stream` (count, offsets, place:
+ * csrc/l2_terms.h); the call enqueues count and offsets, waits for them only to read the total, sizes the records, enqueues
+ * the placement and returns.  The buffers belong to the context, are allocated at the first call, only grow, and are valid
+ * until the next terms call; the next batch or finish invalidates the state, not the buffers.  A `stream` other than the
+ * one of the finish, the values call or the text call is ordered behind each of them with an event (their placements are
+ * not waited for by their own calls).  SP_ERR_INVALID when the last batch is not finished, for flags 0 or unknown bits, and
+ * when a selected source was not built since that finish or was built without the results family; SP_ERR_NOMEM when a
+ * buffer cannot be allocated (the context stays usable). */
+int sp_matcher_ctx_finished_terms_device(sp_matcher_ctx_t* c, uint32_t flags, void* stream, sp_match_terms_device_t* out);
+/* plain copy of the buffers of the last sp_matcher_ctx_finished_terms_device to the host (waits for it) */
+int sp_matcher_ctx_finished_terms_fetch(sp_matcher_ctx_t* c, sp_match_terms_t* out);
+void sp_match_terms_free(sp_match_terms_t* t);
+/* duration of all passes of the last terms call in milliseconds (HIP events on its stream round them; waits for them; the
+ * host's wait for the total between offsets and place lies inside) */
+int sp_matcher_ctx_last_terms_ms(sp_matcher_ctx_t* c, double* ms);
+/* diagnostics and tests: the largest number of results of one document whose terms the device finds in a table in LDS; a
+ * larger document uses working memory in HBM */
+uint32_t sp_matcher_term_tile(void);
+/* test hook (tests only): the device keeps only the low `bits` bits of the hash of a term (32 and more: all of them, the
+ * default; 0: every term collides with every other).  The outputs do not change by a bit. */
+void sp_test_term_hash_bits(unsigned bits);
+/* The same rule over host arrays, needs no device, and the yardstick of the device passes: the terms of a batch already
+ * fetched, with the host copies of its values (their results family, for SP_TERM_VALUES) and of its text (for SP_TERM_TEXT).
+ * Fills `out` (sp_match_terms_free); SP_ERR_INVALID with the message in `err` for flags 0 or unknown bits, a NULL source or
+ * one without its results family where `flags` selects it, sources whose ndocs or nresults are not those of `mb`, a bound
+ * of 0, and offsets (of the documents or of a selected source) that do not ascend or do not cover their total. */
+int sp_match_batch_terms(const sp_match_batch_t* mb, const sp_match_values_t* values, const sp_match_text_t* text,
+                         uint32_t handle_bound, uint32_t flags, sp_match_terms_t* out, char* err, size_t errsize);
 /* copies the results of the last device batch to the host, grouped by document (as sp_matcher_ctx_match_docs
  * returns them, `exclusive` elimination included) */
 int sp_matcher_ctx_batch_fetch(sp_matcher_ctx_t* c, sp_match_batch_t* out);

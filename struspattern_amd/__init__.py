@@ -13,12 +13,13 @@ from . import capi
 from .capi import SpLexem, SpResult, SpResultItem
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
-           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq"]
+           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
 SP_TEXT_RESULTS, SP_TEXT_ITEMS = 1, 2   # include/strus_pattern_amd.h: the families of spans of a text call
 SP_VALUE_RESULTS, SP_VALUE_ITEMS = 1, 2  # include/strus_pattern_amd.h: the families of records of a values call
+SP_TERM_VALUES, SP_TERM_TEXT = 1, 2    # include/strus_pattern_amd.h: the sources of the term values of a terms call
 SP_ERR_UNAVAILABLE = -6     # include/strus_pattern_amd.h: a value that does not exist for the context
 
 JOIN_OP = {"sequence": 0, "sequence_imm": 1, "sequence_struct": 2, "within": 3, "within_struct": 4, "any": 5, "and": 6}
@@ -242,6 +243,97 @@ def batchPatternFreq(mb, handle_bound):
         L.sp_pattern_freq_batch_free(ctypes.byref(f))
 
 
+class MatchTerms:
+    """The index terms of a finished batch (host copies): per document one record per distinct pair (handle, value bytes),
+    ascending by handle, then by first_result, and per result the index of its term inside its document's block
+    (include/strus_pattern_amd.h "index terms").  A term owns no bytes: its value is the range of its first result in the
+    values or the text it was built from."""
+
+    def __init__(self, records, doc_offsets, result_term, status, flags=SP_TERM_VALUES | SP_TERM_TEXT):
+        self.records = records          # (n, 6) u32: handle, count, first_ordpos, last_ordend, first_result, value_bytes
+        self.doc_offsets = doc_offsets  # (ndocs+1,) u64
+        self.result_term = result_term  # (nresults,) u32, 0xFFFFFFFF throughout a failed document
+        self.status = status            # (ndocs,) i32: 0, or 5 for a failed document (no records)
+        self.flags = flags
+
+    def doc(self, i):
+        return self.records[int(self.doc_offsets[i]):int(self.doc_offsets[i + 1])]
+
+    def terms(self, d, mb, values=None, text=None):
+        """yields (handle, value bytes, count, first_ordpos, last_ordend) per term of document d; mb: the finished batch,
+        values / text: the MatchValues / MatchText the terms were built from"""
+        first = int(mb.doc_offsets[d])
+        for h, count, pos, end, fr, size in self.doc(d).tolist():
+            r = first + fr
+            use_text = not (self.flags & SP_TERM_VALUES)
+            if self.flags == (SP_TERM_VALUES | SP_TERM_TEXT):
+                use_text = mb.result_format is None or int(mb.result_format[r]) == 0
+            value = text.result(r) if use_text else values.result(r)
+            assert len(value) == size
+            yield h, value, count, pos, end
+
+
+def _match_terms_of(t):
+    """the MatchTerms of a capi.SpMatchTerms (copies)"""
+    return MatchTerms(_rows(t.records, t.nrecords, 6), _rows(t.doc_term_offsets, t.ndocs + 1, 0, ctypes.c_uint64),
+                      _rows(t.result_term, t.nresults, 0), _rows(t.doc_term_status, t.ndocs, 0, ctypes.c_int32), t.flags)
+
+
+def batchTerms(mb, values=None, text=None, handle_bound=0, flags=SP_TERM_VALUES | SP_TERM_TEXT):
+    """The index terms of a batch already on the host (a MatchBatch in document order: finishedFetch, batchFetch, matchDocs)
+    with its MatchValues and / or MatchText (their results family), by the rule of the device call, without a device.
+    handle_bound: PatternMatcherInstance.handleBound().  Returns a MatchTerms."""
+    L = capi.lib()
+    res = np.ascontiguousarray(mb.results, dtype=np.uint32).reshape(-1, 9)
+    offs = np.ascontiguousarray(mb.doc_offsets, dtype=np.uint64)
+    status = None if mb.status is None else np.ascontiguousarray(mb.status, dtype=np.int32)
+    keep = [res, offs, status]
+    b = capi.SpMatchBatch()
+    b.ndocs, b.nresults = len(offs) - 1, len(res)
+    b.results = ctypes.cast(res.ctypes.data, ctypes.POINTER(SpResult))
+    b.doc_result_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
+    if status is not None:
+        b.doc_status = ctypes.cast(status.ctypes.data, ctypes.POINTER(ctypes.c_int32))
+    if mb.result_format is not None:
+        rf = np.ascontiguousarray(mb.result_format, dtype=np.uint32).reshape(-1)
+        if len(rf) != len(res):
+            raise PatternError("format array of the batch is not parallel to its results")
+        keep.append(rf)
+        b.result_format = ctypes.cast(rf.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
+
+    def source(cls, family, names):
+        """the C struct of a MatchValues / MatchText: its results family only"""
+        if family is None:
+            return None
+        c = cls()
+        c.ndocs, c.nresults = len(family.status), (len(family.result_offsets) - 1 if family.result_offsets is not None else 0)
+        st = np.ascontiguousarray(family.status, dtype=np.int32)
+        keep.append(st)
+        setattr(c, names[2], ctypes.cast(st.ctypes.data, ctypes.POINTER(ctypes.c_int32)))
+        if family.result_offsets is not None:
+            data = bytes(getattr(family, names[3]))
+            ro = np.ascontiguousarray(family.result_offsets, dtype=np.uint64)
+            buf = ctypes.create_string_buffer(data, len(data) + 1)
+            keep.extend([ro, buf])
+            setattr(c, names[0], ctypes.cast(buf, ctypes.POINTER(ctypes.c_uint8)))
+            setattr(c, names[1], ctypes.cast(ro.ctypes.data, ctypes.POINTER(ctypes.c_uint64)))
+            c.totals[0] = len(data)
+        return c
+
+    v = source(capi.SpMatchValues, values, ("result_values", "result_value_offsets", "doc_value_status", "result_values"))
+    x = source(capi.SpMatchText, text, ("result_text", "result_text_offsets", "doc_text_status", "result_text"))
+    t = capi.SpMatchTerms()
+    err = ctypes.create_string_buffer(256)
+    rc = L.sp_match_batch_terms(ctypes.byref(b), ctypes.byref(v) if v is not None else None, ctypes.byref(x) if x is not None else None,
+                                handle_bound, flags, ctypes.byref(t), err, 256)
+    try:
+        if rc != 0:
+            raise PatternError("no terms of the batch (%d): %s" % (rc, err.value.decode()))
+        return _match_terms_of(t)
+    finally:
+        L.sp_match_terms_free(ctypes.byref(t))
+
+
 class PatternMatcherContext:
     """PatternMatcherContextInterface (src/patternMatcher.cpp:107-341) + batch mode."""
 
@@ -456,6 +548,36 @@ class PatternMatcherContext:
         a = ctypes.c_double(-1.0)
         if self._L.sp_matcher_ctx_last_pattern_freq_ms(self._h, ctypes.byref(a)) != 0:
             raise PatternError("no timed pattern frequency call")
+        return a.value
+
+    def finishedTermsDevice(self, flags=SP_TERM_VALUES | SP_TERM_TEXT, stream=0):
+        """group the results of the batch finished by batchFinishDevice into index terms on the device (the placement is
+        asynchronous on `stream`): per document one record per distinct (handle, value), per result the index of its term.
+        flags: SP_TERM_VALUES (finishedValuesDevice has run since the finish, with the results family), SP_TERM_TEXT
+        (finishedTextDevice has, with results=True), or both.  Returns the device pointers (capi.SpMatchTermsDevice), valid
+        until the next call."""
+        out = capi.SpMatchTermsDevice()
+        rc = self._L.sp_matcher_ctx_finished_terms_device(self._h, flags, stream or None, ctypes.byref(out))
+        if rc != 0:
+            raise PatternError("grouping the terms of the batch on the device failed (%d): %s" % (rc, self._err()))
+        return out
+
+    def finishedTermsFetch(self):
+        """plain host copy of the terms grouped by finishedTermsDevice: a MatchTerms"""
+        t = capi.SpMatchTerms()
+        rc = self._L.sp_matcher_ctx_finished_terms_fetch(self._h, ctypes.byref(t))
+        try:
+            if rc != 0:
+                raise PatternError("fetching the terms of the batch failed (%d): %s" % (rc, self._err()))
+            return _match_terms_of(t)
+        finally:
+            self._L.sp_match_terms_free(ctypes.byref(t))
+
+    def lastTermsMs(self):
+        """duration of the passes of the last finishedTermsDevice in milliseconds"""
+        a = ctypes.c_double(-1.0)
+        if self._L.sp_matcher_ctx_last_terms_ms(self._h, ctypes.byref(a)) != 0:
+            raise PatternError("no timed terms call")
         return a.value
 
     def batchFetch(self, first_doc=None, ndocs=None):
@@ -931,14 +1053,17 @@ class PatternLexer:
         return "std"
 
 
-def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False):
+def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False, with_terms=False):
     """Segmented documents, host buffers in and out: `text` holds the segments back to back (seg_offsets: nseg+1 byte
     offsets), document d consists of the segments [doc_seg_offsets[d], doc_seg_offsets[d+1]).  Lexer -> stitch on the
     device -> rule matcher -> fetch; only the text goes up and the results come down.  Returns the MatchBatch, whose
     status of a document is the stitch's where that is not 0 (a failed segment, a bad segment range), else the matcher's.
     with_text: the batch is finished on the device and the text its results and items cover gathered there; returns
     (MatchBatch, MatchText).  with_values: the values of the format strings are built there too; returns
-    (MatchBatch, MatchValues), or (MatchBatch, MatchText, MatchValues) with both."""
+    (MatchBatch, MatchValues), or (MatchBatch, MatchText, MatchValues) with both.  with_terms: the results are grouped into
+    index terms there (value where a result has a format, else text: text and values are built for it); returns
+    (MatchBatch, MatchText, MatchValues, MatchTerms)."""
+    with_text, with_values = with_text or with_terms, with_values or with_terms
     import torch
     text = bytes(text)
     seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
@@ -971,14 +1096,17 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
             mctx.finishedTextDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), nseg, d_dso.data_ptr(), stream=stream)
         if with_values:
             mctx.finishedValuesDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), nseg, d_dso.data_ptr(), stream=stream)
+        if with_terms:
+            mctx.finishedTermsDevice(stream=stream)
         mb = mctx.finishedFetch()
         mt = mctx.finishedTextFetch() if with_text else None
         mv = mctx.finishedValuesFetch() if with_values else None
+        mterms = mctx.finishedTermsFetch() if with_terms else None
     else:
         mb = mctx.batchFetch()
     stitch_status = lctx.stitchedStatus()
     mb.status = np.where(stitch_status != 0, stitch_status, mb.status).astype(np.int32)
-    out = (mb,) + ((mt,) if with_text else ()) + ((mv,) if with_values else ())
+    out = (mb,) + ((mt,) if with_text else ()) + ((mv,) if with_values else ()) + ((mterms,) if with_terms else ())
     return out if len(out) > 1 else mb
 
 

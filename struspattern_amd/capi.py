@@ -122,6 +122,25 @@ class SpPatternFreqBatch(ctypes.Structure):
     ]
 
 
+class SpMatchTerm(ctypes.Structure):
+    _fields_ = [(n, c_u32) for n in ("handle", "count", "first_ordpos", "last_ordend", "first_result", "value_bytes")]
+
+
+class SpMatchTermsDevice(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("handle_bound", c_u32), ("flags", c_u32), ("d_records", c_vp), ("d_doc_term_offsets", c_vp),
+        ("d_result_term", c_vp), ("d_doc_term_status", c_vp), ("d_totals", c_vp),
+    ]
+
+
+class SpMatchTerms(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("nresults", ctypes.c_size_t), ("nrecords", ctypes.c_size_t), ("handle_bound", c_u32), ("flags", c_u32),
+        ("records", P(SpMatchTerm)), ("doc_term_offsets", P(c_u64)), ("result_term", P(c_u32)), ("doc_term_status", P(ctypes.c_int32)),
+        ("totals", c_u64 * 1),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/strus_pattern_amd.h
 SIGNATURES = {
     "sp_version": (c_cp, []),
@@ -195,6 +214,13 @@ SIGNATURES = {
     "sp_matcher_ctx_last_pattern_freq_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
     "sp_matcher_pattern_freq_window": (c_u32, []),
     "sp_match_batch_pattern_freq": (ctypes.c_int, [P(SpMatchBatch), c_u32, P(SpPatternFreqBatch), ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_matcher_ctx_finished_terms_device": (ctypes.c_int, [c_vp, c_u32, c_vp, P(SpMatchTermsDevice)]),
+    "sp_matcher_ctx_finished_terms_fetch": (ctypes.c_int, [c_vp, P(SpMatchTerms)]),
+    "sp_match_terms_free": (None, [P(SpMatchTerms)]),
+    "sp_matcher_ctx_last_terms_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_matcher_term_tile": (c_u32, []),
+    "sp_test_term_hash_bits": (None, [ctypes.c_uint]),
+    "sp_match_batch_terms": (ctypes.c_int, [P(SpMatchBatch), P(SpMatchValues), P(SpMatchText), c_u32, c_u32, P(SpMatchTerms), ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_ctx_batch_counters": (ctypes.c_int, [c_vp, P(c_u64)]),
     "sp_matcher_ctx_last_kernel_ms": (ctypes.c_double, [c_vp]),
     "sp_matcher_ctx_kernel_kind": (ctypes.c_int, [c_vp]),

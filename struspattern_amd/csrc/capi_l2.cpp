@@ -5,6 +5,8 @@
 #include "l2_text.h"
 #include "l2_freq.h"
 #include "l2_values.h"
+#include "l2_terms.h"
+#include "match_terms.hpp"
 #include "span_text.hpp"
 #include "result_values.hpp"
 #include "pattern_freq.hpp"
@@ -170,6 +172,15 @@ struct sp_matcher_ctx
 		uint32_t handleBound = 0;
 		uint64_t total = 0;
 	} frq;
+	// the index terms of the last finished batch (l2_terms.h); nothing is allocated before the first sp_matcher_ctx_finished_terms_device
+	struct Terms
+	{
+		PassRun<2> run;
+		DeviceBuffer dRecords, dDocOffsets, dResultTerm, dStatus, dTotals, dLeader, dTable, dHistogram, dDocCount, dCursor;
+		size_t ndocs = 0;
+		uint32_t handleBound = 0, flags = 0;
+		uint64_t nresults = 0, total = 0;
+	} trm;
 	// single-document mode
 	struct SingleDoc
 	{
@@ -582,7 +593,7 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 	const L2LaunchPlan plan = planL2Launch( c->kind, rerun != 0, c->numCUs, c->flat.blocksPerCU, rerun ? rerun->size() : ndocs, ndocs, nlexems,
 						c->exact.layout, &c->flat.plan, c->io.minResults, c->io.minItems);
 	HIP_CHECK( hipSetDevice( c->device));
-	c->fin.run.done = false; c->txt.run.done = false; c->val.run.done = false; c->frq.run.done = false;	// (a new batch: what was finished is of the one before)
+	c->fin.run.done = false; c->txt.run.done = false; c->val.run.done = false; c->frq.run.done = false; c->trm.run.done = false;	// (a new batch: what was finished is of the one before)
 	ensureArena( c, plan);
 	ensureOutput( c, plan, ndocs);
 	resetCursorAndCounters( c, rerun != 0, stream);
@@ -676,7 +687,7 @@ int sp_matcher_ctx_batch_finish_device_ex( sp_matcher_ctx_t* c, void* stream_, u
 		if (!c->haveBatch) throw std::runtime_error( "no batch to finish: no batch has run on this context");
 		hipStream_t stream = (hipStream_t)stream_;
 		HIP_CHECK( hipSetDevice( c->device));
-		c->fin.run.done = false; c->txt.run.done = false; c->val.run.done = false; c->frq.run.done = false;
+		c->fin.run.done = false; c->txt.run.done = false; c->val.run.done = false; c->frq.run.done = false; c->trm.run.done = false;
 		// the buffers are sized from what the batch counted: this read waits for the batch, the passes below do not
 		HIP_CHECK( hipStreamSynchronize( c->lastStream));
 		const BatchCounts counts = readCounts( c);
@@ -1145,6 +1156,124 @@ int sp_matcher_ctx_finished_pattern_freq_fetch( sp_matcher_ctx_t* c, sp_pattern_
 int sp_matcher_ctx_last_pattern_freq_ms( sp_matcher_ctx_t* c, double* ms) { return c->frq.run.ms( 0, 1, ms); }
 
 uint32_t sp_matcher_pattern_freq_window(void) { return FREQ_WINDOW; }
+
+// ---- the index terms of the finished batch, grouped on the device (l2_terms.h)
+namespace {
+// test hook: the bits of a term's hash that the device keeps (32 and more = all)
+std::atomic<unsigned>& termHashBits() { static std::atomic<unsigned> bits( 32); return bits; }
+}
+
+void sp_test_term_hash_bits( unsigned bits) { termHashBits().store( bits, std::memory_order_relaxed); }
+
+int sp_matcher_ctx_finished_terms_device( sp_matcher_ctx_t* c, uint32_t flags, void* stream_, sp_match_terms_device_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (!flags || (flags & ~(uint32_t)(SP_TERM_VALUES | SP_TERM_TEXT))) throw std::runtime_error( "unknown or no term flags");
+		if (!c->fin.run.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
+		const sp_matcher_ctx::Values& v = c->val;
+		const sp_matcher_ctx::Text& x = c->txt;
+		if ((flags & SP_TERM_VALUES) && !(v.run.done && (v.flags & SP_VALUE_RESULTS)))
+			throw std::runtime_error( "no values of the results of the last finished batch (sp_matcher_ctx_finished_values_device with SP_VALUE_RESULTS)");
+		if ((flags & SP_TERM_TEXT) && !(x.run.done && (x.flags & SP_TEXT_RESULTS)))
+			throw std::runtime_error( "no text of the results of the last finished batch (sp_matcher_ctx_finished_text_device with SP_TEXT_RESULTS)");
+		const size_t ndocs = c->lastNdocs;
+		const uint32_t bound = sp_matcher_handle_bound( c->inst);
+		sp_matcher_ctx::Terms& t = c->trm;
+		hipStream_t stream = (hipStream_t)stream_;
+		HIP_CHECK( hipSetDevice( c->device));
+		t.run.done = t.run.evValid = false;
+		// every result index is checked against the total of the finish: this read waits for it
+		HIP_CHECK( hipStreamSynchronize( c->fin.run.stream));
+		uint64_t finished[ 2];
+		copySync( c->own, finished, c->fin.dTotals.ptr, sizeof(finished), hipMemcpyDeviceToHost);
+		const uint64_t nresults = finished[ 0];
+		if ((flags & SP_TERM_VALUES) && v.nrecords[ 0] != nresults) throw std::runtime_error( "the values are not those of the finished batch");
+		if ((flags & SP_TERM_TEXT) && x.nrecords[ 0] != nresults) throw std::runtime_error( "the text is not that of the finished batch");
+		const unsigned waves = l2TermsWaves( ndocs, c->numCUs);
+		reserveOrNoMem( t.dLeader, (nresults+1)*sizeof(uint32_t));
+		reserveOrNoMem( t.dTable, (nresults+1)*2*sizeof(uint32_t));
+		reserveOrNoMem( t.dResultTerm, (nresults+1)*sizeof(uint32_t));
+		reserveOrNoMem( t.dHistogram, (size_t)waves*bound*sizeof(uint32_t));
+		reserveOrNoMem( t.dDocCount, (ndocs+1)*sizeof(uint32_t));
+		reserveOrNoMem( t.dStatus, (ndocs+1)*sizeof(int32_t));
+		reserveOrNoMem( t.dDocOffsets, (ndocs+1)*sizeof(uint64_t));
+		reserveOrNoMem( t.dTotals, sizeof(uint64_t));
+		reserveOrNoMem( t.dCursor, 2*sizeof(uint32_t));
+
+		// another stream than the finish's runs behind the finish, and behind the values and the text call, whose placements
+		// nobody has waited for yet
+		t.run.begin( stream, c->fin.run.stream, c->fin.run.ev[ 3]);
+		if ((flags & SP_TERM_VALUES) && stream != v.run.stream) HIP_CHECK( hipStreamWaitEvent( stream, v.run.ev[ 1], 0));
+		if ((flags & SP_TERM_TEXT) && stream != x.run.stream) HIP_CHECK( hipStreamWaitEvent( stream, x.run.ev[ 1], 0));
+		HIP_CHECK( hipMemsetAsync( t.dCursor.ptr, 0, 2*sizeof(uint32_t), stream));
+		HIP_CHECK( hipMemsetAsync( t.dTotals.ptr, 0, sizeof(uint64_t), stream));
+		HIP_CHECK( hipMemsetAsync( t.dStatus.ptr, 0, (ndocs+1)*sizeof(int32_t), stream));
+		TermsParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.results = (const uint32_t*)c->fin.dResults.ptr; P.docOffsets = (const uint64_t*)c->fin.dDocResultOffsets.ptr;
+		P.resultFormat = c->io.withFormats ? (const uint32_t*)c->fin.dResultFormat.ptr : 0;
+		P.nresults = nresults; P.ndocs = (uint32_t)ndocs; P.handleBound = bound; P.flags = flags;
+		const unsigned bits = termHashBits().load( std::memory_order_relaxed);
+		P.hashMask = bits >= 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
+		if (flags & SP_TERM_VALUES)
+		{
+			const TermSourceDevice S = { (const uint8_t*)v.dValues[ 0].ptr, (const uint64_t*)v.dValueOffsets[ 0].ptr, v.totals[ 0], (const int32_t*)v.dStatus.ptr };
+			P.source[ 0] = S;
+		}
+		if (flags & SP_TERM_TEXT)
+		{
+			const TermSourceDevice S = { (const uint8_t*)x.dText[ 0].ptr, (const uint64_t*)x.dSpanOffsets[ 0].ptr, x.totals[ 0], (const int32_t*)x.dStatus.ptr };
+			P.source[ 1] = S;
+		}
+		P.leader = (uint32_t*)t.dLeader.ptr; P.table = (uint32_t*)t.dTable.ptr; P.histogram = (uint32_t*)t.dHistogram.ptr;
+		P.docCount = (uint32_t*)t.dDocCount.ptr; P.cursor = (uint32_t*)t.dCursor.ptr;
+		P.docStatus = (int32_t*)t.dStatus.ptr; P.docTermOffsets = (uint64_t*)t.dDocOffsets.ptr; P.total = (uint64_t*)t.dTotals.ptr;
+		P.resultTerm = (uint32_t*)t.dResultTerm.ptr;
+		HIP_CHECK( hipEventRecord( t.run.ev[ 0], stream));
+		HIP_CHECK( launchL2TermsCount( P, c->numCUs, stream));
+		// the records are sized from what the passes counted: this read waits for them, the placement below is not waited for
+		HIP_CHECK( hipStreamSynchronize( stream));
+		uint64_t total = 0;
+		copySync( c->own, &total, t.dTotals.ptr, sizeof(total), hipMemcpyDeviceToHost);
+		reserveOrNoMem( t.dRecords, (total+1)*sizeof(sp_match_term_t));
+		P.records = (uint32_t*)t.dRecords.ptr; P.capacity = total;
+		HIP_CHECK( launchL2TermsPlace( P, c->numCUs, stream));
+		HIP_CHECK( hipEventRecord( t.run.ev[ 1], stream));
+		t.run.completed( stream); t.ndocs = ndocs; t.handleBound = bound; t.flags = flags; t.nresults = nresults; t.total = total;
+		if (out)
+		{
+			out->ndocs = ndocs; out->handle_bound = bound; out->flags = flags;
+			out->d_records = t.dRecords.ptr; out->d_doc_term_offsets = t.dDocOffsets.ptr; out->d_result_term = t.dResultTerm.ptr;
+			out->d_doc_term_status = t.dStatus.ptr; out->d_totals = t.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the term buffers
+int sp_matcher_ctx_finished_terms_fetch( sp_matcher_ctx_t* c, sp_match_terms_t* out)
+{
+	std::memset( out, 0, sizeof(*out));
+	const int rc = guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		const sp_matcher_ctx::Terms& t = c->trm;
+		if (!t.run.done) throw std::runtime_error( "no terms of the last batch of this context (sp_matcher_ctx_finished_terms_device)");
+		HIP_CHECK( hipSetDevice( c->device));
+		HIP_CHECK( hipStreamSynchronize( t.run.stream));
+		allocMatchTerms( out, t.ndocs, t.nresults, t.handleBound, t.flags);
+		allocMatchTermRecords( out, t.total);
+		if (t.total) copySync( c->own, out->records, t.dRecords.ptr, t.total*sizeof(sp_match_term_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->doc_term_offsets, t.dDocOffsets.ptr, (t.ndocs+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		if (t.nresults) copySync( c->own, out->result_term, t.dResultTerm.ptr, t.nresults*sizeof(uint32_t), hipMemcpyDeviceToHost);
+		if (t.ndocs) copySync( c->own, out->doc_term_status, t.dStatus.ptr, t.ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+	});
+	if (rc != SP_OK) sp_match_terms_free( out);
+	return rc;
+}
+
+// duration of the passes of the last terms call in milliseconds (HIP events on its stream)
+int sp_matcher_ctx_last_terms_ms( sp_matcher_ctx_t* c, double* ms) { return c->trm.run.ms( 0, 1, ms); }
+
+uint32_t sp_matcher_term_tile(void) { return TERM_TILE; }
 
 double sp_matcher_ctx_last_kernel_ms( sp_matcher_ctx_t* c) { return lastKernelMs( c); }
 

@@ -2,7 +2,7 @@
 through the MI355X lexer + rule automaton, print tokens (-K) and results in the reference tool's
 listing format (doc/webpage/introduction_struspattern.htm:178-260).
 
-    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] file [file ...]
+    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] file [file ...]
 
 Every file is one document (plain UTF-8 text; the reference tool segments XML with strusAnalyzer's
 segmenters, which are outside this engine -- pass -o to add the offset of the text inside its original
@@ -14,7 +14,10 @@ listing of a file is followed by one line per pattern that matched in it, ascend
 `frequency NAME: count N first ORDPOS last ORDEND` -- how often, the first ordinal position a match starts at
 and the last one a match ends at, summed on the GPU (finishedPatternFreqDevice).  With --device-values the values of
 the format strings in the listing are built on the GPU (finishedValuesDevice) instead of resultformat.Formatter; the listing
-is the same.  All files go to the
+is the same.  With --terms the listing of a file is followed by one line per index term of it -- a distinct pair of pattern
+and value, the value of a result being that of its format string, or the text it covers where it has none -- ascending by
+pattern handle, then by first occurrence: `term NAME 'VALUE': count N first ORDPOS`, grouped on the GPU
+(finishedTermsDevice).  All files go to the
 GPU as one batch.  There is no CPU fallback.
 """
 import argparse
@@ -34,6 +37,7 @@ def main(argv=None):
     ap.add_argument("--paragraphs", action="store_true", help="every file is a document whose segments are its paragraphs")
     ap.add_argument("--frequencies", action="store_true", help="after the listing of a file, one line per pattern that matched in it")
     ap.add_argument("--device-values", action="store_true", help="the values of the format strings are built on the device")
+    ap.add_argument("--terms", action="store_true", help="after the listing of a file, one line per distinct (pattern, value) of it")
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("files", nargs="+")
     args = ap.parse_args(argv)
@@ -57,6 +61,7 @@ def main(argv=None):
     mctx = mt.createContext(args.device)
     mb = mctx.matchDocs(lb.lexems, lb.doc_offsets)
     values = device_values(mctx, text, offs) if args.device_values else None
+    terms = device_terms(mctx, text, offs) if args.terms else None
     freq = frequencies(mctx) if args.frequencies else None
     for di, fn in enumerate(args.files):
         print("%s:" % fn)
@@ -70,8 +75,38 @@ def main(argv=None):
                                             first_result=int(mb.doc_offsets[di]), values=values):
             print(line)
         print_frequencies(freq, di, mt)
+        print_terms(terms, di, mt)
     print("OK done")
     return 0
+
+
+def device_terms(mctx, text, offs):
+    """--terms: the last batch of the context finished on the device, its values and the text of its results built there and
+    the results grouped into terms; every document is one segment of `text`.  Returns (batch, text, values, terms)."""
+    import torch
+    d_text = torch.frombuffer(bytearray(text + b"\0" * 16), dtype=torch.uint8).cuda()
+    d_so = torch.from_numpy(np.ascontiguousarray(offs, dtype=np.uint64).view(np.int64)).cuda()
+    mctx.batchFinishDevice()
+    mctx.finishedValuesDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), len(offs) - 1, flags=spa.SP_VALUE_RESULTS)
+    mctx.finishedTextDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), len(offs) - 1, items=False)
+    mctx.finishedTermsDevice()
+    return mctx.finishedFetch(), mctx.finishedTextFetch(), mctx.finishedValuesFetch(), mctx.finishedTermsFetch()
+
+
+def term_lines(found, di, pattern_name):
+    """the lines of --terms for document di; found: (batch, text, values, terms) of the terms call"""
+    mb, mt, mv, terms = found
+    if int(terms.status[di]) != 0:
+        raise spa.PatternError("no terms of document %d: status %d" % (di, int(terms.status[di])))
+    return ["term %s '%s': count %d first %d" % (pattern_name(int(h)), value.decode("utf-8", "replace"), count, first)
+            for h, value, count, first, _ in terms.terms(di, mb, values=mv, text=mt)]
+
+
+def print_terms(found, di, mt):
+    if found is None:
+        return
+    for line in term_lines(found, di, mt.patternName):
+        print(line)
 
 
 def device_values(mctx, text, offs):
@@ -109,8 +144,12 @@ def paragraphs(args, prg, lx, mt, docs):
     text, seg_offsets, doc_seg_offsets, posmaps = segments.segmented_batch(docs)
     lctx = lx.createContext(args.device)
     mctx = mt.createContext(args.device)
-    values = None
-    if args.device_values:
+    values = terms = None
+    if args.terms:
+        mb, mtext, mvalues, mterms = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_terms=True)
+        terms = (mb, mtext, mvalues, mterms)
+        values = mvalues if args.device_values else None
+    elif args.device_values:
         mb, values = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_values=True)
     else:
         mb = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets)
@@ -138,6 +177,7 @@ def paragraphs(args, prg, lx, mt, docs):
                                             first_result=int(mb.doc_offsets[di]), values=values):
             print(line)
         print_frequencies(freq, di, mt)
+        print_terms(terms, di, mt)
     print("OK done")
     return 0
 
