@@ -71,9 +71,90 @@ def _match_batch_of(b):
                       _rows(b.doc_stats, b.ndocs, 4, ctypes.c_uint64), _rows(b.doc_status, b.ndocs, 0, ctypes.c_int32), *_formats_of(b))
 
 
-class MatchText:
+def _product(struct_type, call, free, convert, failed):
+    """One C call that fills a struct the library allocates for: call(struct) is the return code, failed(rc) the message of
+    the PatternError for one that is not 0, convert(struct) the Python copy.  The struct is freed whatever happens."""
+    s = struct_type()
+    rc = call(s)
+    try:
+        if rc != 0:
+            raise PatternError(failed(rc))
+        return convert(s)
+    finally:
+        free(ctypes.byref(s))
+
+
+def _host_batch(mb, items=False, formats=None, status=False):
+    """The capi.SpMatchBatch of a MatchBatch for a host twin, and the arrays it points into: the caller holds them until its
+    C call has returned.  items: with the items; formats: "results" with the format handles of the results, "all" with those
+    of the items too (where the batch has them); status: with the document status (where the batch has one)."""
+    b, keep = capi.SpMatchBatch(), []
+
+    def point(field, array, ctype):
+        keep.append(array)
+        setattr(b, field, ctypes.cast(array.ctypes.data, ctypes.POINTER(ctype)))
+
+    res = np.ascontiguousarray(mb.results, dtype=np.uint32).reshape(-1, 9)
+    offs = np.ascontiguousarray(mb.doc_offsets, dtype=np.uint64)
+    b.ndocs, b.nresults = len(offs) - 1, len(res)
+    point("results", res, SpResult)
+    point("doc_result_offsets", offs, ctypes.c_uint64)
+    if items:
+        its = np.ascontiguousarray(mb.items, dtype=np.uint32).reshape(-1, 7)
+        b.nitems = len(its)
+        point("items", its, SpResultItem)
+    if status and mb.status is not None:
+        point("doc_status", np.ascontiguousarray(mb.status, dtype=np.int32), ctypes.c_int32)
+    if formats == "results" and mb.result_format is not None:
+        rf = np.ascontiguousarray(mb.result_format, dtype=np.uint32).reshape(-1)
+        if len(rf) != len(res):
+            raise PatternError("format array of the batch is not parallel to its results")
+        point("result_format", rf, ctypes.c_uint32)
+    if formats == "all" and mb.result_format is not None and mb.item_format is not None:
+        rf = np.ascontiguousarray(mb.result_format, dtype=np.uint32).reshape(-1)
+        itf = np.ascontiguousarray(mb.item_format, dtype=np.uint32).reshape(-1, 2)
+        if len(rf) != len(res) or len(itf) != b.nitems:
+            raise PatternError("format arrays of the batch are not parallel to its results and items")
+        point("result_format", rf, ctypes.c_uint32)
+        point("item_format", itf, ctypes.c_uint32)
+    return b, keep
+
+
+def _host_text(text, seg_offsets, doc_seg_offsets):
+    """The text source arguments of a host twin (text, nbytes, seg_offsets, nseg, doc_seg_offsets), and what they point into"""
+    text = bytes(text)
+    so = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
+    dso = None if doc_seg_offsets is None else np.ascontiguousarray(doc_seg_offsets, dtype=np.uint64)
+    return (text, len(text), so.ctypes.data, len(so) - 1, dso.ctypes.data if dso is not None else None), [text, so, dso]
+
+
+class _ByteFamilies:
+    """Bytes per result and per item of a batch (host copies): those of record i of a family are bytes[offsets[i]:offsets[i+1]],
+    parallel to the results / items of the batch.  A family that was not asked for is None."""
+    _results = _items = None    # the attributes with the bytes of the two families
+
+    def result(self, i):
+        return getattr(self, self._results)[int(self.result_offsets[i]):int(self.result_offsets[i + 1])]
+
+    def item(self, i):
+        return getattr(self, self._items)[int(self.item_offsets[i]):int(self.item_offsets[i + 1])]
+
+
+def _byte_families_of(cls, s, result, item, status):
+    """the MatchText / MatchValues (`cls`) of its C struct `s` (copies); result, item: the fields (bytes, offsets) of a family
+    of `s`, status: its status field"""
+    def family(fields, n, total):
+        data, offsets = getattr(s, fields[0]), getattr(s, fields[1])
+        if not offsets:
+            return None, None
+        return (ctypes.string_at(data, total) if total else b""), _rows(offsets, n + 1, 0, ctypes.c_uint64)
+    return cls(*family(result, s.nresults, s.totals[0]), *family(item, s.nitems, s.totals[1]), _rows(getattr(s, status), s.ndocs, 0, ctypes.c_int32))
+
+
+class MatchText(_ByteFamilies):
     """The text that the results and items of a finished batch cover (host copies): the bytes of span i of a family are
     text[offsets[i]:offsets[i+1]], parallel to the results / items of the batch.  A family that was not asked for is None."""
+    _results, _items = "result_text", "item_text"
 
     def __init__(self, result_text, result_offsets, item_text, item_offsets, status):
         self.result_text = result_text        # bytes
@@ -82,22 +163,10 @@ class MatchText:
         self.item_offsets = item_offsets      # (nitems+1,) u64
         self.status = status                  # (ndocs,) i32: 0, or 5 for a document with a span outside the text (all its spans empty)
 
-    def result(self, i):
-        return self.result_text[int(self.result_offsets[i]):int(self.result_offsets[i + 1])]
-
-    def item(self, i):
-        return self.item_text[int(self.item_offsets[i]):int(self.item_offsets[i + 1])]
-
 
 def _match_text_of(t):
     """the MatchText of a capi.SpMatchText (copies)"""
-    def family(text, offsets, n, total):
-        if not offsets:
-            return None, None
-        return (ctypes.string_at(text, total) if total else b""), _rows(offsets, n + 1, 0, ctypes.c_uint64)
-    rt, ro = family(t.result_text, t.result_text_offsets, t.nresults, t.totals[0])
-    it, io = family(t.item_text, t.item_text_offsets, t.nitems, t.totals[1])
-    return MatchText(rt, ro, it, io, _rows(t.doc_text_status, t.ndocs, 0, ctypes.c_int32))
+    return _byte_families_of(MatchText, t, ("result_text", "result_text_offsets"), ("item_text", "item_text_offsets"), "doc_text_status")
 
 
 def batchText(mb, text, seg_offsets, doc_seg_offsets=None, results=True, items=True):
@@ -106,34 +175,19 @@ def batchText(mb, text, seg_offsets, doc_seg_offsets=None, results=True, items=T
     `text` holds the segments back to back (seg_offsets: nseg+1 byte offsets), document d is the segments
     [doc_seg_offsets[d], doc_seg_offsets[d+1]), or segment d without doc_seg_offsets.  Returns a MatchText."""
     L = capi.lib()
-    text = bytes(text)
-    seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
-    dso = None if doc_seg_offsets is None else np.ascontiguousarray(doc_seg_offsets, dtype=np.uint64)
-    res = np.ascontiguousarray(mb.results, dtype=np.uint32).reshape(-1, 9)
-    its = np.ascontiguousarray(mb.items, dtype=np.uint32).reshape(-1, 7)
-    offs = np.ascontiguousarray(mb.doc_offsets, dtype=np.uint64)
-    b = capi.SpMatchBatch()
-    b.ndocs, b.nresults, b.nitems = len(offs) - 1, len(res), len(its)
-    b.results = ctypes.cast(res.ctypes.data, ctypes.POINTER(SpResult))
-    b.items = ctypes.cast(its.ctypes.data, ctypes.POINTER(SpResultItem))
-    b.doc_result_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
-    t = capi.SpMatchText()
+    b, keep = _host_batch(mb, items=True)
+    source, keep_text = _host_text(text, seg_offsets, doc_seg_offsets)      # (keep, keep_text: until the call has returned)
     err = ctypes.create_string_buffer(256)
     flags = (SP_TEXT_RESULTS if results else 0) | (SP_TEXT_ITEMS if items else 0)
-    rc = L.sp_match_batch_text(ctypes.byref(b), text, len(text), seg_offsets.ctypes.data, len(seg_offsets) - 1,
-                               dso.ctypes.data if dso is not None else None, flags, ctypes.byref(t), err, 256)
-    try:
-        if rc != 0:
-            raise PatternError("no text of the batch (%d): %s" % (rc, err.value.decode()))
-        return _match_text_of(t)
-    finally:
-        L.sp_match_text_free(ctypes.byref(t))
+    return _product(capi.SpMatchText, lambda t: L.sp_match_batch_text(ctypes.byref(b), *source, flags, ctypes.byref(t), err, 256),
+                    L.sp_match_text_free, _match_text_of, lambda rc: "no text of the batch (%d): %s" % (rc, err.value.decode()))
 
 
-class MatchValues:
+class MatchValues(_ByteFamilies):
     """The values of the format strings of a finished batch (host copies): the value of record i of a family is
     values[offsets[i]:offsets[i+1]], parallel to the results / items of the batch; a record without a format has an empty
     range (the format arrays of the batch tell an empty value from no value).  A family that was not asked for is None."""
+    _results, _items = "result_values", "item_values"
 
     def __init__(self, result_values, result_offsets, item_values, item_offsets, status):
         self.result_values = result_values    # bytes
@@ -142,22 +196,10 @@ class MatchValues:
         self.item_offsets = item_offsets
         self.status = status                  # (ndocs,) i32: 0, or 5 for a document whose values cannot be built (all of them empty)
 
-    def result(self, i):
-        return self.result_values[int(self.result_offsets[i]):int(self.result_offsets[i + 1])]
-
-    def item(self, i):
-        return self.item_values[int(self.item_offsets[i]):int(self.item_offsets[i + 1])]
-
 
 def _match_values_of(v):
     """the MatchValues of a capi.SpMatchValues (copies)"""
-    def family(values, offsets, n, total):
-        if not offsets:
-            return None, None
-        return (ctypes.string_at(values, total) if total else b""), _rows(offsets, n + 1, 0, ctypes.c_uint64)
-    rv, ro = family(v.result_values, v.result_value_offsets, v.nresults, v.totals[0])
-    iv, io = family(v.item_values, v.item_value_offsets, v.nitems, v.totals[1])
-    return MatchValues(rv, ro, iv, io, _rows(v.doc_value_status, v.ndocs, 0, ctypes.c_int32))
+    return _byte_families_of(MatchValues, v, ("result_values", "result_value_offsets"), ("item_values", "item_value_offsets"), "doc_value_status")
 
 
 def batchValues(matcher, mb, text, seg_offsets, doc_seg_offsets=None, flags=SP_VALUE_RESULTS | SP_VALUE_ITEMS):
@@ -166,34 +208,11 @@ def batchValues(matcher, mb, text, seg_offsets, doc_seg_offsets=None, flags=SP_V
     (include/strus_pattern_amd.h "result values"), without a device.  The text source is that of batchText.  Returns a
     MatchValues."""
     L = capi.lib()
-    text = bytes(text)
-    seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
-    dso = None if doc_seg_offsets is None else np.ascontiguousarray(doc_seg_offsets, dtype=np.uint64)
-    res = np.ascontiguousarray(mb.results, dtype=np.uint32).reshape(-1, 9)
-    its = np.ascontiguousarray(mb.items, dtype=np.uint32).reshape(-1, 7)
-    offs = np.ascontiguousarray(mb.doc_offsets, dtype=np.uint64)
-    b = capi.SpMatchBatch()
-    b.ndocs, b.nresults, b.nitems = len(offs) - 1, len(res), len(its)
-    b.results = ctypes.cast(res.ctypes.data, ctypes.POINTER(SpResult))
-    b.items = ctypes.cast(its.ctypes.data, ctypes.POINTER(SpResultItem))
-    b.doc_result_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
-    if mb.result_format is not None and mb.item_format is not None:
-        rf = np.ascontiguousarray(mb.result_format, dtype=np.uint32).reshape(-1)
-        itf = np.ascontiguousarray(mb.item_format, dtype=np.uint32).reshape(-1, 2)
-        if len(rf) != len(res) or len(itf) != len(its):
-            raise PatternError("format arrays of the batch are not parallel to its results and items")
-        b.result_format = ctypes.cast(rf.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
-        b.item_format = ctypes.cast(itf.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
-    v = capi.SpMatchValues()
+    b, keep = _host_batch(mb, items=True, formats="all")
+    source, keep_text = _host_text(text, seg_offsets, doc_seg_offsets)      # (keep, keep_text: until the call has returned)
     err = ctypes.create_string_buffer(512)
-    rc = L.sp_match_batch_values(matcher._h, ctypes.byref(b), text, len(text), seg_offsets.ctypes.data, len(seg_offsets) - 1,
-                                 dso.ctypes.data if dso is not None else None, flags, ctypes.byref(v), err, 512)
-    try:
-        if rc != 0:
-            raise PatternError("no values of the batch (%d): %s" % (rc, err.value.decode(errors="replace")))
-        return _match_values_of(v)
-    finally:
-        L.sp_match_values_free(ctypes.byref(v))
+    return _product(capi.SpMatchValues, lambda v: L.sp_match_batch_values(matcher._h, ctypes.byref(b), *source, flags, ctypes.byref(v), err, 512),
+                    L.sp_match_values_free, _match_values_of, lambda rc: "no values of the batch (%d): %s" % (rc, err.value.decode(errors="replace")))
 
 
 class PatternFreq:
@@ -223,24 +242,10 @@ def batchPatternFreq(mb, handle_bound):
     matchDocs), by the rule of the device call, without a device.  handle_bound: PatternMatcherInstance.handleBound().
     Returns a PatternFreq."""
     L = capi.lib()
-    res = np.ascontiguousarray(mb.results, dtype=np.uint32).reshape(-1, 9)
-    offs = np.ascontiguousarray(mb.doc_offsets, dtype=np.uint64)
-    status = None if mb.status is None else np.ascontiguousarray(mb.status, dtype=np.int32)
-    b = capi.SpMatchBatch()
-    b.ndocs, b.nresults = len(offs) - 1, len(res)
-    b.results = ctypes.cast(res.ctypes.data, ctypes.POINTER(SpResult))
-    b.doc_result_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
-    if status is not None:
-        b.doc_status = ctypes.cast(status.ctypes.data, ctypes.POINTER(ctypes.c_int32))
-    f = capi.SpPatternFreqBatch()
+    b, keep = _host_batch(mb, status=True)      # (keep: until the call has returned)
     err = ctypes.create_string_buffer(256)
-    rc = L.sp_match_batch_pattern_freq(ctypes.byref(b), handle_bound, ctypes.byref(f), err, 256)
-    try:
-        if rc != 0:
-            raise PatternError("no pattern frequencies of the batch (%d): %s" % (rc, err.value.decode()))
-        return _pattern_freq_of(f)
-    finally:
-        L.sp_pattern_freq_batch_free(ctypes.byref(f))
+    return _product(capi.SpPatternFreqBatch, lambda f: L.sp_match_batch_pattern_freq(ctypes.byref(b), handle_bound, ctypes.byref(f), err, 256),
+                    L.sp_pattern_freq_batch_free, _pattern_freq_of, lambda rc: "no pattern frequencies of the batch (%d): %s" % (rc, err.value.decode()))
 
 
 class MatchTerms:
@@ -284,22 +289,7 @@ def batchTerms(mb, values=None, text=None, handle_bound=0, flags=SP_TERM_VALUES 
     with its MatchValues and / or MatchText (their results family), by the rule of the device call, without a device.
     handle_bound: PatternMatcherInstance.handleBound().  Returns a MatchTerms."""
     L = capi.lib()
-    res = np.ascontiguousarray(mb.results, dtype=np.uint32).reshape(-1, 9)
-    offs = np.ascontiguousarray(mb.doc_offsets, dtype=np.uint64)
-    status = None if mb.status is None else np.ascontiguousarray(mb.status, dtype=np.int32)
-    keep = [res, offs, status]
-    b = capi.SpMatchBatch()
-    b.ndocs, b.nresults = len(offs) - 1, len(res)
-    b.results = ctypes.cast(res.ctypes.data, ctypes.POINTER(SpResult))
-    b.doc_result_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
-    if status is not None:
-        b.doc_status = ctypes.cast(status.ctypes.data, ctypes.POINTER(ctypes.c_int32))
-    if mb.result_format is not None:
-        rf = np.ascontiguousarray(mb.result_format, dtype=np.uint32).reshape(-1)
-        if len(rf) != len(res):
-            raise PatternError("format array of the batch is not parallel to its results")
-        keep.append(rf)
-        b.result_format = ctypes.cast(rf.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
+    b, keep = _host_batch(mb, formats="results", status=True)       # (keep: until the call has returned)
 
     def source(cls, family, names):
         """the C struct of a MatchValues / MatchText: its results family only"""
@@ -322,16 +312,12 @@ def batchTerms(mb, values=None, text=None, handle_bound=0, flags=SP_TERM_VALUES 
 
     v = source(capi.SpMatchValues, values, ("result_values", "result_value_offsets", "doc_value_status", "result_values"))
     x = source(capi.SpMatchText, text, ("result_text", "result_text_offsets", "doc_text_status", "result_text"))
-    t = capi.SpMatchTerms()
     err = ctypes.create_string_buffer(256)
-    rc = L.sp_match_batch_terms(ctypes.byref(b), ctypes.byref(v) if v is not None else None, ctypes.byref(x) if x is not None else None,
-                                handle_bound, flags, ctypes.byref(t), err, 256)
-    try:
-        if rc != 0:
-            raise PatternError("no terms of the batch (%d): %s" % (rc, err.value.decode()))
-        return _match_terms_of(t)
-    finally:
-        L.sp_match_terms_free(ctypes.byref(t))
+    return _product(capi.SpMatchTerms, lambda t: L.sp_match_batch_terms(ctypes.byref(b), ctypes.byref(v) if v is not None else None,
+                                                                       ctypes.byref(x) if x is not None else None, handle_bound, flags, ctypes.byref(t), err, 256),
+                    L.sp_match_terms_free, _match_terms_of, lambda rc: "no terms of the batch (%d): %s" % (rc, err.value.decode()))
+
+
 
 
 class PatternMatcherContext:
@@ -446,7 +432,19 @@ class PatternMatcherContext:
 
     def finishedFetch(self):
         """plain host copy of the batch finished by batchFinishDevice: what batchFetch() returns, with no work on the host."""
-        return self._fetched(lambda b: self._L.sp_matcher_ctx_finished_fetch(self._h, ctypes.byref(b)))
+        return self._fetched(self._L.sp_matcher_ctx_finished_fetch)
+
+    def _fetch_product(self, struct_type, call, free, convert, what):
+        """host copy of a product of the last batch: call(handle, ..., struct pointer) fills what `free` frees, `convert` copies"""
+        return _product(struct_type, lambda s: call(self._h, ctypes.byref(s)), free, convert,
+                        lambda rc: "fetching %s failed (%d): %s" % (what, rc, self._err()))
+
+    def _last_ms(self, fn, what):
+        """the one duration a timing call reports, in milliseconds"""
+        a = ctypes.c_double(-1.0)
+        if fn(self._h, ctypes.byref(a)) != 0:
+            raise PatternError("no timed " + what)
+        return a.value
 
     def lastFinishMs(self):
         """(count, offsets, place) pass durations of the last batchFinishDevice in milliseconds"""
@@ -457,10 +455,7 @@ class PatternMatcherContext:
 
     def lastFinishSortMs(self):
         """duration of the sorting pass of the last batchFinishDevice in milliseconds (0.0 without canonical=True)"""
-        a = ctypes.c_double(-1.0)
-        if self._L.sp_matcher_ctx_last_finish_sort_ms(self._h, ctypes.byref(a)) != 0:
-            raise PatternError("no timed finish")
-        return a.value
+        return self._last_ms(self._L.sp_matcher_ctx_last_finish_sort_ms, "finish")
 
     def finishedTextDevice(self, d_text, nbytes, d_seg_offsets, nseg, d_doc_seg_offsets=0, results=True, items=True, stream=0):
         """gather the text that the results and / or items of the batch finished by batchFinishDevice cover, on the device
@@ -477,21 +472,11 @@ class PatternMatcherContext:
 
     def finishedTextFetch(self):
         """plain host copy of the text gathered by finishedTextDevice: a MatchText"""
-        t = capi.SpMatchText()
-        rc = self._L.sp_matcher_ctx_finished_text_fetch(self._h, ctypes.byref(t))
-        try:
-            if rc != 0:
-                raise PatternError("fetching the text of the batch failed (%d): %s" % (rc, self._err()))
-            return _match_text_of(t)
-        finally:
-            self._L.sp_match_text_free(ctypes.byref(t))
+        return self._fetch_product(capi.SpMatchText, self._L.sp_matcher_ctx_finished_text_fetch, self._L.sp_match_text_free, _match_text_of, "the text of the batch")
 
     def lastTextMs(self):
         """duration of the passes of the last finishedTextDevice in milliseconds"""
-        a = ctypes.c_double(-1.0)
-        if self._L.sp_matcher_ctx_last_text_ms(self._h, ctypes.byref(a)) != 0:
-            raise PatternError("no timed text call")
-        return a.value
+        return self._last_ms(self._L.sp_matcher_ctx_last_text_ms, "text call")
 
     def finishedValuesDevice(self, d_text, nbytes, d_seg_offsets, nseg, d_doc_seg_offsets=0, flags=SP_VALUE_RESULTS | SP_VALUE_ITEMS, stream=0):
         """build the values of the format strings of the results and / or items of the batch finished by batchFinishDevice,
@@ -506,21 +491,11 @@ class PatternMatcherContext:
 
     def finishedValuesFetch(self):
         """plain host copy of the values built by finishedValuesDevice: a MatchValues"""
-        v = capi.SpMatchValues()
-        rc = self._L.sp_matcher_ctx_finished_values_fetch(self._h, ctypes.byref(v))
-        try:
-            if rc != 0:
-                raise PatternError("fetching the values of the batch failed (%d): %s" % (rc, self._err()))
-            return _match_values_of(v)
-        finally:
-            self._L.sp_match_values_free(ctypes.byref(v))
+        return self._fetch_product(capi.SpMatchValues, self._L.sp_matcher_ctx_finished_values_fetch, self._L.sp_match_values_free, _match_values_of, "the values of the batch")
 
     def lastValuesMs(self):
         """duration of the passes of the last finishedValuesDevice in milliseconds"""
-        a = ctypes.c_double()
-        if self._L.sp_matcher_ctx_last_values_ms(self._h, ctypes.byref(a)) != 0:
-            raise PatternError("no timed values call")
-        return a.value
+        return self._last_ms(self._L.sp_matcher_ctx_last_values_ms, "values call")
 
     def finishedPatternFreqDevice(self, stream=0):
         """sum the pattern frequencies of the batch finished by batchFinishDevice on the device (the placement is
@@ -534,21 +509,12 @@ class PatternMatcherContext:
 
     def finishedPatternFreqFetch(self):
         """plain host copy of the frequencies summed by finishedPatternFreqDevice: a PatternFreq"""
-        f = capi.SpPatternFreqBatch()
-        rc = self._L.sp_matcher_ctx_finished_pattern_freq_fetch(self._h, ctypes.byref(f))
-        try:
-            if rc != 0:
-                raise PatternError("fetching the pattern frequencies of the batch failed (%d): %s" % (rc, self._err()))
-            return _pattern_freq_of(f)
-        finally:
-            self._L.sp_pattern_freq_batch_free(ctypes.byref(f))
+        return self._fetch_product(capi.SpPatternFreqBatch, self._L.sp_matcher_ctx_finished_pattern_freq_fetch, self._L.sp_pattern_freq_batch_free, _pattern_freq_of,
+                                   "the pattern frequencies of the batch")
 
     def lastPatternFreqMs(self):
         """duration of the passes of the last finishedPatternFreqDevice in milliseconds"""
-        a = ctypes.c_double(-1.0)
-        if self._L.sp_matcher_ctx_last_pattern_freq_ms(self._h, ctypes.byref(a)) != 0:
-            raise PatternError("no timed pattern frequency call")
-        return a.value
+        return self._last_ms(self._L.sp_matcher_ctx_last_pattern_freq_ms, "pattern frequency call")
 
     def finishedTermsDevice(self, flags=SP_TERM_VALUES | SP_TERM_TEXT, stream=0):
         """group the results of the batch finished by batchFinishDevice into index terms on the device (the placement is
@@ -564,38 +530,21 @@ class PatternMatcherContext:
 
     def finishedTermsFetch(self):
         """plain host copy of the terms grouped by finishedTermsDevice: a MatchTerms"""
-        t = capi.SpMatchTerms()
-        rc = self._L.sp_matcher_ctx_finished_terms_fetch(self._h, ctypes.byref(t))
-        try:
-            if rc != 0:
-                raise PatternError("fetching the terms of the batch failed (%d): %s" % (rc, self._err()))
-            return _match_terms_of(t)
-        finally:
-            self._L.sp_match_terms_free(ctypes.byref(t))
+        return self._fetch_product(capi.SpMatchTerms, self._L.sp_matcher_ctx_finished_terms_fetch, self._L.sp_match_terms_free, _match_terms_of, "the terms of the batch")
 
     def lastTermsMs(self):
         """duration of the passes of the last finishedTermsDevice in milliseconds"""
-        a = ctypes.c_double(-1.0)
-        if self._L.sp_matcher_ctx_last_terms_ms(self._h, ctypes.byref(a)) != 0:
-            raise PatternError("no timed terms call")
-        return a.value
+        return self._last_ms(self._L.sp_matcher_ctx_last_terms_ms, "terms call")
 
     def batchFetch(self, first_doc=None, ndocs=None):
         """host copy of the last device batch, grouped by document; with (first_doc, ndocs) only of
         that range of documents."""
         if first_doc is None:
-            return self._fetched(lambda b: self._L.sp_matcher_ctx_batch_fetch(self._h, ctypes.byref(b)))
-        return self._fetched(lambda b: self._L.sp_matcher_ctx_batch_fetch_docs(self._h, first_doc, ndocs, ctypes.byref(b)))
+            return self._fetched(self._L.sp_matcher_ctx_batch_fetch)
+        return self._fetched(lambda h, b: self._L.sp_matcher_ctx_batch_fetch_docs(h, first_doc, ndocs, b))
 
     def _fetched(self, call):
-        b = capi.SpMatchBatch()
-        rc = call(b)
-        try:
-            if rc != 0:
-                raise PatternError("fetching the batch failed (%d): %s" % (rc, self._err()))
-            return _match_batch_of(b)
-        finally:
-            self._L.sp_match_batch_free(ctypes.byref(b))
+        return self._fetch_product(capi.SpMatchBatch, call, self._L.sp_match_batch_free, _match_batch_of, "the batch")
 
     def batchCounters(self):
         arr = (ctypes.c_uint64 * 8)()

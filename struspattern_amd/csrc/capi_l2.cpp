@@ -1,48 +1,8 @@
-// C-ABI of level 2 (include/strus_pattern_amd.h): rule compiler handle + GPU match context.
+// C-ABI of level 2 (include/strus_pattern_amd.h): rule compiler handle + GPU match context (capi_l2_ctx.hpp), the batch launch,
+// the host entry points, single-document mode.  What is made of a finished batch: capi_l2_finished.cpp.
 // No CPU fallback: a context cannot be created without a usable HIP device.
-#include "l2_plan.hpp"
-#include "l2_finish.h"
-#include "l2_text.h"
-#include "l2_freq.h"
-#include "l2_values.h"
-#include "l2_terms.h"
-#include "match_terms.hpp"
-#include "span_text.hpp"
-#include "result_values.hpp"
-#include "pattern_freq.hpp"
-#include "capi_util.hpp"
+#include "capi_l2_ctx.hpp"
 #include <cstdio>
-#include <mutex>
-
-using namespace spa;
-
-struct sp_matcher
-{
-	RuleCompiler compiler;
-	bool compiled = false;	// compile() is optional for the matcher (reference: tests/randomTokenPatternMatch :317-320)
-	mutable std::string lasterror;
-	// the parts of the format strings (result_values.hpp): built when the rule set compiles or is loaded, else at the first values call
-	mutable std::mutex formatMutex;
-	mutable FormatTable formatTable;
-	mutable bool haveFormatTable = false;
-	mutable size_t formatTableVariables = 0;	// the variable names the table was resolved against
-
-	// rebuild = true (every compile, every load): the definitions may have changed under the same counts
-	const FormatTable& formats( bool rebuild = false) const
-	{
-		std::lock_guard<std::mutex> lock( formatMutex);
-		const size_t nvariables = compiler.variables().names().size();
-		if (rebuild || !haveFormatTable || formatTable.count != compiler.formatCount() || formatTableVariables != nvariables)
-		{
-			formatTableVariables = nvariables;
-			formatTable = buildFormatTable( compiler.formatCount(),
-				[this]( uint32_t f) { return compiler.formatString( f); },
-				[this]( const std::string& name) { return compiler.variables().get( name); });
-			haveFormatTable = true;
-		}
-		return formatTable;
-	}
-};
 
 namespace {
 
@@ -85,117 +45,6 @@ int tierQuery( const sp_matcher* m, uint32_t flags, L2EngineKind kind, char* why
 }
 
 } // namespace
-
-struct sp_matcher_ctx
-{
-	const sp_matcher* inst = 0;
-	int device = 0;
-	unsigned numCUs = 256;
-	L2Switches sw;			// read when the context is created
-	L2EngineKind kind = L2_GENERAL;
-	std::string lasterror;
-	// the exact engine (l2_kernel.hip): compiled tables, working memory, the documents of a launch in list mode
-	struct Exact
-	{
-		DeviceBuffer dPrograms, dTrigdefs, dKeytab, dKeylist, dDocList;
-		uint32_t keymask = 0, nofStopWords = 0;
-		ArenaLayout layout = initialArena();
-		CountedBuffer arena;		// count: waves; 0 forces a new layout at the next launch
-	} exact;
-	// flat tier (l2_fast.h): flat rule sets run with their hot state in LDS; the general kernel takes what it hands over
-	struct Flat
-	{
-		bool on = false;
-		std::string whyNot;
-		DeviceBuffer dKeyinst, dStatics;
-		FlatPlan plan;			// kernel instance = LDS capacities (l2_fast_kernel.hip), spill layout
-		CountedBuffer spill;		// count: waves
-		unsigned blocksPerCU = 0;
-	} flat;
-	// result-set mode (l2_join.h; SP_CTX_RESULT_SETS or SPA_L2_JOIN=1): result multisets without materialised rule instances
-	struct ResultSets
-	{
-		bool on = false, altRules = false;
-		std::string whyNot;
-		uint32_t keymask = 0, maxRange = 0, delimiter = 0;
-		DeviceBuffer dKeytab, dRules, dFilter, dCounts;
-	} join;
-	// batch buffers (grown on demand): the input of the host entry points, the output of every rule kernel
-	struct BatchIO
-	{
-		DeviceBuffer dCursor, dCounters;
-		DeviceBuffer dLexems, dOrigseg, dDocOffsets;
-		CountedBuffer results, items;	// count: sp_result_t, sp_result_item_t
-		DeviceBuffer dDocRange, dDocStats, dDocStatus;
-		DeviceBuffer dResultFormat, dItemFormat;	// only for matchers with format strings
-		bool withFormats = false, withItems = true;
-		uint64_t minResults = 0, minItems = 0;
-	} io;
-	// the last batch finished on the device (l2_finish.h); nothing is allocated before the first sp_matcher_ctx_batch_finish_device
-	struct Finished
-	{
-		PassRun<5> run;		// ev[4]: between the sort and the placement of a canonical finish
-		DeviceBuffer dResults, dItems, dResultFormat, dItemFormat, dDocResultOffsets, dDocItemOffsets, dTotals, dKept, dCovered, dCursor;
-		bool canonical = false;
-		// working memory of the canonical order, allocated at the first finish that asks for it
-		DeviceBuffer dSortKeys[ 2], dSortIdx[ 2], dSortCursor;
-	} fin;
-	// the matched text of the last finished batch (l2_text.h); nothing is allocated before the first sp_matcher_ctx_finished_text_device
-	struct Text
-	{
-		PassRun<2> run;
-		DeviceBuffer dText[ 2], dSpanOffsets[ 2], dSpanWork[ 2], dDocBytes[ 2], dDocTextOffsets[ 2];	// [0] results, [1] items
-		DeviceBuffer dStatus, dTotals, dCursor;
-		uint32_t flags = 0;
-		size_t ndocs = 0;
-		uint64_t nrecords[ 2] = {0, 0}, totals[ 2] = {0, 0};
-	} txt;
-	// the values of the format strings of the last finished batch (l2_values.h); nothing is allocated before the first sp_matcher_ctx_finished_values_device
-	struct Values
-	{
-		PassRun<2> run;
-		DeviceBuffer dFmtParts, dParts, dPool;		// the format table, uploaded at the first call
-		bool uploaded = false;
-		uint32_t poolBytes = 0;
-		DeviceBuffer dValues[ 2], dValueOffsets[ 2], dValueWork[ 2], dDocBytes[ 2], dDocValueOffsets[ 2];	// [0] results, [1] items
-		DeviceBuffer dStatus, dTotals, dCursor;
-		uint32_t flags = 0;
-		size_t ndocs = 0;
-		uint64_t nrecords[ 2] = {0, 0}, totals[ 2] = {0, 0};
-	} val;
-	// the pattern frequencies of the last finished batch (l2_freq.h); nothing is allocated before the first sp_matcher_ctx_finished_pattern_freq_device
-	struct Freq
-	{
-		PassRun<2> run;
-		DeviceBuffer dRecords, dDocOffsets, dStatus, dHandleResults, dHandleDocs, dTotals, dDocCount, dDocMeta, dCursor;
-		size_t ndocs = 0;
-		uint32_t handleBound = 0;
-		uint64_t total = 0;
-	} frq;
-	// the index terms of the last finished batch (l2_terms.h); nothing is allocated before the first sp_matcher_ctx_finished_terms_device
-	struct Terms
-	{
-		PassRun<2> run;
-		DeviceBuffer dRecords, dDocOffsets, dResultTerm, dStatus, dTotals, dLeader, dTable, dHistogram, dDocCount, dCursor;
-		size_t ndocs = 0;
-		uint32_t handleBound = 0, flags = 0;
-		uint64_t nresults = 0, total = 0;
-	} trm;
-	// single-document mode
-	struct SingleDoc
-	{
-		std::vector<sp_lexem_t> lexems;
-		std::vector<uint32_t> origseg; bool hasSeg = false;
-		std::vector<uint32_t> resultFormat, itemFormat;	// of the last sp_matcher_ctx_fetch_results
-		sp_matcher_stats_t stats = {};
-	} cur;
-	// the last launch
-	bool haveBatch = false;
-	size_t lastNdocs = 0;
-	hipStream_t lastStream = 0;
-	Event evStart, evStop; bool evValid = false;
-	Stream own;			// the context's own stream (non-blocking): see sp_lexer_ctx; last member: it waits for its work before anything else goes
-};
 
 extern "C" {
 
@@ -394,17 +243,6 @@ int sp_matcher_ctx_set_arena( sp_matcher_ctx_t* c, uint32_t max_rules, uint32_t 
 
 namespace {
 
-// the counters of the last batch (its stream has been waited for), and what of its output lies inside the buffers
-struct BatchCounts { uint64_t counters[ SPC_COUNT]; uint64_t results, items; };
-BatchCounts readCounts( sp_matcher_ctx* c)
-{
-	BatchCounts b;
-	copySync( c->own, b.counters, c->io.dCounters.ptr, sizeof(b.counters), hipMemcpyDeviceToHost);
-	b.results = clampCount( b.counters[ SPC_RESULTS], c->io.results.count);
-	b.items = clampCount( b.counters[ SPC_ITEMS], c->io.items.count);
-	return b;
-}
-
 // Host copy of the device results of the last launch for the documents [firstDoc, firstDoc+ndocs), regrouped by document with
 // the `exclusive` elimination of fetchResults applied on the way: the plan, the copy segments and the regroup of batch_fetch.hpp
 void copyOutBatch( sp_matcher_ctx* c, size_t firstDoc, size_t ndocs, const BatchCounts& counts, sp_match_batch_t* out)
@@ -593,7 +431,7 @@ void launchBatch( sp_matcher_ctx* c, const void* d_lexems, const void* d_origseg
 	const L2LaunchPlan plan = planL2Launch( c->kind, rerun != 0, c->numCUs, c->flat.blocksPerCU, rerun ? rerun->size() : ndocs, ndocs, nlexems,
 						c->exact.layout, &c->flat.plan, c->io.minResults, c->io.minItems);
 	HIP_CHECK( hipSetDevice( c->device));
-	c->fin.run.done = false; c->txt.run.done = false; c->val.run.done = false; c->frq.run.done = false; c->trm.run.done = false;	// (a new batch: what was finished is of the one before)
+	c->prod.drop();		// (a new batch: what was finished is of the one before)
 	ensureArena( c, plan);
 	ensureOutput( c, plan, ndocs);
 	resetCursorAndCounters( c, rerun != 0, stream);
@@ -672,608 +510,6 @@ int sp_matcher_ctx_batch_counters( sp_matcher_ctx_t* c, uint64_t counters[8])
 		}
 	});
 }
-
-// ---- the last device batch finished on the device: document order, `exclusive` applied, items without gaps (l2_finish.h)
-int sp_matcher_ctx_batch_finish_device( sp_matcher_ctx_t* c, void* stream, sp_match_finished_batch_t* out)
-{ return sp_matcher_ctx_batch_finish_device_ex( c, stream, 0, out); }
-
-// flags: SP_FINISH_CANONICAL orders the results of every document by the tuple T of the header
-int sp_matcher_ctx_batch_finish_device_ex( sp_matcher_ctx_t* c, void* stream_, uint32_t flags, sp_match_finished_batch_t* out)
-{
-	if (out) std::memset( out, 0, sizeof(*out));
-	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
-		if (flags & ~(uint32_t)SP_FINISH_CANONICAL) throw std::runtime_error( "unknown finish flags");
-		const bool canonical = (flags & SP_FINISH_CANONICAL) != 0;
-		if (!c->haveBatch) throw std::runtime_error( "no batch to finish: no batch has run on this context");
-		hipStream_t stream = (hipStream_t)stream_;
-		HIP_CHECK( hipSetDevice( c->device));
-		c->fin.run.done = false; c->txt.run.done = false; c->val.run.done = false; c->frq.run.done = false; c->trm.run.done = false;
-		// the buffers are sized from what the batch counted: this read waits for the batch, the passes below do not
-		HIP_CHECK( hipStreamSynchronize( c->lastStream));
-		const BatchCounts counts = readCounts( c);
-		const uint64_t devResults = counts.results, devItems = counts.items;
-		const size_t ndocs = c->lastNdocs;
-		const bool exclusive = c->inst->compiler.exclusive();
-		c->fin.dResults.reserve( (devResults+1)*sizeof(sp_result_t));
-		c->fin.dItems.reserve( (devItems+1)*sizeof(sp_result_item_t));
-		if (c->io.withFormats)
-		{
-			c->fin.dResultFormat.reserve( (devResults+1)*sizeof(uint32_t));
-			c->fin.dItemFormat.reserve( (devItems+1)*2*sizeof(uint32_t));
-		}
-		c->fin.dDocResultOffsets.reserve( (ndocs+1)*sizeof(uint64_t));
-		c->fin.dDocItemOffsets.reserve( (ndocs+1)*sizeof(uint64_t));
-		c->fin.dKept.reserve( (ndocs+1)*2*sizeof(uint32_t));
-		if (!c->fin.dTotals.ptr) c->fin.dTotals.alloc( 2*sizeof(uint64_t));
-		if (!c->fin.dCursor.ptr) c->fin.dCursor.alloc( 2*sizeof(uint32_t));
-		if (exclusive) c->fin.dCovered.reserve( devResults+1);
-		if (canonical)
-		{
-			for (int i=0; i<2; ++i)
-			{
-				c->fin.dSortKeys[ i].reserve( (devResults+1)*sizeof(uint64_t));
-				c->fin.dSortIdx[ i].reserve( (devResults+1)*sizeof(uint32_t));
-			}
-			if (!c->fin.dSortCursor.ptr) c->fin.dSortCursor.alloc( sizeof(uint32_t));
-		}
-		// another stream than the batch's runs behind the batch (evStop closes every launch sequence, reruns included)
-		c->fin.run.begin( stream, c->lastStream, c->evStop);
-		hipEvent_t ev[ 5];
-		c->fin.run.events( ev);
-		HIP_CHECK( hipMemsetAsync( c->fin.dCursor.ptr, 0, 2*sizeof(uint32_t), stream));
-		if (exclusive) HIP_CHECK( hipMemsetAsync( c->fin.dCovered.ptr, 0, devResults+1, stream));
-		if (canonical) HIP_CHECK( hipMemsetAsync( c->fin.dSortCursor.ptr, 0, sizeof(uint32_t), stream));
-		FinishParams F;
-		std::memset( &F, 0, sizeof(F));
-		F.results = (const uint32_t*)c->io.results.ptr(); F.items = (const uint32_t*)c->io.items.ptr();
-		F.docRange = (const uint64_t*)c->io.dDocRange.ptr; F.docStatus = (const int32_t*)c->io.dDocStatus.ptr;
-		F.resultFormat = (const uint32_t*)c->io.dResultFormat.ptr; F.itemFormat = (const uint32_t*)c->io.dItemFormat.ptr;
-		F.nofResults = devResults; F.nofItems = devItems;
-		F.ndocs = (uint32_t)ndocs; F.withFormats = c->io.withFormats ? 1u : 0u;
-		F.exclusive = exclusive ? 1u : 0u; F.maxResultSize = c->inst->compiler.maxResultSize();
-		F.covered = (uint8_t*)c->fin.dCovered.ptr; F.kept = (uint32_t*)c->fin.dKept.ptr; F.cursor = (uint32_t*)c->fin.dCursor.ptr;
-		F.outResults = (uint32_t*)c->fin.dResults.ptr; F.outItems = (uint32_t*)c->fin.dItems.ptr;
-		F.docResultOffsets = (uint64_t*)c->fin.dDocResultOffsets.ptr; F.docItemOffsets = (uint64_t*)c->fin.dDocItemOffsets.ptr;
-		F.outResultFormat = (uint32_t*)c->fin.dResultFormat.ptr; F.outItemFormat = (uint32_t*)c->fin.dItemFormat.ptr;
-		F.totals = (uint64_t*)c->fin.dTotals.ptr;
-		if (canonical)
-		{
-			F.canonical = 1;
-			for (int i=0; i<2; ++i) { F.sortKeys[ i] = (uint64_t*)c->fin.dSortKeys[ i].ptr; F.sortIdx[ i] = (uint32_t*)c->fin.dSortIdx[ i].ptr; }
-			F.sortCursor = (uint32_t*)c->fin.dSortCursor.ptr;
-		}
-		HIP_CHECK( launchL2Finish( F, c->numCUs, stream, ev));
-		c->fin.run.completed( stream); c->fin.canonical = canonical;
-		if (out)
-		{
-			out->ndocs = ndocs;
-			out->d_results = c->fin.dResults.ptr; out->d_items = c->fin.dItems.ptr;
-			out->d_doc_result_offsets = c->fin.dDocResultOffsets.ptr; out->d_doc_item_offsets = c->fin.dDocItemOffsets.ptr;
-			out->d_result_format = c->io.withFormats ? c->fin.dResultFormat.ptr : 0;
-			out->d_item_format = c->io.withFormats ? c->fin.dItemFormat.ptr : 0;
-			out->d_totals = c->fin.dTotals.ptr;
-		}
-	});
-}
-
-// plain copy of the finished buffers: nothing is regrouped or eliminated on the host
-int sp_matcher_ctx_finished_fetch( sp_matcher_ctx_t* c, sp_match_batch_t* out)
-{
-	std::memset( out, 0, sizeof(*out));
-	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
-		if (!c->fin.run.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
-		HIP_CHECK( hipSetDevice( c->device));
-		HIP_CHECK( hipStreamSynchronize( c->fin.run.stream));
-		const size_t ndocs = c->lastNdocs;
-		uint64_t totals[ 2];
-		copySync( c->own, totals, c->fin.dTotals.ptr, sizeof(totals), hipMemcpyDeviceToHost);
-		allocMatchBatch( out, ndocs, totals[ 0], totals[ 1], c->io.withFormats);
-		if (totals[ 0]) copySync( c->own, out->results, c->fin.dResults.ptr, totals[ 0]*sizeof(sp_result_t), hipMemcpyDeviceToHost);
-		if (totals[ 1]) copySync( c->own, out->items, c->fin.dItems.ptr, totals[ 1]*sizeof(sp_result_item_t), hipMemcpyDeviceToHost);
-		copySync( c->own, out->doc_result_offsets, c->fin.dDocResultOffsets.ptr, (ndocs+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
-		if (ndocs)
-		{
-			copySync( c->own, out->doc_stats, c->io.dDocStats.ptr, ndocs*4*sizeof(uint64_t), hipMemcpyDeviceToHost);
-			copySync( c->own, out->doc_status, c->io.dDocStatus.ptr, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
-		}
-		if (c->io.withFormats)
-		{
-			if (totals[ 0]) copySync( c->own, out->result_format, c->fin.dResultFormat.ptr, totals[ 0]*sizeof(uint32_t), hipMemcpyDeviceToHost);
-			if (totals[ 1]) copySync( c->own, out->item_format, c->fin.dItemFormat.ptr, totals[ 1]*2*sizeof(uint32_t), hipMemcpyDeviceToHost);
-		}
-	});
-}
-
-// durations of the three passes of the last finish in milliseconds (HIP events on its stream)
-int sp_matcher_ctx_last_finish_ms( sp_matcher_ctx_t* c, double* count_ms, double* offsets_ms, double* place_ms)
-{
-	*offsets_ms = *place_ms = -1.0;
-	// (a canonical finish sorts between the offsets and the placement: the placement starts at ev[4] then)
-	int rc = c->fin.run.ms( 0, 1, count_ms);
-	if (rc == SP_OK) rc = c->fin.run.ms( 1, 2, offsets_ms);
-	if (rc == SP_OK) rc = c->fin.run.ms( c->fin.canonical ? 4 : 2, 3, place_ms);
-	return rc;
-}
-
-// duration of the sorting pass of the last finish (0.0 after a finish without SP_FINISH_CANONICAL)
-int sp_matcher_ctx_last_finish_sort_ms( sp_matcher_ctx_t* c, double* sort_ms)
-{
-	if (c->fin.run.evValid && !c->fin.canonical) { *sort_ms = 0.0; return SP_OK; }
-	return c->fin.run.ms( 2, 4, sort_ms);
-}
-
-uint32_t sp_matcher_finish_sort_tile(void) { return FINISH_SORT_TILE; }
-
-// ---- the text that the results and items of the finished batch cover, gathered on the device (l2_text.h)
-namespace {
-// grow-only, a failure is SP_ERR_NOMEM (the buffer is left empty, the context usable)
-void reserveOrNoMem( DeviceBuffer& buf, size_t n)
-{
-	try { buf.reserve( n); }
-	catch (const HipError&) { (void)hipGetLastError(); throw std::bad_alloc(); }
-}
-}
-
-int sp_matcher_ctx_finished_text_device( sp_matcher_ctx_t* c, const sp_text_source_t* src, uint32_t flags, void* stream_, sp_match_text_batch_t* out)
-{
-	if (out) std::memset( out, 0, sizeof(*out));
-	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
-		if (!flags || (flags & ~(uint32_t)(SP_TEXT_RESULTS | SP_TEXT_ITEMS))) throw std::runtime_error( "unknown or no text flags");
-		if (!src || !src->d_seg_offsets || (!src->d_text && src->nbytes)) throw std::runtime_error( "no text source");
-		if (!c->fin.run.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
-		const size_t ndocs = c->lastNdocs;
-		if (!src->d_doc_seg_offsets && src->nseg != ndocs) throw std::runtime_error( "without document segment offsets every document is one segment: nseg must be ndocs");
-		sp_matcher_ctx::Text& t = c->txt;
-		hipStream_t stream = (hipStream_t)stream_;
-		HIP_CHECK( hipSetDevice( c->device));
-		t.run.done = t.run.evValid = false;
-		// the span arrays are sized from the totals of the finish: this read waits for it
-		HIP_CHECK( hipStreamSynchronize( c->fin.run.stream));
-		uint64_t records[ 2];
-		copySync( c->own, records, c->fin.dTotals.ptr, sizeof(records), hipMemcpyDeviceToHost);
-		for (int f=0; f<2; ++f) if (flags & (1u << f))
-		{
-			reserveOrNoMem( t.dSpanWork[ f], (records[ f]+1)*sizeof(uint32_t));
-			reserveOrNoMem( t.dSpanOffsets[ f], (records[ f]+1)*sizeof(uint64_t));
-			reserveOrNoMem( t.dDocBytes[ f], (ndocs+1)*sizeof(uint64_t));
-			reserveOrNoMem( t.dDocTextOffsets[ f], (ndocs+1)*sizeof(uint64_t));
-		}
-		reserveOrNoMem( t.dStatus, (ndocs+1)*sizeof(int32_t));
-		reserveOrNoMem( t.dTotals, 2*sizeof(uint64_t));
-		reserveOrNoMem( t.dCursor, 4*sizeof(uint32_t));
-
-		// another stream than the finish's runs behind the finish
-		t.run.begin( stream, c->fin.run.stream, c->fin.run.ev[ 3]);
-		HIP_CHECK( hipMemsetAsync( t.dCursor.ptr, 0, 4*sizeof(uint32_t), stream));
-		HIP_CHECK( hipMemsetAsync( t.dTotals.ptr, 0, 2*sizeof(uint64_t), stream));
-		HIP_CHECK( hipMemsetAsync( t.dStatus.ptr, 0, (ndocs+1)*sizeof(int32_t), stream));
-		TextParams P;
-		std::memset( &P, 0, sizeof(P));
-		P.text = (const uint8_t*)src->d_text; P.nbytes = src->nbytes;
-		P.segOffsets = (const uint64_t*)src->d_seg_offsets; P.nseg = src->nseg;
-		P.docSegOffsets = (const uint64_t*)src->d_doc_seg_offsets;
-		P.ndocs = (uint32_t)ndocs; P.docStatus = (int32_t*)t.dStatus.ptr; P.families = flags;
-		for (int f=0; f<2; ++f) if (flags & (1u << f))
-		{
-			TextFamily& F = P.family[ f];
-			F.records = (const uint32_t*)(f ? c->fin.dItems.ptr : c->fin.dResults.ptr);
-			F.docOffsets = (const uint64_t*)(f ? c->fin.dDocItemOffsets.ptr : c->fin.dDocResultOffsets.ptr);
-			F.nrecords = records[ f];
-			F.spanWork = (uint32_t*)t.dSpanWork[ f].ptr; F.docBytes = (uint64_t*)t.dDocBytes[ f].ptr;
-			F.docTextOffsets = (uint64_t*)t.dDocTextOffsets[ f].ptr; F.spanOffsets = (uint64_t*)t.dSpanOffsets[ f].ptr;
-			F.total = (uint64_t*)t.dTotals.ptr + f; F.cursor = (uint32_t*)t.dCursor.ptr + 2*f;
-		}
-		HIP_CHECK( hipEventRecord( t.run.ev[ 0], stream));
-		HIP_CHECK( launchL2TextCount( P, c->numCUs, stream));
-		// the text buffers are sized from what the passes counted: this read waits for them, the placement below is not waited for
-		HIP_CHECK( hipStreamSynchronize( stream));
-		uint64_t totals[ 2];
-		copySync( c->own, totals, t.dTotals.ptr, sizeof(totals), hipMemcpyDeviceToHost);
-		for (int f=0; f<2; ++f) if (flags & (1u << f))
-		{
-			reserveOrNoMem( t.dText[ f], totals[ f] + 16);
-			P.family[ f].outText = (uint8_t*)t.dText[ f].ptr; P.family[ f].outCapacity = totals[ f];
-		}
-		HIP_CHECK( launchL2TextPlace( P, c->numCUs, stream));
-		HIP_CHECK( hipEventRecord( t.run.ev[ 1], stream));
-		t.run.completed( stream); t.flags = flags; t.ndocs = ndocs;
-		for (int f=0; f<2; ++f) { t.nrecords[ f] = records[ f]; t.totals[ f] = (flags & (1u << f)) ? totals[ f] : 0; }
-		if (out)
-		{
-			out->ndocs = ndocs;
-			if (flags & SP_TEXT_RESULTS) { out->d_result_text = t.dText[ 0].ptr; out->d_result_text_offsets = t.dSpanOffsets[ 0].ptr; }
-			if (flags & SP_TEXT_ITEMS) { out->d_item_text = t.dText[ 1].ptr; out->d_item_text_offsets = t.dSpanOffsets[ 1].ptr; }
-			out->d_doc_text_status = t.dStatus.ptr; out->d_totals = t.dTotals.ptr;
-		}
-	});
-}
-
-// plain copy of the text buffers
-int sp_matcher_ctx_finished_text_fetch( sp_matcher_ctx_t* c, sp_match_text_t* out)
-{
-	std::memset( out, 0, sizeof(*out));
-	const int rc = guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
-		const sp_matcher_ctx::Text& t = c->txt;
-		if (!t.run.done) throw std::runtime_error( "no text of the last batch of this context (sp_matcher_ctx_finished_text_device)");
-		HIP_CHECK( hipSetDevice( c->device));
-		HIP_CHECK( hipStreamSynchronize( t.run.stream));
-		allocMatchText( out, t.ndocs, t.nrecords[ 0], t.nrecords[ 1], t.flags);
-		out->totals[ 0] = t.totals[ 0]; out->totals[ 1] = t.totals[ 1];
-		allocMatchTextBytes( out, t.flags);
-		if (t.ndocs) copySync( c->own, out->doc_text_status, t.dStatus.ptr, t.ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
-		char* const text[ 2] = {out->result_text, out->item_text};
-		uint64_t* const offsets[ 2] = {out->result_text_offsets, out->item_text_offsets};
-		for (int f=0; f<2; ++f) if (t.flags & (1u << f))
-		{
-			copySync( c->own, offsets[ f], t.dSpanOffsets[ f].ptr, (t.nrecords[ f]+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
-			if (t.totals[ f]) copySync( c->own, text[ f], t.dText[ f].ptr, t.totals[ f], hipMemcpyDeviceToHost);
-		}
-	});
-	if (rc != SP_OK) sp_match_text_free( out);
-	return rc;
-}
-
-// duration of the passes of the last text call in milliseconds (HIP events on its stream)
-int sp_matcher_ctx_last_text_ms( sp_matcher_ctx_t* c, double* ms) { return c->txt.run.ms( 0, 1, ms); }
-
-uint32_t sp_matcher_text_long_span(void) { return TEXT_LONG_SPAN; }
-
-// ---- the values of the format strings of the finished batch, built on the device (l2_values.h)
-int sp_matcher_ctx_finished_values_device( sp_matcher_ctx_t* c, const sp_text_source_t* src, uint32_t flags, void* stream_, sp_match_values_batch_t* out)
-{
-	if (out) std::memset( out, 0, sizeof(*out));
-	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
-		if (!flags || (flags & ~(uint32_t)(SP_VALUE_RESULTS | SP_VALUE_ITEMS))) throw std::runtime_error( "unknown or no value flags");
-		if (!src || !src->d_seg_offsets || (!src->d_text && src->nbytes)) throw std::runtime_error( "no text source");
-		if (!c->fin.run.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
-		const size_t ndocs = c->lastNdocs;
-		if (!src->d_doc_seg_offsets && src->nseg != ndocs) throw std::runtime_error( "without document segment offsets every document is one segment: nseg must be ndocs");
-		const FormatTable& table = c->inst->formats();
-		if (!table.error.empty()) throw std::runtime_error( table.error);
-		sp_matcher_ctx::Values& v = c->val;
-		hipStream_t stream = (hipStream_t)stream_;
-		HIP_CHECK( hipSetDevice( c->device));
-		v.run.done = v.run.evValid = false;
-		if (!v.uploaded)
-		{
-			// the format table: once per context
-			reserveOrNoMem( v.dFmtParts, (table.fmtParts.size()+1)*sizeof(uint32_t));
-			reserveOrNoMem( v.dParts, (table.parts.size()+1)*sizeof(uint32_t));
-			reserveOrNoMem( v.dPool, table.pool.size()+16);
-			copySync( c->own, v.dFmtParts.ptr, table.fmtParts.data(), table.fmtParts.size()*sizeof(uint32_t), hipMemcpyHostToDevice);
-			if (!table.parts.empty()) copySync( c->own, v.dParts.ptr, table.parts.data(), table.parts.size()*sizeof(uint32_t), hipMemcpyHostToDevice);
-			if (!table.pool.empty()) copySync( c->own, v.dPool.ptr, table.pool.data(), table.pool.size(), hipMemcpyHostToDevice);
-			v.poolBytes = (uint32_t)table.pool.size();
-			v.uploaded = true;
-		}
-		// the value arrays are sized from the totals of the finish: this read waits for it
-		HIP_CHECK( hipStreamSynchronize( c->fin.run.stream));
-		uint64_t records[ 2];
-		copySync( c->own, records, c->fin.dTotals.ptr, sizeof(records), hipMemcpyDeviceToHost);
-		for (int f=0; f<2; ++f) if (flags & (1u << f))
-		{
-			reserveOrNoMem( v.dValueWork[ f], (records[ f]+1)*sizeof(uint32_t));
-			reserveOrNoMem( v.dValueOffsets[ f], (records[ f]+1)*sizeof(uint64_t));
-			reserveOrNoMem( v.dDocBytes[ f], (ndocs+1)*sizeof(uint64_t));
-			reserveOrNoMem( v.dDocValueOffsets[ f], (ndocs+1)*sizeof(uint64_t));
-		}
-		reserveOrNoMem( v.dStatus, (ndocs+1)*sizeof(int32_t));
-		reserveOrNoMem( v.dTotals, 2*sizeof(uint64_t));
-		reserveOrNoMem( v.dCursor, 4*sizeof(uint32_t));
-
-		// another stream than the finish's runs behind the finish
-		v.run.begin( stream, c->fin.run.stream, c->fin.run.ev[ 3]);
-		HIP_CHECK( hipMemsetAsync( v.dCursor.ptr, 0, 4*sizeof(uint32_t), stream));
-		HIP_CHECK( hipMemsetAsync( v.dTotals.ptr, 0, 2*sizeof(uint64_t), stream));
-		HIP_CHECK( hipMemsetAsync( v.dStatus.ptr, 0, (ndocs+1)*sizeof(int32_t), stream));
-		// a matcher without format strings has no format arrays: every value is empty, the passes only lay out the offsets
-		const bool withFormats = c->io.withFormats && table.count;
-		for (int f=0; f<2; ++f) if ((flags & (1u << f)) && !withFormats)
-		{
-			HIP_CHECK( hipMemsetAsync( v.dValueOffsets[ f].ptr, 0, (records[ f]+1)*sizeof(uint64_t), stream));
-		}
-		ValuesParams P;
-		std::memset( &P, 0, sizeof(P));
-		P.text = (const uint8_t*)src->d_text; P.nbytes = src->nbytes;
-		P.segOffsets = (const uint64_t*)src->d_seg_offsets; P.nseg = src->nseg;
-		P.docSegOffsets = (const uint64_t*)src->d_doc_seg_offsets;
-		P.fmtParts = (const uint32_t*)v.dFmtParts.ptr; P.parts = (const uint32_t*)v.dParts.ptr; P.pool = (const uint8_t*)v.dPool.ptr;
-		P.formatCount = table.count; P.poolBytes = v.poolBytes;
-		P.items = (const uint32_t*)c->fin.dItems.ptr; P.itemFormat = (const uint32_t*)c->fin.dItemFormat.ptr;
-		P.docItemOffsets = (const uint64_t*)c->fin.dDocItemOffsets.ptr; P.nitems = records[ 1];
-		P.ndocs = (uint32_t)ndocs; P.docStatus = (int32_t*)v.dStatus.ptr; P.families = withFormats ? flags : 0;
-		for (int f=0; f<2; ++f) if (flags & (1u << f))
-		{
-			ValuesFamily& F = P.family[ f];
-			F.records = (const uint32_t*)(f ? c->fin.dItems.ptr : c->fin.dResults.ptr);
-			F.format = (const uint32_t*)(f ? c->fin.dItemFormat.ptr : c->fin.dResultFormat.ptr);
-			F.docOffsets = (const uint64_t*)(f ? c->fin.dDocItemOffsets.ptr : c->fin.dDocResultOffsets.ptr);
-			F.nrecords = records[ f];
-			F.valueWork = (uint32_t*)v.dValueWork[ f].ptr; F.docBytes = (uint64_t*)v.dDocBytes[ f].ptr;
-			F.docValueOffsets = (uint64_t*)v.dDocValueOffsets[ f].ptr; F.valueOffsets = (uint64_t*)v.dValueOffsets[ f].ptr;
-			F.total = (uint64_t*)v.dTotals.ptr + f; F.cursor = (uint32_t*)v.dCursor.ptr + 2*f;
-		}
-		HIP_CHECK( hipEventRecord( v.run.ev[ 0], stream));
-		HIP_CHECK( launchL2ValuesCount( P, c->numCUs, stream));
-		// the value buffers are sized from what the passes counted: this read waits for them, the placement below is not waited for
-		HIP_CHECK( hipStreamSynchronize( stream));
-		uint64_t totals[ 2];
-		copySync( c->own, totals, v.dTotals.ptr, sizeof(totals), hipMemcpyDeviceToHost);
-		for (int f=0; f<2; ++f) if (flags & (1u << f))
-		{
-			reserveOrNoMem( v.dValues[ f], totals[ f] + 16);
-			P.family[ f].outValues = (uint8_t*)v.dValues[ f].ptr; P.family[ f].outCapacity = totals[ f];
-		}
-		HIP_CHECK( launchL2ValuesPlace( P, c->numCUs, stream));
-		HIP_CHECK( hipEventRecord( v.run.ev[ 1], stream));
-		v.run.completed( stream); v.flags = flags; v.ndocs = ndocs;
-		for (int f=0; f<2; ++f) { v.nrecords[ f] = records[ f]; v.totals[ f] = (flags & (1u << f)) ? totals[ f] : 0; }
-		if (out)
-		{
-			out->ndocs = ndocs;
-			if (flags & SP_VALUE_RESULTS) { out->d_result_values = v.dValues[ 0].ptr; out->d_result_value_offsets = v.dValueOffsets[ 0].ptr; }
-			if (flags & SP_VALUE_ITEMS) { out->d_item_values = v.dValues[ 1].ptr; out->d_item_value_offsets = v.dValueOffsets[ 1].ptr; }
-			out->d_doc_value_status = v.dStatus.ptr; out->d_totals = v.dTotals.ptr;
-		}
-	});
-}
-
-// plain copy of the value buffers
-int sp_matcher_ctx_finished_values_fetch( sp_matcher_ctx_t* c, sp_match_values_t* out)
-{
-	std::memset( out, 0, sizeof(*out));
-	const int rc = guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
-		const sp_matcher_ctx::Values& v = c->val;
-		if (!v.run.done) throw std::runtime_error( "no values of the last batch of this context (sp_matcher_ctx_finished_values_device)");
-		HIP_CHECK( hipSetDevice( c->device));
-		HIP_CHECK( hipStreamSynchronize( v.run.stream));
-		allocMatchValues( out, v.ndocs, v.nrecords[ 0], v.nrecords[ 1], v.flags);
-		out->totals[ 0] = v.totals[ 0]; out->totals[ 1] = v.totals[ 1];
-		allocMatchValuesBytes( out, v.flags);
-		if (v.ndocs) copySync( c->own, out->doc_value_status, v.dStatus.ptr, v.ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
-		char* const bytes[ 2] = {out->result_values, out->item_values};
-		uint64_t* const offsets[ 2] = {out->result_value_offsets, out->item_value_offsets};
-		for (int f=0; f<2; ++f) if (v.flags & (1u << f))
-		{
-			copySync( c->own, offsets[ f], v.dValueOffsets[ f].ptr, (v.nrecords[ f]+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
-			if (v.totals[ f]) copySync( c->own, bytes[ f], v.dValues[ f].ptr, v.totals[ f], hipMemcpyDeviceToHost);
-		}
-	});
-	if (rc != SP_OK) sp_match_values_free( out);
-	return rc;
-}
-
-// duration of the passes of the last values call in milliseconds (HIP events on its stream)
-int sp_matcher_ctx_last_values_ms( sp_matcher_ctx_t* c, double* ms) { return c->val.run.ms( 0, 1, ms); }
-
-uint32_t sp_matcher_value_max_depth(void) { return VALUE_MAX_DEPTH; }
-
-// the same rule over host arrays (result_values.hpp)
-int sp_match_batch_values( const sp_matcher_t* m, const sp_match_batch_t* mb, const char* text, uint64_t nbytes, const uint64_t* seg_offsets,
-			   size_t nseg, const uint64_t* doc_seg_offsets, uint32_t flags, sp_match_values_t* out, char* err, size_t errsize)
-{
-	std::memset( out, 0, sizeof(*out));
-	copyText( err, errsize, "");
-	try
-	{
-		if (!m) throw std::runtime_error( "no matcher");
-		if (!mb) throw std::runtime_error( "no batch");
-		const TextSource S = { text, nbytes, seg_offsets, nseg, doc_seg_offsets };
-		matchBatchValues( m->formats(), *mb, S, flags, out);
-		return SP_OK;
-	}
-	catch (const std::bad_alloc&) { sp_match_values_free( out); return SP_ERR_NOMEM; }
-	catch (const std::exception& e)
-	{
-		sp_match_values_free( out);
-		copyText( err, errsize, e.what());
-		return SP_ERR_INVALID;
-	}
-}
-
-// ---- the pattern frequencies of the finished batch, summed on the device (l2_freq.h)
-int sp_matcher_ctx_finished_pattern_freq_device( sp_matcher_ctx_t* c, void* stream_, sp_pattern_freq_device_t* out)
-{
-	if (out) std::memset( out, 0, sizeof(*out));
-	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
-		if (!c->fin.run.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
-		const size_t ndocs = c->lastNdocs;
-		const uint32_t bound = sp_matcher_handle_bound( c->inst);
-		sp_matcher_ctx::Freq& q = c->frq;
-		hipStream_t stream = (hipStream_t)stream_;
-		HIP_CHECK( hipSetDevice( c->device));
-		q.run.done = q.run.evValid = false;
-		// every result index is checked against the total of the finish: this read waits for it
-		HIP_CHECK( hipStreamSynchronize( c->fin.run.stream));
-		uint64_t finished[ 2];
-		copySync( c->own, finished, c->fin.dTotals.ptr, sizeof(finished), hipMemcpyDeviceToHost);
-		reserveOrNoMem( q.dDocCount, (ndocs+1)*sizeof(uint32_t));
-		reserveOrNoMem( q.dDocMeta, (ndocs+1)*4*sizeof(uint32_t));
-		reserveOrNoMem( q.dStatus, (ndocs+1)*sizeof(int32_t));
-		reserveOrNoMem( q.dDocOffsets, (ndocs+1)*sizeof(uint64_t));
-		reserveOrNoMem( q.dHandleResults, (size_t)bound*sizeof(uint64_t));
-		reserveOrNoMem( q.dHandleDocs, (size_t)bound*sizeof(uint32_t));
-		reserveOrNoMem( q.dTotals, sizeof(uint64_t));
-		reserveOrNoMem( q.dCursor, 2*sizeof(uint32_t));
-
-		// another stream than the finish's runs behind the finish
-		q.run.begin( stream, c->fin.run.stream, c->fin.run.ev[ 3]);
-		HIP_CHECK( hipMemsetAsync( q.dCursor.ptr, 0, 2*sizeof(uint32_t), stream));
-		HIP_CHECK( hipMemsetAsync( q.dTotals.ptr, 0, sizeof(uint64_t), stream));
-		HIP_CHECK( hipMemsetAsync( q.dStatus.ptr, 0, (ndocs+1)*sizeof(int32_t), stream));
-		HIP_CHECK( hipMemsetAsync( q.dHandleResults.ptr, 0, (size_t)bound*sizeof(uint64_t), stream));
-		HIP_CHECK( hipMemsetAsync( q.dHandleDocs.ptr, 0, (size_t)bound*sizeof(uint32_t), stream));
-		FreqParams P;
-		std::memset( &P, 0, sizeof(P));
-		P.results = (const uint32_t*)c->fin.dResults.ptr; P.docOffsets = (const uint64_t*)c->fin.dDocResultOffsets.ptr;
-		P.nresults = finished[ 0]; P.ndocs = (uint32_t)ndocs; P.handleBound = bound;
-		P.docCount = (uint32_t*)q.dDocCount.ptr; P.docMeta = (uint32_t*)q.dDocMeta.ptr; P.cursor = (uint32_t*)q.dCursor.ptr;
-		P.docStatus = (int32_t*)q.dStatus.ptr; P.docFreqOffsets = (uint64_t*)q.dDocOffsets.ptr; P.total = (uint64_t*)q.dTotals.ptr;
-		P.handleResults = (uint64_t*)q.dHandleResults.ptr; P.handleDocs = (uint32_t*)q.dHandleDocs.ptr;
-		HIP_CHECK( hipEventRecord( q.run.ev[ 0], stream));
-		HIP_CHECK( launchL2FreqCount( P, c->numCUs, stream));
-		// the records are sized from what the passes counted: this read waits for them, the passes below are not waited for
-		HIP_CHECK( hipStreamSynchronize( stream));
-		uint64_t total = 0;
-		copySync( c->own, &total, q.dTotals.ptr, sizeof(total), hipMemcpyDeviceToHost);
-		reserveOrNoMem( q.dRecords, (total+1)*sizeof(sp_pattern_freq_t));
-		P.records = (uint32_t*)q.dRecords.ptr; P.capacity = total;
-		if (total) HIP_CHECK( hipMemsetAsync( q.dRecords.ptr, 0, total*sizeof(sp_pattern_freq_t), stream));
-		HIP_CHECK( launchL2FreqPlace( P, c->numCUs, stream));
-		HIP_CHECK( hipEventRecord( q.run.ev[ 1], stream));
-		q.run.completed( stream); q.ndocs = ndocs; q.handleBound = bound; q.total = total;
-		if (out)
-		{
-			out->ndocs = ndocs; out->handle_bound = bound;
-			out->d_records = q.dRecords.ptr; out->d_doc_offsets = q.dDocOffsets.ptr; out->d_doc_freq_status = q.dStatus.ptr;
-			out->d_handle_results = q.dHandleResults.ptr; out->d_handle_docs = q.dHandleDocs.ptr; out->d_totals = q.dTotals.ptr;
-		}
-	});
-}
-
-// plain copy of the frequency buffers
-int sp_matcher_ctx_finished_pattern_freq_fetch( sp_matcher_ctx_t* c, sp_pattern_freq_batch_t* out)
-{
-	std::memset( out, 0, sizeof(*out));
-	const int rc = guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
-		const sp_matcher_ctx::Freq& q = c->frq;
-		if (!q.run.done) throw std::runtime_error( "no pattern frequencies of the last batch of this context (sp_matcher_ctx_finished_pattern_freq_device)");
-		HIP_CHECK( hipSetDevice( c->device));
-		HIP_CHECK( hipStreamSynchronize( q.run.stream));
-		allocPatternFreq( out, q.ndocs, q.handleBound);
-		allocPatternFreqRecords( out, q.total);
-		if (q.total) copySync( c->own, out->records, q.dRecords.ptr, q.total*sizeof(sp_pattern_freq_t), hipMemcpyDeviceToHost);
-		copySync( c->own, out->doc_offsets, q.dDocOffsets.ptr, (q.ndocs+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
-		if (q.ndocs) copySync( c->own, out->doc_freq_status, q.dStatus.ptr, q.ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
-		copySync( c->own, out->handle_results, q.dHandleResults.ptr, (size_t)q.handleBound*sizeof(uint64_t), hipMemcpyDeviceToHost);
-		copySync( c->own, out->handle_docs, q.dHandleDocs.ptr, (size_t)q.handleBound*sizeof(uint32_t), hipMemcpyDeviceToHost);
-	});
-	if (rc != SP_OK) sp_pattern_freq_batch_free( out);
-	return rc;
-}
-
-// duration of the passes of the last frequency call in milliseconds (HIP events on its stream)
-int sp_matcher_ctx_last_pattern_freq_ms( sp_matcher_ctx_t* c, double* ms) { return c->frq.run.ms( 0, 1, ms); }
-
-uint32_t sp_matcher_pattern_freq_window(void) { return FREQ_WINDOW; }
-
-// ---- the index terms of the finished batch, grouped on the device (l2_terms.h)
-namespace {
-// test hook: the bits of a term's hash that the device keeps (32 and more = all)
-std::atomic<unsigned>& termHashBits() { static std::atomic<unsigned> bits( 32); return bits; }
-}
-
-void sp_test_term_hash_bits( unsigned bits) { termHashBits().store( bits, std::memory_order_relaxed); }
-
-int sp_matcher_ctx_finished_terms_device( sp_matcher_ctx_t* c, uint32_t flags, void* stream_, sp_match_terms_device_t* out)
-{
-	if (out) std::memset( out, 0, sizeof(*out));
-	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
-		if (!flags || (flags & ~(uint32_t)(SP_TERM_VALUES | SP_TERM_TEXT))) throw std::runtime_error( "unknown or no term flags");
-		if (!c->fin.run.done) throw std::runtime_error( "the last batch of this context has not been finished (sp_matcher_ctx_batch_finish_device)");
-		const sp_matcher_ctx::Values& v = c->val;
-		const sp_matcher_ctx::Text& x = c->txt;
-		if ((flags & SP_TERM_VALUES) && !(v.run.done && (v.flags & SP_VALUE_RESULTS)))
-			throw std::runtime_error( "no values of the results of the last finished batch (sp_matcher_ctx_finished_values_device with SP_VALUE_RESULTS)");
-		if ((flags & SP_TERM_TEXT) && !(x.run.done && (x.flags & SP_TEXT_RESULTS)))
-			throw std::runtime_error( "no text of the results of the last finished batch (sp_matcher_ctx_finished_text_device with SP_TEXT_RESULTS)");
-		const size_t ndocs = c->lastNdocs;
-		const uint32_t bound = sp_matcher_handle_bound( c->inst);
-		sp_matcher_ctx::Terms& t = c->trm;
-		hipStream_t stream = (hipStream_t)stream_;
-		HIP_CHECK( hipSetDevice( c->device));
-		t.run.done = t.run.evValid = false;
-		// every result index is checked against the total of the finish: this read waits for it
-		HIP_CHECK( hipStreamSynchronize( c->fin.run.stream));
-		uint64_t finished[ 2];
-		copySync( c->own, finished, c->fin.dTotals.ptr, sizeof(finished), hipMemcpyDeviceToHost);
-		const uint64_t nresults = finished[ 0];
-		if ((flags & SP_TERM_VALUES) && v.nrecords[ 0] != nresults) throw std::runtime_error( "the values are not those of the finished batch");
-		if ((flags & SP_TERM_TEXT) && x.nrecords[ 0] != nresults) throw std::runtime_error( "the text is not that of the finished batch");
-		const unsigned waves = l2TermsWaves( ndocs, c->numCUs);
-		reserveOrNoMem( t.dLeader, (nresults+1)*sizeof(uint32_t));
-		reserveOrNoMem( t.dTable, (nresults+1)*2*sizeof(uint32_t));
-		reserveOrNoMem( t.dResultTerm, (nresults+1)*sizeof(uint32_t));
-		reserveOrNoMem( t.dHistogram, (size_t)waves*bound*sizeof(uint32_t));
-		reserveOrNoMem( t.dDocCount, (ndocs+1)*sizeof(uint32_t));
-		reserveOrNoMem( t.dStatus, (ndocs+1)*sizeof(int32_t));
-		reserveOrNoMem( t.dDocOffsets, (ndocs+1)*sizeof(uint64_t));
-		reserveOrNoMem( t.dTotals, sizeof(uint64_t));
-		reserveOrNoMem( t.dCursor, 2*sizeof(uint32_t));
-
-		// another stream than the finish's runs behind the finish, and behind the values and the text call, whose placements
-		// nobody has waited for yet
-		t.run.begin( stream, c->fin.run.stream, c->fin.run.ev[ 3]);
-		if ((flags & SP_TERM_VALUES) && stream != v.run.stream) HIP_CHECK( hipStreamWaitEvent( stream, v.run.ev[ 1], 0));
-		if ((flags & SP_TERM_TEXT) && stream != x.run.stream) HIP_CHECK( hipStreamWaitEvent( stream, x.run.ev[ 1], 0));
-		HIP_CHECK( hipMemsetAsync( t.dCursor.ptr, 0, 2*sizeof(uint32_t), stream));
-		HIP_CHECK( hipMemsetAsync( t.dTotals.ptr, 0, sizeof(uint64_t), stream));
-		HIP_CHECK( hipMemsetAsync( t.dStatus.ptr, 0, (ndocs+1)*sizeof(int32_t), stream));
-		TermsParams P;
-		std::memset( &P, 0, sizeof(P));
-		P.results = (const uint32_t*)c->fin.dResults.ptr; P.docOffsets = (const uint64_t*)c->fin.dDocResultOffsets.ptr;
-		P.resultFormat = c->io.withFormats ? (const uint32_t*)c->fin.dResultFormat.ptr : 0;
-		P.nresults = nresults; P.ndocs = (uint32_t)ndocs; P.handleBound = bound; P.flags = flags;
-		const unsigned bits = termHashBits().load( std::memory_order_relaxed);
-		P.hashMask = bits >= 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
-		if (flags & SP_TERM_VALUES)
-		{
-			const TermSourceDevice S = { (const uint8_t*)v.dValues[ 0].ptr, (const uint64_t*)v.dValueOffsets[ 0].ptr, v.totals[ 0], (const int32_t*)v.dStatus.ptr };
-			P.source[ 0] = S;
-		}
-		if (flags & SP_TERM_TEXT)
-		{
-			const TermSourceDevice S = { (const uint8_t*)x.dText[ 0].ptr, (const uint64_t*)x.dSpanOffsets[ 0].ptr, x.totals[ 0], (const int32_t*)x.dStatus.ptr };
-			P.source[ 1] = S;
-		}
-		P.leader = (uint32_t*)t.dLeader.ptr; P.table = (uint32_t*)t.dTable.ptr; P.histogram = (uint32_t*)t.dHistogram.ptr;
-		P.docCount = (uint32_t*)t.dDocCount.ptr; P.cursor = (uint32_t*)t.dCursor.ptr;
-		P.docStatus = (int32_t*)t.dStatus.ptr; P.docTermOffsets = (uint64_t*)t.dDocOffsets.ptr; P.total = (uint64_t*)t.dTotals.ptr;
-		P.resultTerm = (uint32_t*)t.dResultTerm.ptr;
-		HIP_CHECK( hipEventRecord( t.run.ev[ 0], stream));
-		HIP_CHECK( launchL2TermsCount( P, c->numCUs, stream));
-		// the records are sized from what the passes counted: this read waits for them, the placement below is not waited for
-		HIP_CHECK( hipStreamSynchronize( stream));
-		uint64_t total = 0;
-		copySync( c->own, &total, t.dTotals.ptr, sizeof(total), hipMemcpyDeviceToHost);
-		reserveOrNoMem( t.dRecords, (total+1)*sizeof(sp_match_term_t));
-		P.records = (uint32_t*)t.dRecords.ptr; P.capacity = total;
-		HIP_CHECK( launchL2TermsPlace( P, c->numCUs, stream));
-		HIP_CHECK( hipEventRecord( t.run.ev[ 1], stream));
-		t.run.completed( stream); t.ndocs = ndocs; t.handleBound = bound; t.flags = flags; t.nresults = nresults; t.total = total;
-		if (out)
-		{
-			out->ndocs = ndocs; out->handle_bound = bound; out->flags = flags;
-			out->d_records = t.dRecords.ptr; out->d_doc_term_offsets = t.dDocOffsets.ptr; out->d_result_term = t.dResultTerm.ptr;
-			out->d_doc_term_status = t.dStatus.ptr; out->d_totals = t.dTotals.ptr;
-		}
-	});
-}
-
-// plain copy of the term buffers
-int sp_matcher_ctx_finished_terms_fetch( sp_matcher_ctx_t* c, sp_match_terms_t* out)
-{
-	std::memset( out, 0, sizeof(*out));
-	const int rc = guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
-		const sp_matcher_ctx::Terms& t = c->trm;
-		if (!t.run.done) throw std::runtime_error( "no terms of the last batch of this context (sp_matcher_ctx_finished_terms_device)");
-		HIP_CHECK( hipSetDevice( c->device));
-		HIP_CHECK( hipStreamSynchronize( t.run.stream));
-		allocMatchTerms( out, t.ndocs, t.nresults, t.handleBound, t.flags);
-		allocMatchTermRecords( out, t.total);
-		if (t.total) copySync( c->own, out->records, t.dRecords.ptr, t.total*sizeof(sp_match_term_t), hipMemcpyDeviceToHost);
-		copySync( c->own, out->doc_term_offsets, t.dDocOffsets.ptr, (t.ndocs+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
-		if (t.nresults) copySync( c->own, out->result_term, t.dResultTerm.ptr, t.nresults*sizeof(uint32_t), hipMemcpyDeviceToHost);
-		if (t.ndocs) copySync( c->own, out->doc_term_status, t.dStatus.ptr, t.ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
-	});
-	if (rc != SP_OK) sp_match_terms_free( out);
-	return rc;
-}
-
-// duration of the passes of the last terms call in milliseconds (HIP events on its stream)
-int sp_matcher_ctx_last_terms_ms( sp_matcher_ctx_t* c, double* ms) { return c->trm.run.ms( 0, 1, ms); }
-
-uint32_t sp_matcher_term_tile(void) { return TERM_TILE; }
 
 double sp_matcher_ctx_last_kernel_ms( sp_matcher_ctx_t* c) { return lastKernelMs( c); }
 

@@ -1,0 +1,529 @@
+// C-ABI of level 2, second half: the last device batch finished on the device and what is made of the finished batch there --
+// matched text, result values, pattern frequencies, index terms -- with their fetch and timing calls.  Every product is one
+// ProductCall (capi_l2_ctx.hpp) behind the finish; sp_matcher_ctx::Products::drop() is what a new batch or finish does to them.
+#include "capi_l2_ctx.hpp"
+#include "l2_finish.h"
+#include "l2_text.h"
+#include "l2_freq.h"
+#include "l2_values.h"
+#include "l2_terms.h"
+#include "match_terms.hpp"
+#include "span_text.hpp"
+#include "pattern_freq.hpp"
+
+typedef sp_matcher_ctx::ByteFamilies ByteFamilies;
+
+namespace {
+
+// a fetch call: the host waits for the product `run` (without one: `missing`), `copy` fills `out`, which is empty after a failure
+template <int N, class OUT, class FN>
+int fetchProduct( sp_matcher_ctx* c, const PassRun<N>& run, const char* missing, OUT* out, void (*release)( OUT*), FN copy)
+{
+	std::memset( out, 0, sizeof(*out));
+	const int rc = guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (!run.done) throw std::runtime_error( missing);
+		HIP_CHECK( hipSetDevice( c->device));
+		HIP_CHECK( hipStreamSynchronize( run.stream));
+		copy();
+	});
+	if (rc != SP_OK) release( out);
+	return rc;
+}
+
+// ---- the two products of bytes per record (text, values)
+
+// the text source of both calls, checked against the finished batch
+void checkTextSource( const sp_matcher_ctx* c, const sp_text_source_t* src)
+{
+	if (!src || !src->d_seg_offsets || (!src->d_text && src->nbytes)) throw std::runtime_error( "no text source");
+	requireFinished( c);
+	if (!src->d_doc_seg_offsets && src->nseg != c->lastNdocs) throw std::runtime_error( "without document segment offsets every document is one segment: nseg must be ndocs");
+}
+
+// The working arrays of the families in `flags`, sized from the totals of the finish; the run begins; P gets what TextParams and
+// ValuesParams name alike: the text source, and per family the records of the finish and the buffers.  `named` sets what
+// the family structs name differently.
+template <class PARAMS, class NAMED>
+void beginByteFamilies( ProductCall& call, ByteFamilies& b, uint32_t flags, const sp_text_source_t* src, PARAMS& P, NAMED named)
+{
+	const sp_matcher_ctx::Finished& fin = call.c->prod.fin;
+	for (int f=0; f<2; ++f) if (flags & (1u << f))
+	{
+		reserveOrNoMem( b.dWork[ f], (call.finished[ f]+1)*sizeof(uint32_t));
+		reserveOrNoMem( b.dOffsets[ f], (call.finished[ f]+1)*sizeof(uint64_t));
+		reserveOrNoMem( b.dDocBytes[ f], (call.ndocs+1)*sizeof(uint64_t));
+		reserveOrNoMem( b.dDocOffsets[ f], (call.ndocs+1)*sizeof(uint64_t));
+	}
+	call.begin( b.dStatus, b.dTotals, 2, b.dCursor, 4);
+	std::memset( &P, 0, sizeof(P));
+	P.text = (const uint8_t*)src->d_text; P.nbytes = src->nbytes;
+	P.segOffsets = (const uint64_t*)src->d_seg_offsets; P.nseg = src->nseg;
+	P.docSegOffsets = (const uint64_t*)src->d_doc_seg_offsets;
+	P.ndocs = (uint32_t)call.ndocs; P.docStatus = (int32_t*)b.dStatus.ptr; P.families = flags;
+	for (int f=0; f<2; ++f) if (flags & (1u << f))
+	{
+		auto& F = P.family[ f];
+		F.records = (const uint32_t*)(f ? fin.dItems.ptr : fin.dResults.ptr);
+		F.docOffsets = (const uint64_t*)(f ? fin.dDocItemOffsets.ptr : fin.dDocResultOffsets.ptr);
+		F.nrecords = call.finished[ f];
+		F.docBytes = (uint64_t*)b.dDocBytes[ f].ptr; F.total = (uint64_t*)b.dTotals.ptr + f; F.cursor = (uint32_t*)b.dCursor.ptr + 2*f;
+		named( F, (uint32_t*)b.dWork[ f].ptr, (uint64_t*)b.dDocOffsets[ f].ptr, (uint64_t*)b.dOffsets[ f].ptr, f);
+	}
+}
+
+// the passes of both calls: the byte buffers are sized from what the counting passes counted
+template <class PARAMS, class FAMILY>
+void byteFamilyPasses( ProductCall& call, ByteFamilies& b, uint32_t flags, PARAMS& P, uint8_t* FAMILY::*outBytes,
+		       hipError_t (*count)( const PARAMS&, unsigned, hipStream_t), hipError_t (*place)( const PARAMS&, unsigned, hipStream_t))
+{
+	uint64_t totals[ 2];
+	call.passes( P, count, place, b.dTotals, totals, 2, [&]{
+		for (int f=0; f<2; ++f) if (flags & (1u << f))
+		{
+			reserveOrNoMem( b.dBytes[ f], totals[ f] + 16);
+			P.family[ f].*outBytes = (uint8_t*)b.dBytes[ f].ptr; P.family[ f].outCapacity = totals[ f];
+		}
+	});
+	b.flags = flags; b.ndocs = call.ndocs;
+	for (int f=0; f<2; ++f) { b.nrecords[ f] = call.finished[ f]; b.totals[ f] = (flags & (1u << f)) ? totals[ f] : 0; }
+}
+
+// plain copy of the buffers into the arrays of a host struct allocated for b.nrecords and b.totals
+void fetchByteFamilies( const sp_matcher_ctx* c, const ByteFamilies& b, int32_t* status, char* const bytes[ 2], uint64_t* const offsets[ 2])
+{
+	if (b.ndocs) copySync( c->own, status, b.dStatus.ptr, b.ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+	for (int f=0; f<2; ++f) if (b.flags & (1u << f))
+	{
+		copySync( c->own, offsets[ f], b.dOffsets[ f].ptr, (b.nrecords[ f]+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		if (b.totals[ f]) copySync( c->own, bytes[ f], b.dBytes[ f].ptr, b.totals[ f], hipMemcpyDeviceToHost);
+	}
+}
+
+// test hook: the bits of a term's hash that the device keeps (32 and more = all)
+std::atomic<unsigned>& termHashBits() { static std::atomic<unsigned> bits( 32); return bits; }
+
+} // namespace
+
+extern "C" {
+
+// ---- the last device batch finished on the device: document order, `exclusive` applied, items without gaps (l2_finish.h)
+int sp_matcher_ctx_batch_finish_device( sp_matcher_ctx_t* c, void* stream, sp_match_finished_batch_t* out)
+{ return sp_matcher_ctx_batch_finish_device_ex( c, stream, 0, out); }
+
+// flags: SP_FINISH_CANONICAL orders the results of every document by the tuple T of the header
+int sp_matcher_ctx_batch_finish_device_ex( sp_matcher_ctx_t* c, void* stream_, uint32_t flags, sp_match_finished_batch_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (flags & ~(uint32_t)SP_FINISH_CANONICAL) throw std::runtime_error( "unknown finish flags");
+		const bool canonical = (flags & SP_FINISH_CANONICAL) != 0;
+		if (!c->haveBatch) throw std::runtime_error( "no batch to finish: no batch has run on this context");
+		hipStream_t stream = (hipStream_t)stream_;
+		HIP_CHECK( hipSetDevice( c->device));
+		c->prod.drop();
+		sp_matcher_ctx::Finished& fin = c->prod.fin;
+		// the buffers are sized from what the batch counted: this read waits for the batch, the passes below do not
+		HIP_CHECK( hipStreamSynchronize( c->lastStream));
+		const BatchCounts counts = readCounts( c);
+		const uint64_t devResults = counts.results, devItems = counts.items;
+		const size_t ndocs = c->lastNdocs;
+		const bool exclusive = c->inst->compiler.exclusive();
+		fin.dResults.reserve( (devResults+1)*sizeof(sp_result_t));
+		fin.dItems.reserve( (devItems+1)*sizeof(sp_result_item_t));
+		if (c->io.withFormats)
+		{
+			fin.dResultFormat.reserve( (devResults+1)*sizeof(uint32_t));
+			fin.dItemFormat.reserve( (devItems+1)*2*sizeof(uint32_t));
+		}
+		fin.dDocResultOffsets.reserve( (ndocs+1)*sizeof(uint64_t));
+		fin.dDocItemOffsets.reserve( (ndocs+1)*sizeof(uint64_t));
+		fin.dKept.reserve( (ndocs+1)*2*sizeof(uint32_t));
+		if (!fin.dTotals.ptr) fin.dTotals.alloc( 2*sizeof(uint64_t));
+		if (!fin.dCursor.ptr) fin.dCursor.alloc( 2*sizeof(uint32_t));
+		if (exclusive) fin.dCovered.reserve( devResults+1);
+		if (canonical)
+		{
+			for (int i=0; i<2; ++i)
+			{
+				fin.dSortKeys[ i].reserve( (devResults+1)*sizeof(uint64_t));
+				fin.dSortIdx[ i].reserve( (devResults+1)*sizeof(uint32_t));
+			}
+			if (!fin.dSortCursor.ptr) fin.dSortCursor.alloc( sizeof(uint32_t));
+		}
+		// another stream than the batch's runs behind the batch (evStop closes every launch sequence, reruns included)
+		fin.run.begin( stream, c->lastStream, c->evStop);
+		hipEvent_t ev[ 5];
+		fin.run.events( ev);
+		HIP_CHECK( hipMemsetAsync( fin.dCursor.ptr, 0, 2*sizeof(uint32_t), stream));
+		if (exclusive) HIP_CHECK( hipMemsetAsync( fin.dCovered.ptr, 0, devResults+1, stream));
+		if (canonical) HIP_CHECK( hipMemsetAsync( fin.dSortCursor.ptr, 0, sizeof(uint32_t), stream));
+		FinishParams F;
+		std::memset( &F, 0, sizeof(F));
+		F.results = (const uint32_t*)c->io.results.ptr(); F.items = (const uint32_t*)c->io.items.ptr();
+		F.docRange = (const uint64_t*)c->io.dDocRange.ptr; F.docStatus = (const int32_t*)c->io.dDocStatus.ptr;
+		F.resultFormat = (const uint32_t*)c->io.dResultFormat.ptr; F.itemFormat = (const uint32_t*)c->io.dItemFormat.ptr;
+		F.nofResults = devResults; F.nofItems = devItems;
+		F.ndocs = (uint32_t)ndocs; F.withFormats = c->io.withFormats ? 1u : 0u;
+		F.exclusive = exclusive ? 1u : 0u; F.maxResultSize = c->inst->compiler.maxResultSize();
+		F.covered = (uint8_t*)fin.dCovered.ptr; F.kept = (uint32_t*)fin.dKept.ptr; F.cursor = (uint32_t*)fin.dCursor.ptr;
+		F.outResults = (uint32_t*)fin.dResults.ptr; F.outItems = (uint32_t*)fin.dItems.ptr;
+		F.docResultOffsets = (uint64_t*)fin.dDocResultOffsets.ptr; F.docItemOffsets = (uint64_t*)fin.dDocItemOffsets.ptr;
+		F.outResultFormat = (uint32_t*)fin.dResultFormat.ptr; F.outItemFormat = (uint32_t*)fin.dItemFormat.ptr;
+		F.totals = (uint64_t*)fin.dTotals.ptr;
+		if (canonical)
+		{
+			F.canonical = 1;
+			for (int i=0; i<2; ++i) { F.sortKeys[ i] = (uint64_t*)fin.dSortKeys[ i].ptr; F.sortIdx[ i] = (uint32_t*)fin.dSortIdx[ i].ptr; }
+			F.sortCursor = (uint32_t*)fin.dSortCursor.ptr;
+		}
+		HIP_CHECK( launchL2Finish( F, c->numCUs, stream, ev));
+		fin.run.completed( stream); fin.canonical = canonical;
+		if (out)
+		{
+			out->ndocs = ndocs;
+			out->d_results = fin.dResults.ptr; out->d_items = fin.dItems.ptr;
+			out->d_doc_result_offsets = fin.dDocResultOffsets.ptr; out->d_doc_item_offsets = fin.dDocItemOffsets.ptr;
+			out->d_result_format = c->io.withFormats ? fin.dResultFormat.ptr : 0;
+			out->d_item_format = c->io.withFormats ? fin.dItemFormat.ptr : 0;
+			out->d_totals = fin.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the finished buffers: nothing is regrouped or eliminated on the host
+int sp_matcher_ctx_finished_fetch( sp_matcher_ctx_t* c, sp_match_batch_t* out)
+{
+	std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		const sp_matcher_ctx::Finished& fin = c->prod.fin;
+		requireFinished( c);
+		HIP_CHECK( hipSetDevice( c->device));
+		HIP_CHECK( hipStreamSynchronize( fin.run.stream));
+		const size_t ndocs = c->lastNdocs;
+		uint64_t totals[ 2];
+		copySync( c->own, totals, fin.dTotals.ptr, sizeof(totals), hipMemcpyDeviceToHost);
+		allocMatchBatch( out, ndocs, totals[ 0], totals[ 1], c->io.withFormats);
+		if (totals[ 0]) copySync( c->own, out->results, fin.dResults.ptr, totals[ 0]*sizeof(sp_result_t), hipMemcpyDeviceToHost);
+		if (totals[ 1]) copySync( c->own, out->items, fin.dItems.ptr, totals[ 1]*sizeof(sp_result_item_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->doc_result_offsets, fin.dDocResultOffsets.ptr, (ndocs+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		if (ndocs)
+		{
+			copySync( c->own, out->doc_stats, c->io.dDocStats.ptr, ndocs*4*sizeof(uint64_t), hipMemcpyDeviceToHost);
+			copySync( c->own, out->doc_status, c->io.dDocStatus.ptr, ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+		}
+		if (c->io.withFormats)
+		{
+			if (totals[ 0]) copySync( c->own, out->result_format, fin.dResultFormat.ptr, totals[ 0]*sizeof(uint32_t), hipMemcpyDeviceToHost);
+			if (totals[ 1]) copySync( c->own, out->item_format, fin.dItemFormat.ptr, totals[ 1]*2*sizeof(uint32_t), hipMemcpyDeviceToHost);
+		}
+	});
+}
+
+// durations of the three passes of the last finish in milliseconds (HIP events on its stream)
+int sp_matcher_ctx_last_finish_ms( sp_matcher_ctx_t* c, double* count_ms, double* offsets_ms, double* place_ms)
+{
+	const sp_matcher_ctx::Finished& fin = c->prod.fin;
+	*offsets_ms = *place_ms = -1.0;
+	// (a canonical finish sorts between the offsets and the placement: the placement starts at ev[4] then)
+	int rc = fin.run.ms( 0, 1, count_ms);
+	if (rc == SP_OK) rc = fin.run.ms( 1, 2, offsets_ms);
+	if (rc == SP_OK) rc = fin.run.ms( fin.canonical ? 4 : 2, 3, place_ms);
+	return rc;
+}
+
+// duration of the sorting pass of the last finish (0.0 after a finish without SP_FINISH_CANONICAL)
+int sp_matcher_ctx_last_finish_sort_ms( sp_matcher_ctx_t* c, double* sort_ms)
+{
+	const sp_matcher_ctx::Finished& fin = c->prod.fin;
+	if (fin.run.evValid && !fin.canonical) { *sort_ms = 0.0; return SP_OK; }
+	return fin.run.ms( 2, 4, sort_ms);
+}
+
+uint32_t sp_matcher_finish_sort_tile(void) { return FINISH_SORT_TILE; }
+
+// ---- the text that the results and items of the finished batch cover, gathered on the device (l2_text.h)
+int sp_matcher_ctx_finished_text_device( sp_matcher_ctx_t* c, const sp_text_source_t* src, uint32_t flags, void* stream, sp_match_text_batch_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (!flags || (flags & ~(uint32_t)(SP_TEXT_RESULTS | SP_TEXT_ITEMS))) throw std::runtime_error( "unknown or no text flags");
+		checkTextSource( c, src);
+		ByteFamilies& t = c->prod.txt;
+		ProductCall call( c, t.run, stream);
+		TextParams P;
+		beginByteFamilies( call, t, flags, src, P, []( TextFamily& F, uint32_t* work, uint64_t* docOffsets, uint64_t* offsets, int){
+			F.spanWork = work; F.docTextOffsets = docOffsets; F.spanOffsets = offsets;
+		});
+		byteFamilyPasses( call, t, flags, P, &TextFamily::outText, launchL2TextCount, launchL2TextPlace);
+		if (out)
+		{
+			out->ndocs = call.ndocs;
+			if (flags & SP_TEXT_RESULTS) { out->d_result_text = t.dBytes[ 0].ptr; out->d_result_text_offsets = t.dOffsets[ 0].ptr; }
+			if (flags & SP_TEXT_ITEMS) { out->d_item_text = t.dBytes[ 1].ptr; out->d_item_text_offsets = t.dOffsets[ 1].ptr; }
+			out->d_doc_text_status = t.dStatus.ptr; out->d_totals = t.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the text buffers
+int sp_matcher_ctx_finished_text_fetch( sp_matcher_ctx_t* c, sp_match_text_t* out)
+{
+	const ByteFamilies& t = c->prod.txt;
+	return fetchProduct( c, t.run, "no text of the last batch of this context (sp_matcher_ctx_finished_text_device)", out, sp_match_text_free, [&]{
+		allocMatchText( out, t.ndocs, t.nrecords[ 0], t.nrecords[ 1], t.flags);
+		out->totals[ 0] = t.totals[ 0]; out->totals[ 1] = t.totals[ 1];
+		allocMatchTextBytes( out, t.flags);
+		char* const text[ 2] = {out->result_text, out->item_text};
+		uint64_t* const offsets[ 2] = {out->result_text_offsets, out->item_text_offsets};
+		fetchByteFamilies( c, t, out->doc_text_status, text, offsets);
+	});
+}
+
+// duration of the passes of the last text call in milliseconds (HIP events on its stream)
+int sp_matcher_ctx_last_text_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.txt.run.ms( 0, 1, ms); }
+
+uint32_t sp_matcher_text_long_span(void) { return TEXT_LONG_SPAN; }
+
+// ---- the values of the format strings of the finished batch, built on the device (l2_values.h)
+int sp_matcher_ctx_finished_values_device( sp_matcher_ctx_t* c, const sp_text_source_t* src, uint32_t flags, void* stream, sp_match_values_batch_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (!flags || (flags & ~(uint32_t)(SP_VALUE_RESULTS | SP_VALUE_ITEMS))) throw std::runtime_error( "unknown or no value flags");
+		checkTextSource( c, src);
+		const FormatTable& table = c->inst->formats();
+		if (!table.error.empty()) throw std::runtime_error( table.error);
+		const sp_matcher_ctx::Finished& fin = c->prod.fin;
+		sp_matcher_ctx::Values& v = c->prod.val;
+		ProductCall call( c, v.run, stream);
+		if (!v.uploaded)
+		{
+			// the format table: once per context
+			reserveOrNoMem( v.dFmtParts, (table.fmtParts.size()+1)*sizeof(uint32_t));
+			reserveOrNoMem( v.dParts, (table.parts.size()+1)*sizeof(uint32_t));
+			reserveOrNoMem( v.dPool, table.pool.size()+16);
+			copySync( c->own, v.dFmtParts.ptr, table.fmtParts.data(), table.fmtParts.size()*sizeof(uint32_t), hipMemcpyHostToDevice);
+			if (!table.parts.empty()) copySync( c->own, v.dParts.ptr, table.parts.data(), table.parts.size()*sizeof(uint32_t), hipMemcpyHostToDevice);
+			if (!table.pool.empty()) copySync( c->own, v.dPool.ptr, table.pool.data(), table.pool.size(), hipMemcpyHostToDevice);
+			v.poolBytes = (uint32_t)table.pool.size();
+			v.uploaded = true;
+		}
+		ValuesParams P;
+		beginByteFamilies( call, v, flags, src, P, [&]( ValuesFamily& F, uint32_t* work, uint64_t* docOffsets, uint64_t* offsets, int f){
+			F.valueWork = work; F.docValueOffsets = docOffsets; F.valueOffsets = offsets;
+			F.format = (const uint32_t*)(f ? fin.dItemFormat.ptr : fin.dResultFormat.ptr);
+		});
+		// a matcher without format strings has no format arrays: every value is empty, the passes only lay out the offsets
+		const bool withFormats = c->io.withFormats && table.count;
+		for (int f=0; f<2; ++f) if ((flags & (1u << f)) && !withFormats)
+		{
+			HIP_CHECK( hipMemsetAsync( v.dOffsets[ f].ptr, 0, (call.finished[ f]+1)*sizeof(uint64_t), call.stream));
+		}
+		P.families = withFormats ? flags : 0;
+		P.fmtParts = (const uint32_t*)v.dFmtParts.ptr; P.parts = (const uint32_t*)v.dParts.ptr; P.pool = (const uint8_t*)v.dPool.ptr;
+		P.formatCount = table.count; P.poolBytes = v.poolBytes;
+		P.items = (const uint32_t*)fin.dItems.ptr; P.itemFormat = (const uint32_t*)fin.dItemFormat.ptr;
+		P.docItemOffsets = (const uint64_t*)fin.dDocItemOffsets.ptr; P.nitems = call.finished[ 1];
+		byteFamilyPasses( call, v, flags, P, &ValuesFamily::outValues, launchL2ValuesCount, launchL2ValuesPlace);
+		if (out)
+		{
+			out->ndocs = call.ndocs;
+			if (flags & SP_VALUE_RESULTS) { out->d_result_values = v.dBytes[ 0].ptr; out->d_result_value_offsets = v.dOffsets[ 0].ptr; }
+			if (flags & SP_VALUE_ITEMS) { out->d_item_values = v.dBytes[ 1].ptr; out->d_item_value_offsets = v.dOffsets[ 1].ptr; }
+			out->d_doc_value_status = v.dStatus.ptr; out->d_totals = v.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the value buffers
+int sp_matcher_ctx_finished_values_fetch( sp_matcher_ctx_t* c, sp_match_values_t* out)
+{
+	const ByteFamilies& v = c->prod.val;
+	return fetchProduct( c, v.run, "no values of the last batch of this context (sp_matcher_ctx_finished_values_device)", out, sp_match_values_free, [&]{
+		allocMatchValues( out, v.ndocs, v.nrecords[ 0], v.nrecords[ 1], v.flags);
+		out->totals[ 0] = v.totals[ 0]; out->totals[ 1] = v.totals[ 1];
+		allocMatchValuesBytes( out, v.flags);
+		char* const bytes[ 2] = {out->result_values, out->item_values};
+		uint64_t* const offsets[ 2] = {out->result_value_offsets, out->item_value_offsets};
+		fetchByteFamilies( c, v, out->doc_value_status, bytes, offsets);
+	});
+}
+
+// duration of the passes of the last values call in milliseconds (HIP events on its stream)
+int sp_matcher_ctx_last_values_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.val.run.ms( 0, 1, ms); }
+
+uint32_t sp_matcher_value_max_depth(void) { return VALUE_MAX_DEPTH; }
+
+// the same rule over host arrays (result_values.hpp)
+int sp_match_batch_values( const sp_matcher_t* m, const sp_match_batch_t* mb, const char* text, uint64_t nbytes, const uint64_t* seg_offsets,
+			   size_t nseg, const uint64_t* doc_seg_offsets, uint32_t flags, sp_match_values_t* out, char* err, size_t errsize)
+{
+	std::memset( out, 0, sizeof(*out));
+	copyText( err, errsize, "");
+	try
+	{
+		if (!m) throw std::runtime_error( "no matcher");
+		if (!mb) throw std::runtime_error( "no batch");
+		const TextSource S = { text, nbytes, seg_offsets, nseg, doc_seg_offsets };
+		matchBatchValues( m->formats(), *mb, S, flags, out);
+		return SP_OK;
+	}
+	catch (const std::bad_alloc&) { sp_match_values_free( out); return SP_ERR_NOMEM; }
+	catch (const std::exception& e)
+	{
+		sp_match_values_free( out);
+		copyText( err, errsize, e.what());
+		return SP_ERR_INVALID;
+	}
+}
+
+// ---- the pattern frequencies of the finished batch, summed on the device (l2_freq.h)
+int sp_matcher_ctx_finished_pattern_freq_device( sp_matcher_ctx_t* c, void* stream, sp_pattern_freq_device_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		const sp_matcher_ctx::Finished& fin = c->prod.fin;
+		sp_matcher_ctx::Freq& q = c->prod.frq;
+		// (every result index is checked against the total of the finish)
+		ProductCall call( c, q.run, stream);
+		const size_t ndocs = call.ndocs;
+		const uint32_t bound = sp_matcher_handle_bound( c->inst);
+		reserveOrNoMem( q.dDocCount, (ndocs+1)*sizeof(uint32_t));
+		reserveOrNoMem( q.dDocMeta, (ndocs+1)*4*sizeof(uint32_t));
+		reserveOrNoMem( q.dDocOffsets, (ndocs+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dHandleResults, (size_t)bound*sizeof(uint64_t));
+		reserveOrNoMem( q.dHandleDocs, (size_t)bound*sizeof(uint32_t));
+		call.begin( q.dStatus, q.dTotals, 1, q.dCursor, 2);
+		HIP_CHECK( hipMemsetAsync( q.dHandleResults.ptr, 0, (size_t)bound*sizeof(uint64_t), call.stream));
+		HIP_CHECK( hipMemsetAsync( q.dHandleDocs.ptr, 0, (size_t)bound*sizeof(uint32_t), call.stream));
+		FreqParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.results = (const uint32_t*)fin.dResults.ptr; P.docOffsets = (const uint64_t*)fin.dDocResultOffsets.ptr;
+		P.nresults = call.finished[ 0]; P.ndocs = (uint32_t)ndocs; P.handleBound = bound;
+		P.docCount = (uint32_t*)q.dDocCount.ptr; P.docMeta = (uint32_t*)q.dDocMeta.ptr; P.cursor = (uint32_t*)q.dCursor.ptr;
+		P.docStatus = (int32_t*)q.dStatus.ptr; P.docFreqOffsets = (uint64_t*)q.dDocOffsets.ptr; P.total = (uint64_t*)q.dTotals.ptr;
+		P.handleResults = (uint64_t*)q.dHandleResults.ptr; P.handleDocs = (uint32_t*)q.dHandleDocs.ptr;
+		uint64_t total = 0;
+		call.passes( P, launchL2FreqCount, launchL2FreqPlace, q.dTotals, &total, 1, [&]{
+			reserveOrNoMem( q.dRecords, (total+1)*sizeof(sp_pattern_freq_t));
+			P.records = (uint32_t*)q.dRecords.ptr; P.capacity = total;
+			if (total) HIP_CHECK( hipMemsetAsync( q.dRecords.ptr, 0, total*sizeof(sp_pattern_freq_t), call.stream));
+		});
+		q.ndocs = ndocs; q.handleBound = bound; q.total = total;
+		if (out)
+		{
+			out->ndocs = ndocs; out->handle_bound = bound;
+			out->d_records = q.dRecords.ptr; out->d_doc_offsets = q.dDocOffsets.ptr; out->d_doc_freq_status = q.dStatus.ptr;
+			out->d_handle_results = q.dHandleResults.ptr; out->d_handle_docs = q.dHandleDocs.ptr; out->d_totals = q.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the frequency buffers
+int sp_matcher_ctx_finished_pattern_freq_fetch( sp_matcher_ctx_t* c, sp_pattern_freq_batch_t* out)
+{
+	const sp_matcher_ctx::Freq& q = c->prod.frq;
+	return fetchProduct( c, q.run, "no pattern frequencies of the last batch of this context (sp_matcher_ctx_finished_pattern_freq_device)", out, sp_pattern_freq_batch_free, [&]{
+		allocPatternFreq( out, q.ndocs, q.handleBound);
+		allocPatternFreqRecords( out, q.total);
+		if (q.total) copySync( c->own, out->records, q.dRecords.ptr, q.total*sizeof(sp_pattern_freq_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->doc_offsets, q.dDocOffsets.ptr, (q.ndocs+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		if (q.ndocs) copySync( c->own, out->doc_freq_status, q.dStatus.ptr, q.ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->handle_results, q.dHandleResults.ptr, (size_t)q.handleBound*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->handle_docs, q.dHandleDocs.ptr, (size_t)q.handleBound*sizeof(uint32_t), hipMemcpyDeviceToHost);
+	});
+}
+
+// duration of the passes of the last frequency call in milliseconds (HIP events on its stream)
+int sp_matcher_ctx_last_pattern_freq_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.frq.run.ms( 0, 1, ms); }
+
+uint32_t sp_matcher_pattern_freq_window(void) { return FREQ_WINDOW; }
+
+// ---- the index terms of the finished batch, grouped on the device (l2_terms.h)
+void sp_test_term_hash_bits( unsigned bits) { termHashBits().store( bits, std::memory_order_relaxed); }
+
+int sp_matcher_ctx_finished_terms_device( sp_matcher_ctx_t* c, uint32_t flags, void* stream, sp_match_terms_device_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		if (!flags || (flags & ~(uint32_t)(SP_TERM_VALUES | SP_TERM_TEXT))) throw std::runtime_error( "unknown or no term flags");
+		requireFinished( c);
+		const sp_matcher_ctx::Finished& fin = c->prod.fin;
+		const ByteFamilies& v = c->prod.val;
+		const ByteFamilies& x = c->prod.txt;
+		if ((flags & SP_TERM_VALUES) && !(v.run.done && (v.flags & SP_VALUE_RESULTS)))
+			throw std::runtime_error( "no values of the results of the last finished batch (sp_matcher_ctx_finished_values_device with SP_VALUE_RESULTS)");
+		if ((flags & SP_TERM_TEXT) && !(x.run.done && (x.flags & SP_TEXT_RESULTS)))
+			throw std::runtime_error( "no text of the results of the last finished batch (sp_matcher_ctx_finished_text_device with SP_TEXT_RESULTS)");
+		sp_matcher_ctx::Terms& t = c->prod.trm;
+		// (every result index is checked against the total of the finish)
+		ProductCall call( c, t.run, stream);
+		const size_t ndocs = call.ndocs;
+		const uint32_t bound = sp_matcher_handle_bound( c->inst);
+		const uint64_t nresults = call.finished[ 0];
+		if ((flags & SP_TERM_VALUES) && v.nrecords[ 0] != nresults) throw std::runtime_error( "the values are not those of the finished batch");
+		if ((flags & SP_TERM_TEXT) && x.nrecords[ 0] != nresults) throw std::runtime_error( "the text is not that of the finished batch");
+		const unsigned waves = l2TermsWaves( ndocs, c->numCUs);
+		reserveOrNoMem( t.dLeader, (nresults+1)*sizeof(uint32_t));
+		reserveOrNoMem( t.dTable, (nresults+1)*2*sizeof(uint32_t));
+		reserveOrNoMem( t.dResultTerm, (nresults+1)*sizeof(uint32_t));
+		reserveOrNoMem( t.dHistogram, (size_t)waves*bound*sizeof(uint32_t));
+		reserveOrNoMem( t.dDocCount, (ndocs+1)*sizeof(uint32_t));
+		reserveOrNoMem( t.dDocOffsets, (ndocs+1)*sizeof(uint64_t));
+		// behind the finish, and behind the values and the text call, whose placements nobody has waited for yet
+		call.begin( t.dStatus, t.dTotals, 1, t.dCursor, 2);
+		if ((flags & SP_TERM_VALUES) && call.stream != v.run.stream) HIP_CHECK( hipStreamWaitEvent( call.stream, v.run.ev[ 1], 0));
+		if ((flags & SP_TERM_TEXT) && call.stream != x.run.stream) HIP_CHECK( hipStreamWaitEvent( call.stream, x.run.ev[ 1], 0));
+		TermsParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.results = (const uint32_t*)fin.dResults.ptr; P.docOffsets = (const uint64_t*)fin.dDocResultOffsets.ptr;
+		P.resultFormat = c->io.withFormats ? (const uint32_t*)fin.dResultFormat.ptr : 0;
+		P.nresults = nresults; P.ndocs = (uint32_t)ndocs; P.handleBound = bound; P.flags = flags;
+		const unsigned bits = termHashBits().load( std::memory_order_relaxed);
+		P.hashMask = bits >= 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
+		const ByteFamilies* const source[ 2] = {&v, &x};
+		for (int s=0; s<2; ++s) if (flags & (1u << s))
+		{
+			const ByteFamilies& b = *source[ s];
+			const TermSourceDevice S = { (const uint8_t*)b.dBytes[ 0].ptr, (const uint64_t*)b.dOffsets[ 0].ptr, b.totals[ 0], (const int32_t*)b.dStatus.ptr };
+			P.source[ s] = S;
+		}
+		P.leader = (uint32_t*)t.dLeader.ptr; P.table = (uint32_t*)t.dTable.ptr; P.histogram = (uint32_t*)t.dHistogram.ptr;
+		P.docCount = (uint32_t*)t.dDocCount.ptr; P.cursor = (uint32_t*)t.dCursor.ptr;
+		P.docStatus = (int32_t*)t.dStatus.ptr; P.docTermOffsets = (uint64_t*)t.dDocOffsets.ptr; P.total = (uint64_t*)t.dTotals.ptr;
+		P.resultTerm = (uint32_t*)t.dResultTerm.ptr;
+		uint64_t total = 0;
+		call.passes( P, launchL2TermsCount, launchL2TermsPlace, t.dTotals, &total, 1, [&]{
+			reserveOrNoMem( t.dRecords, (total+1)*sizeof(sp_match_term_t));
+			P.records = (uint32_t*)t.dRecords.ptr; P.capacity = total;
+		});
+		t.ndocs = ndocs; t.handleBound = bound; t.flags = flags; t.nresults = nresults; t.total = total;
+		if (out)
+		{
+			out->ndocs = ndocs; out->handle_bound = bound; out->flags = flags;
+			out->d_records = t.dRecords.ptr; out->d_doc_term_offsets = t.dDocOffsets.ptr; out->d_result_term = t.dResultTerm.ptr;
+			out->d_doc_term_status = t.dStatus.ptr; out->d_totals = t.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the term buffers
+int sp_matcher_ctx_finished_terms_fetch( sp_matcher_ctx_t* c, sp_match_terms_t* out)
+{
+	const sp_matcher_ctx::Terms& t = c->prod.trm;
+	return fetchProduct( c, t.run, "no terms of the last batch of this context (sp_matcher_ctx_finished_terms_device)", out, sp_match_terms_free, [&]{
+		allocMatchTerms( out, t.ndocs, t.nresults, t.handleBound, t.flags);
+		allocMatchTermRecords( out, t.total);
+		if (t.total) copySync( c->own, out->records, t.dRecords.ptr, t.total*sizeof(sp_match_term_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->doc_term_offsets, t.dDocOffsets.ptr, (t.ndocs+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		if (t.nresults) copySync( c->own, out->result_term, t.dResultTerm.ptr, t.nresults*sizeof(uint32_t), hipMemcpyDeviceToHost);
+		if (t.ndocs) copySync( c->own, out->doc_term_status, t.dStatus.ptr, t.ndocs*sizeof(int32_t), hipMemcpyDeviceToHost);
+	});
+}
+
+// duration of the passes of the last terms call in milliseconds (HIP events on its stream)
+int sp_matcher_ctx_last_terms_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.trm.run.ms( 0, 1, ms); }
+
+uint32_t sp_matcher_term_tile(void) { return TERM_TILE; }
+
+} // extern "C"

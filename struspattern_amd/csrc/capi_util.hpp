@@ -1,4 +1,4 @@
-// What the two halves of the C-ABI (capi_l1.cpp, capi_l2.cpp) share: exception -> return code, text and blob export,
+// What the two halves of the C-ABI (capi_l1.cpp; capi_l2.cpp, capi_l2_finished.cpp) share: exception -> return code, text and blob export,
 // the entry points that are the same for a lexer and a matcher context.
 #ifndef SPA_CAPI_UTIL_HPP
 #define SPA_CAPI_UTIL_HPP

@@ -387,6 +387,35 @@ def test_call_order_grown_batch_and_foreign_stream():
         ctx.finishedValuesFetch()
 
 
+def test_failed_allocation_then_a_normal_call():
+    """a device allocation that fails is SP_ERR_NOMEM (-2) and leaves no values; the context stays usable, and a second
+    call on the same batch reuses the buffers of the first"""
+    rng = np.random.default_rng(17)
+    m = _matcher()
+    ctx = m.createContext()
+    pieces = [_random_text(rng, 20) for _ in range(3)]
+    L = Lexems().add(T_SPAN, 3, 5).add(T_LIT, 9, 1).doc().add(T_J1, 0, 2).add(T_J2, 4, 3).doc().add(T_YEAR, 1, 4).add(T_EV, 6, 2).doc()
+    src = Source(pieces)
+    RunAny(ctx, *L.arrays())
+    lib = capi.lib()
+    out = capi.SpMatchValuesBatch()
+    c_src = capi.SpTextSource(src.d_text.data_ptr(), len(src.text), src.d_so.data_ptr(), src.nseg, None)
+    lib.sp_test_fail_alloc_above(1)
+    try:
+        assert lib.sp_matcher_ctx_finished_values_device(ctx._h, ctypes.byref(c_src), BOTH, None, ctypes.byref(out)) == -2
+    finally:
+        lib.sp_test_fail_alloc_above(0)
+    with pytest.raises(spa.PatternError):                         # the failed call left nothing to fetch
+        ctx.finishedValuesFetch()
+    first = _values(ctx, src)
+    mb, got = _assert_values(m, ctx, src, first)
+    assert len(mb.results) >= 3 and len(got.result_values) > 0 and not got.status.any()
+    second = _values(ctx, src)
+    for name, _ in capi.SpMatchValuesBatch._fields_:
+        assert getattr(first, name) == getattr(second, name)
+    _assert_values(m, ctx, src, second)
+
+
 # ---- 8. finish modes
 def test_plain_against_canonical_finish():
     rng = np.random.default_rng(16)
