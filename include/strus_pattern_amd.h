@@ -591,8 +591,8 @@ int sp_match_batch_pattern_freq(const sp_match_batch_t* mb, uint32_t handle_boun
  * the exact engines and result-set mode leave the same bytes.  A hash only chooses where the device looks for a term; two
  * results are one term only after their bytes were compared (sp_test_term_hash_bits).  No byte outside the outputs is written,
  * no record at or beyond the finished total and no source byte outside the source's total read, whatever the records hold.
- * The dictionary of the whole batch (the distinct terms across documents with their document frequency) is NOT built: the
- * per-handle sums of the frequency pass stay what the batch offers. */
+ * The dictionary of the whole batch (the distinct terms across documents with their document frequency) is built from the
+ * terms batch by a call of its own: "batch dictionary" below. */
 #define SP_TERM_VALUES 1u
 #define SP_TERM_TEXT   2u
 typedef struct sp_match_term {
@@ -658,6 +658,100 @@ void sp_test_term_hash_bits(unsigned bits);
  * of 0, and offsets (of the documents or of a selected source) that do not ascend or do not cover their total. */
 int sp_match_batch_terms(const sp_match_batch_t* mb, const sp_match_values_t* values, const sp_match_text_t* text,
                          uint32_t handle_bound, uint32_t flags, sp_match_terms_t* out, char* err, size_t errsize);
+
+/* ---- batch dictionary: every distinct term (pattern, value) of a terms batch ONCE, across its documents, with its document
+ * frequency and its collection frequency, and the way from every term record to its entry -- what an indexer needs to number
+ * the new terms of a batch without de-duplicating strings on the host; built on the device (csrc/l2_dict.h) or, for a batch
+ * already fetched, on the host (csrc/match_dict.hpp).  The rule is the project's own, unpinned by a reference vector.
+ * INPUT: the terms batch built last on a context (sp_matcher_ctx_finished_terms_device) for the batch finished last, with the
+ * sources its `flags` selected.  Write N for the number of term records.  Record i belongs to document d(i); its term is
+ * (handle, value bytes), the value being the range of its first_result in the selected source, exactly as the terms rule
+ * defines it.
+ * SAME TERM: two term records are the same dictionary term iff their handles are equal and their values are equal byte
+ * strings: the same length and the same bytes.  The empty value is a value.  The same bytes under two handles are two
+ * entries.  With both flags a record may take its bytes from the values in one document and from the text in another: equal
+ * bytes are one entry.
+ * ORDER AND ENTRIES: one entry per distinct term, ordered by first occurrence, that is ascending by the smallest global record
+ * index i of the term = (first document, index inside that document's block).  The entries first seen in document d are
+ * contiguous, doc_dict_offsets[d] .. doc_dict_offsets[d+1], and ascend by handle inside that range, as the records do.  A
+ * document that failed its terms (no records), that the matcher failed, or that has no results contributes nothing.
+ * OUTPUTS:
+ *   records[ndict]               sp_dict_term_t, below,                      totals[0]  ndict,
+ *   term_dict[N]                 parallel to the term records: the entry of every record,
+ *   doc_dict_offsets[ndocs+1]    the entries first seen in every document,
+ *   handle_terms[handle_bound]   distinct terms per handle over the batch (a consumer that wants the entries by handle buckets
+ *                                them with these counts).
+ * INVARIANTS: the sum of doc_freq is N; the sum of count is the number of results of the documents that have records; per
+ * handle the sum of count over its entries is handle_results[h] of the frequency pass when no document has a term or
+ * frequency status; the sum of handle_terms is ndict; term_dict[i] < ndict for every i.
+ * DETERMINISM: every output word is a function of the terms batch and its sources alone -- sums, maxima, minima of indices;
+ * neither timing nor the hash enters (sp_test_term_hash_bits masks the dictionary's hash too).  After a canonical finish the
+ * exact engines and result-set mode leave the same bytes.
+ * SAFETY, as for the terms: no byte outside the outputs is written; no term record at or beyond N, no result at or beyond
+ * the finished total and no source byte beyond the source's total is read, whatever the records hold; every index read from
+ * working memory is compared against its bound before use.
+ * LIMIT: N below 2^32 - 1 (indices are 32 bits), else SP_ERR_INVALID.
+ * A dictionary sorted by (handle, value bytes) is not offered: it needs a batch-wide stable sort of variable-length keys;
+ * first-occurrence order needs only a compaction, is how an indexer numbers new terms, and is fully deterministic. */
+typedef struct sp_dict_term {
+	uint32_t handle;        /* pattern handle */
+	uint32_t value_bytes;   /* length of the value */
+	uint32_t first_doc;     /* first document with the term */
+	uint32_t first_term;    /* index of the term's record inside first_doc's block; that record's first_result range IS
+	                           the entry's bytes: an entry owns no bytes of its own */
+	uint32_t doc_freq;      /* term records with this term = documents that contain it */
+	uint32_t max_count;     /* the largest per-document count */
+	uint64_t count;         /* sum of the per-document count: the collection frequency */
+} sp_dict_term_t;
+typedef struct sp_match_dictionary_device {
+	size_t ndocs;
+	uint32_t handle_bound;
+	uint32_t flags;              /* those of the terms call */
+	void* d_records;             /* sp_dict_term_t[ndict] */
+	void* d_term_dict;           /* uint32_t[N], parallel to the term records */
+	void* d_doc_dict_offsets;    /* uint64_t[ndocs+1] */
+	void* d_handle_terms;        /* uint32_t[handle_bound] */
+	void* d_totals;              /* uint64_t[1]: ndict */
+} sp_match_dictionary_device_t;
+/* host copy of a dictionary (sp_match_dictionary_free) */
+typedef struct sp_match_dictionary {
+	size_t ndocs;
+	size_t nterms;                /* N */
+	size_t ndict;
+	uint32_t handle_bound;
+	uint32_t flags;
+	sp_dict_term_t* records;      /* ndict */
+	uint32_t* term_dict;          /* nterms */
+	uint64_t* doc_dict_offsets;   /* ndocs+1 */
+	uint32_t* handle_terms;       /* handle_bound */
+	uint64_t totals[1];           /* ndict */
+} sp_match_dictionary_t;
+/* Builds the dictionary of the terms built last on this context.  Five launches on `stream` (insert, resolve, offsets, place,
+ * accumulate: csrc/l2_dict.h); the call enqueues the first three, waits for them only to read ndict, sizes the records,
+ * enqueues the other two and returns.  The buffers belong to the context, are allocated at the first call, only grow (working
+ * memory: 4 bytes x (table slots + 2N) + 4 x ndocs, the table having min(2N, 2^32 - 1) slots), and are valid until the next
+ * dictionary call; the next batch, finish or terms call invalidates the state, not the buffers.  A `stream` other than the one
+ * of the finish, the terms call, or the values or text call whose buffers the terms point into is ordered behind each of them
+ * with an event (none of those calls waits for its own placement).  SP_ERR_INVALID when the last batch is not finished, when
+ * no terms were built since that finish, when a source that the terms' flags select is not built with its results family for
+ * this finish, and for N >= 2^32 - 1; SP_ERR_NOMEM when a buffer cannot be allocated (the context stays usable). */
+int sp_matcher_ctx_finished_dictionary_device(sp_matcher_ctx_t* c, void* stream, sp_match_dictionary_device_t* out);
+/* plain copy of the buffers of the last sp_matcher_ctx_finished_dictionary_device to the host (waits for it) */
+int sp_matcher_ctx_finished_dictionary_fetch(sp_matcher_ctx_t* c, sp_match_dictionary_t* out);
+void sp_match_dictionary_free(sp_match_dictionary_t* d);
+/* duration of the five launches of the last dictionary call in milliseconds (HIP events on its stream round them; waits for
+ * them; the host's wait for ndict between offsets and place lies inside; the hipMemsetAsync calls that clear the table, the
+ * counters and handle_terms are enqueued before the first event and lie outside, as the clearing of every other product does) */
+int sp_matcher_ctx_last_dictionary_ms(sp_matcher_ctx_t* c, double* ms);
+/* The same rule over host arrays, needs no device, and the yardstick of the device passes: the dictionary of a terms batch
+ * already fetched (or made by sp_match_batch_terms), with the batch and the host copies of the sources the terms were built
+ * from; `flags` and the handle bound are those of `terms`.  Fills `out` (sp_match_dictionary_free); SP_ERR_INVALID with the
+ * message in `err` for a NULL argument that the flags select or a source without its results family, for ndocs or nresults
+ * that do not agree between `mb`, the sources and `terms`, for term offsets that do not ascend or do not cover nrecords, for
+ * a first_result outside its document, a source range outside the source's bytes, and a value_bytes that is not the length
+ * of its range; SP_ERR_NOMEM when memory runs out. */
+int sp_match_batch_dictionary(const sp_match_batch_t* mb, const sp_match_values_t* values, const sp_match_text_t* text,
+                              const sp_match_terms_t* terms, sp_match_dictionary_t* out, char* err, size_t errsize);
 /* copies the results of the last device batch to the host, grouped by document (as sp_matcher_ctx_match_docs
  * returns them, `exclusive` elimination included) */
 int sp_matcher_ctx_batch_fetch(sp_matcher_ctx_t* c, sp_match_batch_t* out);

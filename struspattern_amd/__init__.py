@@ -13,7 +13,7 @@ from . import capi
 from .capi import SpLexem, SpResult, SpResultItem
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
-           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms"]
+           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms", "MatchDictionary", "batchDictionary"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
@@ -254,7 +254,8 @@ class MatchTerms:
     (include/strus_pattern_amd.h "index terms").  A term owns no bytes: its value is the range of its first result in the
     values or the text it was built from."""
 
-    def __init__(self, records, doc_offsets, result_term, status, flags=SP_TERM_VALUES | SP_TERM_TEXT):
+    def __init__(self, records, doc_offsets, result_term, status, flags=SP_TERM_VALUES | SP_TERM_TEXT, handle_bound=0):
+        self.handle_bound = handle_bound    # the bound the terms were built with (0: not known; batchDictionary then needs it as an argument)
         self.records = records          # (n, 6) u32: handle, count, first_ordpos, last_ordend, first_result, value_bytes
         self.doc_offsets = doc_offsets  # (ndocs+1,) u64
         self.result_term = result_term  # (nresults,) u32, 0xFFFFFFFF throughout a failed document
@@ -281,18 +282,13 @@ class MatchTerms:
 def _match_terms_of(t):
     """the MatchTerms of a capi.SpMatchTerms (copies)"""
     return MatchTerms(_rows(t.records, t.nrecords, 6), _rows(t.doc_term_offsets, t.ndocs + 1, 0, ctypes.c_uint64),
-                      _rows(t.result_term, t.nresults, 0), _rows(t.doc_term_status, t.ndocs, 0, ctypes.c_int32), t.flags)
+                      _rows(t.result_term, t.nresults, 0), _rows(t.doc_term_status, t.ndocs, 0, ctypes.c_int32), t.flags, t.handle_bound)
 
 
-def batchTerms(mb, values=None, text=None, handle_bound=0, flags=SP_TERM_VALUES | SP_TERM_TEXT):
-    """The index terms of a batch already on the host (a MatchBatch in document order: finishedFetch, batchFetch, matchDocs)
-    with its MatchValues and / or MatchText (their results family), by the rule of the device call, without a device.
-    handle_bound: PatternMatcherInstance.handleBound().  Returns a MatchTerms."""
-    L = capi.lib()
-    b, keep = _host_batch(mb, formats="results", status=True)       # (keep: until the call has returned)
-
+def _host_sources(values, text, keep):
+    """the C structs (capi.SpMatchValues, capi.SpMatchText) of a MatchValues / MatchText for a host twin, their results family
+    only; either may be None.  What they point into is appended to `keep`."""
     def source(cls, family, names):
-        """the C struct of a MatchValues / MatchText: its results family only"""
         if family is None:
             return None
         c = cls()
@@ -310,14 +306,82 @@ def batchTerms(mb, values=None, text=None, handle_bound=0, flags=SP_TERM_VALUES 
             c.totals[0] = len(data)
         return c
 
-    v = source(capi.SpMatchValues, values, ("result_values", "result_value_offsets", "doc_value_status", "result_values"))
-    x = source(capi.SpMatchText, text, ("result_text", "result_text_offsets", "doc_text_status", "result_text"))
+    return (source(capi.SpMatchValues, values, ("result_values", "result_value_offsets", "doc_value_status", "result_values")),
+            source(capi.SpMatchText, text, ("result_text", "result_text_offsets", "doc_text_status", "result_text")))
+
+
+def batchTerms(mb, values=None, text=None, handle_bound=0, flags=SP_TERM_VALUES | SP_TERM_TEXT):
+    """The index terms of a batch already on the host (a MatchBatch in document order: finishedFetch, batchFetch, matchDocs)
+    with its MatchValues and / or MatchText (their results family), by the rule of the device call, without a device.
+    handle_bound: PatternMatcherInstance.handleBound().  Returns a MatchTerms."""
+    L = capi.lib()
+    b, keep = _host_batch(mb, formats="results", status=True)       # (keep: until the call has returned)
+    v, x = _host_sources(values, text, keep)
     err = ctypes.create_string_buffer(256)
     return _product(capi.SpMatchTerms, lambda t: L.sp_match_batch_terms(ctypes.byref(b), ctypes.byref(v) if v is not None else None,
                                                                        ctypes.byref(x) if x is not None else None, handle_bound, flags, ctypes.byref(t), err, 256),
                     L.sp_match_terms_free, _match_terms_of, lambda rc: "no terms of the batch (%d): %s" % (rc, err.value.decode()))
 
 
+class MatchDictionary:
+    """The dictionary of a terms batch (host copies): one entry per distinct pair (handle, value bytes) over all documents, in
+    the order of first occurrence, and per term record the index of its entry (include/strus_pattern_amd.h "batch
+    dictionary").  An entry owns no bytes: its value is that of term record first_term of document first_doc."""
+
+    def __init__(self, records, term_dict, doc_offsets, handle_terms):
+        self.records = records            # (ndict, 8) u32: handle, value_bytes, first_doc, first_term, doc_freq, max_count, count (low, high)
+        self.counts = np.ascontiguousarray(records[:, 6:8]).view(np.uint64).reshape(-1)   # (ndict,) u64: the collection frequencies
+        self.term_dict = term_dict        # (nterms,) u32, parallel to the term records
+        self.doc_offsets = doc_offsets    # (ndocs+1,) u64: the entries first seen in every document
+        self.handle_terms = handle_terms  # (handle_bound,) u32: distinct terms per handle
+
+    def entries(self, mb, terms, values=None, text=None):
+        """yields (handle, value bytes, doc_freq, count, max_count) per entry, in dictionary order; mb: the finished batch,
+        terms: the MatchTerms the dictionary was built from, values / text: the MatchValues / MatchText of those"""
+        for (h, size, d, t, df, mx, _, _), count in zip(self.records.tolist(), self.counts.tolist()):
+            r = int(mb.doc_offsets[d]) + int(terms.doc(d)[t][4])
+            use_text = not (terms.flags & SP_TERM_VALUES)
+            if terms.flags == (SP_TERM_VALUES | SP_TERM_TEXT):
+                use_text = mb.result_format is None or int(mb.result_format[r]) == 0
+            value = text.result(r) if use_text else values.result(r)
+            assert len(value) == size
+            yield h, value, df, count, mx
+
+
+def _match_dictionary_of(d):
+    """the MatchDictionary of a capi.SpMatchDictionary (copies)"""
+    return MatchDictionary(_rows(d.records, d.ndict, 8), _rows(d.term_dict, d.nterms, 0), _rows(d.doc_dict_offsets, d.ndocs + 1, 0, ctypes.c_uint64),
+                           _rows(d.handle_terms, d.handle_bound, 0))
+
+
+def batchDictionary(mb, terms, values=None, text=None, handle_bound=0):
+    """The dictionary of the terms of a batch already on the host (terms: the MatchTerms of finishedTermsFetch or batchTerms,
+    mb, values, text: what they were built from), by the rule of the device call, without a device.  The handle bound, which
+    is the length of handle_terms, is that of `terms`; a MatchTerms made by hand without one needs `handle_bound`
+    (PatternMatcherInstance.handleBound()): it is not guessed from the records.  Returns a MatchDictionary."""
+    bound = handle_bound or terms.handle_bound
+    if not bound:
+        raise PatternError("no dictionary of the batch: the terms carry no handle bound and none was given")
+    L = capi.lib()
+    b, keep = _host_batch(mb, formats="results", status=True)       # (keep: until the call has returned)
+    v, x = _host_sources(values, text, keep)
+    t = capi.SpMatchTerms()
+    rec = np.ascontiguousarray(terms.records, dtype=np.uint32).reshape(-1, 6)
+    offs = np.ascontiguousarray(terms.doc_offsets, dtype=np.uint64)
+    rt = np.ascontiguousarray(terms.result_term, dtype=np.uint32)
+    st = np.ascontiguousarray(terms.status, dtype=np.int32)
+    keep.extend([rec, offs, rt, st])
+    t.ndocs, t.nresults, t.nrecords, t.flags = len(offs) - 1, len(rt), len(rec), terms.flags
+    t.handle_bound = bound
+    t.records = ctypes.cast(rec.ctypes.data, ctypes.POINTER(capi.SpMatchTerm))
+    t.doc_term_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
+    t.result_term = ctypes.cast(rt.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
+    t.doc_term_status = ctypes.cast(st.ctypes.data, ctypes.POINTER(ctypes.c_int32))
+    t.totals[0] = len(rec)
+    err = ctypes.create_string_buffer(256)
+    return _product(capi.SpMatchDictionary, lambda d: L.sp_match_batch_dictionary(ctypes.byref(b), ctypes.byref(v) if v is not None else None,
+                                                                                 ctypes.byref(x) if x is not None else None, ctypes.byref(t), ctypes.byref(d), err, 256),
+                    L.sp_match_dictionary_free, _match_dictionary_of, lambda rc: "no dictionary of the batch (%d): %s" % (rc, err.value.decode()))
 
 
 class PatternMatcherContext:
@@ -535,6 +599,26 @@ class PatternMatcherContext:
     def lastTermsMs(self):
         """duration of the passes of the last finishedTermsDevice in milliseconds"""
         return self._last_ms(self._L.sp_matcher_ctx_last_terms_ms, "terms call")
+
+    def finishedDictionaryDevice(self, stream=0):
+        """build the dictionary of the terms grouped by finishedTermsDevice on the device (the placement is asynchronous on
+        `stream`): every distinct (handle, value) of the batch once, in the order of first occurrence, with its document
+        and collection frequency, and per term record the index of its entry.  Returns the device pointers
+        (capi.SpMatchDictionaryDevice), valid until the next call."""
+        out = capi.SpMatchDictionaryDevice()
+        rc = self._L.sp_matcher_ctx_finished_dictionary_device(self._h, stream or None, ctypes.byref(out))
+        if rc != 0:
+            raise PatternError("building the dictionary of the batch on the device failed (%d): %s" % (rc, self._err()))
+        return out
+
+    def finishedDictionaryFetch(self):
+        """plain host copy of the dictionary built by finishedDictionaryDevice: a MatchDictionary"""
+        return self._fetch_product(capi.SpMatchDictionary, self._L.sp_matcher_ctx_finished_dictionary_fetch, self._L.sp_match_dictionary_free,
+                                   _match_dictionary_of, "the dictionary of the batch")
+
+    def lastDictionaryMs(self):
+        """duration of the launches of the last finishedDictionaryDevice in milliseconds"""
+        return self._last_ms(self._L.sp_matcher_ctx_last_dictionary_ms, "dictionary call")
 
     def batchFetch(self, first_doc=None, ndocs=None):
         """host copy of the last device batch, grouped by document; with (first_doc, ndocs) only of
@@ -1002,7 +1086,7 @@ class PatternLexer:
         return "std"
 
 
-def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False, with_terms=False):
+def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False, with_terms=False, with_dictionary=False):
     """Segmented documents, host buffers in and out: `text` holds the segments back to back (seg_offsets: nseg+1 byte
     offsets), document d consists of the segments [doc_seg_offsets[d], doc_seg_offsets[d+1]).  Lexer -> stitch on the
     device -> rule matcher -> fetch; only the text goes up and the results come down.  Returns the MatchBatch, whose
@@ -1011,7 +1095,9 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
     (MatchBatch, MatchText).  with_values: the values of the format strings are built there too; returns
     (MatchBatch, MatchValues), or (MatchBatch, MatchText, MatchValues) with both.  with_terms: the results are grouped into
     index terms there (value where a result has a format, else text: text and values are built for it); returns
-    (MatchBatch, MatchText, MatchValues, MatchTerms)."""
+    (MatchBatch, MatchText, MatchValues, MatchTerms).  with_dictionary implies with_terms: the dictionary of the terms is built
+    there too and returned as a fifth element, a MatchDictionary."""
+    with_terms = with_terms or with_dictionary
     with_text, with_values = with_text or with_terms, with_values or with_terms
     import torch
     text = bytes(text)
@@ -1047,15 +1133,18 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
             mctx.finishedValuesDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), nseg, d_dso.data_ptr(), stream=stream)
         if with_terms:
             mctx.finishedTermsDevice(stream=stream)
+        if with_dictionary:
+            mctx.finishedDictionaryDevice(stream=stream)
         mb = mctx.finishedFetch()
         mt = mctx.finishedTextFetch() if with_text else None
         mv = mctx.finishedValuesFetch() if with_values else None
         mterms = mctx.finishedTermsFetch() if with_terms else None
+        mdict = mctx.finishedDictionaryFetch() if with_dictionary else None
     else:
         mb = mctx.batchFetch()
     stitch_status = lctx.stitchedStatus()
     mb.status = np.where(stitch_status != 0, stitch_status, mb.status).astype(np.int32)
-    out = (mb,) + ((mt,) if with_text else ()) + ((mv,) if with_values else ()) + ((mterms,) if with_terms else ())
+    out = (mb,) + ((mt,) if with_text else ()) + ((mv,) if with_values else ()) + ((mterms,) if with_terms else ()) + ((mdict,) if with_dictionary else ())
     return out if len(out) > 1 else mb
 
 

@@ -141,6 +141,25 @@ class SpMatchTerms(ctypes.Structure):
     ]
 
 
+class SpDictTerm(ctypes.Structure):
+    _fields_ = [(n, c_u32) for n in ("handle", "value_bytes", "first_doc", "first_term", "doc_freq", "max_count")] + [("count", c_u64)]
+
+
+class SpMatchDictionaryDevice(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("handle_bound", c_u32), ("flags", c_u32), ("d_records", c_vp), ("d_term_dict", c_vp),
+        ("d_doc_dict_offsets", c_vp), ("d_handle_terms", c_vp), ("d_totals", c_vp),
+    ]
+
+
+class SpMatchDictionary(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("nterms", ctypes.c_size_t), ("ndict", ctypes.c_size_t), ("handle_bound", c_u32), ("flags", c_u32),
+        ("records", P(SpDictTerm)), ("term_dict", P(c_u32)), ("doc_dict_offsets", P(c_u64)), ("handle_terms", P(c_u32)),
+        ("totals", c_u64 * 1),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/strus_pattern_amd.h
 SIGNATURES = {
     "sp_version": (c_cp, []),
@@ -221,6 +240,11 @@ SIGNATURES = {
     "sp_matcher_term_tile": (c_u32, []),
     "sp_test_term_hash_bits": (None, [ctypes.c_uint]),
     "sp_match_batch_terms": (ctypes.c_int, [P(SpMatchBatch), P(SpMatchValues), P(SpMatchText), c_u32, c_u32, P(SpMatchTerms), ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_matcher_ctx_finished_dictionary_device": (ctypes.c_int, [c_vp, c_vp, P(SpMatchDictionaryDevice)]),
+    "sp_matcher_ctx_finished_dictionary_fetch": (ctypes.c_int, [c_vp, P(SpMatchDictionary)]),
+    "sp_match_dictionary_free": (None, [P(SpMatchDictionary)]),
+    "sp_matcher_ctx_last_dictionary_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_match_batch_dictionary": (ctypes.c_int, [P(SpMatchBatch), P(SpMatchValues), P(SpMatchText), P(SpMatchTerms), P(SpMatchDictionary), ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_ctx_batch_counters": (ctypes.c_int, [c_vp, P(c_u64)]),
     "sp_matcher_ctx_last_kernel_ms": (ctypes.c_double, [c_vp]),
     "sp_matcher_ctx_kernel_kind": (ctypes.c_int, [c_vp]),

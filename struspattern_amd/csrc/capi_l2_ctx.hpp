@@ -126,6 +126,15 @@ struct sp_matcher_ctx
 		uint32_t handleBound = 0, flags = 0;
 		uint64_t nresults = 0, total = 0;
 	};
+	// the dictionary of the last terms batch (l2_dict.h); nothing is allocated before the first sp_matcher_ctx_finished_dictionary_device
+	struct Dict
+	{
+		PassRun<2> run;
+		DeviceBuffer dRecords, dTermDict, dDocOffsets, dHandleTerms, dTotals, dTable, dSlot, dLeader, dDocCount, dCursor;
+		size_t ndocs = 0;
+		uint32_t handleBound = 0, flags = 0;
+		uint64_t nterms = 0, total = 0;
+	};
 	// the finish of the last batch and everything made of it (capi_l2_finished.cpp).  A product is a member here and is listed in drop().
 	struct Products
 	{
@@ -134,8 +143,9 @@ struct sp_matcher_ctx
 		Values val;
 		Freq frq;
 		Terms trm;
+		Dict dct;
 		// a new batch, a new finish: what stands here is of the one before
-		void drop() { fin.run.done = false; txt.run.done = false; val.run.done = false; frq.run.done = false; trm.run.done = false; }
+		void drop() { fin.run.done = false; txt.run.done = false; val.run.done = false; frq.run.done = false; trm.run.done = false; dct.run.done = false; }
 	} prod;
 	// single-document mode
 	struct SingleDoc

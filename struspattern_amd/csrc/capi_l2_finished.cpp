@@ -1,5 +1,5 @@
 // C-ABI of level 2, second half: the last device batch finished on the device and what is made of the finished batch there --
-// matched text, result values, pattern frequencies, index terms -- with their fetch and timing calls.  Every product is one
+// matched text, result values, pattern frequencies, index terms, the batch dictionary -- with their fetch and timing calls.  Every product is one
 // ProductCall (capi_l2_ctx.hpp) behind the finish; sp_matcher_ctx::Products::drop() is what a new batch or finish does to them.
 #include "capi_l2_ctx.hpp"
 #include "l2_finish.h"
@@ -7,7 +7,9 @@
 #include "l2_freq.h"
 #include "l2_values.h"
 #include "l2_terms.h"
+#include "l2_dict.h"
 #include "match_terms.hpp"
+#include "match_dict.hpp"
 #include "span_text.hpp"
 #include "pattern_freq.hpp"
 
@@ -456,6 +458,7 @@ int sp_matcher_ctx_finished_terms_device( sp_matcher_ctx_t* c, uint32_t flags, v
 		if ((flags & SP_TERM_TEXT) && !(x.run.done && (x.flags & SP_TEXT_RESULTS)))
 			throw std::runtime_error( "no text of the results of the last finished batch (sp_matcher_ctx_finished_text_device with SP_TEXT_RESULTS)");
 		sp_matcher_ctx::Terms& t = c->prod.trm;
+		c->prod.dct.run.done = false;		// (a dictionary is that of the terms it was built from)
 		// (every result index is checked against the total of the finish)
 		ProductCall call( c, t.run, stream);
 		const size_t ndocs = call.ndocs;
@@ -525,5 +528,96 @@ int sp_matcher_ctx_finished_terms_fetch( sp_matcher_ctx_t* c, sp_match_terms_t* 
 int sp_matcher_ctx_last_terms_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.trm.run.ms( 0, 1, ms); }
 
 uint32_t sp_matcher_term_tile(void) { return TERM_TILE; }
+
+// ---- the dictionary of the terms of the finished batch, built on the device (l2_dict.h)
+int sp_matcher_ctx_finished_dictionary_device( sp_matcher_ctx_t* c, void* stream, sp_match_dictionary_device_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		requireFinished( c);
+		const sp_matcher_ctx::Finished& fin = c->prod.fin;
+		const sp_matcher_ctx::Terms& t = c->prod.trm;
+		const ByteFamilies& v = c->prod.val;
+		const ByteFamilies& x = c->prod.txt;
+		if (!t.run.done) throw std::runtime_error( "no terms of the last finished batch (sp_matcher_ctx_finished_terms_device)");
+		const uint32_t flags = t.flags;
+		if ((flags & SP_TERM_VALUES) && !(v.run.done && (v.flags & SP_VALUE_RESULTS)))
+			throw std::runtime_error( "no values of the results of the last finished batch (sp_matcher_ctx_finished_values_device with SP_VALUE_RESULTS)");
+		if ((flags & SP_TERM_TEXT) && !(x.run.done && (x.flags & SP_TEXT_RESULTS)))
+			throw std::runtime_error( "no text of the results of the last finished batch (sp_matcher_ctx_finished_text_device with SP_TEXT_RESULTS)");
+		sp_matcher_ctx::Dict& q = c->prod.dct;
+		ProductCall call( c, q.run, stream);
+		const size_t ndocs = call.ndocs;
+		const uint64_t nresults = call.finished[ 0], nterms = t.total;
+		if (t.ndocs != ndocs || t.nresults != nresults) throw std::runtime_error( "the terms are not those of the finished batch");
+		if ((flags & SP_TERM_VALUES) && v.nrecords[ 0] != nresults) throw std::runtime_error( "the values are not those of the finished batch");
+		if ((flags & SP_TERM_TEXT) && x.nrecords[ 0] != nresults) throw std::runtime_error( "the text is not that of the finished batch");
+		if (nterms >= 0xFFFFFFFFull) throw std::runtime_error( "2^32 - 1 term records or more: the indices of a dictionary are 32 bits");
+		const uint32_t bound = t.handleBound, slots = l2DictTableSlots( nterms);
+		reserveOrNoMem( q.dTable, (size_t)slots*sizeof(uint32_t));
+		reserveOrNoMem( q.dSlot, (nterms+1)*sizeof(uint32_t));
+		reserveOrNoMem( q.dLeader, (nterms+1)*sizeof(uint32_t));
+		reserveOrNoMem( q.dTermDict, (nterms+1)*sizeof(uint32_t));
+		reserveOrNoMem( q.dDocOffsets, (ndocs+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dHandleTerms, ((size_t)bound+1)*sizeof(uint32_t));
+		// behind the finish, and behind the terms call and the calls whose buffers the terms point into, whose placements nobody
+		// has waited for yet.  (The entries first seen per document are counted where every other product keeps a status.)
+		call.begin( q.dDocCount, q.dTotals, 1, q.dCursor, 4);
+		if (call.stream != t.run.stream) HIP_CHECK( hipStreamWaitEvent( call.stream, t.run.ev[ 1], 0));
+		if ((flags & SP_TERM_VALUES) && call.stream != v.run.stream) HIP_CHECK( hipStreamWaitEvent( call.stream, v.run.ev[ 1], 0));
+		if ((flags & SP_TERM_TEXT) && call.stream != x.run.stream) HIP_CHECK( hipStreamWaitEvent( call.stream, x.run.ev[ 1], 0));
+		HIP_CHECK( hipMemsetAsync( q.dTable.ptr, 0xFF, (size_t)slots*sizeof(uint32_t), call.stream));
+		HIP_CHECK( hipMemsetAsync( q.dHandleTerms.ptr, 0, ((size_t)bound+1)*sizeof(uint32_t), call.stream));
+		DictParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.terms = (const uint32_t*)t.dRecords.ptr; P.docTermOffsets = (const uint64_t*)t.dDocOffsets.ptr; P.nterms = nterms;
+		P.docOffsets = (const uint64_t*)fin.dDocResultOffsets.ptr;
+		P.resultFormat = c->io.withFormats ? (const uint32_t*)fin.dResultFormat.ptr : 0;
+		P.nresults = nresults; P.ndocs = (uint32_t)ndocs; P.handleBound = bound; P.flags = flags;
+		const unsigned bits = termHashBits().load( std::memory_order_relaxed);
+		P.hashMask = bits >= 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
+		const ByteFamilies* const source[ 2] = {&v, &x};
+		for (int s=0; s<2; ++s) if (flags & (1u << s))
+		{
+			const ByteFamilies& b = *source[ s];
+			const TermSourceDevice S = { (const uint8_t*)b.dBytes[ 0].ptr, (const uint64_t*)b.dOffsets[ 0].ptr, b.totals[ 0], (const int32_t*)b.dStatus.ptr };
+			P.source[ s] = S;
+		}
+		P.table = (uint32_t*)q.dTable.ptr; P.tableSlots = slots; P.slot = (uint32_t*)q.dSlot.ptr; P.leader = (uint32_t*)q.dLeader.ptr;
+		P.docCount = (uint32_t*)q.dDocCount.ptr; P.cursor = (uint32_t*)q.dCursor.ptr;
+		P.docDictOffsets = (uint64_t*)q.dDocOffsets.ptr; P.total = (uint64_t*)q.dTotals.ptr;
+		P.termDict = (uint32_t*)q.dTermDict.ptr; P.handleTerms = (uint32_t*)q.dHandleTerms.ptr;
+		uint64_t total = 0;
+		call.passes( P, launchL2DictCount, launchL2DictPlace, q.dTotals, &total, 1, [&]{
+			reserveOrNoMem( q.dRecords, (total+1)*sizeof(sp_dict_term_t));
+			P.records = (uint32_t*)q.dRecords.ptr; P.capacity = total;
+		});
+		q.ndocs = ndocs; q.handleBound = bound; q.flags = flags; q.nterms = nterms; q.total = total;
+		if (out)
+		{
+			out->ndocs = ndocs; out->handle_bound = bound; out->flags = flags;
+			out->d_records = q.dRecords.ptr; out->d_term_dict = q.dTermDict.ptr; out->d_doc_dict_offsets = q.dDocOffsets.ptr;
+			out->d_handle_terms = q.dHandleTerms.ptr; out->d_totals = q.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the dictionary buffers
+int sp_matcher_ctx_finished_dictionary_fetch( sp_matcher_ctx_t* c, sp_match_dictionary_t* out)
+{
+	const sp_matcher_ctx::Dict& q = c->prod.dct;
+	return fetchProduct( c, q.run, "no dictionary of the last terms of this context (sp_matcher_ctx_finished_dictionary_device)", out, sp_match_dictionary_free, [&]{
+		allocMatchDictionary( out, q.ndocs, q.nterms, q.handleBound, q.flags);
+		allocMatchDictionaryRecords( out, q.total);
+		if (q.total) copySync( c->own, out->records, q.dRecords.ptr, q.total*sizeof(sp_dict_term_t), hipMemcpyDeviceToHost);
+		if (q.nterms) copySync( c->own, out->term_dict, q.dTermDict.ptr, q.nterms*sizeof(uint32_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->doc_dict_offsets, q.dDocOffsets.ptr, (q.ndocs+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		if (q.handleBound) copySync( c->own, out->handle_terms, q.dHandleTerms.ptr, (size_t)q.handleBound*sizeof(uint32_t), hipMemcpyDeviceToHost);
+	});
+}
+
+// duration of the five launches of the last dictionary call in milliseconds (HIP events on its stream; the memsets that clear the
+// table and handle_terms are enqueued before the first event)
+int sp_matcher_ctx_last_dictionary_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.dct.run.ms( 0, 1, ms); }
 
 } // extern "C"

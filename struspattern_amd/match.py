@@ -2,7 +2,7 @@
 through the MI355X lexer + rule automaton, print tokens (-K) and results in the reference tool's
 listing format (doc/webpage/introduction_struspattern.htm:178-260).
 
-    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] file [file ...]
+    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] file [file ...]
 
 Every file is one document (plain UTF-8 text; the reference tool segments XML with strusAnalyzer's
 segmenters, which are outside this engine -- pass -o to add the offset of the text inside its original
@@ -17,7 +17,9 @@ the format strings in the listing are built on the GPU (finishedValuesDevice) in
 is the same.  With --terms the listing of a file is followed by one line per index term of it -- a distinct pair of pattern
 and value, the value of a result being that of its format string, or the text it covers where it has none -- ascending by
 pattern handle, then by first occurrence: `term NAME 'VALUE': count N first ORDPOS`, grouped on the GPU
-(finishedTermsDevice).  All files go to the
+(finishedTermsDevice).  With --dictionary the listing of the last file is followed by one line per distinct index term of
+all files, in the order of first occurrence: `dict NAME 'VALUE': docs D count C` -- in how many files the term occurs and how
+often over all of them, built on the GPU from the terms (finishedDictionaryDevice).  All files go to the
 GPU as one batch.  There is no CPU fallback.
 """
 import argparse
@@ -38,6 +40,7 @@ def main(argv=None):
     ap.add_argument("--frequencies", action="store_true", help="after the listing of a file, one line per pattern that matched in it")
     ap.add_argument("--device-values", action="store_true", help="the values of the format strings are built on the device")
     ap.add_argument("--terms", action="store_true", help="after the listing of a file, one line per distinct (pattern, value) of it")
+    ap.add_argument("--dictionary", action="store_true", help="after the last listing, one line per distinct (pattern, value) of all files")
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("files", nargs="+")
     args = ap.parse_args(argv)
@@ -61,7 +64,8 @@ def main(argv=None):
     mctx = mt.createContext(args.device)
     mb = mctx.matchDocs(lb.lexems, lb.doc_offsets)
     values = device_values(mctx, text, offs) if args.device_values else None
-    terms = device_terms(mctx, text, offs) if args.terms else None
+    terms = device_terms(mctx, text, offs) if args.terms or args.dictionary else None
+    dictionary = device_dictionary(mctx) if args.dictionary else None
     freq = frequencies(mctx) if args.frequencies else None
     for di, fn in enumerate(args.files):
         print("%s:" % fn)
@@ -75,9 +79,30 @@ def main(argv=None):
                                             first_result=int(mb.doc_offsets[di]), values=values):
             print(line)
         print_frequencies(freq, di, mt)
-        print_terms(terms, di, mt)
+        print_terms(terms if args.terms else None, di, mt)
+    print_dictionary(dictionary, terms, mt)
     print("OK done")
     return 0
+
+
+def device_dictionary(mctx):
+    """--dictionary: the dictionary of the terms that device_terms grouped, built on the device"""
+    mctx.finishedDictionaryDevice()
+    return mctx.finishedDictionaryFetch()
+
+
+def dictionary_lines(dictionary, found, pattern_name):
+    """the lines of --dictionary; found: (batch, text, values, terms) of the terms call"""
+    mb, mt, mv, terms = found
+    return ["dict %s '%s': docs %d count %d" % (pattern_name(int(h)), value.decode("utf-8", "replace"), docs, count)
+            for h, value, docs, count, _ in dictionary.entries(mb, terms, values=mv, text=mt)]
+
+
+def print_dictionary(dictionary, found, mt):
+    if dictionary is None:
+        return
+    for line in dictionary_lines(dictionary, found, mt.patternName):
+        print(line)
 
 
 def device_terms(mctx, text, offs):
@@ -144,8 +169,12 @@ def paragraphs(args, prg, lx, mt, docs):
     text, seg_offsets, doc_seg_offsets, posmaps = segments.segmented_batch(docs)
     lctx = lx.createContext(args.device)
     mctx = mt.createContext(args.device)
-    values = terms = None
-    if args.terms:
+    values = terms = dictionary = None
+    if args.dictionary:
+        mb, mtext, mvalues, mterms, dictionary = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_dictionary=True)
+        terms = (mb, mtext, mvalues, mterms)
+        values = mvalues if args.device_values else None
+    elif args.terms:
         mb, mtext, mvalues, mterms = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_terms=True)
         terms = (mb, mtext, mvalues, mterms)
         values = mvalues if args.device_values else None
@@ -177,7 +206,8 @@ def paragraphs(args, prg, lx, mt, docs):
                                             first_result=int(mb.doc_offsets[di]), values=values):
             print(line)
         print_frequencies(freq, di, mt)
-        print_terms(terms, di, mt)
+        print_terms(terms if args.terms else None, di, mt)
+    print_dictionary(dictionary, terms, mt)
     print("OK done")
     return 0
 
