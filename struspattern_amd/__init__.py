@@ -248,6 +248,15 @@ def batchPatternFreq(mb, handle_bound):
                     L.sp_pattern_freq_batch_free, _pattern_freq_of, lambda rc: "no pattern frequencies of the batch (%d): %s" % (rc, err.value.decode()))
 
 
+def _term_value(flags, mb, values, text, r):
+    """the value bytes of result r of the finished batch mb: those of `values` (a MatchValues) unless the flags say `text` (a
+    MatchText); with both flags the text of a result without a format"""
+    use_text = not (flags & SP_TERM_VALUES)
+    if flags == (SP_TERM_VALUES | SP_TERM_TEXT):
+        use_text = mb.result_format is None or int(mb.result_format[r]) == 0
+    return text.result(r) if use_text else values.result(r)
+
+
 class MatchTerms:
     """The index terms of a finished batch (host copies): per document one record per distinct pair (handle, value bytes),
     ascending by handle, then by first_result, and per result the index of its term inside its document's block
@@ -270,11 +279,7 @@ class MatchTerms:
         values / text: the MatchValues / MatchText the terms were built from"""
         first = int(mb.doc_offsets[d])
         for h, count, pos, end, fr, size in self.doc(d).tolist():
-            r = first + fr
-            use_text = not (self.flags & SP_TERM_VALUES)
-            if self.flags == (SP_TERM_VALUES | SP_TERM_TEXT):
-                use_text = mb.result_format is None or int(mb.result_format[r]) == 0
-            value = text.result(r) if use_text else values.result(r)
+            value = _term_value(self.flags, mb, values, text, first + fr)
             assert len(value) == size
             yield h, value, count, pos, end
 
@@ -339,11 +344,7 @@ class MatchDictionary:
         """yields (handle, value bytes, doc_freq, count, max_count) per entry, in dictionary order; mb: the finished batch,
         terms: the MatchTerms the dictionary was built from, values / text: the MatchValues / MatchText of those"""
         for (h, size, d, t, df, mx, _, _), count in zip(self.records.tolist(), self.counts.tolist()):
-            r = int(mb.doc_offsets[d]) + int(terms.doc(d)[t][4])
-            use_text = not (terms.flags & SP_TERM_VALUES)
-            if terms.flags == (SP_TERM_VALUES | SP_TERM_TEXT):
-                use_text = mb.result_format is None or int(mb.result_format[r]) == 0
-            value = text.result(r) if use_text else values.result(r)
+            value = _term_value(terms.flags, mb, values, text, int(mb.doc_offsets[d]) + int(terms.doc(d)[t][4]))
             assert len(value) == size
             yield h, value, df, count, mx
 

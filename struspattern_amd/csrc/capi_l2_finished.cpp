@@ -12,6 +12,7 @@
 #include "match_dict.hpp"
 #include "span_text.hpp"
 #include "pattern_freq.hpp"
+#include "finished_host.hpp"
 
 typedef sp_matcher_ctx::ByteFamilies ByteFamilies;
 
@@ -103,6 +104,45 @@ void fetchByteFamilies( const sp_matcher_ctx* c, const ByteFamilies& b, int32_t*
 
 // test hook: the bits of a term's hash that the device keeps (32 and more = all)
 std::atomic<unsigned>& termHashBits() { static std::atomic<unsigned> bits( 32); return bits; }
+
+// ---- the sources of the terms and of the dictionary call: the results families of the values call (0) and of the text call (1)
+// that `flags` selects, which must have run since the finish
+struct TermSources
+{
+	const ByteFamilies* family[ 2]; uint32_t flags;
+	bool selected( int s) const { return (flags & (1u << s)) != 0; }
+	TermSources( const sp_matcher_ctx* c, uint32_t flags_) :family{ &c->prod.val, &c->prod.txt }, flags(flags_)
+	{
+		if (selected( 0) && !(family[ 0]->run.done && (family[ 0]->flags & SP_VALUE_RESULTS)))
+			throw std::runtime_error( "no values of the results of the last finished batch (sp_matcher_ctx_finished_values_device with SP_VALUE_RESULTS)");
+		if (selected( 1) && !(family[ 1]->run.done && (family[ 1]->flags & SP_TEXT_RESULTS)))
+			throw std::runtime_error( "no text of the results of the last finished batch (sp_matcher_ctx_finished_text_device with SP_TEXT_RESULTS)");
+	}
+	// they are those of the `nresults` results of the finish
+	void requireResults( uint64_t nresults) const
+	{
+		if (selected( 0) && family[ 0]->nrecords[ 0] != nresults) throw std::runtime_error( "the values are not those of the finished batch");
+		if (selected( 1) && family[ 1]->nrecords[ 0] != nresults) throw std::runtime_error( "the text is not that of the finished batch");
+	}
+	// `stream` runs behind their placements, which nobody has waited for yet
+	void waitFor( hipStream_t stream) const
+	{
+		for (int s=0; s<2; ++s) if (selected( s) && stream != family[ s]->run.stream) HIP_CHECK( hipStreamWaitEvent( stream, family[ s]->run.ev[ 1], 0));
+	}
+	// what TermsParams and DictParams name alike: the flags, the hash mask and the sources
+	template <class PARAMS>
+	void describe( PARAMS& P) const
+	{
+		const unsigned bits = termHashBits().load( std::memory_order_relaxed);
+		P.flags = flags; P.hashMask = bits >= 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
+		for (int s=0; s<2; ++s) if (selected( s))
+		{
+			const ByteFamilies& b = *family[ s];
+			const TermSourceDevice S = { (const uint8_t*)b.dBytes[ 0].ptr, (const uint64_t*)b.dOffsets[ 0].ptr, b.totals[ 0], (const int32_t*)b.dStatus.ptr };
+			P.source[ s] = S;
+		}
+	}
+};
 
 } // namespace
 
@@ -360,23 +400,12 @@ uint32_t sp_matcher_value_max_depth(void) { return VALUE_MAX_DEPTH; }
 int sp_match_batch_values( const sp_matcher_t* m, const sp_match_batch_t* mb, const char* text, uint64_t nbytes, const uint64_t* seg_offsets,
 			   size_t nseg, const uint64_t* doc_seg_offsets, uint32_t flags, sp_match_values_t* out, char* err, size_t errsize)
 {
-	std::memset( out, 0, sizeof(*out));
-	copyText( err, errsize, "");
-	try
-	{
+	return hostProduct( out, sp_match_values_free, err, errsize, [&]{
 		if (!m) throw std::runtime_error( "no matcher");
 		if (!mb) throw std::runtime_error( "no batch");
 		const TextSource S = { text, nbytes, seg_offsets, nseg, doc_seg_offsets };
 		matchBatchValues( m->formats(), *mb, S, flags, out);
-		return SP_OK;
-	}
-	catch (const std::bad_alloc&) { sp_match_values_free( out); return SP_ERR_NOMEM; }
-	catch (const std::exception& e)
-	{
-		sp_match_values_free( out);
-		copyText( err, errsize, e.what());
-		return SP_ERR_INVALID;
-	}
+	});
 }
 
 // ---- the pattern frequencies of the finished batch, summed on the device (l2_freq.h)
@@ -451,12 +480,7 @@ int sp_matcher_ctx_finished_terms_device( sp_matcher_ctx_t* c, uint32_t flags, v
 		if (!flags || (flags & ~(uint32_t)(SP_TERM_VALUES | SP_TERM_TEXT))) throw std::runtime_error( "unknown or no term flags");
 		requireFinished( c);
 		const sp_matcher_ctx::Finished& fin = c->prod.fin;
-		const ByteFamilies& v = c->prod.val;
-		const ByteFamilies& x = c->prod.txt;
-		if ((flags & SP_TERM_VALUES) && !(v.run.done && (v.flags & SP_VALUE_RESULTS)))
-			throw std::runtime_error( "no values of the results of the last finished batch (sp_matcher_ctx_finished_values_device with SP_VALUE_RESULTS)");
-		if ((flags & SP_TERM_TEXT) && !(x.run.done && (x.flags & SP_TEXT_RESULTS)))
-			throw std::runtime_error( "no text of the results of the last finished batch (sp_matcher_ctx_finished_text_device with SP_TEXT_RESULTS)");
+		const TermSources sources( c, flags);
 		sp_matcher_ctx::Terms& t = c->prod.trm;
 		c->prod.dct.run.done = false;		// (a dictionary is that of the terms it was built from)
 		// (every result index is checked against the total of the finish)
@@ -464,8 +488,7 @@ int sp_matcher_ctx_finished_terms_device( sp_matcher_ctx_t* c, uint32_t flags, v
 		const size_t ndocs = call.ndocs;
 		const uint32_t bound = sp_matcher_handle_bound( c->inst);
 		const uint64_t nresults = call.finished[ 0];
-		if ((flags & SP_TERM_VALUES) && v.nrecords[ 0] != nresults) throw std::runtime_error( "the values are not those of the finished batch");
-		if ((flags & SP_TERM_TEXT) && x.nrecords[ 0] != nresults) throw std::runtime_error( "the text is not that of the finished batch");
+		sources.requireResults( nresults);
 		const unsigned waves = l2TermsWaves( ndocs, c->numCUs);
 		reserveOrNoMem( t.dLeader, (nresults+1)*sizeof(uint32_t));
 		reserveOrNoMem( t.dTable, (nresults+1)*2*sizeof(uint32_t));
@@ -475,22 +498,13 @@ int sp_matcher_ctx_finished_terms_device( sp_matcher_ctx_t* c, uint32_t flags, v
 		reserveOrNoMem( t.dDocOffsets, (ndocs+1)*sizeof(uint64_t));
 		// behind the finish, and behind the values and the text call, whose placements nobody has waited for yet
 		call.begin( t.dStatus, t.dTotals, 1, t.dCursor, 2);
-		if ((flags & SP_TERM_VALUES) && call.stream != v.run.stream) HIP_CHECK( hipStreamWaitEvent( call.stream, v.run.ev[ 1], 0));
-		if ((flags & SP_TERM_TEXT) && call.stream != x.run.stream) HIP_CHECK( hipStreamWaitEvent( call.stream, x.run.ev[ 1], 0));
+		sources.waitFor( call.stream);
 		TermsParams P;
 		std::memset( &P, 0, sizeof(P));
 		P.results = (const uint32_t*)fin.dResults.ptr; P.docOffsets = (const uint64_t*)fin.dDocResultOffsets.ptr;
 		P.resultFormat = c->io.withFormats ? (const uint32_t*)fin.dResultFormat.ptr : 0;
-		P.nresults = nresults; P.ndocs = (uint32_t)ndocs; P.handleBound = bound; P.flags = flags;
-		const unsigned bits = termHashBits().load( std::memory_order_relaxed);
-		P.hashMask = bits >= 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
-		const ByteFamilies* const source[ 2] = {&v, &x};
-		for (int s=0; s<2; ++s) if (flags & (1u << s))
-		{
-			const ByteFamilies& b = *source[ s];
-			const TermSourceDevice S = { (const uint8_t*)b.dBytes[ 0].ptr, (const uint64_t*)b.dOffsets[ 0].ptr, b.totals[ 0], (const int32_t*)b.dStatus.ptr };
-			P.source[ s] = S;
-		}
+		P.nresults = nresults; P.ndocs = (uint32_t)ndocs; P.handleBound = bound;
+		sources.describe( P);
 		P.leader = (uint32_t*)t.dLeader.ptr; P.table = (uint32_t*)t.dTable.ptr; P.histogram = (uint32_t*)t.dHistogram.ptr;
 		P.docCount = (uint32_t*)t.dDocCount.ptr; P.cursor = (uint32_t*)t.dCursor.ptr;
 		P.docStatus = (int32_t*)t.dStatus.ptr; P.docTermOffsets = (uint64_t*)t.dDocOffsets.ptr; P.total = (uint64_t*)t.dTotals.ptr;
@@ -537,21 +551,15 @@ int sp_matcher_ctx_finished_dictionary_device( sp_matcher_ctx_t* c, void* stream
 		requireFinished( c);
 		const sp_matcher_ctx::Finished& fin = c->prod.fin;
 		const sp_matcher_ctx::Terms& t = c->prod.trm;
-		const ByteFamilies& v = c->prod.val;
-		const ByteFamilies& x = c->prod.txt;
 		if (!t.run.done) throw std::runtime_error( "no terms of the last finished batch (sp_matcher_ctx_finished_terms_device)");
 		const uint32_t flags = t.flags;
-		if ((flags & SP_TERM_VALUES) && !(v.run.done && (v.flags & SP_VALUE_RESULTS)))
-			throw std::runtime_error( "no values of the results of the last finished batch (sp_matcher_ctx_finished_values_device with SP_VALUE_RESULTS)");
-		if ((flags & SP_TERM_TEXT) && !(x.run.done && (x.flags & SP_TEXT_RESULTS)))
-			throw std::runtime_error( "no text of the results of the last finished batch (sp_matcher_ctx_finished_text_device with SP_TEXT_RESULTS)");
+		const TermSources sources( c, flags);
 		sp_matcher_ctx::Dict& q = c->prod.dct;
 		ProductCall call( c, q.run, stream);
 		const size_t ndocs = call.ndocs;
 		const uint64_t nresults = call.finished[ 0], nterms = t.total;
 		if (t.ndocs != ndocs || t.nresults != nresults) throw std::runtime_error( "the terms are not those of the finished batch");
-		if ((flags & SP_TERM_VALUES) && v.nrecords[ 0] != nresults) throw std::runtime_error( "the values are not those of the finished batch");
-		if ((flags & SP_TERM_TEXT) && x.nrecords[ 0] != nresults) throw std::runtime_error( "the text is not that of the finished batch");
+		sources.requireResults( nresults);
 		if (nterms >= 0xFFFFFFFFull) throw std::runtime_error( "2^32 - 1 term records or more: the indices of a dictionary are 32 bits");
 		const uint32_t bound = t.handleBound, slots = l2DictTableSlots( nterms);
 		reserveOrNoMem( q.dTable, (size_t)slots*sizeof(uint32_t));
@@ -564,8 +572,7 @@ int sp_matcher_ctx_finished_dictionary_device( sp_matcher_ctx_t* c, void* stream
 		// has waited for yet.  (The entries first seen per document are counted where every other product keeps a status.)
 		call.begin( q.dDocCount, q.dTotals, 1, q.dCursor, 4);
 		if (call.stream != t.run.stream) HIP_CHECK( hipStreamWaitEvent( call.stream, t.run.ev[ 1], 0));
-		if ((flags & SP_TERM_VALUES) && call.stream != v.run.stream) HIP_CHECK( hipStreamWaitEvent( call.stream, v.run.ev[ 1], 0));
-		if ((flags & SP_TERM_TEXT) && call.stream != x.run.stream) HIP_CHECK( hipStreamWaitEvent( call.stream, x.run.ev[ 1], 0));
+		sources.waitFor( call.stream);
 		HIP_CHECK( hipMemsetAsync( q.dTable.ptr, 0xFF, (size_t)slots*sizeof(uint32_t), call.stream));
 		HIP_CHECK( hipMemsetAsync( q.dHandleTerms.ptr, 0, ((size_t)bound+1)*sizeof(uint32_t), call.stream));
 		DictParams P;
@@ -573,16 +580,8 @@ int sp_matcher_ctx_finished_dictionary_device( sp_matcher_ctx_t* c, void* stream
 		P.terms = (const uint32_t*)t.dRecords.ptr; P.docTermOffsets = (const uint64_t*)t.dDocOffsets.ptr; P.nterms = nterms;
 		P.docOffsets = (const uint64_t*)fin.dDocResultOffsets.ptr;
 		P.resultFormat = c->io.withFormats ? (const uint32_t*)fin.dResultFormat.ptr : 0;
-		P.nresults = nresults; P.ndocs = (uint32_t)ndocs; P.handleBound = bound; P.flags = flags;
-		const unsigned bits = termHashBits().load( std::memory_order_relaxed);
-		P.hashMask = bits >= 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
-		const ByteFamilies* const source[ 2] = {&v, &x};
-		for (int s=0; s<2; ++s) if (flags & (1u << s))
-		{
-			const ByteFamilies& b = *source[ s];
-			const TermSourceDevice S = { (const uint8_t*)b.dBytes[ 0].ptr, (const uint64_t*)b.dOffsets[ 0].ptr, b.totals[ 0], (const int32_t*)b.dStatus.ptr };
-			P.source[ s] = S;
-		}
+		P.nresults = nresults; P.ndocs = (uint32_t)ndocs; P.handleBound = bound;
+		sources.describe( P);
 		P.table = (uint32_t*)q.dTable.ptr; P.tableSlots = slots; P.slot = (uint32_t*)q.dSlot.ptr; P.leader = (uint32_t*)q.dLeader.ptr;
 		P.docCount = (uint32_t*)q.dDocCount.ptr; P.cursor = (uint32_t*)q.dCursor.ptr;
 		P.docDictOffsets = (uint64_t*)q.dDocOffsets.ptr; P.total = (uint64_t*)q.dTotals.ptr;

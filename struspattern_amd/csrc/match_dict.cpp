@@ -1,6 +1,6 @@
 // Batch dictionary of a terms batch over host arrays (match_dict.hpp): host only, no device needed.
 #include "match_dict.hpp"
-#include "batch_fetch.hpp"
+#include "finished_host.hpp"
 #include <string_view>
 #include <unordered_map>
 #include <vector>
@@ -8,14 +8,6 @@
 namespace spa {
 
 namespace {
-
-template <class T>
-T* filledArray( uint64_t n, int byte)
-{
-	T* p = hostArray<T>( n ? n : 1);
-	std::memset( p, byte, (size_t)(n ? n : 1) * sizeof(T));
-	return p;
-}
 
 // a dictionary term: the bytes are those of a source, which outlives the map
 struct Key
@@ -28,12 +20,6 @@ struct KeyHash
 {
 	size_t operator()( const Key& k) const { return std::hash<std::string_view>()( k.bytes) * 31u + k.handle; }
 };
-
-void checkSource( const TermSource& S, const char* name)
-{
-	if (!S.offsets) throw std::runtime_error( std::string( "no ") + name + " of the results of the batch");
-	if (S.total && !S.bytes) throw std::runtime_error( std::string( name) + " without bytes");
-}
 
 } // namespace
 
@@ -63,17 +49,15 @@ void matchDictionary( const sp_match_term_t* records, uint64_t nrecords, const u
 	if (nrecords && !records) throw std::runtime_error( "terms without records");
 	if (nrecords >= 0xFFFFFFFFull) throw std::runtime_error( "2^32 - 1 term records or more");
 	if (ndocs > 0xFFFFFFFFull) throw std::runtime_error( "2^32 documents or more");
-	if (docOffsets[ 0] != 0) throw std::runtime_error( "document offsets of the batch do not start at its first result");
+	checkDocOffsets( docOffsets, ndocs, nresults);
 	if (docTermOffsets[ 0] != 0) throw std::runtime_error( "term offsets do not start at the first record");
 	for (size_t d=0; d<ndocs; ++d)
 	{
-		if (docOffsets[ d] > docOffsets[ d+1] || docOffsets[ d+1] > nresults) throw std::runtime_error( "document offsets of the batch do not ascend inside its results");
 		if (docTermOffsets[ d] > docTermOffsets[ d+1] || docTermOffsets[ d+1] > nrecords) throw std::runtime_error( "term offsets do not ascend inside the records");
 	}
-	if (docOffsets[ ndocs] != nresults) throw std::runtime_error( "document offsets of the batch do not cover its results");
 	if (docTermOffsets[ ndocs] != nrecords) throw std::runtime_error( "term offsets do not cover the records");
-	if (flags & SP_TERM_VALUES) checkSource( source[ 0], "values");
-	if (flags & SP_TERM_TEXT) checkSource( source[ 1], "text");
+	if (flags & SP_TERM_VALUES) checkTermSource( source[ 0], "values");
+	if (flags & SP_TERM_TEXT) checkTermSource( source[ 1], "text");
 
 	allocMatchDictionary( out, ndocs, nrecords, handleBound, flags);
 	std::vector<sp_dict_term_t> entries;
@@ -88,10 +72,7 @@ void matchDictionary( const sp_match_term_t* records, uint64_t nrecords, const u
 			if (rec.handle < 1 || rec.handle >= handleBound) throw std::runtime_error( "a term record with a handle outside the bound");
 			if (rec.first_result >= r1 - r0) throw std::runtime_error( "a term record whose first_result lies outside its document");
 			const uint64_t r = r0 + rec.first_result;
-			// the source of this record's value
-			int s = (flags & SP_TERM_VALUES) ? 0 : 1;
-			if (flags == (SP_TERM_VALUES | SP_TERM_TEXT) && !(resultFormat && resultFormat[ r] != 0)) s = 1;
-			const TermSource& S = source[ s];
+			const TermSource& S = source[ termSourceIndex( flags, resultFormat, r)];
 			if (S.offsets[ r] > S.offsets[ r+1] || S.offsets[ r+1] > S.total) throw std::runtime_error( "a term value outside the bytes of its source");
 			const uint64_t size = S.offsets[ r+1] - S.offsets[ r];
 			if (size != rec.value_bytes) throw std::runtime_error( "a term record whose value_bytes is not the length of its value");
@@ -126,38 +107,13 @@ extern "C" void sp_match_dictionary_free( sp_match_dictionary_t* d)
 extern "C" int sp_match_batch_dictionary( const sp_match_batch_t* mb, const sp_match_values_t* values, const sp_match_text_t* text,
 					  const sp_match_terms_t* terms, sp_match_dictionary_t* out, char* err, size_t errsize)
 {
-	std::memset( out, 0, sizeof(*out));
-	if (err && errsize) err[ 0] = 0;
-	try
-	{
+	return spa::hostProduct( out, sp_match_dictionary_free, err, errsize, [&]{
 		if (!mb) throw std::runtime_error( "no batch");
 		if (!terms) throw std::runtime_error( "no terms");
 		if (terms->ndocs != mb->ndocs || terms->nresults != mb->nresults) throw std::runtime_error( "the terms are not those of the batch: other counts of documents or results");
-		const uint32_t flags = terms->flags;
 		spa::TermSource source[ 2] = {};
-		if (flags & SP_TERM_VALUES)
-		{
-			if (!values || !values->result_value_offsets) throw std::runtime_error( "no values of the results of the batch");
-			if (values->ndocs != mb->ndocs || values->nresults != mb->nresults) throw std::runtime_error( "the values are not those of the batch: other counts of documents or results");
-			const spa::TermSource S = { (const char*)values->result_values, values->result_value_offsets, values->totals[ 0], values->doc_value_status };
-			source[ 0] = S;
-		}
-		if (flags & SP_TERM_TEXT)
-		{
-			if (!text || !text->result_text_offsets) throw std::runtime_error( "no text of the results of the batch");
-			if (text->ndocs != mb->ndocs || text->nresults != mb->nresults) throw std::runtime_error( "the text is not that of the batch: other counts of documents or results");
-			const spa::TermSource S = { (const char*)text->result_text, text->result_text_offsets, text->totals[ 0], text->doc_text_status };
-			source[ 1] = S;
-		}
+		spa::termSources( *mb, values, text, terms->flags, source);
 		spa::matchDictionary( terms->records, terms->nrecords, terms->doc_term_offsets, mb->doc_result_offsets, mb->nresults,
-				      mb->result_format, mb->ndocs, source, terms->handle_bound, flags, out);
-		return SP_OK;
-	}
-	catch (const std::bad_alloc&) { sp_match_dictionary_free( out); return SP_ERR_NOMEM; }
-	catch (const std::exception& e)
-	{
-		sp_match_dictionary_free( out);
-		if (err && errsize) { std::strncpy( err, e.what(), errsize-1); err[ errsize-1] = 0; }
-		return SP_ERR_INVALID;
-	}
+				      mb->result_format, mb->ndocs, source, terms->handle_bound, terms->flags, out);
+	});
 }

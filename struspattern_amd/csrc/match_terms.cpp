@@ -1,6 +1,6 @@
 // Index terms of a finished batch over host arrays (match_terms.hpp): host only, no device needed.
 #include "match_terms.hpp"
-#include "batch_fetch.hpp"
+#include "finished_host.hpp"
 #include <algorithm>
 #include <vector>
 
@@ -9,14 +9,6 @@ namespace spa {
 namespace {
 enum {TERM_ERR_RANGE = SP_DOC_ERR_RANGE};
 const uint32_t NO_TERM = 0xFFFFFFFFu;
-
-template <class T>
-T* filledArray( uint64_t n, int byte)
-{
-	T* p = hostArray<T>( n ? n : 1);
-	std::memset( p, byte, (size_t)(n ? n : 1) * sizeof(T));
-	return p;
-}
 
 // a result of one document with its term value
 struct Occurrence
@@ -30,18 +22,6 @@ int compareValue( const Occurrence& a, const Occurrence& b)
 	if (a.handle != b.handle) return a.handle < b.handle ? -1 : 1;
 	if (a.size != b.size) return a.size < b.size ? -1 : 1;
 	return a.size ? std::memcmp( a.bytes, b.bytes, (size_t)a.size) : 0;
-}
-
-void checkSource( const TermSource& S, uint64_t nresults, const char* name)
-{
-	if (!S.offsets) throw std::runtime_error( std::string( "no ") + name + " of the results of the batch");
-	if (S.total && !S.bytes) throw std::runtime_error( std::string( name) + " without bytes");
-	if (S.offsets[ 0] != 0) throw std::runtime_error( std::string( "offsets of the ") + name + " do not start at the first byte");
-	for (uint64_t r=0; r<nresults; ++r)
-	{
-		if (S.offsets[ r] > S.offsets[ r+1] || S.offsets[ r+1] > S.total) throw std::runtime_error( std::string( "offsets of the ") + name + " do not ascend inside its bytes");
-	}
-	if (S.offsets[ nresults] != S.total) throw std::runtime_error( std::string( "offsets of the ") + name + " do not cover its bytes");
 }
 
 } // namespace
@@ -69,15 +49,13 @@ void matchTerms( const sp_result_t* results, uint64_t nresults, const uint64_t* 
 	if (!handleBound) throw std::runtime_error( "a handle bound of 0 leaves no valid handle");
 	if (!docOffsets) throw std::runtime_error( "batch without document offsets");
 	if (nresults && !results) throw std::runtime_error( "batch without results");
-	if (docOffsets[ 0] != 0) throw std::runtime_error( "document offsets of the batch do not start at its first result");
+	checkDocOffsets( docOffsets, ndocs, nresults);
 	for (size_t d=0; d<ndocs; ++d)
 	{
-		if (docOffsets[ d] > docOffsets[ d+1] || docOffsets[ d+1] > nresults) throw std::runtime_error( "document offsets of the batch do not ascend inside its results");
 		if (docOffsets[ d+1] - docOffsets[ d] >= NO_TERM) throw std::runtime_error( "a document of 2^32 results or more");
 	}
-	if (docOffsets[ ndocs] != nresults) throw std::runtime_error( "document offsets of the batch do not cover its results");
-	if (flags & SP_TERM_VALUES) checkSource( source[ 0], nresults, "values");
-	if (flags & SP_TERM_TEXT) checkSource( source[ 1], nresults, "text");
+	if (flags & SP_TERM_VALUES) checkTermSource( source[ 0], nresults, "values");
+	if (flags & SP_TERM_TEXT) checkTermSource( source[ 1], nresults, "text");
 
 	allocMatchTerms( out, ndocs, nresults, handleBound, flags);
 	std::vector<sp_match_term_t> records;
@@ -95,10 +73,7 @@ void matchTerms( const sp_result_t* results, uint64_t nresults, const uint64_t* 
 		{
 			const sp_result_t& r = results[ i];
 			valid = r.handle >= 1 && r.handle < handleBound;
-			// the source of this result's value
-			int s = (flags & SP_TERM_VALUES) ? 0 : 1;
-			if (flags == (SP_TERM_VALUES | SP_TERM_TEXT) && !(resultFormat && resultFormat[ i] != 0)) s = 1;
-			const TermSource& S = source[ s];
+			const TermSource& S = source[ termSourceIndex( flags, resultFormat, i)];
 			const Occurrence o = { (uint32_t)(i - r0), r.handle, r.ordpos, r.ordend, S.bytes + S.offsets[ i], S.offsets[ i+1] - S.offsets[ i] };
 			occ.push_back( o);
 		}
@@ -149,35 +124,11 @@ extern "C" void sp_match_terms_free( sp_match_terms_t* t)
 extern "C" int sp_match_batch_terms( const sp_match_batch_t* mb, const sp_match_values_t* values, const sp_match_text_t* text,
 				     uint32_t handle_bound, uint32_t flags, sp_match_terms_t* out, char* err, size_t errsize)
 {
-	std::memset( out, 0, sizeof(*out));
-	if (err && errsize) err[ 0] = 0;
-	try
-	{
+	return spa::hostProduct( out, sp_match_terms_free, err, errsize, [&]{
 		if (!mb) throw std::runtime_error( "no batch");
 		spa::TermSource source[ 2] = {};
-		if (flags & SP_TERM_VALUES)
-		{
-			if (!values || !values->result_value_offsets) throw std::runtime_error( "no values of the results of the batch");
-			if (values->ndocs != mb->ndocs || values->nresults != mb->nresults) throw std::runtime_error( "the values are not those of the batch: other counts of documents or results");
-			const spa::TermSource S = { values->result_values, values->result_value_offsets, values->totals[ 0], values->doc_value_status };
-			source[ 0] = S;
-		}
-		if (flags & SP_TERM_TEXT)
-		{
-			if (!text || !text->result_text_offsets) throw std::runtime_error( "no text of the results of the batch");
-			if (text->ndocs != mb->ndocs || text->nresults != mb->nresults) throw std::runtime_error( "the text is not that of the batch: other counts of documents or results");
-			const spa::TermSource S = { text->result_text, text->result_text_offsets, text->totals[ 0], text->doc_text_status };
-			source[ 1] = S;
-		}
+		spa::termSources( *mb, values, text, flags, source);
 		spa::matchTerms( mb->results, mb->nresults, mb->doc_result_offsets, mb->doc_status, mb->result_format, mb->ndocs,
 				 source, handle_bound, flags, out);
-		return SP_OK;
-	}
-	catch (const std::bad_alloc&) { sp_match_terms_free( out); return SP_ERR_NOMEM; }
-	catch (const std::exception& e)
-	{
-		sp_match_terms_free( out);
-		if (err && errsize) { std::strncpy( err, e.what(), errsize-1); err[ errsize-1] = 0; }
-		return SP_ERR_INVALID;
-	}
+	});
 }

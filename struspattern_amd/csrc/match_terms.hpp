@@ -13,6 +13,8 @@
 #include "../../include/strus_pattern_amd.h"
 #include <cstddef>
 #include <cstdint>
+#include <stdexcept>
+#include <string>
 
 namespace spa {
 
@@ -24,6 +26,59 @@ struct TermSource
 	uint64_t total;			// bytes of `bytes`
 	const int32_t* docStatus;	// ndocs, may be NULL
 };
+
+// ---- what matchTerms, matchDictionary (match_dict.hpp) and their entry points share, with internal linkage as in
+// finished_host.hpp: the library exports nothing of it
+namespace {
+
+// The sources that `flags` selects, from the values and the text of the results of `mb`: source[0] the values, source[1] the
+// text.  Throws std::runtime_error for a selected one that is absent, has no results family or other counts than the batch.
+void termSources( const sp_match_batch_t& mb, const sp_match_values_t* values, const sp_match_text_t* text, uint32_t flags, TermSource (&source)[ 2])
+{
+	if (flags & SP_TERM_VALUES)
+	{
+		if (!values || !values->result_value_offsets) throw std::runtime_error( "no values of the results of the batch");
+		if (values->ndocs != mb.ndocs || values->nresults != mb.nresults) throw std::runtime_error( "the values are not those of the batch: other counts of documents or results");
+		const TermSource S = { values->result_values, values->result_value_offsets, values->totals[ 0], values->doc_value_status };
+		source[ 0] = S;
+	}
+	if (flags & SP_TERM_TEXT)
+	{
+		if (!text || !text->result_text_offsets) throw std::runtime_error( "no text of the results of the batch");
+		if (text->ndocs != mb.ndocs || text->nresults != mb.nresults) throw std::runtime_error( "the text is not that of the batch: other counts of documents or results");
+		const TermSource S = { text->result_text, text->result_text_offsets, text->totals[ 0], text->doc_text_status };
+		source[ 1] = S;
+	}
+}
+
+// which source holds the value of result r: the values unless the flags say text; with both flags the text of a result
+// without a format (resultFormat may be NULL: no result has one)
+inline int termSourceIndex( uint32_t flags, const uint32_t* resultFormat, uint64_t r)
+{
+	if (flags == (SP_TERM_VALUES | SP_TERM_TEXT)) return (resultFormat && resultFormat[ r] != 0) ? 0 : 1;
+	return (flags & SP_TERM_VALUES) ? 0 : 1;
+}
+
+// a selected source is there (matchDictionary, which reads the ranges of the first results only and checks each of them) ...
+void checkTermSource( const TermSource& S, const char* name)
+{
+	if (!S.offsets) throw std::runtime_error( std::string( "no ") + name + " of the results of the batch");
+	if (S.total && !S.bytes) throw std::runtime_error( std::string( name) + " without bytes");
+}
+
+// ... and its offsets start at 0, ascend inside its bytes and cover them (matchTerms, which reads every range)
+void checkTermSource( const TermSource& S, uint64_t nresults, const char* name)
+{
+	checkTermSource( S, name);
+	if (S.offsets[ 0] != 0) throw std::runtime_error( std::string( "offsets of the ") + name + " do not start at the first byte");
+	for (uint64_t r=0; r<nresults; ++r)
+	{
+		if (S.offsets[ r] > S.offsets[ r+1] || S.offsets[ r+1] > S.total) throw std::runtime_error( std::string( "offsets of the ") + name + " do not ascend inside its bytes");
+	}
+	if (S.offsets[ nresults] != S.total) throw std::runtime_error( std::string( "offsets of the ") + name + " do not cover its bytes");
+}
+
+} // namespace
 
 // the host arrays of the terms of `ndocs` documents and `nresults` results, everything but the records: offsets and status
 // zeroed, result_term all 0xFFFFFFFF (sp_match_terms_free)

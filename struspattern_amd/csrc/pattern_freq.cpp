@@ -1,20 +1,12 @@
 // Pattern frequencies of a finished batch over host arrays (pattern_freq.hpp): host only, no device needed.
 #include "pattern_freq.hpp"
-#include "batch_fetch.hpp"
+#include "finished_host.hpp"
 #include <algorithm>
 
 namespace spa {
 
 namespace {
 enum {FREQ_ERR_RANGE = SP_DOC_ERR_RANGE};
-
-template <class T>
-T* zeroedArray( uint64_t n)
-{
-	T* p = hostArray<T>( n ? n : 1);
-	std::memset( p, 0, (size_t)(n ? n : 1) * sizeof(T));
-	return p;
-}
 
 // the results of one document as (handle, ordpos, ordend), ascending by handle: equal handles are neighbours
 struct Occurrence
@@ -28,15 +20,15 @@ struct Occurrence
 void allocPatternFreq( sp_pattern_freq_batch_t* out, size_t ndocs, uint32_t handleBound)
 {
 	out->ndocs = ndocs; out->nrecords = 0; out->handle_bound = handleBound; out->totals[ 0] = 0;
-	out->doc_offsets = zeroedArray<uint64_t>( ndocs + 1);
-	out->doc_freq_status = zeroedArray<int32_t>( ndocs + 1);
-	out->handle_results = zeroedArray<uint64_t>( handleBound);
-	out->handle_docs = zeroedArray<uint32_t>( handleBound);
+	out->doc_offsets = filledArray<uint64_t>( ndocs + 1);
+	out->doc_freq_status = filledArray<int32_t>( ndocs + 1);
+	out->handle_results = filledArray<uint64_t>( handleBound);
+	out->handle_docs = filledArray<uint32_t>( handleBound);
 }
 
 void allocPatternFreqRecords( sp_pattern_freq_batch_t* out, uint64_t nrecords)
 {
-	out->records = zeroedArray<sp_pattern_freq_t>( nrecords);
+	out->records = filledArray<sp_pattern_freq_t>( nrecords);
 	out->nrecords = (size_t)nrecords; out->totals[ 0] = nrecords;
 }
 
@@ -46,12 +38,7 @@ void patternFreq( const sp_result_t* results, uint64_t nresults, const uint64_t*
 	if (!handleBound) throw std::runtime_error( "a handle bound of 0 leaves no valid handle");
 	if (!docOffsets) throw std::runtime_error( "batch without document offsets");
 	if (nresults && !results) throw std::runtime_error( "batch without results");
-	if (docOffsets[ 0] != 0) throw std::runtime_error( "document offsets of the batch do not start at its first result");
-	for (size_t d=0; d<ndocs; ++d)
-	{
-		if (docOffsets[ d] > docOffsets[ d+1] || docOffsets[ d+1] > nresults) throw std::runtime_error( "document offsets of the batch do not ascend inside its results");
-	}
-	if (docOffsets[ ndocs] != nresults) throw std::runtime_error( "document offsets of the batch do not cover its results");
+	checkDocOffsets( docOffsets, ndocs, nresults);
 
 	allocPatternFreq( out, ndocs, handleBound);
 	std::vector<sp_pattern_freq_t> records;
@@ -105,19 +92,8 @@ extern "C" void sp_pattern_freq_batch_free( sp_pattern_freq_batch_t* b)
 
 extern "C" int sp_match_batch_pattern_freq( const sp_match_batch_t* mb, uint32_t handle_bound, sp_pattern_freq_batch_t* out, char* err, size_t errsize)
 {
-	std::memset( out, 0, sizeof(*out));
-	if (err && errsize) err[ 0] = 0;
-	try
-	{
+	return spa::hostProduct( out, sp_pattern_freq_batch_free, err, errsize, [&]{
 		if (!mb) throw std::runtime_error( "no batch");
 		spa::patternFreq( mb->results, mb->nresults, mb->doc_result_offsets, mb->doc_status, mb->ndocs, handle_bound, out);
-		return SP_OK;
-	}
-	catch (const std::bad_alloc&) { sp_pattern_freq_batch_free( out); return SP_ERR_NOMEM; }
-	catch (const std::exception& e)
-	{
-		sp_pattern_freq_batch_free( out);
-		if (err && errsize) { std::strncpy( err, e.what(), errsize-1); err[ errsize-1] = 0; }
-		return SP_ERR_INVALID;
-	}
+	});
 }

@@ -1,20 +1,11 @@
 // The values of the format strings of a finished batch over host arrays (result_values.hpp): host only, no device needed.
 #include "result_values.hpp"
-#include "batch_fetch.hpp"
+#include "finished_host.hpp"
 
 namespace spa {
 
 namespace {
 const uint64_t MAX32 = 0xFFFFFFFFull;
-enum {VALUE_ERR_RANGE = SP_DOC_ERR_RANGE};
-
-template <class T>
-T* zeroedArray( uint64_t n)
-{
-	T* p = hostArray<T>( n);
-	std::memset( p, 0, (size_t)n * sizeof(T));
-	return p;
-}
 
 struct HostStack
 {
@@ -31,100 +22,55 @@ struct DocItems
 	bool span( uint32_t i, uint64_t& begin, uint64_t& length) const { return spanRange( S, doc, (const uint32_t*)(mb.items + first + i) + 3, begin, length); }
 };
 
-struct Batch
+// the records of one family: the bytes of a record with a format are its value, a record without one has none
+struct Values
 {
-	const FormatTable& table; const sp_match_batch_t& mb; const TextSource& S;
-	std::vector<uint64_t> docItems;		// ndocs+1: the items of a finished batch have no gaps and are in result order
-};
-
-// one family: the records of document d are [docOffsets[d], docOffsets[d+1])
-struct Family
-{
+	const FormatTable& table; const ValueFormats T; const sp_match_batch_t& mb; const TextSource& S;
+	const uint64_t* docItems;		// ndocs+1
 	int items;				// 0: results, 1: item records
-	const uint64_t* docOffsets;
-	std::vector<uint32_t> work;		// per record: the offset of its value inside the document
-	std::vector<uint64_t> docBytes;
-	char** bytes; uint64_t* offsets; uint64_t* total;
+
+	// Whether record `i` has a value in document d: its format and its list, relative to the document's items.
+	// ok = false: the record makes the document fail.
+	bool valueOf( size_t d, uint64_t i, uint32_t& fmt, uint32_t& b, uint32_t& e, bool& ok) const
+	{
+		const uint64_t i0 = docItems[ d], i1 = docItems[ d+1];
+		uint64_t lb, le;
+		if (items) { fmt = mb.item_format[ 2*i]; lb = i + 1; le = lb + mb.item_format[ 2*i + 1]; }
+		else { fmt = mb.result_format[ i]; lb = mb.results[ i].item_begin; le = lb + mb.results[ i].item_count; }
+		ok = true;
+		if (!fmt) return false;
+		ok = fmt <= table.count && lb >= i0 && le <= i1 && i1 - i0 <= MAX32;
+		b = (uint32_t)(lb - i0); e = (uint32_t)(le - i0);
+		return ok;
+	}
+	// the pieces of the value of record i, one after the other, to `piece`, which says whether to go on; false: the document fails
+	template <class FN>
+	bool walk( size_t d, uint64_t i, FN piece) const
+	{
+		uint32_t fmt, b, e;
+		bool ok;
+		if (!valueOf( d, i, fmt, b, e, ok)) return ok;
+		const DocItems list = { mb, S, d, docItems[ d] };
+		HostStack stack;
+		ValueWalk<HostStack, DocItems> w( T, stack, list);
+		w.start( fmt, b, e);
+		ValuePiece p;
+		while (w.next( p) && piece( p)) {}
+		return !w.failed;
+	}
+	bool length( size_t d, uint64_t i, uint64_t& n) const
+	{
+		return walk( d, i, [&]( const ValuePiece& p) { n += p.len; return n <= MAX32; });
+	}
+	void write( size_t d, uint64_t i, char* at) const
+	{
+		walk( d, i, [&]( const ValuePiece& p) {
+			std::memcpy( at, (p.kind == VALUE_PIECE_TEXT ? S.text : table.pool.data()) + p.src, p.len);
+			at += p.len;
+			return true;
+		});
+	}
 };
-
-// Whether record `i` of the family has a value in document d: its format and its list, relative to the document's items.
-// ok = false: the record makes the document fail.
-bool valueOf( const Batch& B, const Family& F, size_t d, uint64_t i, uint32_t& fmt, uint32_t& b, uint32_t& e, bool& ok)
-{
-	const uint64_t i0 = B.docItems[ d], i1 = B.docItems[ d+1];
-	uint64_t lb, le;
-	if (F.items) { fmt = B.mb.item_format[ 2*i]; lb = i + 1; le = lb + B.mb.item_format[ 2*i + 1]; }
-	else { fmt = B.mb.result_format[ i]; lb = B.mb.results[ i].item_begin; le = lb + B.mb.results[ i].item_count; }
-	ok = true;
-	if (!fmt) return false;
-	ok = fmt <= B.table.count && lb >= i0 && le <= i1 && i1 - i0 <= MAX32;
-	b = (uint32_t)(lb - i0); e = (uint32_t)(le - i0);
-	return ok;
-}
-
-// pass A of the device: offsets inside the document, its byte count, its status
-void countFamily( const Batch& B, Family& F, int32_t* status)
-{
-	const size_t ndocs = B.mb.ndocs;
-	const ValueFormats T = B.table.view();
-	F.work.assign( (size_t)F.docOffsets[ ndocs] + 1, 0);
-	F.docBytes.assign( ndocs + 1, 0);
-	for (size_t d=0; d<ndocs; ++d)
-	{
-		uint64_t total = 0;
-		bool ok = true;
-		const DocItems items = { B.mb, B.S, d, B.docItems[ d] };
-		for (uint64_t i=F.docOffsets[ d]; ok && i<F.docOffsets[ d+1]; ++i)
-		{
-			uint32_t fmt, b, e;
-			F.work[ i] = (uint32_t)total;
-			if (!valueOf( B, F, d, i, fmt, b, e, ok)) continue;
-			HostStack stack;
-			ValueWalk<HostStack, DocItems> walk( T, stack, items);
-			walk.start( fmt, b, e);
-			ValuePiece p;
-			uint64_t length = 0;
-			while (length <= MAX32 && walk.next( p)) length += p.len;
-			ok = !walk.failed && length <= MAX32;
-			if (ok) total += length;
-			if (total > MAX32) ok = false;
-		}
-		if (ok) F.docBytes[ d] = total; else status[ d] = VALUE_ERR_RANGE;
-	}
-}
-
-// passes B and C of the device
-void placeFamily( const Batch& B, Family& F, const int32_t* status)
-{
-	const size_t ndocs = B.mb.ndocs;
-	const ValueFormats T = B.table.view();
-	std::vector<uint64_t> docAt( ndocs + 1, 0);
-	for (size_t d=0; d<ndocs; ++d) docAt[ d+1] = docAt[ d] + (status[ d] ? 0 : F.docBytes[ d]);
-	*F.total = docAt[ ndocs];
-	*F.bytes = hostArray<char>( docAt[ ndocs] + 1);
-	for (size_t d=0; d<ndocs; ++d)
-	{
-		const DocItems items = { B.mb, B.S, d, B.docItems[ d] };
-		for (uint64_t i=F.docOffsets[ d]; i<F.docOffsets[ d+1]; ++i)
-		{
-			F.offsets[ i] = docAt[ d] + (status[ d] ? 0 : F.work[ i]);
-			uint32_t fmt, b, e;
-			bool ok;
-			if (status[ d] || !valueOf( B, F, d, i, fmt, b, e, ok)) continue;
-			HostStack stack;
-			ValueWalk<HostStack, DocItems> walk( T, stack, items);
-			walk.start( fmt, b, e);
-			ValuePiece p;
-			char* at = *F.bytes + F.offsets[ i];
-			while (walk.next( p))
-			{
-				std::memcpy( at, (p.kind == VALUE_PIECE_TEXT ? B.S.text : B.table.pool.data()) + p.src, p.len);
-				at += p.len;
-			}
-		}
-	}
-	F.offsets[ F.docOffsets[ ndocs]] = docAt[ ndocs];
-}
 
 void appendLiteral( FormatTable& T, std::string& lit)
 {
@@ -195,9 +141,9 @@ FormatTable buildFormatTable( uint32_t count, const std::function<const char*(ui
 void allocMatchValues( sp_match_values_t* out, size_t ndocs, uint64_t nresults, uint64_t nitems, uint32_t flags)
 {
 	out->ndocs = ndocs; out->nresults = (size_t)nresults; out->nitems = (size_t)nitems;
-	out->doc_value_status = zeroedArray<int32_t>( ndocs + 1);
-	if (flags & SP_VALUE_RESULTS) out->result_value_offsets = zeroedArray<uint64_t>( nresults + 1);
-	if (flags & SP_VALUE_ITEMS) out->item_value_offsets = zeroedArray<uint64_t>( nitems + 1);
+	out->doc_value_status = filledArray<int32_t>( ndocs + 1);
+	if (flags & SP_VALUE_RESULTS) out->result_value_offsets = filledArray<uint64_t>( nresults + 1);
+	if (flags & SP_VALUE_ITEMS) out->item_value_offsets = filledArray<uint64_t>( nitems + 1);
 }
 
 void allocMatchValuesBytes( sp_match_values_t* out, uint32_t flags)
@@ -213,31 +159,17 @@ void matchBatchValues( const FormatTable& table, const sp_match_batch_t& mb, con
 	if (!S.docSegOffsets && S.nseg != mb.ndocs) throw std::runtime_error( "without document segment offsets every document is one segment: nseg must be ndocs");
 	if (!table.error.empty()) throw std::runtime_error( table.error);
 	const size_t ndocs = mb.ndocs;
-	if (ndocs && !mb.doc_result_offsets) throw std::runtime_error( "batch without document offsets");
-	Batch B = { table, mb, S, std::vector<uint64_t>( ndocs + 1, 0) };
-	for (size_t d=0; d<ndocs; ++d)
-	{
-		const uint64_t r0 = mb.doc_result_offsets[ d], r1 = mb.doc_result_offsets[ d+1];
-		if (r0 > r1 || r1 > mb.nresults || (d == 0 && r0 != 0)) throw std::runtime_error( "document offsets of the batch do not ascend inside its results");
-		uint64_t n = 0;
-		for (uint64_t i=r0; i<r1; ++i) n += mb.results[ i].item_count;
-		B.docItems[ d+1] = B.docItems[ d] + n;
-	}
-	if ((ndocs ? mb.doc_result_offsets[ ndocs] : 0) != mb.nresults || B.docItems[ ndocs] != mb.nitems) throw std::runtime_error( "not a finished batch: results or items outside the documents");
+	const DocRecords docs = finishedDocRecords( mb);
 	allocMatchValues( out, ndocs, mb.nresults, mb.nitems, flags);
 	// a batch without formats: all values empty
 	if (!table.count || !mb.result_format || !mb.item_format) { allocMatchValuesBytes( out, flags); return; }
-	std::vector<uint64_t> docResults( ndocs + 1, 0);
-	if (ndocs) docResults.assign( mb.doc_result_offsets, mb.doc_result_offsets + ndocs + 1);
-	Family R, I;
-	R.items = 0; R.docOffsets = docResults.data();
-	I.items = 1; I.docOffsets = B.docItems.data();
-	R.bytes = &out->result_values; R.offsets = out->result_value_offsets; R.total = &out->totals[ 0];
-	I.bytes = &out->item_values; I.offsets = out->item_value_offsets; I.total = &out->totals[ 1];
-	if (flags & SP_VALUE_RESULTS) countFamily( B, R, out->doc_value_status);
-	if (flags & SP_VALUE_ITEMS) countFamily( B, I, out->doc_value_status);
-	if (flags & SP_VALUE_RESULTS) placeFamily( B, R, out->doc_value_status);
-	if (flags & SP_VALUE_ITEMS) placeFamily( B, I, out->doc_value_status);
+	const Values results = { table, table.view(), mb, S, docs.items.data(), 0 }, items = { table, table.view(), mb, S, docs.items.data(), 1 };
+	ByteFamily R = { docs.results.data(), ndocs, &out->result_values, out->result_value_offsets, &out->totals[ 0] };
+	ByteFamily I = { docs.items.data(), ndocs, &out->item_values, out->item_value_offsets, &out->totals[ 1] };
+	if (flags & SP_VALUE_RESULTS) R.count( results, out->doc_value_status);
+	if (flags & SP_VALUE_ITEMS) I.count( items, out->doc_value_status);
+	if (flags & SP_VALUE_RESULTS) R.place( results, out->doc_value_status);
+	if (flags & SP_VALUE_ITEMS) I.place( items, out->doc_value_status);
 }
 
 } // namespace

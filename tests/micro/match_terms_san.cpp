@@ -2,62 +2,8 @@
 // batches of tests/test_terms_abi.py, the invalid handles and the refused arguments included.  No HIP code is linked:
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -Istruspattern_amd/csrc \
 //       tests/micro/match_terms_san.cpp struspattern_amd/csrc/match_terms.cpp -o match_terms_san && ./match_terms_san
-#include "match_terms.hpp"
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
-
-#define CHECK( COND) do { if (!(COND)) { std::fprintf( stderr, "%s:%d: failed: %s\n", __FILE__, __LINE__, #COND); std::exit( 1); } } while (0)
-
-// A finished batch with the text of its results.  Every array is exactly as long as what it holds (the bytes live in a
-// heap block of their exact size), so a read past it is the sanitizer's to report.
-struct Batch
-{
-	std::vector<sp_result_t> results;
-	std::vector<uint64_t> offsets = {0};
-	std::vector<int32_t> status, sourceStatus;
-	std::vector<uint32_t> format;
-	std::vector<uint64_t> valueOffsets = {0};
-	std::string bytes;
-	std::vector<char> exact;
-
-	void document() { offsets.push_back( results.size()); status.push_back( 0); sourceStatus.push_back( 0); }
-	void result( uint32_t handle, uint32_t ordpos, uint32_t ordend, const std::string& value, uint32_t fmt = 0)
-	{
-		sp_result_t r = {};
-		r.handle = handle; r.ordpos = ordpos; r.ordend = ordend;
-		results.push_back( r); format.push_back( fmt);
-		bytes += value; valueOffsets.push_back( bytes.size());
-	}
-	sp_match_batch_t view()
-	{
-		sp_match_batch_t mb = {};
-		mb.ndocs = status.size(); mb.nresults = results.size();
-		mb.results = results.empty() ? 0 : results.data(); mb.doc_result_offsets = offsets.data(); mb.doc_status = status.empty() ? 0 : status.data();
-		mb.result_format = format.empty() ? 0 : format.data();
-		return mb;
-	}
-	sp_match_text_t text()
-	{
-		exact.assign( bytes.begin(), bytes.end());
-		sp_match_text_t t = {};
-		t.ndocs = status.size(); t.nresults = results.size();
-		t.result_text = exact.empty() ? 0 : exact.data(); t.result_text_offsets = valueOffsets.data();
-		t.doc_text_status = sourceStatus.empty() ? 0 : sourceStatus.data(); t.totals[ 0] = exact.size();
-		return t;
-	}
-	sp_match_values_t values()
-	{
-		exact.assign( bytes.begin(), bytes.end());
-		sp_match_values_t v = {};
-		v.ndocs = status.size(); v.nresults = results.size();
-		v.result_values = exact.empty() ? 0 : exact.data(); v.result_value_offsets = valueOffsets.data();
-		v.doc_value_status = sourceStatus.empty() ? 0 : sourceStatus.data(); v.totals[ 0] = exact.size();
-		return v;
-	}
-};
+// (the batch is that of finished_batch_fixture.hpp: one string per result serves as its text and as its value)
+#include "finished_batch_fixture.hpp"
 
 struct Terms
 {
@@ -67,8 +13,8 @@ struct Terms
 	Terms( Batch& b, uint32_t bound, uint32_t flags = SP_TERM_TEXT)
 	{
 		sp_match_batch_t mb = b.view();
-		sp_match_text_t x = b.text();
-		sp_match_values_t v = b.values();
+		sp_match_text_t x = b.textView();
+		sp_match_values_t v = b.valuesView();
 		rc = sp_match_batch_terms( &mb, (flags & SP_TERM_VALUES) ? &v : 0, (flags & SP_TERM_TEXT) ? &x : 0, bound, flags, &t, err, sizeof(err));
 	}
 	~Terms() { sp_match_terms_free( &t); }
@@ -139,7 +85,7 @@ static void rangeRule()
 	// a source status between two good documents; a document the matcher failed
 	Batch b;
 	b.result( 1, 0, 1, "x"); b.document();
-	b.result( 1, 0, 1, "x"); b.document(); b.sourceStatus[ 1] = SP_DOC_ERR_RANGE;
+	b.result( 1, 0, 1, "x"); b.document(); b.textStatus[ 1] = SP_DOC_ERR_RANGE;
 	b.result( 1, 0, 1, "x"); b.document();
 	b.result( 1, 0, 1, "x"); b.document(); b.status[ 3] = 1;
 	Terms q( b, 2);
@@ -155,7 +101,7 @@ static void refusedArguments()
 	{ Terms q( b, 2, 0); CHECK( q.rc == SP_ERR_INVALID); }
 	{ Terms q( b, 2, 4); CHECK( q.rc == SP_ERR_INVALID); }
 	sp_match_batch_t mb = b.view();
-	sp_match_text_t x = b.text();
+	sp_match_text_t x = b.textView();
 	sp_match_terms_t t;
 	char err[ 8];
 	CHECK( sp_match_batch_terms( &mb, 0, &x, 2, SP_TERM_VALUES, &t, err, sizeof(err)) == SP_ERR_INVALID && std::strlen( err) == 7);	// (the message is cut to the buffer)
@@ -163,13 +109,13 @@ static void refusedArguments()
 	CHECK( sp_match_batch_terms( 0, 0, &x, 2, SP_TERM_TEXT, &t, 0, 0) == SP_ERR_INVALID);
 	x.nresults -= 1;
 	CHECK( sp_match_batch_terms( &mb, 0, &x, 2, SP_TERM_TEXT, &t, 0, 0) == SP_ERR_INVALID);
-	x = b.text(); x.result_text_offsets = 0;
+	x = b.textView(); x.result_text_offsets = 0;
 	CHECK( sp_match_batch_terms( &mb, 0, &x, 2, SP_TERM_TEXT, &t, 0, 0) == SP_ERR_INVALID);
 	const uint64_t sourceOffsets[ 3][ 4] = {{0, 3, 2, 3}, {0, 2, 3, 4}, {1, 2, 3, 3}};
 	for (const uint64_t* o : sourceOffsets)
 	{
 		Batch c = b;
-		c.valueOffsets.assign( o, o+4);
+		c.textOffsets.assign( o, o+4);
 		Terms q( c, 2);
 		CHECK( q.rc == SP_ERR_INVALID && std::strstr( q.err, "offsets"));
 	}
