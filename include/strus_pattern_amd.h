@@ -752,6 +752,93 @@ int sp_matcher_ctx_last_dictionary_ms(sp_matcher_ctx_t* c, double* ms);
  * of its range; SP_ERR_NOMEM when memory runs out. */
 int sp_match_batch_dictionary(const sp_match_batch_t* mb, const sp_match_values_t* values, const sp_match_text_t* text,
                               const sp_match_terms_t* terms, sp_match_dictionary_t* out, char* err, size_t errsize);
+
+/* ---- batch postings: for every entry of the batch dictionary the documents that hold it -- the list (document, term
+ * frequency, first position), ascending by document, that an indexer appends to its inverted index, and the way from every
+ * term record to its posting; built on the device (csrc/l2_postings.h) or, for a batch already fetched, on the host
+ * (csrc/match_postings.hpp).  The rule is the project's own, unpinned by a reference vector.
+ * INPUT: the dictionary built last on a context (sp_matcher_ctx_finished_dictionary_device), which implies the terms batch it
+ * was built from.  Write N for the number of term records and ndict for the number of entries.  Record i lies in document
+ * d(i), at index t(i) = i - doc_term_offsets[d(i)] inside that document's block, and term_dict[i] is its entry.  No source
+ * byte is read: term_dict already says which records are the same term.
+ * POSTING: one 16-byte record sp_posting_t per term record: {d(i), t(i), records[i].count, records[i].first_ordpos}.
+ * OUTPUTS:
+ *   entry_offsets[ndict+1]   (uint64) the exclusive prefix sums of doc_freq in dictionary order; entry_offsets[ndict] is N,
+ *   postings[N]              the postings of entry e are [entry_offsets[e], entry_offsets[e+1]), strictly ascending by `doc`
+ *                            inside an entry: a document has at most one record per term, so this is also the ascending
+ *                            order of the global record index i,
+ *   record_posting[N]        (uint32) parallel to the term records: the index of record i's posting, a permutation of 0..N-1,
+ *   totals[0]                N.
+ * INVARIANTS: postings[record_posting[i]] is {d(i), t(i), records[i].count, records[i].first_ordpos}; the first posting of
+ * entry e is {first_doc, first_term, ..}; the list of e has doc_freq postings; the sum of `count` over the list of e is the
+ * entry's count and the maximum its max_count; record_posting[i] lies in the range of entry term_dict[i].
+ * DETERMINISM: every output word is a function of the terms batch and its dictionary alone; no timing enters (the device
+ * partitions the records with a stable radix partition over fixed tiles of records, without an atomic on its data).  After a
+ * canonical finish the exact engines and result-set mode leave the same bytes.
+ * SAFETY, as for the terms and the dictionary: no byte outside the outputs is written; a record index is compared against N
+ * before a term record is read, an entry index against ndict and a document index against ndocs before use, and so is
+ * every position read from working memory.  A term_dict[i] at or beyond ndict cannot come from this context's own
+ * dictionary; were it there, the device would take ndict - 1 for the record's entry and touch nothing out of bounds (the host
+ * twin refuses such a dictionary).
+ * LIMIT: N below 2^32 - 1, which the dictionary enforces.
+ * The positions of EVERY occurrence of a term in a document are not part of a posting: they are a gather through result_term
+ * (the results of doc whose result_term is `term`) and record_posting.  Postings or entries ordered by (handle, value bytes)
+ * are not offered, as for the dictionary. */
+typedef struct sp_posting {
+	uint32_t doc;           /* the document */
+	uint32_t term;          /* index of the term record inside doc's block: everything else about the occurrence hangs off it */
+	uint32_t count;         /* that record's count: the term frequency in doc */
+	uint32_t first_ordpos;  /* that record's first_ordpos */
+} sp_posting_t;
+typedef struct sp_match_postings_device {
+	size_t ndocs;
+	size_t nterms;               /* N */
+	size_t ndict;
+	void* d_postings;            /* sp_posting_t[N] */
+	void* d_entry_offsets;       /* uint64_t[ndict+1] */
+	void* d_record_posting;      /* uint32_t[N], parallel to the term records */
+	void* d_totals;              /* uint64_t[1]: N */
+} sp_match_postings_device_t;
+/* host copy of the postings (sp_match_postings_free) */
+typedef struct sp_match_postings {
+	size_t ndocs;
+	size_t nterms;                /* N */
+	size_t ndict;
+	sp_posting_t* postings;       /* nterms */
+	uint64_t* entry_offsets;      /* ndict+1 */
+	uint32_t* record_posting;     /* nterms */
+	uint64_t totals[1];           /* N */
+} sp_match_postings_t;
+/* Builds the postings of the dictionary built last on this context.  The host knows N and ndict from the dictionary call, so
+ * this call enqueues every launch on `stream` and returns without waiting for anything: keys, entry offsets, then per radix
+ * pass histogram, scan and scatter, then place (csrc/l2_postings.h); ceil(bitwidth(ndict - 1) / 8) passes, none for ndict <= 1.
+ * The buffers belong to the context, are allocated at the first call, only grow (working memory: 4N bytes for the document of
+ * every record, 2 x 8N for the two buffers of (entry, record) pairs, 4 x 256 x ceil(N / tile) for the digit counts of the tiles
+ * (sp_matcher_postings_tile), and 66 cursor words), and are valid until the next postings call; the next batch, finish, terms
+ * or dictionary call invalidates the state, not the buffers.  A `stream` other than the dictionary's is ordered behind the
+ * dictionary with an event (its placement is not waited for by its own call).  SP_ERR_INVALID when no dictionary was built
+ * since the last terms call of the last finish; SP_ERR_NOMEM when a buffer cannot be allocated (the context stays usable,
+ * `out` is empty). */
+int sp_matcher_ctx_finished_postings_device(sp_matcher_ctx_t* c, void* stream, sp_match_postings_device_t* out);
+/* plain copy of the buffers of the last sp_matcher_ctx_finished_postings_device to the host (waits for it) */
+int sp_matcher_ctx_finished_postings_fetch(sp_matcher_ctx_t* c, sp_match_postings_t* out);
+void sp_match_postings_free(sp_match_postings_t* p);
+/* duration of the launches of the last postings call in milliseconds (HIP events on its stream round them; waits for them;
+ * the hipMemsetAsync that clears the cursors is enqueued before the first event, as the clearing of every other product) */
+int sp_matcher_ctx_last_postings_ms(sp_matcher_ctx_t* c, double* ms);
+/* diagnostics and tests: the records of one tile of the device's partition; tile k is always the records
+ * [k * tile, (k+1) * tile) in the order of the pass, whichever wave takes it */
+uint32_t sp_matcher_postings_tile(void);
+/* test hook (tests only): the bits of a radix digit, 1..8; anything else selects the default, 8.  The outputs do not change
+ * by a bit. */
+void sp_test_postings_digit_bits(unsigned bits);
+/* The same rule over host arrays, needs no device, and the yardstick of the device passes: the postings of a terms batch and
+ * its dictionary already fetched (or made by sp_match_batch_terms and sp_match_batch_dictionary), by a counting sort.  Fills
+ * `out` (sp_match_postings_free); SP_ERR_INVALID with the message in `err` for a NULL argument, for ndocs or nterms that do not
+ * agree between `terms` and `dict`, for term offsets that do not ascend or do not cover nrecords, for a term_dict[i] at or
+ * beyond ndict, and for a doc_freq that is not the number of records of its entry; SP_ERR_NOMEM when memory runs out. */
+int sp_match_batch_postings(const sp_match_terms_t* terms, const sp_match_dictionary_t* dict, sp_match_postings_t* out,
+                            char* err, size_t errsize);
 /* copies the results of the last device batch to the host, grouped by document (as sp_matcher_ctx_match_docs
  * returns them, `exclusive` elimination included) */
 int sp_matcher_ctx_batch_fetch(sp_matcher_ctx_t* c, sp_match_batch_t* out);

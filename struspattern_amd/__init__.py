@@ -13,7 +13,7 @@ from . import capi
 from .capi import SpLexem, SpResult, SpResultItem
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
-           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms", "MatchDictionary", "batchDictionary"]
+           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms", "MatchDictionary", "batchDictionary", "MatchPostings", "batchPostings"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
@@ -366,6 +366,15 @@ def batchDictionary(mb, terms, values=None, text=None, handle_bound=0):
     L = capi.lib()
     b, keep = _host_batch(mb, formats="results", status=True)       # (keep: until the call has returned)
     v, x = _host_sources(values, text, keep)
+    t = _host_terms(terms, bound, keep)
+    err = ctypes.create_string_buffer(256)
+    return _product(capi.SpMatchDictionary, lambda d: L.sp_match_batch_dictionary(ctypes.byref(b), ctypes.byref(v) if v is not None else None,
+                                                                                 ctypes.byref(x) if x is not None else None, ctypes.byref(t), ctypes.byref(d), err, 256),
+                    L.sp_match_dictionary_free, _match_dictionary_of, lambda rc: "no dictionary of the batch (%d): %s" % (rc, err.value.decode()))
+
+
+def _host_terms(terms, bound, keep):
+    """the capi.SpMatchTerms of a MatchTerms for a host twin; the arrays it points into are appended to `keep`"""
     t = capi.SpMatchTerms()
     rec = np.ascontiguousarray(terms.records, dtype=np.uint32).reshape(-1, 6)
     offs = np.ascontiguousarray(terms.doc_offsets, dtype=np.uint64)
@@ -379,10 +388,55 @@ def batchDictionary(mb, terms, values=None, text=None, handle_bound=0):
     t.result_term = ctypes.cast(rt.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
     t.doc_term_status = ctypes.cast(st.ctypes.data, ctypes.POINTER(ctypes.c_int32))
     t.totals[0] = len(rec)
+    return t
+
+
+class MatchPostings:
+    """The postings of a dictionary (host copies): per term record one posting (doc, term, count, first_ordpos), the postings
+    of dictionary entry e together and ascending by document, and per term record the index of its posting
+    (include/strus_pattern_amd.h "batch postings")."""
+
+    def __init__(self, records, entry_offsets, record_posting):
+        self.records = records                # (nterms, 4) u32: doc, term, count, first_ordpos
+        self.entry_offsets = entry_offsets    # (ndict+1,) u64: the postings of entry e are records[entry_offsets[e]:entry_offsets[e+1]]
+        self.record_posting = record_posting  # (nterms,) u32, parallel to the term records
+
+    def entry(self, e):
+        """the postings of dictionary entry e, in document order: rows (doc, term, count, first_ordpos)"""
+        return self.records[int(self.entry_offsets[e]):int(self.entry_offsets[e + 1])]
+
+    def docs(self, e):
+        """the documents that hold dictionary entry e, ascending"""
+        return self.entry(e)[:, 0]
+
+
+def _match_postings_of(p):
+    """the MatchPostings of a capi.SpMatchPostings (copies)"""
+    return MatchPostings(_rows(p.postings, p.nterms, 4), _rows(p.entry_offsets, p.ndict + 1, 0, ctypes.c_uint64), _rows(p.record_posting, p.nterms, 0))
+
+
+def batchPostings(terms, dictionary):
+    """The postings of a dictionary already on the host (terms: the MatchTerms, dictionary: the MatchDictionary built from
+    them: the fetches of a context, or batchTerms and batchDictionary), by the rule of the device call, without a device.
+    Returns a MatchPostings."""
+    L = capi.lib()
+    keep = []                                                        # (until the call has returned)
+    t = _host_terms(terms, terms.handle_bound, keep)
+    d = capi.SpMatchDictionary()
+    rec = np.ascontiguousarray(dictionary.records, dtype=np.uint32).reshape(-1, 8)
+    td = np.ascontiguousarray(dictionary.term_dict, dtype=np.uint32)
+    offs = np.ascontiguousarray(dictionary.doc_offsets, dtype=np.uint64)
+    ht = np.ascontiguousarray(dictionary.handle_terms, dtype=np.uint32)
+    keep.extend([rec, td, offs, ht])
+    d.ndocs, d.nterms, d.ndict, d.handle_bound, d.flags = len(offs) - 1, len(td), len(rec), len(ht), terms.flags
+    d.records = ctypes.cast(rec.ctypes.data, ctypes.POINTER(capi.SpDictTerm))
+    d.term_dict = ctypes.cast(td.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
+    d.doc_dict_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
+    d.handle_terms = ctypes.cast(ht.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
+    d.totals[0] = len(rec)
     err = ctypes.create_string_buffer(256)
-    return _product(capi.SpMatchDictionary, lambda d: L.sp_match_batch_dictionary(ctypes.byref(b), ctypes.byref(v) if v is not None else None,
-                                                                                 ctypes.byref(x) if x is not None else None, ctypes.byref(t), ctypes.byref(d), err, 256),
-                    L.sp_match_dictionary_free, _match_dictionary_of, lambda rc: "no dictionary of the batch (%d): %s" % (rc, err.value.decode()))
+    return _product(capi.SpMatchPostings, lambda p: L.sp_match_batch_postings(ctypes.byref(t), ctypes.byref(d), ctypes.byref(p), err, 256),
+                    L.sp_match_postings_free, _match_postings_of, lambda rc: "no postings of the batch (%d): %s" % (rc, err.value.decode()))
 
 
 class PatternMatcherContext:
@@ -620,6 +674,26 @@ class PatternMatcherContext:
     def lastDictionaryMs(self):
         """duration of the launches of the last finishedDictionaryDevice in milliseconds"""
         return self._last_ms(self._L.sp_matcher_ctx_last_dictionary_ms, "dictionary call")
+
+    def finishedPostingsDevice(self, stream=0):
+        """build the postings of the dictionary built by finishedDictionaryDevice on the device (everything is asynchronous
+        on `stream`: the call waits for nothing): per dictionary entry the list of (doc, term, count, first_ordpos) in
+        document order, and per term record the index of its posting.  Returns the device pointers
+        (capi.SpMatchPostingsDevice), valid until the next call."""
+        out = capi.SpMatchPostingsDevice()
+        rc = self._L.sp_matcher_ctx_finished_postings_device(self._h, stream or None, ctypes.byref(out))
+        if rc != 0:
+            raise PatternError("building the postings of the batch on the device failed (%d): %s" % (rc, self._err()))
+        return out
+
+    def finishedPostingsFetch(self):
+        """plain host copy of the postings built by finishedPostingsDevice: a MatchPostings"""
+        return self._fetch_product(capi.SpMatchPostings, self._L.sp_matcher_ctx_finished_postings_fetch, self._L.sp_match_postings_free,
+                                   _match_postings_of, "the postings of the batch")
+
+    def lastPostingsMs(self):
+        """duration of the launches of the last finishedPostingsDevice in milliseconds"""
+        return self._last_ms(self._L.sp_matcher_ctx_last_postings_ms, "postings call")
 
     def batchFetch(self, first_doc=None, ndocs=None):
         """host copy of the last device batch, grouped by document; with (first_doc, ndocs) only of
@@ -1087,7 +1161,7 @@ class PatternLexer:
         return "std"
 
 
-def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False, with_terms=False, with_dictionary=False):
+def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False, with_terms=False, with_dictionary=False, with_postings=False):
     """Segmented documents, host buffers in and out: `text` holds the segments back to back (seg_offsets: nseg+1 byte
     offsets), document d consists of the segments [doc_seg_offsets[d], doc_seg_offsets[d+1]).  Lexer -> stitch on the
     device -> rule matcher -> fetch; only the text goes up and the results come down.  Returns the MatchBatch, whose
@@ -1097,7 +1171,9 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
     (MatchBatch, MatchValues), or (MatchBatch, MatchText, MatchValues) with both.  with_terms: the results are grouped into
     index terms there (value where a result has a format, else text: text and values are built for it); returns
     (MatchBatch, MatchText, MatchValues, MatchTerms).  with_dictionary implies with_terms: the dictionary of the terms is built
-    there too and returned as a fifth element, a MatchDictionary."""
+    there too and returned as a fifth element, a MatchDictionary.  with_postings implies with_dictionary: the postings of
+    the dictionary are built there too and returned as a sixth element, a MatchPostings."""
+    with_dictionary = with_dictionary or with_postings
     with_terms = with_terms or with_dictionary
     with_text, with_values = with_text or with_terms, with_values or with_terms
     import torch
@@ -1136,16 +1212,20 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
             mctx.finishedTermsDevice(stream=stream)
         if with_dictionary:
             mctx.finishedDictionaryDevice(stream=stream)
+        if with_postings:
+            mctx.finishedPostingsDevice(stream=stream)
         mb = mctx.finishedFetch()
         mt = mctx.finishedTextFetch() if with_text else None
         mv = mctx.finishedValuesFetch() if with_values else None
         mterms = mctx.finishedTermsFetch() if with_terms else None
         mdict = mctx.finishedDictionaryFetch() if with_dictionary else None
+        mpost = mctx.finishedPostingsFetch() if with_postings else None
     else:
         mb = mctx.batchFetch()
     stitch_status = lctx.stitchedStatus()
     mb.status = np.where(stitch_status != 0, stitch_status, mb.status).astype(np.int32)
-    out = (mb,) + ((mt,) if with_text else ()) + ((mv,) if with_values else ()) + ((mterms,) if with_terms else ()) + ((mdict,) if with_dictionary else ())
+    out = (mb,) + ((mt,) if with_text else ()) + ((mv,) if with_values else ()) + ((mterms,) if with_terms else ()) + ((mdict,) if with_dictionary else ()) \
+        + ((mpost,) if with_postings else ())
     return out if len(out) > 1 else mb
 
 

@@ -160,6 +160,24 @@ class SpMatchDictionary(ctypes.Structure):
     ]
 
 
+class SpPosting(ctypes.Structure):
+    _fields_ = [(n, c_u32) for n in ("doc", "term", "count", "first_ordpos")]
+
+
+class SpMatchPostingsDevice(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("nterms", ctypes.c_size_t), ("ndict", ctypes.c_size_t), ("d_postings", c_vp), ("d_entry_offsets", c_vp),
+        ("d_record_posting", c_vp), ("d_totals", c_vp),
+    ]
+
+
+class SpMatchPostings(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("nterms", ctypes.c_size_t), ("ndict", ctypes.c_size_t),
+        ("postings", P(SpPosting)), ("entry_offsets", P(c_u64)), ("record_posting", P(c_u32)), ("totals", c_u64 * 1),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/strus_pattern_amd.h
 SIGNATURES = {
     "sp_version": (c_cp, []),
@@ -245,6 +263,13 @@ SIGNATURES = {
     "sp_match_dictionary_free": (None, [P(SpMatchDictionary)]),
     "sp_matcher_ctx_last_dictionary_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
     "sp_match_batch_dictionary": (ctypes.c_int, [P(SpMatchBatch), P(SpMatchValues), P(SpMatchText), P(SpMatchTerms), P(SpMatchDictionary), ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_matcher_ctx_finished_postings_device": (ctypes.c_int, [c_vp, c_vp, P(SpMatchPostingsDevice)]),
+    "sp_matcher_ctx_finished_postings_fetch": (ctypes.c_int, [c_vp, P(SpMatchPostings)]),
+    "sp_match_postings_free": (None, [P(SpMatchPostings)]),
+    "sp_matcher_ctx_last_postings_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_matcher_postings_tile": (c_u32, []),
+    "sp_test_postings_digit_bits": (None, [ctypes.c_uint]),
+    "sp_match_batch_postings": (ctypes.c_int, [P(SpMatchTerms), P(SpMatchDictionary), P(SpMatchPostings), ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_ctx_batch_counters": (ctypes.c_int, [c_vp, P(c_u64)]),
     "sp_matcher_ctx_last_kernel_ms": (ctypes.c_double, [c_vp]),
     "sp_matcher_ctx_kernel_kind": (ctypes.c_int, [c_vp]),

@@ -135,6 +135,14 @@ struct sp_matcher_ctx
 		uint32_t handleBound = 0, flags = 0;
 		uint64_t nterms = 0, total = 0;
 	};
+	// the postings of the last dictionary (l2_postings.h); nothing is allocated before the first sp_matcher_ctx_finished_postings_device
+	struct Postings
+	{
+		PassRun<2> run;
+		DeviceBuffer dPostings, dEntryOffsets, dRecordPosting, dTotals, dDocOf, dPairs[ 2], dHist, dCursor;
+		size_t ndocs = 0;
+		uint64_t nterms = 0, ndict = 0;
+	};
 	// the finish of the last batch and everything made of it (capi_l2_finished.cpp).  A product is a member here and is listed in drop().
 	struct Products
 	{
@@ -144,8 +152,11 @@ struct sp_matcher_ctx
 		Freq frq;
 		Terms trm;
 		Dict dct;
+		Postings pst;
 		// a new batch, a new finish: what stands here is of the one before
-		void drop() { fin.run.done = false; txt.run.done = false; val.run.done = false; frq.run.done = false; trm.run.done = false; dct.run.done = false; }
+		void drop() { fin.run.done = false; txt.run.done = false; val.run.done = false; frq.run.done = false; trm.run.done = false; dropDictionary(); }
+		// a new terms call: a dictionary is that of the terms it was built from, and postings are those of their dictionary
+		void dropDictionary() { dct.run.done = false; pst.run.done = false; }
 	} prod;
 	// single-document mode
 	struct SingleDoc
@@ -200,25 +211,36 @@ struct ProductCall
 
 	// drops the product's last run and waits for the finish, whose totals size the working arrays
 	ProductCall( sp_matcher_ctx* c_, PassRun<2>& run_, void* stream_)
-		:c(c_),run(run_),stream((hipStream_t)stream_),ndocs(c_->lastNdocs)
+		:ProductCall( c_, run_, stream_, Sized())
+	{
+		HIP_CHECK( hipStreamSynchronize( c->prod.fin.run.stream));
+		copySync( c->own, finished, c->prod.fin.dTotals.ptr, sizeof(finished), hipMemcpyDeviceToHost);
+	}
+	// the same for a product whose sizes the host read at an earlier call: nothing is waited for, `finished` stays zero
+	struct Sized {};
+	ProductCall( sp_matcher_ctx* c_, PassRun<2>& run_, void* stream_, Sized)
+		:c(c_),run(run_),stream((hipStream_t)stream_),ndocs(c_->lastNdocs),finished{ 0, 0}
 	{
 		requireFinished( c);
 		HIP_CHECK( hipSetDevice( c->device));
 		run.done = run.evValid = false;
-		HIP_CHECK( hipStreamSynchronize( c->prod.fin.run.stream));
-		copySync( c->own, finished, c->prod.fin.dTotals.ptr, sizeof(finished), hipMemcpyDeviceToHost);
 	}
 	// after the product's other reserves, before anything goes to the stream: another stream than the finish's runs behind the
 	// finish; the status per document, the totals (u64) and the cursor (u32) that every product has start at zero
 	void begin( DeviceBuffer& dStatus, DeviceBuffer& dTotals, size_t ntotals, DeviceBuffer& dCursor, size_t ncursor)
 	{
 		reserveOrNoMem( dStatus, (ndocs+1)*sizeof(int32_t));
+		beginBehind( c->prod.fin.run.stream, c->prod.fin.run.ev[ 3], dTotals, ntotals, dCursor, ncursor);
+		HIP_CHECK( hipMemsetAsync( dStatus.ptr, 0, (ndocs+1)*sizeof(int32_t), stream));
+	}
+	// the same without a status, behind the stage that ran on `prevStream` and closed with `prevEvent`
+	void beginBehind( hipStream_t prevStream, hipEvent_t prevEvent, DeviceBuffer& dTotals, size_t ntotals, DeviceBuffer& dCursor, size_t ncursor)
+	{
 		reserveOrNoMem( dTotals, ntotals*sizeof(uint64_t));
 		reserveOrNoMem( dCursor, ncursor*sizeof(uint32_t));
-		run.begin( stream, c->prod.fin.run.stream, c->prod.fin.run.ev[ 3]);
+		run.begin( stream, prevStream, prevEvent);
 		HIP_CHECK( hipMemsetAsync( dCursor.ptr, 0, ncursor*sizeof(uint32_t), stream));
 		HIP_CHECK( hipMemsetAsync( dTotals.ptr, 0, ntotals*sizeof(uint64_t), stream));
-		HIP_CHECK( hipMemsetAsync( dStatus.ptr, 0, (ndocs+1)*sizeof(int32_t), stream));
 	}
 	// count, read the n totals counted, let `sized` reserve the output for them (it fills P in), place
 	template <class PARAMS, class SIZED>

@@ -1,5 +1,5 @@
 // C-ABI of level 2, second half: the last device batch finished on the device and what is made of the finished batch there --
-// matched text, result values, pattern frequencies, index terms, the batch dictionary -- with their fetch and timing calls.  Every product is one
+// matched text, result values, pattern frequencies, index terms, the batch dictionary, the batch postings -- with their fetch and timing calls.  Every product is one
 // ProductCall (capi_l2_ctx.hpp) behind the finish; sp_matcher_ctx::Products::drop() is what a new batch or finish does to them.
 #include "capi_l2_ctx.hpp"
 #include "l2_finish.h"
@@ -8,8 +8,10 @@
 #include "l2_values.h"
 #include "l2_terms.h"
 #include "l2_dict.h"
+#include "l2_postings.h"
 #include "match_terms.hpp"
 #include "match_dict.hpp"
+#include "match_postings.hpp"
 #include "span_text.hpp"
 #include "pattern_freq.hpp"
 #include "finished_host.hpp"
@@ -104,6 +106,8 @@ void fetchByteFamilies( const sp_matcher_ctx* c, const ByteFamilies& b, int32_t*
 
 // test hook: the bits of a term's hash that the device keeps (32 and more = all)
 std::atomic<unsigned>& termHashBits() { static std::atomic<unsigned> bits( 32); return bits; }
+// test hook: the bits of a radix digit of the postings' partition
+std::atomic<unsigned>& postingsDigitBits() { static std::atomic<unsigned> bits( POSTINGS_MAX_DIGIT_BITS); return bits; }
 
 // ---- the sources of the terms and of the dictionary call: the results families of the values call (0) and of the text call (1)
 // that `flags` selects, which must have run since the finish
@@ -482,7 +486,7 @@ int sp_matcher_ctx_finished_terms_device( sp_matcher_ctx_t* c, uint32_t flags, v
 		const sp_matcher_ctx::Finished& fin = c->prod.fin;
 		const TermSources sources( c, flags);
 		sp_matcher_ctx::Terms& t = c->prod.trm;
-		c->prod.dct.run.done = false;		// (a dictionary is that of the terms it was built from)
+		c->prod.dropDictionary();		// (a dictionary is that of the terms it was built from)
 		// (every result index is checked against the total of the finish)
 		ProductCall call( c, t.run, stream);
 		const size_t ndocs = call.ndocs;
@@ -555,6 +559,7 @@ int sp_matcher_ctx_finished_dictionary_device( sp_matcher_ctx_t* c, void* stream
 		const uint32_t flags = t.flags;
 		const TermSources sources( c, flags);
 		sp_matcher_ctx::Dict& q = c->prod.dct;
+		c->prod.pst.run.done = false;		// (postings are those of the dictionary they were built from)
 		ProductCall call( c, q.run, stream);
 		const size_t ndocs = call.ndocs;
 		const uint64_t nresults = call.finished[ 0], nterms = t.total;
@@ -618,5 +623,79 @@ int sp_matcher_ctx_finished_dictionary_fetch( sp_matcher_ctx_t* c, sp_match_dict
 // duration of the five launches of the last dictionary call in milliseconds (HIP events on its stream; the memsets that clear the
 // table and handle_terms are enqueued before the first event)
 int sp_matcher_ctx_last_dictionary_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.dct.run.ms( 0, 1, ms); }
+
+// ---- the postings of the dictionary of the finished batch, partitioned on the device (l2_postings.h)
+void sp_test_postings_digit_bits( unsigned bits)
+{
+	postingsDigitBits().store( bits >= 1 && bits <= POSTINGS_MAX_DIGIT_BITS ? bits : POSTINGS_MAX_DIGIT_BITS, std::memory_order_relaxed);
+}
+
+int sp_matcher_ctx_finished_postings_device( sp_matcher_ctx_t* c, void* stream, sp_match_postings_device_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		requireFinished( c);
+		const sp_matcher_ctx::Terms& t = c->prod.trm;
+		const sp_matcher_ctx::Dict& d = c->prod.dct;
+		if (!t.run.done || !d.run.done) throw std::runtime_error( "no dictionary of the last terms of the last finished batch (sp_matcher_ctx_finished_dictionary_device)");
+		sp_matcher_ctx::Postings& q = c->prod.pst;
+		// (the dictionary call waited for ndict and knows N: nothing is waited for here)
+		ProductCall call( c, q.run, stream, ProductCall::Sized());
+		const size_t ndocs = call.ndocs;
+		const uint64_t nterms = d.nterms, ndict = d.total;
+		if (d.ndocs != ndocs || t.total != nterms) throw std::runtime_error( "the dictionary is not that of the terms of the finished batch");
+		if (nterms >= 0xFFFFFFFFull || ndict > nterms) throw std::runtime_error( "a dictionary of more entries than term records, or of 2^32 - 1 records or more");
+		const uint32_t bits = postingsDigitBits().load( std::memory_order_relaxed);
+		const uint32_t tiles = l2PostingsTiles( nterms), passes = l2PostingsPasses( ndict, bits);
+		reserveOrNoMem( q.dPostings, (nterms+1)*sizeof(sp_posting_t));
+		reserveOrNoMem( q.dEntryOffsets, (ndict+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dRecordPosting, (nterms+1)*sizeof(uint32_t));
+		reserveOrNoMem( q.dDocOf, (nterms+1)*sizeof(uint32_t));
+		for (int i=0; i<2; ++i) reserveOrNoMem( q.dPairs[ i], (nterms+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dHist, ((size_t)tiles+1)*sizeof(uint32_t) << POSTINGS_MAX_DIGIT_BITS);
+		// behind the dictionary, whose placement nobody has waited for yet; that runs behind the terms and the finish
+		call.beginBehind( d.run.stream, d.run.ev[ 1], q.dTotals, 1, q.dCursor, POSTINGS_CURSORS);
+		PostingsParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.terms = (const uint32_t*)t.dRecords.ptr; P.docTermOffsets = (const uint64_t*)t.dDocOffsets.ptr;
+		P.termDict = (const uint32_t*)d.dTermDict.ptr; P.dictRecords = (const uint32_t*)d.dRecords.ptr;
+		P.nterms = nterms; P.ndict = (uint32_t)ndict; P.ndocs = (uint32_t)ndocs;
+		P.digitBits = bits; P.passes = passes; P.tiles = tiles;
+		P.docOf = (uint32_t*)q.dDocOf.ptr; P.hist = (uint32_t*)q.dHist.ptr; P.cursor = (uint32_t*)q.dCursor.ptr;
+		for (int i=0; i<2; ++i) P.pairs[ i] = (uint64_t*)q.dPairs[ i].ptr;
+		P.postings = (uint32_t*)q.dPostings.ptr; P.entryOffsets = (uint64_t*)q.dEntryOffsets.ptr;
+		P.recordPosting = (uint32_t*)q.dRecordPosting.ptr; P.total = (uint64_t*)q.dTotals.ptr;
+		HIP_CHECK( hipEventRecord( q.run.ev[ 0], call.stream));
+		HIP_CHECK( launchL2Postings( P, c->numCUs, call.stream));
+		HIP_CHECK( hipEventRecord( q.run.ev[ 1], call.stream));
+		q.run.completed( call.stream);
+		q.ndocs = ndocs; q.nterms = nterms; q.ndict = ndict;
+		if (out)
+		{
+			out->ndocs = ndocs; out->nterms = (size_t)nterms; out->ndict = (size_t)ndict;
+			out->d_postings = q.dPostings.ptr; out->d_entry_offsets = q.dEntryOffsets.ptr;
+			out->d_record_posting = q.dRecordPosting.ptr; out->d_totals = q.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the postings' buffers
+int sp_matcher_ctx_finished_postings_fetch( sp_matcher_ctx_t* c, sp_match_postings_t* out)
+{
+	const sp_matcher_ctx::Postings& q = c->prod.pst;
+	return fetchProduct( c, q.run, "no postings of the last dictionary of this context (sp_matcher_ctx_finished_postings_device)", out, sp_match_postings_free, [&]{
+		allocMatchPostings( out, q.ndocs, q.nterms, q.ndict);
+		if (q.nterms) copySync( c->own, out->postings, q.dPostings.ptr, q.nterms*sizeof(sp_posting_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->entry_offsets, q.dEntryOffsets.ptr, (q.ndict+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		if (q.nterms) copySync( c->own, out->record_posting, q.dRecordPosting.ptr, q.nterms*sizeof(uint32_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->totals, q.dTotals.ptr, sizeof(uint64_t), hipMemcpyDeviceToHost);
+	});
+}
+
+// duration of the launches of the last postings call in milliseconds (HIP events on its stream; the memsets that clear the
+// cursors and the total are enqueued before the first event)
+int sp_matcher_ctx_last_postings_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.pst.run.ms( 0, 1, ms); }
+
+uint32_t sp_matcher_postings_tile(void) { return POSTINGS_TILE; }
 
 } // extern "C"

@@ -2,7 +2,7 @@
 through the MI355X lexer + rule automaton, print tokens (-K) and results in the reference tool's
 listing format (doc/webpage/introduction_struspattern.htm:178-260).
 
-    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] file [file ...]
+    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] [--postings] file [file ...]
 
 Every file is one document (plain UTF-8 text; the reference tool segments XML with strusAnalyzer's
 segmenters, which are outside this engine -- pass -o to add the offset of the text inside its original
@@ -19,8 +19,11 @@ and value, the value of a result being that of its format string, or the text it
 pattern handle, then by first occurrence: `term NAME 'VALUE': count N first ORDPOS`, grouped on the GPU
 (finishedTermsDevice).  With --dictionary the listing of the last file is followed by one line per distinct index term of
 all files, in the order of first occurrence: `dict NAME 'VALUE': docs D count C` -- in how many files the term occurs and how
-often over all of them, built on the GPU from the terms (finishedDictionaryDevice).  All files go to the
-GPU as one batch.  There is no CPU fallback.
+often over all of them, built on the GPU from the terms (finishedDictionaryDevice).  --postings implies --dictionary; the
+dictionary lines are followed by one line per entry, in the same order, with the files that hold the term in the order given:
+`post NAME 'VALUE': FILEINDEX:COUNT@FIRSTPOS ...` -- the index of the file among the arguments (from 0), how often the term
+occurs in it and the first ordinal position it starts at, built on the GPU from the dictionary (finishedPostingsDevice).
+All files go to the GPU as one batch.  There is no CPU fallback.
 """
 import argparse
 import sys
@@ -41,9 +44,11 @@ def main(argv=None):
     ap.add_argument("--device-values", action="store_true", help="the values of the format strings are built on the device")
     ap.add_argument("--terms", action="store_true", help="after the listing of a file, one line per distinct (pattern, value) of it")
     ap.add_argument("--dictionary", action="store_true", help="after the last listing, one line per distinct (pattern, value) of all files")
+    ap.add_argument("--postings", action="store_true", help="implies --dictionary; after its lines, per distinct (pattern, value) the files that hold it")
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("files", nargs="+")
     args = ap.parse_args(argv)
+    args.dictionary = args.dictionary or args.postings
 
     with open(args.program, encoding="utf-8") as f:
         program = f.read()
@@ -66,6 +71,7 @@ def main(argv=None):
     values = device_values(mctx, text, offs) if args.device_values else None
     terms = device_terms(mctx, text, offs) if args.terms or args.dictionary else None
     dictionary = device_dictionary(mctx) if args.dictionary else None
+    postings = device_postings(mctx) if args.postings else None
     freq = frequencies(mctx) if args.frequencies else None
     for di, fn in enumerate(args.files):
         print("%s:" % fn)
@@ -81,6 +87,7 @@ def main(argv=None):
         print_frequencies(freq, di, mt)
         print_terms(terms if args.terms else None, di, mt)
     print_dictionary(dictionary, terms, mt)
+    print_postings(postings, dictionary, terms, mt)
     print("OK done")
     return 0
 
@@ -102,6 +109,27 @@ def print_dictionary(dictionary, found, mt):
     if dictionary is None:
         return
     for line in dictionary_lines(dictionary, found, mt.patternName):
+        print(line)
+
+
+def device_postings(mctx):
+    """--postings: the postings of the dictionary that device_dictionary built, partitioned on the device"""
+    mctx.finishedPostingsDevice()
+    return mctx.finishedPostingsFetch()
+
+
+def postings_lines(postings, dictionary, found, pattern_name):
+    """the lines of --postings; found: (batch, text, values, terms) of the terms call"""
+    mb, mt, mv, terms = found
+    return ["post %s '%s': %s" % (pattern_name(int(h)), value.decode("utf-8", "replace"),
+                                  " ".join("%d:%d@%d" % (doc, count, first) for doc, _, count, first in postings.entry(e).tolist()))
+            for e, (h, value, _, _, _) in enumerate(dictionary.entries(mb, terms, values=mv, text=mt))]
+
+
+def print_postings(postings, dictionary, found, mt):
+    if postings is None:
+        return
+    for line in postings_lines(postings, dictionary, found, mt.patternName):
         print(line)
 
 
@@ -169,8 +197,12 @@ def paragraphs(args, prg, lx, mt, docs):
     text, seg_offsets, doc_seg_offsets, posmaps = segments.segmented_batch(docs)
     lctx = lx.createContext(args.device)
     mctx = mt.createContext(args.device)
-    values = terms = dictionary = None
-    if args.dictionary:
+    values = terms = dictionary = postings = None
+    if args.postings:
+        mb, mtext, mvalues, mterms, dictionary, postings = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_postings=True)
+        terms = (mb, mtext, mvalues, mterms)
+        values = mvalues if args.device_values else None
+    elif args.dictionary:
         mb, mtext, mvalues, mterms, dictionary = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_dictionary=True)
         terms = (mb, mtext, mvalues, mterms)
         values = mvalues if args.device_values else None
@@ -208,6 +240,7 @@ def paragraphs(args, prg, lx, mt, docs):
         print_frequencies(freq, di, mt)
         print_terms(terms if args.terms else None, di, mt)
     print_dictionary(dictionary, terms, mt)
+    print_postings(postings, dictionary, terms, mt)
     print("OK done")
     return 0
 
