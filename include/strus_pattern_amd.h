@@ -781,9 +781,9 @@ int sp_match_batch_dictionary(const sp_match_batch_t* mb, const sp_match_values_
  * dictionary; were it there, the device would take ndict - 1 for the record's entry and touch nothing out of bounds (the host
  * twin refuses such a dictionary).
  * LIMIT: N below 2^32 - 1, which the dictionary enforces.
- * The positions of EVERY occurrence of a term in a document are not part of a posting: they are a gather through result_term
- * (the results of doc whose result_term is `term`) and record_posting.  Postings or entries ordered by (handle, value bytes)
- * are not offered, as for the dictionary. */
+ * The positions of EVERY occurrence of a term in a document are not part of a posting: they are a product of their own,
+ * built from the postings ("posting positions", below).  Postings or entries ordered by (handle, value bytes) are not
+ * offered, as for the dictionary. */
 typedef struct sp_posting {
 	uint32_t doc;           /* the document */
 	uint32_t term;          /* index of the term record inside doc's block: everything else about the occurrence hangs off it */
@@ -839,6 +839,101 @@ void sp_test_postings_digit_bits(unsigned bits);
  * beyond ndict, and for a doc_freq that is not the number of records of its entry; SP_ERR_NOMEM when memory runs out. */
 int sp_match_batch_postings(const sp_match_terms_t* terms, const sp_match_dictionary_t* dict, sp_match_postings_t* out,
                             char* err, size_t errsize);
+
+/* ---- posting positions: for every posting the list of ALL occurrences of its term in its document -- the position list that
+ * an inverted index stores per posting -- without fetching the finished batch; built on the device (csrc/l2_positions.h) or,
+ * for a batch already fetched, on the host (csrc/match_positions.hpp).  The rule is the project's own, unpinned by a reference
+ * vector.
+ * INPUT: the postings built last on a context (sp_matcher_ctx_finished_postings_device), which implies their dictionary, their
+ * terms batch and the finished batch.  Write N for the number of term records = the number of postings, and doc_offsets for
+ * the finished batch's result range per document.
+ * PARTICIPATING RESULTS: result r of document d participates iff result_term[r] != 0xFFFFFFFF.  Its posting is
+ * p(r) = record_posting[doc_term_offsets[d] + result_term[r]].  The results of documents that failed their terms, or that the
+ * matcher failed, contribute nothing.  nocc is the number of participating results = the sum of `count` over the postings.
+ * OCCURRENCE: one 8-byte record sp_occurrence_t {ordpos, result} per participating result; `result` is the index of the result
+ * inside its document's finished block: ordend, the original positions and the items hang off it, an occurrence owns
+ * nothing else.
+ * OUTPUTS:
+ *   posting_offsets[N+1]     (uint64) the exclusive prefix sums of postings[p].count in posting order; posting_offsets[N] is nocc,
+ *   occurrences[nocc]        those of posting p are [posting_offsets[p], posting_offsets[p+1]), ascending by ordpos (unsigned),
+ *                            equal positions in finished order, that is ascending `result`,
+ *   posting_positions[N]     (uint32) the number of DISTINCT ordpos in the list of p: the length of the position set an index
+ *                            stores; two results of a term that start at the same token and end at different ones are one position,
+ *   totals[2]                (uint64) nocc, and the sum of posting_positions.
+ * The postings lie entry by entry and ascend by document inside an entry, so the concatenated lists of an entry are that
+ * term's positional posting list.
+ * INVARIANTS: the list of p has postings[p].count records; its first ordpos is postings[p].first_ordpos; for every occurrence
+ * result_term[doc_offsets[doc] + result] == postings[p].term; the smallest `result` of the list is the term record's
+ * first_result; 1 <= posting_positions[p] <= count; every participating result appears exactly once.
+ * DETERMINISM: every output word is a function of the finished batch, the terms and the postings; no timing enters (the device
+ * partitions the results with the postings' stable radix partition over fixed tiles, without an atomic on its data).  The
+ * ordpos words and posting_positions depend on the results alone; `result` follows the finished order, as first_result does.
+ * After a canonical finish the exact engines and result-set mode leave the same bytes.
+ * SAFETY, as for the postings: no byte outside the outputs is written; a result index is compared against the finished total
+ * before a result is read, a result_term against its document's record count, a posting index against N, and a rank against
+ * the number of sorted slots (the finished total on the device, where the results that do not participate are sorted behind
+ * the nocc occurrences; only those are placed) before use.  A slot that no valid result reaches holds 0xFFFFFFFF words.
+ * LIMIT: the finished total below 2^32 - 1, else SP_ERR_INVALID. */
+typedef struct sp_occurrence {
+	uint32_t ordpos;        /* ordinal position the result starts at */
+	uint32_t result;        /* index of the result inside its document's finished block */
+} sp_occurrence_t;
+typedef struct sp_match_positions_device {
+	size_t ndocs;
+	size_t nterms;               /* N */
+	size_t nocc;
+	void* d_occurrences;         /* sp_occurrence_t[nocc] */
+	void* d_posting_offsets;     /* uint64_t[N+1] */
+	void* d_posting_positions;   /* uint32_t[N], parallel to the postings */
+	void* d_totals;              /* uint64_t[2]: nocc, the sum of posting_positions */
+} sp_match_positions_device_t;
+/* host copy of the positions (sp_match_positions_free) */
+typedef struct sp_match_positions {
+	size_t ndocs;
+	size_t nterms;                /* N */
+	size_t nocc;
+	sp_occurrence_t* occurrences; /* nocc */
+	uint64_t* posting_offsets;    /* nterms+1 */
+	uint32_t* posting_positions;  /* nterms */
+	uint64_t totals[2];           /* nocc, the sum of posting_positions */
+} sp_match_positions_t;
+/* Builds the positions of the postings built last on this context.  Launches on `stream` (csrc/l2_positions.h): keys and
+ * posting offsets; then the host waits, once, for nocc and the largest participating ordpos, which it does not know and which
+ * set the passes; then ceil(bitwidth(largest ordpos) / 8) radix passes of histogram, scan and scatter by position, a rekey
+ * launch, ceil(bitwidth(N - 1) / 8) passes by posting (of N where a result does not participate), and place, which nobody
+ * waits for.  The buffers belong to the context, are allocated at the first call, only grow (working memory, R being the
+ * finished total: 4R bytes for the document of every result, 2 x 8R for the two buffers of (key, result) pairs, 4 x 256 x
+ * ceil(R / tile) for the digit counts of the tiles (sp_matcher_positions_tile), and 131 cursor words), and are valid until
+ * the next positions call; the next batch, finish, terms, dictionary or postings call invalidates the state, not the buffers.
+ * A `stream` other than the postings' is ordered behind the postings with an event (their placement is not waited for by
+ * their own call).  SP_ERR_INVALID when no postings were built since the last dictionary call of the last finish, and for a
+ * finished total of 2^32 - 1 or more; SP_ERR_NOMEM when a buffer cannot be allocated (the context stays usable, `out` is empty). */
+int sp_matcher_ctx_finished_positions_device(sp_matcher_ctx_t* c, void* stream, sp_match_positions_device_t* out);
+/* plain copy of the buffers of the last sp_matcher_ctx_finished_positions_device to the host (waits for it) */
+int sp_matcher_ctx_finished_positions_fetch(sp_matcher_ctx_t* c, sp_match_positions_t* out);
+void sp_match_positions_free(sp_match_positions_t* p);
+/* duration of the launches of the last positions call in milliseconds (HIP events on its stream round them; waits for them;
+ * the host's wait between the posting offsets and the first pass lies inside; the hipMemsetAsync calls that clear the cursors,
+ * the totals and posting_positions are enqueued before the first event, as the clearing of every other product) */
+int sp_matcher_ctx_last_positions_ms(sp_matcher_ctx_t* c, double* ms);
+/* diagnostics and tests: the (key, result) pairs of one tile of the device's partition; tile k is always the pairs
+ * [k * tile, (k+1) * tile) in the order of the pass, whichever wave takes it.  sp_test_postings_digit_bits selects the digit
+ * of this partition too. */
+uint32_t sp_matcher_positions_tile(void);
+/* diagnostics (measurements only): with on != 0 every later positions call records a HIP event behind each of its launches,
+ * and sp_matcher_ctx_last_positions_launch_ms gives the time of the last call's launches summed by kind, ms[0..5] = keys,
+ * histogram, scan, scatter, rekey, place (the scan of the posting offsets is not among them; waits for the call).
+ * SP_ERR_INVALID when the last positions call recorded none.  The outputs do not change by a bit. */
+void sp_test_positions_launch_events(unsigned on);
+int sp_matcher_ctx_last_positions_launch_ms(sp_matcher_ctx_t* c, double ms[6]);
+/* The same rule over host arrays, needs no device, and the yardstick of the device passes: the positions of a finished batch
+ * already fetched with its terms and their postings (or made by the twins), by a counting sort by posting, then a stable sort
+ * by ordpos inside each list.  Fills `out` (sp_match_positions_free); SP_ERR_INVALID with the message in `err` for a NULL
+ * argument, for ndocs, nresults or nterms that do not agree between `mb`, `terms` and `postings`, for document or term offsets
+ * that do not ascend or do not cover their total, for a result_term at or beyond its document's records, a record_posting at
+ * or beyond N, and a posting whose count is not the number of its results; SP_ERR_NOMEM when memory runs out. */
+int sp_match_batch_positions(const sp_match_batch_t* mb, const sp_match_terms_t* terms, const sp_match_postings_t* postings,
+                             sp_match_positions_t* out, char* err, size_t errsize);
 /* copies the results of the last device batch to the host, grouped by document (as sp_matcher_ctx_match_docs
  * returns them, `exclusive` elimination included) */
 int sp_matcher_ctx_batch_fetch(sp_matcher_ctx_t* c, sp_match_batch_t* out);

@@ -13,7 +13,7 @@ from . import capi
 from .capi import SpLexem, SpResult, SpResultItem
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
-           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms", "MatchDictionary", "batchDictionary", "MatchPostings", "batchPostings"]
+           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms", "MatchDictionary", "batchDictionary", "MatchPostings", "batchPostings", "MatchPositions", "batchPositions"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
@@ -439,6 +439,61 @@ def batchPostings(terms, dictionary):
                     L.sp_match_postings_free, _match_postings_of, lambda rc: "no postings of the batch (%d): %s" % (rc, err.value.decode()))
 
 
+def _host_postings(postings, ndocs, keep):
+    """the capi.SpMatchPostings of a MatchPostings for a host twin; the arrays it points into are appended to `keep`"""
+    p = capi.SpMatchPostings()
+    rec = np.ascontiguousarray(postings.records, dtype=np.uint32).reshape(-1, 4)
+    offs = np.ascontiguousarray(postings.entry_offsets, dtype=np.uint64)
+    rp = np.ascontiguousarray(postings.record_posting, dtype=np.uint32)
+    keep.extend([rec, offs, rp])
+    p.ndocs, p.nterms, p.ndict = ndocs, len(rec), len(offs) - 1
+    p.postings = ctypes.cast(rec.ctypes.data, ctypes.POINTER(capi.SpPosting))
+    p.entry_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
+    p.record_posting = ctypes.cast(rp.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
+    p.totals[0] = len(rec)
+    return p
+
+
+class MatchPositions:
+    """The positions of the postings of a batch (host copies): per participating result one occurrence (ordpos, result), the
+    occurrences of posting p together, ascending by ordpos and then by result, and per posting the number of distinct
+    positions (include/strus_pattern_amd.h "posting positions")."""
+
+    def __init__(self, occurrences, posting_offsets, posting_positions, totals):
+        self.occurrences = occurrences              # (nocc, 2) u32: ordpos, result (index inside the document's finished block)
+        self.posting_offsets = posting_offsets      # (nterms+1,) u64: the occurrences of posting p are occurrences[posting_offsets[p]:posting_offsets[p+1]]
+        self.posting_positions = posting_positions  # (nterms,) u32: distinct ordpos per posting
+        self.totals = totals                        # (2,) u64: nocc, the sum of posting_positions
+
+    def posting(self, p):
+        """the occurrences of posting p, by position: rows (ordpos, result)"""
+        return self.occurrences[int(self.posting_offsets[p]):int(self.posting_offsets[p + 1])]
+
+    def positions(self, p):
+        """the distinct ordinal positions of posting p, ascending: what an index stores"""
+        pos = self.posting(p)[:, 0]
+        return pos[np.concatenate(([True], pos[1:] != pos[:-1]))] if len(pos) else pos
+
+
+def _match_positions_of(p):
+    """the MatchPositions of a capi.SpMatchPositions (copies)"""
+    return MatchPositions(_rows(p.occurrences, p.nocc, 2), _rows(p.posting_offsets, p.nterms + 1, 0, ctypes.c_uint64),
+                          _rows(p.posting_positions, p.nterms, 0), np.array([p.totals[0], p.totals[1]], np.uint64))
+
+
+def batchPositions(mb, terms, postings):
+    """The positions of the postings of a batch already on the host (mb: the finished MatchBatch, terms: its MatchTerms,
+    postings: the MatchPostings built from their dictionary: the fetches of a context, or the twins), by the rule of the device
+    call, without a device.  Returns a MatchPositions."""
+    L = capi.lib()
+    b, keep = _host_batch(mb)                                        # (keep: until the call has returned)
+    t = _host_terms(terms, terms.handle_bound, keep)
+    q = _host_postings(postings, len(terms.doc_offsets) - 1, keep)
+    err = ctypes.create_string_buffer(256)
+    return _product(capi.SpMatchPositions, lambda p: L.sp_match_batch_positions(ctypes.byref(b), ctypes.byref(t), ctypes.byref(q), ctypes.byref(p), err, 256),
+                    L.sp_match_positions_free, _match_positions_of, lambda rc: "no positions of the batch (%d): %s" % (rc, err.value.decode()))
+
+
 class PatternMatcherContext:
     """PatternMatcherContextInterface (src/patternMatcher.cpp:107-341) + batch mode."""
 
@@ -694,6 +749,34 @@ class PatternMatcherContext:
     def lastPostingsMs(self):
         """duration of the launches of the last finishedPostingsDevice in milliseconds"""
         return self._last_ms(self._L.sp_matcher_ctx_last_postings_ms, "postings call")
+
+    def finishedPositionsDevice(self, stream=0):
+        """build the positions of the postings built by finishedPostingsDevice on the device (the call waits once, for the
+        number of occurrences and the largest position, which set its passes; the placement is asynchronous on `stream`; a stream
+        other than the postings' is ordered behind them).  Returns the device pointers (capi.SpMatchPositionsDevice), valid until
+        the next call."""
+        out = capi.SpMatchPositionsDevice()
+        rc = self._L.sp_matcher_ctx_finished_positions_device(self._h, stream or None, ctypes.byref(out))
+        if rc != 0:
+            raise PatternError("building the positions of the batch on the device failed (%d): %s" % (rc, self._err()))
+        return out
+
+    def finishedPositionsFetch(self):
+        """plain host copy of the positions built by finishedPositionsDevice: a MatchPositions"""
+        return self._fetch_product(capi.SpMatchPositions, self._L.sp_matcher_ctx_finished_positions_fetch, self._L.sp_match_positions_free,
+                                   _match_positions_of, "the positions of the batch")
+
+    def lastPositionsMs(self):
+        """duration of the launches of the last finishedPositionsDevice in milliseconds (the host's one wait lies inside)"""
+        return self._last_ms(self._L.sp_matcher_ctx_last_positions_ms, "positions call")
+
+    def lastPositionsLaunchMs(self):
+        """diagnostics: the launches of the last finishedPositionsDevice summed by kind in milliseconds, a dict (keys, histogram,
+        scan, scatter, rekey, place); needs capi.lib().sp_test_positions_launch_events(1) before that call"""
+        a = (ctypes.c_double * 6)()
+        if self._L.sp_matcher_ctx_last_positions_launch_ms(self._h, a) != 0:
+            raise PatternError("no positions call with launch events")
+        return dict(zip(("keys", "histogram", "scan", "scatter", "rekey", "place"), list(a)))
 
     def batchFetch(self, first_doc=None, ndocs=None):
         """host copy of the last device batch, grouped by document; with (first_doc, ndocs) only of
@@ -1161,7 +1244,7 @@ class PatternLexer:
         return "std"
 
 
-def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False, with_terms=False, with_dictionary=False, with_postings=False):
+def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False, with_terms=False, with_dictionary=False, with_postings=False, with_positions=False):
     """Segmented documents, host buffers in and out: `text` holds the segments back to back (seg_offsets: nseg+1 byte
     offsets), document d consists of the segments [doc_seg_offsets[d], doc_seg_offsets[d+1]).  Lexer -> stitch on the
     device -> rule matcher -> fetch; only the text goes up and the results come down.  Returns the MatchBatch, whose
@@ -1172,7 +1255,9 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
     index terms there (value where a result has a format, else text: text and values are built for it); returns
     (MatchBatch, MatchText, MatchValues, MatchTerms).  with_dictionary implies with_terms: the dictionary of the terms is built
     there too and returned as a fifth element, a MatchDictionary.  with_postings implies with_dictionary: the postings of
-    the dictionary are built there too and returned as a sixth element, a MatchPostings."""
+    the dictionary are built there too and returned as a sixth element, a MatchPostings.  with_positions implies
+    with_postings: the positions of every posting are built there too and returned as a seventh element, a MatchPositions."""
+    with_postings = with_postings or with_positions
     with_dictionary = with_dictionary or with_postings
     with_terms = with_terms or with_dictionary
     with_text, with_values = with_text or with_terms, with_values or with_terms
@@ -1214,18 +1299,21 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
             mctx.finishedDictionaryDevice(stream=stream)
         if with_postings:
             mctx.finishedPostingsDevice(stream=stream)
+        if with_positions:
+            mctx.finishedPositionsDevice(stream=stream)
         mb = mctx.finishedFetch()
         mt = mctx.finishedTextFetch() if with_text else None
         mv = mctx.finishedValuesFetch() if with_values else None
         mterms = mctx.finishedTermsFetch() if with_terms else None
         mdict = mctx.finishedDictionaryFetch() if with_dictionary else None
         mpost = mctx.finishedPostingsFetch() if with_postings else None
+        mpos = mctx.finishedPositionsFetch() if with_positions else None
     else:
         mb = mctx.batchFetch()
     stitch_status = lctx.stitchedStatus()
     mb.status = np.where(stitch_status != 0, stitch_status, mb.status).astype(np.int32)
     out = (mb,) + ((mt,) if with_text else ()) + ((mv,) if with_values else ()) + ((mterms,) if with_terms else ()) + ((mdict,) if with_dictionary else ()) \
-        + ((mpost,) if with_postings else ())
+        + ((mpost,) if with_postings else ()) + ((mpos,) if with_positions else ())
     return out if len(out) > 1 else mb
 
 

@@ -178,6 +178,24 @@ class SpMatchPostings(ctypes.Structure):
     ]
 
 
+class SpOccurrence(ctypes.Structure):
+    _fields_ = [(n, c_u32) for n in ("ordpos", "result")]
+
+
+class SpMatchPositionsDevice(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("nterms", ctypes.c_size_t), ("nocc", ctypes.c_size_t), ("d_occurrences", c_vp), ("d_posting_offsets", c_vp),
+        ("d_posting_positions", c_vp), ("d_totals", c_vp),
+    ]
+
+
+class SpMatchPositions(ctypes.Structure):
+    _fields_ = [
+        ("ndocs", ctypes.c_size_t), ("nterms", ctypes.c_size_t), ("nocc", ctypes.c_size_t),
+        ("occurrences", P(SpOccurrence)), ("posting_offsets", P(c_u64)), ("posting_positions", P(c_u32)), ("totals", c_u64 * 2),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/strus_pattern_amd.h
 SIGNATURES = {
     "sp_version": (c_cp, []),
@@ -270,6 +288,14 @@ SIGNATURES = {
     "sp_matcher_postings_tile": (c_u32, []),
     "sp_test_postings_digit_bits": (None, [ctypes.c_uint]),
     "sp_match_batch_postings": (ctypes.c_int, [P(SpMatchTerms), P(SpMatchDictionary), P(SpMatchPostings), ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_matcher_ctx_finished_positions_device": (ctypes.c_int, [c_vp, c_vp, P(SpMatchPositionsDevice)]),
+    "sp_matcher_ctx_finished_positions_fetch": (ctypes.c_int, [c_vp, P(SpMatchPositions)]),
+    "sp_match_positions_free": (None, [P(SpMatchPositions)]),
+    "sp_matcher_ctx_last_positions_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_matcher_positions_tile": (c_u32, []),
+    "sp_test_positions_launch_events": (None, [ctypes.c_uint]),
+    "sp_matcher_ctx_last_positions_launch_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_match_batch_positions": (ctypes.c_int, [P(SpMatchBatch), P(SpMatchTerms), P(SpMatchPostings), P(SpMatchPositions), ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_ctx_batch_counters": (ctypes.c_int, [c_vp, P(c_u64)]),
     "sp_matcher_ctx_last_kernel_ms": (ctypes.c_double, [c_vp]),
     "sp_matcher_ctx_kernel_kind": (ctypes.c_int, [c_vp]),

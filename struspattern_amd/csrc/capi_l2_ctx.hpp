@@ -143,6 +143,19 @@ struct sp_matcher_ctx
 		size_t ndocs = 0;
 		uint64_t nterms = 0, ndict = 0;
 	};
+	// the positions of the last postings (l2_positions.h); nothing is allocated before the first sp_matcher_ctx_finished_positions_device
+	struct Positions
+	{
+		PassRun<2> run;
+		DeviceBuffer dOccurrences, dPostingOffsets, dPostingPositions, dTotals, dDocOf, dPairs[ 2], dHist, dCursor;
+		size_t ndocs = 0;
+		uint64_t nterms = 0, nocc = 0;
+		// diagnostics (sp_test_positions_launch_events): an event behind every launch of the last call, and its kind
+		std::vector<Event> launchEv;
+		std::vector<hipEvent_t> launchEvHandles;
+		std::vector<int> launchKind;
+		size_t launches = 0;
+	};
 	// the finish of the last batch and everything made of it (capi_l2_finished.cpp).  A product is a member here and is listed in drop().
 	struct Products
 	{
@@ -153,10 +166,13 @@ struct sp_matcher_ctx
 		Terms trm;
 		Dict dct;
 		Postings pst;
+		Positions pos;
 		// a new batch, a new finish: what stands here is of the one before
 		void drop() { fin.run.done = false; txt.run.done = false; val.run.done = false; frq.run.done = false; trm.run.done = false; dropDictionary(); }
 		// a new terms call: a dictionary is that of the terms it was built from, and postings are those of their dictionary
-		void dropDictionary() { dct.run.done = false; pst.run.done = false; }
+		void dropDictionary() { dct.run.done = false; dropPostings(); }
+		// a new dictionary call: postings are those of the dictionary they were built from, positions those of their postings
+		void dropPostings() { pst.run.done = false; pos.run.done = false; }
 	} prod;
 	// single-document mode
 	struct SingleDoc

@@ -1,5 +1,5 @@
 // C-ABI of level 2, second half: the last device batch finished on the device and what is made of the finished batch there --
-// matched text, result values, pattern frequencies, index terms, the batch dictionary, the batch postings -- with their fetch and timing calls.  Every product is one
+// matched text, result values, pattern frequencies, index terms, the batch dictionary, the batch postings, the posting positions -- with their fetch and timing calls.  Every product is one
 // ProductCall (capi_l2_ctx.hpp) behind the finish; sp_matcher_ctx::Products::drop() is what a new batch or finish does to them.
 #include "capi_l2_ctx.hpp"
 #include "l2_finish.h"
@@ -9,9 +9,11 @@
 #include "l2_terms.h"
 #include "l2_dict.h"
 #include "l2_postings.h"
+#include "l2_positions.h"
 #include "match_terms.hpp"
 #include "match_dict.hpp"
 #include "match_postings.hpp"
+#include "match_positions.hpp"
 #include "span_text.hpp"
 #include "pattern_freq.hpp"
 #include "finished_host.hpp"
@@ -106,8 +108,11 @@ void fetchByteFamilies( const sp_matcher_ctx* c, const ByteFamilies& b, int32_t*
 
 // test hook: the bits of a term's hash that the device keeps (32 and more = all)
 std::atomic<unsigned>& termHashBits() { static std::atomic<unsigned> bits( 32); return bits; }
-// test hook: the bits of a radix digit of the postings' partition
+// test hook: the bits of a radix digit of the partitions of the postings and of the positions
 std::atomic<unsigned>& postingsDigitBits() { static std::atomic<unsigned> bits( POSTINGS_MAX_DIGIT_BITS); return bits; }
+
+// diagnostics: whether a positions call records an event behind every launch
+std::atomic<unsigned>& positionsLaunchEvents() { static std::atomic<unsigned> on( 0); return on; }
 
 // ---- the sources of the terms and of the dictionary call: the results families of the values call (0) and of the text call (1)
 // that `flags` selects, which must have run since the finish
@@ -559,7 +564,7 @@ int sp_matcher_ctx_finished_dictionary_device( sp_matcher_ctx_t* c, void* stream
 		const uint32_t flags = t.flags;
 		const TermSources sources( c, flags);
 		sp_matcher_ctx::Dict& q = c->prod.dct;
-		c->prod.pst.run.done = false;		// (postings are those of the dictionary they were built from)
+		c->prod.dropPostings();			// (postings are those of the dictionary they were built from)
 		ProductCall call( c, q.run, stream);
 		const size_t ndocs = call.ndocs;
 		const uint64_t nresults = call.finished[ 0], nterms = t.total;
@@ -639,6 +644,7 @@ int sp_matcher_ctx_finished_postings_device( sp_matcher_ctx_t* c, void* stream, 
 		const sp_matcher_ctx::Dict& d = c->prod.dct;
 		if (!t.run.done || !d.run.done) throw std::runtime_error( "no dictionary of the last terms of the last finished batch (sp_matcher_ctx_finished_dictionary_device)");
 		sp_matcher_ctx::Postings& q = c->prod.pst;
+		c->prod.pos.run.done = false;		// (positions are those of the postings they were built from)
 		// (the dictionary call waited for ndict and knows N: nothing is waited for here)
 		ProductCall call( c, q.run, stream, ProductCall::Sized());
 		const size_t ndocs = call.ndocs;
@@ -697,5 +703,111 @@ int sp_matcher_ctx_finished_postings_fetch( sp_matcher_ctx_t* c, sp_match_postin
 int sp_matcher_ctx_last_postings_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.pst.run.ms( 0, 1, ms); }
 
 uint32_t sp_matcher_postings_tile(void) { return POSTINGS_TILE; }
+
+// ---- the positions of the postings of the finished batch, partitioned on the device (l2_positions.h)
+void sp_test_positions_launch_events( unsigned on) { positionsLaunchEvents().store( on, std::memory_order_relaxed); }
+
+int sp_matcher_ctx_finished_positions_device( sp_matcher_ctx_t* c, void* stream, sp_match_positions_device_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		requireFinished( c);
+		const sp_matcher_ctx::Finished& fin = c->prod.fin;
+		const sp_matcher_ctx::Terms& t = c->prod.trm;
+		const sp_matcher_ctx::Postings& s = c->prod.pst;
+		if (!t.run.done || !c->prod.dct.run.done || !s.run.done)
+			throw std::runtime_error( "no postings of the last dictionary of the last finished batch (sp_matcher_ctx_finished_postings_device)");
+		sp_matcher_ctx::Positions& q = c->prod.pos;
+		q.launches = 0;
+		// (the terms call read the finished total and the postings call knows N: the one wait of this call is for nocc and the largest ordpos)
+		ProductCall call( c, q.run, stream, ProductCall::Sized());
+		const size_t ndocs = call.ndocs;
+		const uint64_t nresults = t.nresults, nterms = s.nterms;
+		if (t.ndocs != ndocs || s.ndocs != ndocs || t.total != nterms) throw std::runtime_error( "the postings are not those of the terms of the finished batch");
+		if (nresults >= 0xFFFFFFFFull) throw std::runtime_error( "2^32 - 1 results or more: the indices of the positions are 32 bits");
+		const uint32_t bits = postingsDigitBits().load( std::memory_order_relaxed);
+		reserveOrNoMem( q.dOccurrences, (nresults+1)*sizeof(sp_occurrence_t));		// (sized by the finished total before the wait: nocc is at most that)
+		reserveOrNoMem( q.dPostingOffsets, (nterms+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dPostingPositions, (nterms+1)*sizeof(uint32_t));
+		reserveOrNoMem( q.dDocOf, (nresults+1)*sizeof(uint32_t));
+		for (int i=0; i<2; ++i) reserveOrNoMem( q.dPairs[ i], (nresults+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dHist, radixHistWords( nresults)*sizeof(uint32_t));
+		PositionsLaunchEvents events = { 0, 0, 0, 0};
+		if (positionsLaunchEvents().load( std::memory_order_relaxed))
+		{
+			const size_t capacity = 8 + 3*64;		// (two marks in front, keys, offsets, rekey, place, three a pass)
+			if (q.launchEv.size() < capacity) q.launchEv = std::vector<Event>( capacity);
+			q.launchEvHandles.resize( capacity); q.launchKind.assign( capacity, POS_NONE);
+			for (size_t i=0; i<capacity; ++i) { q.launchEv[ i].create(); q.launchEvHandles[ i] = q.launchEv[ i]; }
+			events.ev = q.launchEvHandles.data(); events.kind = q.launchKind.data(); events.capacity = capacity;
+		}
+		// behind the postings, whose placement nobody has waited for yet; that runs behind the dictionary, the terms and the finish
+		call.beginBehind( s.run.stream, s.run.ev[ 1], q.dTotals, 3, q.dCursor, POSITIONS_CURSORS);
+		HIP_CHECK( hipMemsetAsync( q.dPostingPositions.ptr, 0, (nterms+1)*sizeof(uint32_t), call.stream));
+		PositionsParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.results = (const uint32_t*)fin.dResults.ptr; P.docOffsets = (const uint64_t*)fin.dDocResultOffsets.ptr;
+		P.resultTerm = (const uint32_t*)t.dResultTerm.ptr; P.docTermOffsets = (const uint64_t*)t.dDocOffsets.ptr;
+		P.postings = (const uint32_t*)s.dPostings.ptr; P.recordPosting = (const uint32_t*)s.dRecordPosting.ptr;
+		P.nresults = nresults; P.nterms = nterms; P.ndocs = (uint32_t)ndocs;
+		P.digitBits = bits; P.tiles = radixTiles( nresults);
+		P.docOf = (uint32_t*)q.dDocOf.ptr; P.hist = (uint32_t*)q.dHist.ptr; P.cursor = (uint32_t*)q.dCursor.ptr;
+		for (int i=0; i<2; ++i) P.pairs[ i] = (uint64_t*)q.dPairs[ i].ptr;
+		P.occurrences = (uint32_t*)q.dOccurrences.ptr; P.postingOffsets = (uint64_t*)q.dPostingOffsets.ptr;
+		P.postingPositions = (uint32_t*)q.dPostingPositions.ptr; P.totals = (uint64_t*)q.dTotals.ptr;
+		P.events = events.ev ? &events : 0;
+		uint64_t counted[ 3] = { 0, 0, 0};		// nocc, (the sum of posting_positions: the placement's), the largest participating ordpos
+		call.passes( P, launchL2PositionsCount, launchL2PositionsPlace, q.dTotals, counted, 3, [&]{
+			P.nocc = counted[ 0] < nresults ? counted[ 0] : nresults;
+			P.passes[ 0] = radixPasses( counted[ 2] & 0xFFFFFFFFull, bits);
+			// (a result that does not participate sorts behind the last posting with the key N)
+			P.passes[ 1] = radixPasses( P.nocc < nresults ? nterms : (nterms ? nterms - 1 : 0), bits);
+		});
+		q.ndocs = ndocs; q.nterms = nterms; q.nocc = P.nocc; q.launches = events.n;
+		if (out)
+		{
+			out->ndocs = ndocs; out->nterms = (size_t)nterms; out->nocc = (size_t)P.nocc;
+			out->d_occurrences = q.dOccurrences.ptr; out->d_posting_offsets = q.dPostingOffsets.ptr;
+			out->d_posting_positions = q.dPostingPositions.ptr; out->d_totals = q.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the positions' buffers
+int sp_matcher_ctx_finished_positions_fetch( sp_matcher_ctx_t* c, sp_match_positions_t* out)
+{
+	const sp_matcher_ctx::Positions& q = c->prod.pos;
+	return fetchProduct( c, q.run, "no positions of the last postings of this context (sp_matcher_ctx_finished_positions_device)", out, sp_match_positions_free, [&]{
+		allocMatchPositions( out, q.ndocs, q.nterms, q.nocc);
+		if (q.nocc) copySync( c->own, out->occurrences, q.dOccurrences.ptr, q.nocc*sizeof(sp_occurrence_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->posting_offsets, q.dPostingOffsets.ptr, (q.nterms+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		if (q.nterms) copySync( c->own, out->posting_positions, q.dPostingPositions.ptr, q.nterms*sizeof(uint32_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->totals, q.dTotals.ptr, 2*sizeof(uint64_t), hipMemcpyDeviceToHost);
+	});
+}
+
+// duration of the launches of the last positions call in milliseconds (HIP events on its stream; the memsets that clear the
+// cursors, the totals and posting_positions are enqueued before the first event; the host's one wait lies inside)
+int sp_matcher_ctx_last_positions_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.pos.run.ms( 0, 1, ms); }
+
+// the launches of the last positions call summed by kind (sp_test_positions_launch_events)
+int sp_matcher_ctx_last_positions_launch_ms( sp_matcher_ctx_t* c, double ms[ 6])
+{
+	const sp_matcher_ctx::Positions& q = c->prod.pos;
+	for (int k=0; k<6; ++k) ms[ k] = 0.0;
+	if (!q.run.evValid || !q.launches) return SP_ERR_INVALID;
+	if (hipEventSynchronize( q.run.ev[ 1]) != hipSuccess) return SP_ERR_DEVICE;
+	for (size_t i=1; i<q.launches; ++i)
+	{
+		const int kind = q.launchKind[ i];
+		double one = 0.0;
+		if (kind < 0 || kind >= 6) continue;		// (a mark in front of a half, or the scan of the posting offsets)
+		if (!elapsedMs( q.launchEvHandles[ i-1], q.launchEvHandles[ i], one)) return SP_ERR_DEVICE;
+		ms[ kind] += one;
+	}
+	return SP_OK;
+}
+
+uint32_t sp_matcher_positions_tile(void) { return POSITIONS_TILE; }
 
 } // extern "C"

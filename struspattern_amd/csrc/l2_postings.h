@@ -12,30 +12,20 @@
 //              (termDict[i], i) as one 8-byte store into pairs[0].  A key at or beyond ndict becomes ndict - 1.
 //   offsets    one workgroup: the exclusive prefix sums of doc_freq over the dictionary records in 64 bits (scanDocumentCounts),
 //              and the total.
-//   per pass   histogram  the records are cut into fixed tiles, tile k = the pairs [k*TILE, (k+1)*TILE) of the pass's source
-//                         buffer; a wave takes a tile from the cursor, counts its digits in LDS and writes hist[digit][tile];
-//              scan       one workgroup: the exclusive prefix of hist in (digit-major, tile-minor) order, in 32 bits (N < 2^32 - 1);
-//              scatter    the same tiles, in trips of 64 in record order.  The rank of a lane is its tile's base for its digit
-//                         + the wave's running count of that digit in LDS + the lower lanes of the trip with the same digit
-//                         (digitBits ballots); the pair goes to the other buffer.
+//   per pass   histogram, scan, scatter over fixed tiles of records (radix_passes.h, shared with l2_positions.h).
 //   place      for sorted position p holding record i: postings[p] = {docOf[i], i - docTermOffsets[docOf[i]], count,
 //              first_ordpos} as one 16-byte store and recordPosting[i] = p.
-// POSTINGS_TILE: 2048 records = 32 trips of a wave.  The passes are copies at heart: they run 16 waves per CU as every
-// wave-per-document pass does (wavePerDocumentBlocks), and a wave's 256 digit counters are 1 KiB of LDS, 16 KiB per CU of its
-// 160 KiB, so LDS does not bound the residency.  What the tile sets is the size of hist, 256 words per tile = N/8 words, which
-// ONE workgroup scans per pass: an eighth of a word per record, against the four words per record that the scatter moves; a
-// smaller tile makes the scan the longest launch of a pass, a larger one leaves CUs without a tile at N near 10^5.
+// POSTINGS_TILE is RADIX_TILE; radix_passes.h says what bounds it.
 // Whatever the working arrays hold: a record index is compared against N before a term record is read, a key against ndict,
 // a document against ndocs, a rank against N; a digit is masked to the counters of the wave.
 #ifndef SPA_L2_POSTINGS_H
 #define SPA_L2_POSTINGS_H
-#include <stdint.h>
-#include <hip/hip_runtime_api.h>
+#include "radix_passes.h"
 
 namespace spa {
 
-const uint32_t POSTINGS_TILE = 2048;		// records per tile, a multiple of 64
-const uint32_t POSTINGS_MAX_DIGIT_BITS = 8;	// the digit counters of a wave in LDS: 2^8 words
+const uint32_t POSTINGS_TILE = RADIX_TILE;		// records per tile
+const uint32_t POSTINGS_MAX_DIGIT_BITS = RADIX_MAX_DIGIT_BITS;
 const uint32_t POSTINGS_CURSORS = 2 + 2*32;	// keys, place, and histogram and scatter of at most 32 passes (1-bit digits)
 
 struct PostingsParams
@@ -63,14 +53,9 @@ struct PostingsParams
 	uint64_t* total;
 };
 
-inline uint32_t l2PostingsTiles( uint64_t nterms) { return (uint32_t)((nterms + POSTINGS_TILE - 1) / POSTINGS_TILE); }
+inline uint32_t l2PostingsTiles( uint64_t nterms) { return radixTiles( nterms); }
 // the radix passes for ndict entries: the digits of the largest key, ndict - 1
-inline uint32_t l2PostingsPasses( uint64_t ndict, uint32_t digitBits)
-{
-	uint32_t width = 0;
-	for (uint64_t k = ndict ? ndict - 1 : 0; k; k >>= 1) ++width;
-	return (width + digitBits - 1) / digitBits;
-}
+inline uint32_t l2PostingsPasses( uint64_t ndict, uint32_t digitBits) { return radixPasses( ndict ? ndict - 1 : 0, digitBits); }
 // enqueue every launch
 hipError_t launchL2Postings( const PostingsParams& P, unsigned numCUs, hipStream_t stream);
 

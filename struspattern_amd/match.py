@@ -2,7 +2,7 @@
 through the MI355X lexer + rule automaton, print tokens (-K) and results in the reference tool's
 listing format (doc/webpage/introduction_struspattern.htm:178-260).
 
-    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] [--postings] file [file ...]
+    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] [--postings] [--positions] file [file ...]
 
 Every file is one document (plain UTF-8 text; the reference tool segments XML with strusAnalyzer's
 segmenters, which are outside this engine -- pass -o to add the offset of the text inside its original
@@ -23,6 +23,8 @@ often over all of them, built on the GPU from the terms (finishedDictionaryDevic
 dictionary lines are followed by one line per entry, in the same order, with the files that hold the term in the order given:
 `post NAME 'VALUE': FILEINDEX:COUNT@FIRSTPOS ...` -- the index of the file among the arguments (from 0), how often the term
 occurs in it and the first ordinal position it starts at, built on the GPU from the dictionary (finishedPostingsDevice).
+--positions implies --postings; every FILEINDEX:COUNT@FIRSTPOS is followed by the distinct ordinal positions the term starts at
+in that file, ascending: `FILEINDEX:COUNT@FIRSTPOS[POS,POS,...]`, built on the GPU from the postings (finishedPositionsDevice).
 All files go to the GPU as one batch.  There is no CPU fallback.
 """
 import argparse
@@ -45,9 +47,11 @@ def main(argv=None):
     ap.add_argument("--terms", action="store_true", help="after the listing of a file, one line per distinct (pattern, value) of it")
     ap.add_argument("--dictionary", action="store_true", help="after the last listing, one line per distinct (pattern, value) of all files")
     ap.add_argument("--postings", action="store_true", help="implies --dictionary; after its lines, per distinct (pattern, value) the files that hold it")
+    ap.add_argument("--positions", action="store_true", help="implies --postings; after every file of a posting line, the distinct positions of the term in it")
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("files", nargs="+")
     args = ap.parse_args(argv)
+    args.postings = args.postings or args.positions
     args.dictionary = args.dictionary or args.postings
 
     with open(args.program, encoding="utf-8") as f:
@@ -72,6 +76,7 @@ def main(argv=None):
     terms = device_terms(mctx, text, offs) if args.terms or args.dictionary else None
     dictionary = device_dictionary(mctx) if args.dictionary else None
     postings = device_postings(mctx) if args.postings else None
+    positions = device_positions(mctx) if args.positions else None
     freq = frequencies(mctx) if args.frequencies else None
     for di, fn in enumerate(args.files):
         print("%s:" % fn)
@@ -87,7 +92,7 @@ def main(argv=None):
         print_frequencies(freq, di, mt)
         print_terms(terms if args.terms else None, di, mt)
     print_dictionary(dictionary, terms, mt)
-    print_postings(postings, dictionary, terms, mt)
+    print_postings(postings, dictionary, terms, mt, positions)
     print("OK done")
     return 0
 
@@ -118,18 +123,29 @@ def device_postings(mctx):
     return mctx.finishedPostingsFetch()
 
 
-def postings_lines(postings, dictionary, found, pattern_name):
-    """the lines of --postings; found: (batch, text, values, terms) of the terms call"""
+def device_positions(mctx):
+    """--positions: the positions of the postings that device_postings built, partitioned on the device"""
+    mctx.finishedPositionsDevice()
+    return mctx.finishedPositionsFetch()
+
+
+def postings_lines(postings, dictionary, found, pattern_name, positions=None):
+    """the lines of --postings; found: (batch, text, values, terms) of the terms call; positions: those of --positions"""
     mb, mt, mv, terms = found
+
+    def where(p):
+        return "" if positions is None else "[%s]" % ",".join("%d" % pos for pos in positions.positions(p).tolist())
+
     return ["post %s '%s': %s" % (pattern_name(int(h)), value.decode("utf-8", "replace"),
-                                  " ".join("%d:%d@%d" % (doc, count, first) for doc, _, count, first in postings.entry(e).tolist()))
+                                  " ".join("%d:%d@%d%s" % (doc, count, first, where(int(postings.entry_offsets[e]) + k))
+                                           for k, (doc, _, count, first) in enumerate(postings.entry(e).tolist())))
             for e, (h, value, _, _, _) in enumerate(dictionary.entries(mb, terms, values=mv, text=mt))]
 
 
-def print_postings(postings, dictionary, found, mt):
+def print_postings(postings, dictionary, found, mt, positions=None):
     if postings is None:
         return
-    for line in postings_lines(postings, dictionary, found, mt.patternName):
+    for line in postings_lines(postings, dictionary, found, mt.patternName, positions):
         print(line)
 
 
@@ -197,8 +213,12 @@ def paragraphs(args, prg, lx, mt, docs):
     text, seg_offsets, doc_seg_offsets, posmaps = segments.segmented_batch(docs)
     lctx = lx.createContext(args.device)
     mctx = mt.createContext(args.device)
-    values = terms = dictionary = postings = None
-    if args.postings:
+    values = terms = dictionary = postings = positions = None
+    if args.positions:
+        mb, mtext, mvalues, mterms, dictionary, postings, positions = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_positions=True)
+        terms = (mb, mtext, mvalues, mterms)
+        values = mvalues if args.device_values else None
+    elif args.postings:
         mb, mtext, mvalues, mterms, dictionary, postings = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_postings=True)
         terms = (mb, mtext, mvalues, mterms)
         values = mvalues if args.device_values else None
@@ -240,7 +260,7 @@ def paragraphs(args, prg, lx, mt, docs):
         print_frequencies(freq, di, mt)
         print_terms(terms if args.terms else None, di, mt)
     print_dictionary(dictionary, terms, mt)
-    print_postings(postings, dictionary, terms, mt)
+    print_postings(postings, dictionary, terms, mt, positions)
     print("OK done")
     return 0
 
