@@ -11,15 +11,16 @@ import numpy as np
 
 from . import capi
 from .capi import SpLexem, SpResult, SpResultItem
+from .products import (SP_TERM_TEXT, SP_TERM_VALUES, SP_TEXT_ITEMS, SP_TEXT_RESULTS, SP_VALUE_ITEMS, SP_VALUE_RESULTS,   # noqa: F401 (public names)
+                       MatchBatch, MatchDictionary, MatchPositions, MatchPostings, MatchTerms, MatchText, MatchValues, PatternError, PatternFreq,
+                       batchDictionary, batchPatternFreq, batchPositions, batchPostings, batchTerms, batchText, batchValues,
+                       _match_batch_of, _product, _rows)
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
            "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms", "MatchDictionary", "batchDictionary", "MatchPostings", "batchPostings", "MatchPositions", "batchPositions"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
-SP_TEXT_RESULTS, SP_TEXT_ITEMS = 1, 2   # include/strus_pattern_amd.h: the families of spans of a text call
-SP_VALUE_RESULTS, SP_VALUE_ITEMS = 1, 2  # include/strus_pattern_amd.h: the families of records of a values call
-SP_TERM_VALUES, SP_TERM_TEXT = 1, 2    # include/strus_pattern_amd.h: the sources of the term values of a terms call
 SP_ERR_UNAVAILABLE = -6     # include/strus_pattern_amd.h: a value that does not exist for the context
 
 JOIN_OP = {"sequence": 0, "sequence_imm": 1, "sequence_struct": 2, "within": 3, "within_struct": 4, "any": 5, "and": 6}
@@ -29,469 +30,6 @@ DOC_STATUS = {
     3: "pattern with too many identical key events defined", 4: "internal: encountered past trigger with follow",
     5: "term event out of range", 6: "illegal free of event data reference",
 }
-
-
-class PatternError(RuntimeError):
-    pass
-
-
-class MatchBatch:
-    """Results of a batch of documents (host copies)."""
-
-    def __init__(self, results, items, doc_offsets, stats, status, result_format=None, item_format=None):
-        self.result_format = result_format  # (n,) u32 format handle per result, None without format strings
-        self.item_format = item_format      # (m, 2) u32 {format handle, nsub} per item (see resultformat.py)
-        self.results = results          # (n, 9) u32: handle, ordpos, ordend, origseg, origpos, origendseg, origend, item_begin, item_count
-        self.items = items              # (m, 7) u32: variable, ordpos, ordend, origseg, origpos, origendseg, origend
-        self.doc_offsets = doc_offsets  # (ndocs+1,) u64
-        self.stats = stats              # (ndocs, 4) u64
-        self.status = status            # (ndocs,) i32
-
-    def doc(self, i):
-        return self.results[self.doc_offsets[i]:self.doc_offsets[i + 1]]
-
-
-def _rows(ptr, n, k, ctype=ctypes.c_uint32):
-    """n rows of k columns of `ctype` behind the ctypes pointer `ptr` (to records of any type), copied: shape (n, k), or (n,) for k = 0"""
-    if not n or not ptr:
-        return np.zeros((n, k) if k else n, ctype)
-    a = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctype)), shape=(n * max(k, 1),)).copy()
-    return a.reshape(n, k) if k else a
-
-
-def _formats_of(b):
-    if not b.result_format:
-        return None, None
-    return _rows(b.result_format, b.nresults, 0), _rows(b.item_format, b.nitems, 2)
-
-
-def _match_batch_of(b):
-    """the MatchBatch of a capi.SpMatchBatch (copies)"""
-    return MatchBatch(_rows(b.results, b.nresults, 9), _rows(b.items, b.nitems, 7), _rows(b.doc_result_offsets, b.ndocs + 1, 0, ctypes.c_uint64),
-                      _rows(b.doc_stats, b.ndocs, 4, ctypes.c_uint64), _rows(b.doc_status, b.ndocs, 0, ctypes.c_int32), *_formats_of(b))
-
-
-def _product(struct_type, call, free, convert, failed):
-    """One C call that fills a struct the library allocates for: call(struct) is the return code, failed(rc) the message of
-    the PatternError for one that is not 0, convert(struct) the Python copy.  The struct is freed whatever happens."""
-    s = struct_type()
-    rc = call(s)
-    try:
-        if rc != 0:
-            raise PatternError(failed(rc))
-        return convert(s)
-    finally:
-        free(ctypes.byref(s))
-
-
-def _host_batch(mb, items=False, formats=None, status=False):
-    """The capi.SpMatchBatch of a MatchBatch for a host twin, and the arrays it points into: the caller holds them until its
-    C call has returned.  items: with the items; formats: "results" with the format handles of the results, "all" with those
-    of the items too (where the batch has them); status: with the document status (where the batch has one)."""
-    b, keep = capi.SpMatchBatch(), []
-
-    def point(field, array, ctype):
-        keep.append(array)
-        setattr(b, field, ctypes.cast(array.ctypes.data, ctypes.POINTER(ctype)))
-
-    res = np.ascontiguousarray(mb.results, dtype=np.uint32).reshape(-1, 9)
-    offs = np.ascontiguousarray(mb.doc_offsets, dtype=np.uint64)
-    b.ndocs, b.nresults = len(offs) - 1, len(res)
-    point("results", res, SpResult)
-    point("doc_result_offsets", offs, ctypes.c_uint64)
-    if items:
-        its = np.ascontiguousarray(mb.items, dtype=np.uint32).reshape(-1, 7)
-        b.nitems = len(its)
-        point("items", its, SpResultItem)
-    if status and mb.status is not None:
-        point("doc_status", np.ascontiguousarray(mb.status, dtype=np.int32), ctypes.c_int32)
-    if formats == "results" and mb.result_format is not None:
-        rf = np.ascontiguousarray(mb.result_format, dtype=np.uint32).reshape(-1)
-        if len(rf) != len(res):
-            raise PatternError("format array of the batch is not parallel to its results")
-        point("result_format", rf, ctypes.c_uint32)
-    if formats == "all" and mb.result_format is not None and mb.item_format is not None:
-        rf = np.ascontiguousarray(mb.result_format, dtype=np.uint32).reshape(-1)
-        itf = np.ascontiguousarray(mb.item_format, dtype=np.uint32).reshape(-1, 2)
-        if len(rf) != len(res) or len(itf) != b.nitems:
-            raise PatternError("format arrays of the batch are not parallel to its results and items")
-        point("result_format", rf, ctypes.c_uint32)
-        point("item_format", itf, ctypes.c_uint32)
-    return b, keep
-
-
-def _host_text(text, seg_offsets, doc_seg_offsets):
-    """The text source arguments of a host twin (text, nbytes, seg_offsets, nseg, doc_seg_offsets), and what they point into"""
-    text = bytes(text)
-    so = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
-    dso = None if doc_seg_offsets is None else np.ascontiguousarray(doc_seg_offsets, dtype=np.uint64)
-    return (text, len(text), so.ctypes.data, len(so) - 1, dso.ctypes.data if dso is not None else None), [text, so, dso]
-
-
-class _ByteFamilies:
-    """Bytes per result and per item of a batch (host copies): those of record i of a family are bytes[offsets[i]:offsets[i+1]],
-    parallel to the results / items of the batch.  A family that was not asked for is None."""
-    _results = _items = None    # the attributes with the bytes of the two families
-
-    def result(self, i):
-        return getattr(self, self._results)[int(self.result_offsets[i]):int(self.result_offsets[i + 1])]
-
-    def item(self, i):
-        return getattr(self, self._items)[int(self.item_offsets[i]):int(self.item_offsets[i + 1])]
-
-
-def _byte_families_of(cls, s, result, item, status):
-    """the MatchText / MatchValues (`cls`) of its C struct `s` (copies); result, item: the fields (bytes, offsets) of a family
-    of `s`, status: its status field"""
-    def family(fields, n, total):
-        data, offsets = getattr(s, fields[0]), getattr(s, fields[1])
-        if not offsets:
-            return None, None
-        return (ctypes.string_at(data, total) if total else b""), _rows(offsets, n + 1, 0, ctypes.c_uint64)
-    return cls(*family(result, s.nresults, s.totals[0]), *family(item, s.nitems, s.totals[1]), _rows(getattr(s, status), s.ndocs, 0, ctypes.c_int32))
-
-
-class MatchText(_ByteFamilies):
-    """The text that the results and items of a finished batch cover (host copies): the bytes of span i of a family are
-    text[offsets[i]:offsets[i+1]], parallel to the results / items of the batch.  A family that was not asked for is None."""
-    _results, _items = "result_text", "item_text"
-
-    def __init__(self, result_text, result_offsets, item_text, item_offsets, status):
-        self.result_text = result_text        # bytes
-        self.result_offsets = result_offsets  # (nresults+1,) u64
-        self.item_text = item_text
-        self.item_offsets = item_offsets      # (nitems+1,) u64
-        self.status = status                  # (ndocs,) i32: 0, or 5 for a document with a span outside the text (all its spans empty)
-
-
-def _match_text_of(t):
-    """the MatchText of a capi.SpMatchText (copies)"""
-    return _byte_families_of(MatchText, t, ("result_text", "result_text_offsets"), ("item_text", "item_text_offsets"), "doc_text_status")
-
-
-def batchText(mb, text, seg_offsets, doc_seg_offsets=None, results=True, items=True):
-    """The text of a batch already on the host (a MatchBatch in document order with items without gaps: finishedFetch,
-    batchFetch, matchDocs), by the rule of the device call (include/strus_pattern_amd.h "matched text"), without a device:
-    `text` holds the segments back to back (seg_offsets: nseg+1 byte offsets), document d is the segments
-    [doc_seg_offsets[d], doc_seg_offsets[d+1]), or segment d without doc_seg_offsets.  Returns a MatchText."""
-    L = capi.lib()
-    b, keep = _host_batch(mb, items=True)
-    source, keep_text = _host_text(text, seg_offsets, doc_seg_offsets)      # (keep, keep_text: until the call has returned)
-    err = ctypes.create_string_buffer(256)
-    flags = (SP_TEXT_RESULTS if results else 0) | (SP_TEXT_ITEMS if items else 0)
-    return _product(capi.SpMatchText, lambda t: L.sp_match_batch_text(ctypes.byref(b), *source, flags, ctypes.byref(t), err, 256),
-                    L.sp_match_text_free, _match_text_of, lambda rc: "no text of the batch (%d): %s" % (rc, err.value.decode()))
-
-
-class MatchValues(_ByteFamilies):
-    """The values of the format strings of a finished batch (host copies): the value of record i of a family is
-    values[offsets[i]:offsets[i+1]], parallel to the results / items of the batch; a record without a format has an empty
-    range (the format arrays of the batch tell an empty value from no value).  A family that was not asked for is None."""
-    _results, _items = "result_values", "item_values"
-
-    def __init__(self, result_values, result_offsets, item_values, item_offsets, status):
-        self.result_values = result_values    # bytes
-        self.result_offsets = result_offsets  # (nresults+1,) u64
-        self.item_values = item_values
-        self.item_offsets = item_offsets
-        self.status = status                  # (ndocs,) i32: 0, or 5 for a document whose values cannot be built (all of them empty)
-
-
-def _match_values_of(v):
-    """the MatchValues of a capi.SpMatchValues (copies)"""
-    return _byte_families_of(MatchValues, v, ("result_values", "result_value_offsets"), ("item_values", "item_value_offsets"), "doc_value_status")
-
-
-def batchValues(matcher, mb, text, seg_offsets, doc_seg_offsets=None, flags=SP_VALUE_RESULTS | SP_VALUE_ITEMS):
-    """The values of the format strings of a batch already on the host (a MatchBatch of `matcher`, a PatternMatcherInstance,
-    in document order with items without gaps: finishedFetch, batchFetch, matchDocs), by the rule of the device call
-    (include/strus_pattern_amd.h "result values"), without a device.  The text source is that of batchText.  Returns a
-    MatchValues."""
-    L = capi.lib()
-    b, keep = _host_batch(mb, items=True, formats="all")
-    source, keep_text = _host_text(text, seg_offsets, doc_seg_offsets)      # (keep, keep_text: until the call has returned)
-    err = ctypes.create_string_buffer(512)
-    return _product(capi.SpMatchValues, lambda v: L.sp_match_batch_values(matcher._h, ctypes.byref(b), *source, flags, ctypes.byref(v), err, 512),
-                    L.sp_match_values_free, _match_values_of, lambda rc: "no values of the batch (%d): %s" % (rc, err.value.decode(errors="replace")))
-
-
-class PatternFreq:
-    """The pattern frequencies of a finished batch (host copies): per document one record per distinct handle, ascending by
-    handle, and per handle the sums over the batch (include/strus_pattern_amd.h "pattern frequencies")."""
-
-    def __init__(self, records, doc_offsets, status, handle_results, handle_docs):
-        self.records = records                # (n, 4) u32: handle, count, first_ordpos, last_ordend
-        self.doc_offsets = doc_offsets        # (ndocs+1,) u64
-        self.status = status                  # (ndocs,) i32: 0, or 5 for a document with a handle outside the bound (no records)
-        self.handle_results = handle_results  # (handle_bound,) u64: results per handle over the batch (collection frequency)
-        self.handle_docs = handle_docs        # (handle_bound,) u32: documents per handle (document frequency)
-
-    def doc(self, i):
-        return self.records[int(self.doc_offsets[i]):int(self.doc_offsets[i + 1])]
-
-
-def _pattern_freq_of(b):
-    """the PatternFreq of a capi.SpPatternFreqBatch (copies)"""
-    return PatternFreq(_rows(b.records, b.nrecords, 4), _rows(b.doc_offsets, b.ndocs + 1, 0, ctypes.c_uint64),
-                       _rows(b.doc_freq_status, b.ndocs, 0, ctypes.c_int32), _rows(b.handle_results, b.handle_bound, 0, ctypes.c_uint64),
-                       _rows(b.handle_docs, b.handle_bound, 0))
-
-
-def batchPatternFreq(mb, handle_bound):
-    """The pattern frequencies of a batch already on the host (a MatchBatch in document order: finishedFetch, batchFetch,
-    matchDocs), by the rule of the device call, without a device.  handle_bound: PatternMatcherInstance.handleBound().
-    Returns a PatternFreq."""
-    L = capi.lib()
-    b, keep = _host_batch(mb, status=True)      # (keep: until the call has returned)
-    err = ctypes.create_string_buffer(256)
-    return _product(capi.SpPatternFreqBatch, lambda f: L.sp_match_batch_pattern_freq(ctypes.byref(b), handle_bound, ctypes.byref(f), err, 256),
-                    L.sp_pattern_freq_batch_free, _pattern_freq_of, lambda rc: "no pattern frequencies of the batch (%d): %s" % (rc, err.value.decode()))
-
-
-def _term_value(flags, mb, values, text, r):
-    """the value bytes of result r of the finished batch mb: those of `values` (a MatchValues) unless the flags say `text` (a
-    MatchText); with both flags the text of a result without a format"""
-    use_text = not (flags & SP_TERM_VALUES)
-    if flags == (SP_TERM_VALUES | SP_TERM_TEXT):
-        use_text = mb.result_format is None or int(mb.result_format[r]) == 0
-    return text.result(r) if use_text else values.result(r)
-
-
-class MatchTerms:
-    """The index terms of a finished batch (host copies): per document one record per distinct pair (handle, value bytes),
-    ascending by handle, then by first_result, and per result the index of its term inside its document's block
-    (include/strus_pattern_amd.h "index terms").  A term owns no bytes: its value is the range of its first result in the
-    values or the text it was built from."""
-
-    def __init__(self, records, doc_offsets, result_term, status, flags=SP_TERM_VALUES | SP_TERM_TEXT, handle_bound=0):
-        self.handle_bound = handle_bound    # the bound the terms were built with (0: not known; batchDictionary then needs it as an argument)
-        self.records = records          # (n, 6) u32: handle, count, first_ordpos, last_ordend, first_result, value_bytes
-        self.doc_offsets = doc_offsets  # (ndocs+1,) u64
-        self.result_term = result_term  # (nresults,) u32, 0xFFFFFFFF throughout a failed document
-        self.status = status            # (ndocs,) i32: 0, or 5 for a failed document (no records)
-        self.flags = flags
-
-    def doc(self, i):
-        return self.records[int(self.doc_offsets[i]):int(self.doc_offsets[i + 1])]
-
-    def terms(self, d, mb, values=None, text=None):
-        """yields (handle, value bytes, count, first_ordpos, last_ordend) per term of document d; mb: the finished batch,
-        values / text: the MatchValues / MatchText the terms were built from"""
-        first = int(mb.doc_offsets[d])
-        for h, count, pos, end, fr, size in self.doc(d).tolist():
-            value = _term_value(self.flags, mb, values, text, first + fr)
-            assert len(value) == size
-            yield h, value, count, pos, end
-
-
-def _match_terms_of(t):
-    """the MatchTerms of a capi.SpMatchTerms (copies)"""
-    return MatchTerms(_rows(t.records, t.nrecords, 6), _rows(t.doc_term_offsets, t.ndocs + 1, 0, ctypes.c_uint64),
-                      _rows(t.result_term, t.nresults, 0), _rows(t.doc_term_status, t.ndocs, 0, ctypes.c_int32), t.flags, t.handle_bound)
-
-
-def _host_sources(values, text, keep):
-    """the C structs (capi.SpMatchValues, capi.SpMatchText) of a MatchValues / MatchText for a host twin, their results family
-    only; either may be None.  What they point into is appended to `keep`."""
-    def source(cls, family, names):
-        if family is None:
-            return None
-        c = cls()
-        c.ndocs, c.nresults = len(family.status), (len(family.result_offsets) - 1 if family.result_offsets is not None else 0)
-        st = np.ascontiguousarray(family.status, dtype=np.int32)
-        keep.append(st)
-        setattr(c, names[2], ctypes.cast(st.ctypes.data, ctypes.POINTER(ctypes.c_int32)))
-        if family.result_offsets is not None:
-            data = bytes(getattr(family, names[3]))
-            ro = np.ascontiguousarray(family.result_offsets, dtype=np.uint64)
-            buf = ctypes.create_string_buffer(data, len(data) + 1)
-            keep.extend([ro, buf])
-            setattr(c, names[0], ctypes.cast(buf, ctypes.POINTER(ctypes.c_uint8)))
-            setattr(c, names[1], ctypes.cast(ro.ctypes.data, ctypes.POINTER(ctypes.c_uint64)))
-            c.totals[0] = len(data)
-        return c
-
-    return (source(capi.SpMatchValues, values, ("result_values", "result_value_offsets", "doc_value_status", "result_values")),
-            source(capi.SpMatchText, text, ("result_text", "result_text_offsets", "doc_text_status", "result_text")))
-
-
-def batchTerms(mb, values=None, text=None, handle_bound=0, flags=SP_TERM_VALUES | SP_TERM_TEXT):
-    """The index terms of a batch already on the host (a MatchBatch in document order: finishedFetch, batchFetch, matchDocs)
-    with its MatchValues and / or MatchText (their results family), by the rule of the device call, without a device.
-    handle_bound: PatternMatcherInstance.handleBound().  Returns a MatchTerms."""
-    L = capi.lib()
-    b, keep = _host_batch(mb, formats="results", status=True)       # (keep: until the call has returned)
-    v, x = _host_sources(values, text, keep)
-    err = ctypes.create_string_buffer(256)
-    return _product(capi.SpMatchTerms, lambda t: L.sp_match_batch_terms(ctypes.byref(b), ctypes.byref(v) if v is not None else None,
-                                                                       ctypes.byref(x) if x is not None else None, handle_bound, flags, ctypes.byref(t), err, 256),
-                    L.sp_match_terms_free, _match_terms_of, lambda rc: "no terms of the batch (%d): %s" % (rc, err.value.decode()))
-
-
-class MatchDictionary:
-    """The dictionary of a terms batch (host copies): one entry per distinct pair (handle, value bytes) over all documents, in
-    the order of first occurrence, and per term record the index of its entry (include/strus_pattern_amd.h "batch
-    dictionary").  An entry owns no bytes: its value is that of term record first_term of document first_doc."""
-
-    def __init__(self, records, term_dict, doc_offsets, handle_terms):
-        self.records = records            # (ndict, 8) u32: handle, value_bytes, first_doc, first_term, doc_freq, max_count, count (low, high)
-        self.counts = np.ascontiguousarray(records[:, 6:8]).view(np.uint64).reshape(-1)   # (ndict,) u64: the collection frequencies
-        self.term_dict = term_dict        # (nterms,) u32, parallel to the term records
-        self.doc_offsets = doc_offsets    # (ndocs+1,) u64: the entries first seen in every document
-        self.handle_terms = handle_terms  # (handle_bound,) u32: distinct terms per handle
-
-    def entries(self, mb, terms, values=None, text=None):
-        """yields (handle, value bytes, doc_freq, count, max_count) per entry, in dictionary order; mb: the finished batch,
-        terms: the MatchTerms the dictionary was built from, values / text: the MatchValues / MatchText of those"""
-        for (h, size, d, t, df, mx, _, _), count in zip(self.records.tolist(), self.counts.tolist()):
-            value = _term_value(terms.flags, mb, values, text, int(mb.doc_offsets[d]) + int(terms.doc(d)[t][4]))
-            assert len(value) == size
-            yield h, value, df, count, mx
-
-
-def _match_dictionary_of(d):
-    """the MatchDictionary of a capi.SpMatchDictionary (copies)"""
-    return MatchDictionary(_rows(d.records, d.ndict, 8), _rows(d.term_dict, d.nterms, 0), _rows(d.doc_dict_offsets, d.ndocs + 1, 0, ctypes.c_uint64),
-                           _rows(d.handle_terms, d.handle_bound, 0))
-
-
-def batchDictionary(mb, terms, values=None, text=None, handle_bound=0):
-    """The dictionary of the terms of a batch already on the host (terms: the MatchTerms of finishedTermsFetch or batchTerms,
-    mb, values, text: what they were built from), by the rule of the device call, without a device.  The handle bound, which
-    is the length of handle_terms, is that of `terms`; a MatchTerms made by hand without one needs `handle_bound`
-    (PatternMatcherInstance.handleBound()): it is not guessed from the records.  Returns a MatchDictionary."""
-    bound = handle_bound or terms.handle_bound
-    if not bound:
-        raise PatternError("no dictionary of the batch: the terms carry no handle bound and none was given")
-    L = capi.lib()
-    b, keep = _host_batch(mb, formats="results", status=True)       # (keep: until the call has returned)
-    v, x = _host_sources(values, text, keep)
-    t = _host_terms(terms, bound, keep)
-    err = ctypes.create_string_buffer(256)
-    return _product(capi.SpMatchDictionary, lambda d: L.sp_match_batch_dictionary(ctypes.byref(b), ctypes.byref(v) if v is not None else None,
-                                                                                 ctypes.byref(x) if x is not None else None, ctypes.byref(t), ctypes.byref(d), err, 256),
-                    L.sp_match_dictionary_free, _match_dictionary_of, lambda rc: "no dictionary of the batch (%d): %s" % (rc, err.value.decode()))
-
-
-def _host_terms(terms, bound, keep):
-    """the capi.SpMatchTerms of a MatchTerms for a host twin; the arrays it points into are appended to `keep`"""
-    t = capi.SpMatchTerms()
-    rec = np.ascontiguousarray(terms.records, dtype=np.uint32).reshape(-1, 6)
-    offs = np.ascontiguousarray(terms.doc_offsets, dtype=np.uint64)
-    rt = np.ascontiguousarray(terms.result_term, dtype=np.uint32)
-    st = np.ascontiguousarray(terms.status, dtype=np.int32)
-    keep.extend([rec, offs, rt, st])
-    t.ndocs, t.nresults, t.nrecords, t.flags = len(offs) - 1, len(rt), len(rec), terms.flags
-    t.handle_bound = bound
-    t.records = ctypes.cast(rec.ctypes.data, ctypes.POINTER(capi.SpMatchTerm))
-    t.doc_term_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
-    t.result_term = ctypes.cast(rt.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
-    t.doc_term_status = ctypes.cast(st.ctypes.data, ctypes.POINTER(ctypes.c_int32))
-    t.totals[0] = len(rec)
-    return t
-
-
-class MatchPostings:
-    """The postings of a dictionary (host copies): per term record one posting (doc, term, count, first_ordpos), the postings
-    of dictionary entry e together and ascending by document, and per term record the index of its posting
-    (include/strus_pattern_amd.h "batch postings")."""
-
-    def __init__(self, records, entry_offsets, record_posting):
-        self.records = records                # (nterms, 4) u32: doc, term, count, first_ordpos
-        self.entry_offsets = entry_offsets    # (ndict+1,) u64: the postings of entry e are records[entry_offsets[e]:entry_offsets[e+1]]
-        self.record_posting = record_posting  # (nterms,) u32, parallel to the term records
-
-    def entry(self, e):
-        """the postings of dictionary entry e, in document order: rows (doc, term, count, first_ordpos)"""
-        return self.records[int(self.entry_offsets[e]):int(self.entry_offsets[e + 1])]
-
-    def docs(self, e):
-        """the documents that hold dictionary entry e, ascending"""
-        return self.entry(e)[:, 0]
-
-
-def _match_postings_of(p):
-    """the MatchPostings of a capi.SpMatchPostings (copies)"""
-    return MatchPostings(_rows(p.postings, p.nterms, 4), _rows(p.entry_offsets, p.ndict + 1, 0, ctypes.c_uint64), _rows(p.record_posting, p.nterms, 0))
-
-
-def batchPostings(terms, dictionary):
-    """The postings of a dictionary already on the host (terms: the MatchTerms, dictionary: the MatchDictionary built from
-    them: the fetches of a context, or batchTerms and batchDictionary), by the rule of the device call, without a device.
-    Returns a MatchPostings."""
-    L = capi.lib()
-    keep = []                                                        # (until the call has returned)
-    t = _host_terms(terms, terms.handle_bound, keep)
-    d = capi.SpMatchDictionary()
-    rec = np.ascontiguousarray(dictionary.records, dtype=np.uint32).reshape(-1, 8)
-    td = np.ascontiguousarray(dictionary.term_dict, dtype=np.uint32)
-    offs = np.ascontiguousarray(dictionary.doc_offsets, dtype=np.uint64)
-    ht = np.ascontiguousarray(dictionary.handle_terms, dtype=np.uint32)
-    keep.extend([rec, td, offs, ht])
-    d.ndocs, d.nterms, d.ndict, d.handle_bound, d.flags = len(offs) - 1, len(td), len(rec), len(ht), terms.flags
-    d.records = ctypes.cast(rec.ctypes.data, ctypes.POINTER(capi.SpDictTerm))
-    d.term_dict = ctypes.cast(td.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
-    d.doc_dict_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
-    d.handle_terms = ctypes.cast(ht.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
-    d.totals[0] = len(rec)
-    err = ctypes.create_string_buffer(256)
-    return _product(capi.SpMatchPostings, lambda p: L.sp_match_batch_postings(ctypes.byref(t), ctypes.byref(d), ctypes.byref(p), err, 256),
-                    L.sp_match_postings_free, _match_postings_of, lambda rc: "no postings of the batch (%d): %s" % (rc, err.value.decode()))
-
-
-def _host_postings(postings, ndocs, keep):
-    """the capi.SpMatchPostings of a MatchPostings for a host twin; the arrays it points into are appended to `keep`"""
-    p = capi.SpMatchPostings()
-    rec = np.ascontiguousarray(postings.records, dtype=np.uint32).reshape(-1, 4)
-    offs = np.ascontiguousarray(postings.entry_offsets, dtype=np.uint64)
-    rp = np.ascontiguousarray(postings.record_posting, dtype=np.uint32)
-    keep.extend([rec, offs, rp])
-    p.ndocs, p.nterms, p.ndict = ndocs, len(rec), len(offs) - 1
-    p.postings = ctypes.cast(rec.ctypes.data, ctypes.POINTER(capi.SpPosting))
-    p.entry_offsets = ctypes.cast(offs.ctypes.data, ctypes.POINTER(ctypes.c_uint64))
-    p.record_posting = ctypes.cast(rp.ctypes.data, ctypes.POINTER(ctypes.c_uint32))
-    p.totals[0] = len(rec)
-    return p
-
-
-class MatchPositions:
-    """The positions of the postings of a batch (host copies): per participating result one occurrence (ordpos, result), the
-    occurrences of posting p together, ascending by ordpos and then by result, and per posting the number of distinct
-    positions (include/strus_pattern_amd.h "posting positions")."""
-
-    def __init__(self, occurrences, posting_offsets, posting_positions, totals):
-        self.occurrences = occurrences              # (nocc, 2) u32: ordpos, result (index inside the document's finished block)
-        self.posting_offsets = posting_offsets      # (nterms+1,) u64: the occurrences of posting p are occurrences[posting_offsets[p]:posting_offsets[p+1]]
-        self.posting_positions = posting_positions  # (nterms,) u32: distinct ordpos per posting
-        self.totals = totals                        # (2,) u64: nocc, the sum of posting_positions
-
-    def posting(self, p):
-        """the occurrences of posting p, by position: rows (ordpos, result)"""
-        return self.occurrences[int(self.posting_offsets[p]):int(self.posting_offsets[p + 1])]
-
-    def positions(self, p):
-        """the distinct ordinal positions of posting p, ascending: what an index stores"""
-        pos = self.posting(p)[:, 0]
-        return pos[np.concatenate(([True], pos[1:] != pos[:-1]))] if len(pos) else pos
-
-
-def _match_positions_of(p):
-    """the MatchPositions of a capi.SpMatchPositions (copies)"""
-    return MatchPositions(_rows(p.occurrences, p.nocc, 2), _rows(p.posting_offsets, p.nterms + 1, 0, ctypes.c_uint64),
-                          _rows(p.posting_positions, p.nterms, 0), np.array([p.totals[0], p.totals[1]], np.uint64))
-
-
-def batchPositions(mb, terms, postings):
-    """The positions of the postings of a batch already on the host (mb: the finished MatchBatch, terms: its MatchTerms,
-    postings: the MatchPostings built from their dictionary: the fetches of a context, or the twins), by the rule of the device
-    call, without a device.  Returns a MatchPositions."""
-    L = capi.lib()
-    b, keep = _host_batch(mb)                                        # (keep: until the call has returned)
-    t = _host_terms(terms, terms.handle_bound, keep)
-    q = _host_postings(postings, len(terms.doc_offsets) - 1, keep)
-    err = ctypes.create_string_buffer(256)
-    return _product(capi.SpMatchPositions, lambda p: L.sp_match_batch_positions(ctypes.byref(b), ctypes.byref(t), ctypes.byref(q), ctypes.byref(p), err, 256),
-                    L.sp_match_positions_free, _match_positions_of, lambda rc: "no positions of the batch (%d): %s" % (rc, err.value.decode()))
 
 
 class PatternMatcherContext:
@@ -579,39 +117,42 @@ class PatternMatcherContext:
             self._L.sp_match_batch_free(ctypes.byref(b))
 
     # -- batch mode (device-resident buffers; pointers are raw device addresses, e.g. torch data_ptr())
-    def matchDocsDevice(self, d_lexems, d_doc_offsets, ndocs, nlexems, stream=0, d_origseg=0):
-        out = capi.SpMatchDeviceBatch()
-        rc = self._L.sp_matcher_ctx_match_docs_device(self._h, d_lexems, d_origseg or None, d_doc_offsets, ndocs, nlexems, stream or None, ctypes.byref(out))
+    def _device(self, fn, out_type, phrase, *args):
+        """one device call of the library, fn(handle, *args, struct pointer): the struct of `out_type` it fills with device pointers"""
+        out = out_type()
+        rc = fn(self._h, *args, ctypes.byref(out))
         if rc != 0:
-            raise PatternError("device batch match failed (%d): %s" % (rc, self._err()))
+            raise PatternError("%s failed (%d): %s" % (phrase, rc, self._err()))
         return out
+
+    def matchDocsDevice(self, d_lexems, d_doc_offsets, ndocs, nlexems, stream=0, d_origseg=0):
+        return self._device(self._L.sp_matcher_ctx_match_docs_device, capi.SpMatchDeviceBatch, "device batch match",
+                            d_lexems, d_origseg or None, d_doc_offsets, ndocs, nlexems, stream or None)
 
     def matchLexedDevice(self, d_lexems, d_doc_ranges, ndocs, nlexems_hint, stream=0):
         """consume the device output of PatternLexerContext.matchDocsDevice in place (fused pipeline)."""
-        out = capi.SpMatchDeviceBatch()
-        rc = self._L.sp_matcher_ctx_match_lexed_device(self._h, d_lexems, d_doc_ranges, ndocs, nlexems_hint, stream or None, ctypes.byref(out))
-        if rc != 0:
-            raise PatternError("device batch match failed (%d): %s" % (rc, self._err()))
-        return out
+        return self._device(self._L.sp_matcher_ctx_match_lexed_device, capi.SpMatchDeviceBatch, "device batch match",
+                            d_lexems, d_doc_ranges, ndocs, nlexems_hint, stream or None)
 
     def batchFinishDevice(self, stream=0, canonical=False):
         """finish the last batch on the device (asynchronous on `stream`): document order, `exclusive` applied, failed
         documents empty, items without gaps; returns the device pointers (capi.SpMatchFinishedBatch).  canonical: the
         results of a document in the order of SP_FINISH_CANONICAL, the same bytes from every engine."""
-        out = capi.SpMatchFinishedBatch()
-        rc = self._L.sp_matcher_ctx_batch_finish_device_ex(self._h, stream or None, SP_FINISH_CANONICAL if canonical else 0, ctypes.byref(out))
-        if rc != 0:
-            raise PatternError("finishing the batch on the device failed (%d): %s" % (rc, self._err()))
-        return out
+        return self._device(self._L.sp_matcher_ctx_batch_finish_device_ex, capi.SpMatchFinishedBatch, "finishing the batch on the device",
+                            stream or None, SP_FINISH_CANONICAL if canonical else 0)
 
     def finishedFetch(self):
         """plain host copy of the batch finished by batchFinishDevice: what batchFetch() returns, with no work on the host."""
         return self._fetched(self._L.sp_matcher_ctx_finished_fetch)
 
-    def _fetch_product(self, struct_type, call, free, convert, what):
-        """host copy of a product of the last batch: call(handle, ..., struct pointer) fills what `free` frees, `convert` copies"""
-        return _product(struct_type, lambda s: call(self._h, ctypes.byref(s)), free, convert,
-                        lambda rc: "fetching %s failed (%d): %s" % (what, rc, self._err()))
+    def _fetch_product(self, cls, call=None):
+        """host copy of the product `cls` of the last batch, fetched by its own call of the library or by call(handle, struct pointer)"""
+        call = call or getattr(self._L, cls._FETCH)
+        return _product(cls, lambda s: call(self._h, ctypes.byref(s)), lambda rc: "fetching the %s failed (%d): %s" % (cls._WHAT, rc, self._err()))
+
+    @staticmethod
+    def _text_source(d_text, nbytes, d_seg_offsets, nseg, d_doc_seg_offsets):
+        return ctypes.byref(capi.SpTextSource(d_text or None, nbytes, d_seg_offsets or None, nseg, d_doc_seg_offsets or None))
 
     def _last_ms(self, fn, what):
         """the one duration a timing call reports, in milliseconds"""
@@ -636,17 +177,13 @@ class PatternMatcherContext:
         (the placement is asynchronous on `stream`): d_text is the text the lexer batch ran on, d_seg_offsets the nseg+1
         offsets given to the lexer, d_doc_seg_offsets the ndocs+1 offsets given to the stitch (0: document d is segment d).
         Returns the device pointers (capi.SpMatchTextBatch), valid until the next call."""
-        src = capi.SpTextSource(d_text or None, nbytes, d_seg_offsets or None, nseg, d_doc_seg_offsets or None)
-        out = capi.SpMatchTextBatch()
         flags = (SP_TEXT_RESULTS if results else 0) | (SP_TEXT_ITEMS if items else 0)
-        rc = self._L.sp_matcher_ctx_finished_text_device(self._h, ctypes.byref(src), flags, stream or None, ctypes.byref(out))
-        if rc != 0:
-            raise PatternError("gathering the text of the batch on the device failed (%d): %s" % (rc, self._err()))
-        return out
+        return self._device(self._L.sp_matcher_ctx_finished_text_device, capi.SpMatchTextBatch, "gathering the text of the batch on the device",
+                            self._text_source(d_text, nbytes, d_seg_offsets, nseg, d_doc_seg_offsets), flags, stream or None)
 
     def finishedTextFetch(self):
         """plain host copy of the text gathered by finishedTextDevice: a MatchText"""
-        return self._fetch_product(capi.SpMatchText, self._L.sp_matcher_ctx_finished_text_fetch, self._L.sp_match_text_free, _match_text_of, "the text of the batch")
+        return self._fetch_product(MatchText)
 
     def lastTextMs(self):
         """duration of the passes of the last finishedTextDevice in milliseconds"""
@@ -656,16 +193,12 @@ class PatternMatcherContext:
         """build the values of the format strings of the results and / or items of the batch finished by batchFinishDevice,
         on the device (the placement is asynchronous on `stream`); the text source is that of finishedTextDevice.
         Returns the device pointers (capi.SpMatchValuesBatch), valid until the next call."""
-        src = capi.SpTextSource(d_text or None, nbytes, d_seg_offsets or None, nseg, d_doc_seg_offsets or None)
-        out = capi.SpMatchValuesBatch()
-        rc = self._L.sp_matcher_ctx_finished_values_device(self._h, ctypes.byref(src), flags, stream or None, ctypes.byref(out))
-        if rc != 0:
-            raise PatternError("building the values of the batch on the device failed (%d): %s" % (rc, self._err()))
-        return out
+        return self._device(self._L.sp_matcher_ctx_finished_values_device, capi.SpMatchValuesBatch, "building the values of the batch on the device",
+                            self._text_source(d_text, nbytes, d_seg_offsets, nseg, d_doc_seg_offsets), flags, stream or None)
 
     def finishedValuesFetch(self):
         """plain host copy of the values built by finishedValuesDevice: a MatchValues"""
-        return self._fetch_product(capi.SpMatchValues, self._L.sp_matcher_ctx_finished_values_fetch, self._L.sp_match_values_free, _match_values_of, "the values of the batch")
+        return self._fetch_product(MatchValues)
 
     def lastValuesMs(self):
         """duration of the passes of the last finishedValuesDevice in milliseconds"""
@@ -675,16 +208,11 @@ class PatternMatcherContext:
         """sum the pattern frequencies of the batch finished by batchFinishDevice on the device (the placement is
         asynchronous on `stream`): per document one record per distinct handle, per handle the sums over the batch.
         Returns the device pointers (capi.SpPatternFreqDevice), valid until the next call."""
-        out = capi.SpPatternFreqDevice()
-        rc = self._L.sp_matcher_ctx_finished_pattern_freq_device(self._h, stream or None, ctypes.byref(out))
-        if rc != 0:
-            raise PatternError("summing the pattern frequencies of the batch on the device failed (%d): %s" % (rc, self._err()))
-        return out
+        return self._device(self._L.sp_matcher_ctx_finished_pattern_freq_device, capi.SpPatternFreqDevice, "summing the pattern frequencies of the batch on the device", stream or None)
 
     def finishedPatternFreqFetch(self):
         """plain host copy of the frequencies summed by finishedPatternFreqDevice: a PatternFreq"""
-        return self._fetch_product(capi.SpPatternFreqBatch, self._L.sp_matcher_ctx_finished_pattern_freq_fetch, self._L.sp_pattern_freq_batch_free, _pattern_freq_of,
-                                   "the pattern frequencies of the batch")
+        return self._fetch_product(PatternFreq)
 
     def lastPatternFreqMs(self):
         """duration of the passes of the last finishedPatternFreqDevice in milliseconds"""
@@ -696,15 +224,11 @@ class PatternMatcherContext:
         flags: SP_TERM_VALUES (finishedValuesDevice has run since the finish, with the results family), SP_TERM_TEXT
         (finishedTextDevice has, with results=True), or both.  Returns the device pointers (capi.SpMatchTermsDevice), valid
         until the next call."""
-        out = capi.SpMatchTermsDevice()
-        rc = self._L.sp_matcher_ctx_finished_terms_device(self._h, flags, stream or None, ctypes.byref(out))
-        if rc != 0:
-            raise PatternError("grouping the terms of the batch on the device failed (%d): %s" % (rc, self._err()))
-        return out
+        return self._device(self._L.sp_matcher_ctx_finished_terms_device, capi.SpMatchTermsDevice, "grouping the terms of the batch on the device", flags, stream or None)
 
     def finishedTermsFetch(self):
         """plain host copy of the terms grouped by finishedTermsDevice: a MatchTerms"""
-        return self._fetch_product(capi.SpMatchTerms, self._L.sp_matcher_ctx_finished_terms_fetch, self._L.sp_match_terms_free, _match_terms_of, "the terms of the batch")
+        return self._fetch_product(MatchTerms)
 
     def lastTermsMs(self):
         """duration of the passes of the last finishedTermsDevice in milliseconds"""
@@ -715,16 +239,11 @@ class PatternMatcherContext:
         `stream`): every distinct (handle, value) of the batch once, in the order of first occurrence, with its document
         and collection frequency, and per term record the index of its entry.  Returns the device pointers
         (capi.SpMatchDictionaryDevice), valid until the next call."""
-        out = capi.SpMatchDictionaryDevice()
-        rc = self._L.sp_matcher_ctx_finished_dictionary_device(self._h, stream or None, ctypes.byref(out))
-        if rc != 0:
-            raise PatternError("building the dictionary of the batch on the device failed (%d): %s" % (rc, self._err()))
-        return out
+        return self._device(self._L.sp_matcher_ctx_finished_dictionary_device, capi.SpMatchDictionaryDevice, "building the dictionary of the batch on the device", stream or None)
 
     def finishedDictionaryFetch(self):
         """plain host copy of the dictionary built by finishedDictionaryDevice: a MatchDictionary"""
-        return self._fetch_product(capi.SpMatchDictionary, self._L.sp_matcher_ctx_finished_dictionary_fetch, self._L.sp_match_dictionary_free,
-                                   _match_dictionary_of, "the dictionary of the batch")
+        return self._fetch_product(MatchDictionary)
 
     def lastDictionaryMs(self):
         """duration of the launches of the last finishedDictionaryDevice in milliseconds"""
@@ -735,16 +254,11 @@ class PatternMatcherContext:
         on `stream`: the call waits for nothing): per dictionary entry the list of (doc, term, count, first_ordpos) in
         document order, and per term record the index of its posting.  Returns the device pointers
         (capi.SpMatchPostingsDevice), valid until the next call."""
-        out = capi.SpMatchPostingsDevice()
-        rc = self._L.sp_matcher_ctx_finished_postings_device(self._h, stream or None, ctypes.byref(out))
-        if rc != 0:
-            raise PatternError("building the postings of the batch on the device failed (%d): %s" % (rc, self._err()))
-        return out
+        return self._device(self._L.sp_matcher_ctx_finished_postings_device, capi.SpMatchPostingsDevice, "building the postings of the batch on the device", stream or None)
 
     def finishedPostingsFetch(self):
         """plain host copy of the postings built by finishedPostingsDevice: a MatchPostings"""
-        return self._fetch_product(capi.SpMatchPostings, self._L.sp_matcher_ctx_finished_postings_fetch, self._L.sp_match_postings_free,
-                                   _match_postings_of, "the postings of the batch")
+        return self._fetch_product(MatchPostings)
 
     def lastPostingsMs(self):
         """duration of the launches of the last finishedPostingsDevice in milliseconds"""
@@ -755,16 +269,11 @@ class PatternMatcherContext:
         number of occurrences and the largest position, which set its passes; the placement is asynchronous on `stream`; a stream
         other than the postings' is ordered behind them).  Returns the device pointers (capi.SpMatchPositionsDevice), valid until
         the next call."""
-        out = capi.SpMatchPositionsDevice()
-        rc = self._L.sp_matcher_ctx_finished_positions_device(self._h, stream or None, ctypes.byref(out))
-        if rc != 0:
-            raise PatternError("building the positions of the batch on the device failed (%d): %s" % (rc, self._err()))
-        return out
+        return self._device(self._L.sp_matcher_ctx_finished_positions_device, capi.SpMatchPositionsDevice, "building the positions of the batch on the device", stream or None)
 
     def finishedPositionsFetch(self):
         """plain host copy of the positions built by finishedPositionsDevice: a MatchPositions"""
-        return self._fetch_product(capi.SpMatchPositions, self._L.sp_matcher_ctx_finished_positions_fetch, self._L.sp_match_positions_free,
-                                   _match_positions_of, "the positions of the batch")
+        return self._fetch_product(MatchPositions)
 
     def lastPositionsMs(self):
         """duration of the launches of the last finishedPositionsDevice in milliseconds (the host's one wait lies inside)"""
@@ -786,7 +295,7 @@ class PatternMatcherContext:
         return self._fetched(lambda h, b: self._L.sp_matcher_ctx_batch_fetch_docs(h, first_doc, ndocs, b))
 
     def _fetched(self, call):
-        return self._fetch_product(capi.SpMatchBatch, call, self._L.sp_match_batch_free, _match_batch_of, "the batch")
+        return self._fetch_product(MatchBatch, call)
 
     def batchCounters(self):
         arr = (ctypes.c_uint64 * 8)()
@@ -1244,6 +753,26 @@ class PatternLexer:
         return "std"
 
 
+# The products of a finished batch that matchSegmentedDocs builds, in the order it builds, fetches and returns them: the stem of
+# the context's methods (finished<stem>Device, finished<stem>Fetch) and the products it needs
+_SEGMENT_PRODUCTS = (("Text", ()), ("Values", ()), ("Terms", ("Text", "Values")), ("Dictionary", ("Terms",)), ("Postings", ("Dictionary",)),
+                     ("Positions", ("Postings",)))
+
+
+def _rerun(ctx, ndocs, launch, grow, no_room=frozenset((2, 9)), attempts=12):
+    """Run, look at the status, grow, rerun: launch() on the context until no document of the batch has failed, or none for
+    lack of room (status in no_room); grow(counters) reserves the output before the arena grows.  Returns the counters of the
+    last run; documents that still fail after the last attempt keep their status."""
+    for _ in range(attempts):
+        launch()
+        c = ctx.batchCounters()
+        if not c["failed_docs"] or not set(int(x) for x in ctx.batchStatus(ndocs)) & no_room:
+            break
+        grow(c)
+        ctx.growArena()
+    return c
+
+
 def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False, with_terms=False, with_dictionary=False, with_postings=False, with_positions=False):
     """Segmented documents, host buffers in and out: `text` holds the segments back to back (seg_offsets: nseg+1 byte
     offsets), document d consists of the segments [doc_seg_offsets[d], doc_seg_offsets[d+1]).  Lexer -> stitch on the
@@ -1257,10 +786,11 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
     there too and returned as a fifth element, a MatchDictionary.  with_postings implies with_dictionary: the postings of
     the dictionary are built there too and returned as a sixth element, a MatchPostings.  with_positions implies
     with_postings: the positions of every posting are built there too and returned as a seventh element, a MatchPositions."""
-    with_postings = with_postings or with_positions
-    with_dictionary = with_dictionary or with_postings
-    with_terms = with_terms or with_dictionary
-    with_text, with_values = with_text or with_terms, with_values or with_terms
+    want = {"Text": with_text, "Values": with_values, "Terms": with_terms, "Dictionary": with_dictionary, "Postings": with_postings, "Positions": with_positions}
+    for name, needs in reversed(_SEGMENT_PRODUCTS):
+        if want[name]:
+            want.update(dict.fromkeys(needs, True))
+    chosen = [name for name, _ in _SEGMENT_PRODUCTS if want[name]]
     import torch
     text = bytes(text)
     seg_offsets = np.ascontiguousarray(seg_offsets, dtype=np.uint64)
@@ -1270,51 +800,26 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
     d_so = torch.from_numpy(seg_offsets.view(np.int64)).cuda()
     d_dso = torch.from_numpy(doc_seg_offsets.view(np.int64)).cuda()
     stream = torch.cuda.current_stream().cuda_stream
-    for _ in range(12):
-        lctx.matchDocsDevice(d_text.data_ptr(), d_so.data_ptr(), nseg, len(text), stream)
-        lc = lctx.batchCounters()
-        if not lc["failed_docs"] or not set(int(x) for x in lctx.batchStatus(nseg)) & {2, 9}:
-            break
-        lctx.reserveOutput(int(lc["lexems"] * 1.2) + 1024)      # a segment without room: grow and rerun before stitching
-        lctx.growArena()
+    # (a segment without room: grow and rerun before stitching)
+    lc = _rerun(lctx, nseg, lambda: lctx.matchDocsDevice(d_text.data_ptr(), d_so.data_ptr(), nseg, len(text), stream),
+                lambda c: lctx.reserveOutput(int(c["lexems"] * 1.2) + 1024))
     st = lctx.stitchSegmentsDevice(d_dso.data_ptr(), ndocs, stream)
     nlexems = int(lc["lexems"])                                 # an upper bound of the stitched total
-    for _ in range(12):
-        mctx.matchDocsDevice(st.d_lexems, st.d_doc_offsets, ndocs, nlexems, stream, d_origseg=st.d_origseg)
-        mc = mctx.batchCounters()
-        if not mc["failed_docs"] or not set(int(x) for x in mctx.batchStatus(ndocs)) & {2, 9}:
-            break
-        mctx.reserveOutput(int(mc["results"] * 1.2) + 1024, int(mc["items"] * 1.2) + 1024)
-        mctx.growArena()
-    mt = mv = None
-    if with_text or with_values:
+    _rerun(mctx, ndocs, lambda: mctx.matchDocsDevice(st.d_lexems, st.d_doc_offsets, ndocs, nlexems, stream, d_origseg=st.d_origseg),
+           lambda c: mctx.reserveOutput(int(c["results"] * 1.2) + 1024, int(c["items"] * 1.2) + 1024))
+    products = ()
+    if chosen:
+        source = (d_text.data_ptr(), len(text), d_so.data_ptr(), nseg, d_dso.data_ptr())
         mctx.batchFinishDevice(stream)
-        if with_text:
-            mctx.finishedTextDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), nseg, d_dso.data_ptr(), stream=stream)
-        if with_values:
-            mctx.finishedValuesDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), nseg, d_dso.data_ptr(), stream=stream)
-        if with_terms:
-            mctx.finishedTermsDevice(stream=stream)
-        if with_dictionary:
-            mctx.finishedDictionaryDevice(stream=stream)
-        if with_postings:
-            mctx.finishedPostingsDevice(stream=stream)
-        if with_positions:
-            mctx.finishedPositionsDevice(stream=stream)
+        for name in chosen:
+            getattr(mctx, "finished%sDevice" % name)(*(source if name in ("Text", "Values") else ()), stream=stream)
         mb = mctx.finishedFetch()
-        mt = mctx.finishedTextFetch() if with_text else None
-        mv = mctx.finishedValuesFetch() if with_values else None
-        mterms = mctx.finishedTermsFetch() if with_terms else None
-        mdict = mctx.finishedDictionaryFetch() if with_dictionary else None
-        mpost = mctx.finishedPostingsFetch() if with_postings else None
-        mpos = mctx.finishedPositionsFetch() if with_positions else None
+        products = tuple(getattr(mctx, "finished%sFetch" % name)() for name in chosen)
     else:
         mb = mctx.batchFetch()
     stitch_status = lctx.stitchedStatus()
     mb.status = np.where(stitch_status != 0, stitch_status, mb.status).astype(np.int32)
-    out = (mb,) + ((mt,) if with_text else ()) + ((mv,) if with_values else ()) + ((mterms,) if with_terms else ()) + ((mdict,) if with_dictionary else ()) \
-        + ((mpost,) if with_postings else ()) + ((mpos,) if with_positions else ())
-    return out if len(out) > 1 else mb
+    return (mb,) + products if products else mb
 
 
 def device_count():

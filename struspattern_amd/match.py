@@ -149,15 +149,22 @@ def print_postings(postings, dictionary, found, mt, positions=None):
         print(line)
 
 
-def device_terms(mctx, text, offs):
-    """--terms: the last batch of the context finished on the device, its values and the text of its results built there and
-    the results grouped into terms; every document is one segment of `text`.  Returns (batch, text, values, terms)."""
+def uploaded(text, offs):
+    """the text source arguments (d_text, nbytes, d_seg_offsets, nseg) of a device call for `text`, every document one segment,
+    and the device tensors they point into, which the caller holds until it has fetched"""
     import torch
     d_text = torch.frombuffer(bytearray(text + b"\0" * 16), dtype=torch.uint8).cuda()
     d_so = torch.from_numpy(np.ascontiguousarray(offs, dtype=np.uint64).view(np.int64)).cuda()
+    return (d_text.data_ptr(), len(text), d_so.data_ptr(), len(offs) - 1), (d_text, d_so)
+
+
+def device_terms(mctx, text, offs):
+    """--terms: the last batch of the context finished on the device, its values and the text of its results built there and
+    the results grouped into terms; every document is one segment of `text`.  Returns (batch, text, values, terms)."""
+    source, held = uploaded(text, offs)
     mctx.batchFinishDevice()
-    mctx.finishedValuesDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), len(offs) - 1, flags=spa.SP_VALUE_RESULTS)
-    mctx.finishedTextDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), len(offs) - 1, items=False)
+    mctx.finishedValuesDevice(*source, flags=spa.SP_VALUE_RESULTS)
+    mctx.finishedTextDevice(*source, items=False)
     mctx.finishedTermsDevice()
     return mctx.finishedFetch(), mctx.finishedTextFetch(), mctx.finishedValuesFetch(), mctx.finishedTermsFetch()
 
@@ -181,11 +188,9 @@ def print_terms(found, di, mt):
 def device_values(mctx, text, offs):
     """--device-values: the last batch of the context finished on the device and the values of its format strings built
     there; every document is one segment of `text`"""
-    import torch
-    d_text = torch.frombuffer(bytearray(text + b"\0" * 16), dtype=torch.uint8).cuda()
-    d_so = torch.from_numpy(np.ascontiguousarray(offs, dtype=np.uint64).view(np.int64)).cuda()
+    source, held = uploaded(text, offs)
     mctx.batchFinishDevice()
-    mctx.finishedValuesDevice(d_text.data_ptr(), len(text), d_so.data_ptr(), len(offs) - 1)
+    mctx.finishedValuesDevice(*source)
     values = mctx.finishedValuesFetch()
     if np.any(values.status != 0):
         raise spa.PatternError("no values of document %d: status %d" % (int(np.flatnonzero(values.status)[0]), int(values.status.max())))
@@ -213,27 +218,15 @@ def paragraphs(args, prg, lx, mt, docs):
     text, seg_offsets, doc_seg_offsets, posmaps = segments.segmented_batch(docs)
     lctx = lx.createContext(args.device)
     mctx = mt.createContext(args.device)
-    values = terms = dictionary = postings = positions = None
-    if args.positions:
-        mb, mtext, mvalues, mterms, dictionary, postings, positions = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_positions=True)
-        terms = (mb, mtext, mvalues, mterms)
-        values = mvalues if args.device_values else None
-    elif args.postings:
-        mb, mtext, mvalues, mterms, dictionary, postings = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_postings=True)
-        terms = (mb, mtext, mvalues, mterms)
-        values = mvalues if args.device_values else None
-    elif args.dictionary:
-        mb, mtext, mvalues, mterms, dictionary = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_dictionary=True)
-        terms = (mb, mtext, mvalues, mterms)
-        values = mvalues if args.device_values else None
-    elif args.terms:
-        mb, mtext, mvalues, mterms = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_terms=True)
-        terms = (mb, mtext, mvalues, mterms)
-        values = mvalues if args.device_values else None
-    elif args.device_values:
-        mb, values = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_values=True)
-    else:
-        mb = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets)
+    # (terms need text and values; every later product implies the ones before it)
+    with_terms = args.terms or args.dictionary
+    found = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_values=args.device_values, with_terms=with_terms,
+                                   with_dictionary=args.dictionary, with_postings=args.postings, with_positions=args.positions)
+    names = ("batch", "text", "values", "terms", "dictionary", "postings", "positions") if with_terms else ("batch", "values")
+    got = dict(zip(names, found if isinstance(found, tuple) else (found,)))     # (the products asked for, a prefix of the names)
+    mb, dictionary, postings, positions = got["batch"], got.get("dictionary"), got.get("postings"), got.get("positions")
+    terms = (mb, got["text"], got["values"], got["terms"]) if with_terms else None
+    values = got.get("values") if args.device_values else None
     if np.any(mb.status != 0):
         bad = int(np.flatnonzero(mb.status)[0])
         raise spa.PatternError("at least one document failed: %s has status %d" % (args.files[bad], int(mb.status[bad])))

@@ -11,7 +11,7 @@ import pytest
 import oracle
 import struspattern_amd as spa
 from struspattern_amd import capi, synth
-from .test_formats import _apply, _random_program
+from .finished_support import _apply, _random_program
 
 MAX_RESULT_SIZE = 30
 

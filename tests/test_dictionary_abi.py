@@ -9,42 +9,10 @@ import pytest
 import struspattern_amd as spa
 from struspattern_amd import capi
 from tests import dictionary_model as model
-from tests.test_terms_abi import _batch, _family
+from tests.finished_support import (_batch, DICT_BOUND as BOUND, DICT_DOCS as DOCS, DICT_EXPECTED as EXPECTED, DICT_FORMATS as FORMATS,
+                                    _dict_inputs as _inputs, DICT_TEXT as TEXT, _family)
 
 V, T = spa.SP_TERM_VALUES, spa.SP_TERM_TEXT
-
-# four documents; result r has the handle and the text / value / format below
-DOCS = [
-    [(1, 1, 2), (1, 3, 4), (2, 5, 6), (1, 7, 8), (3, 9, 10)],
-    [(2, 1, 2), (1, 3, 4)],
-    [(1, 1, 2), (3, 3, 4), (1, 5, 6), (1, 7, 8)],
-    [(1, 1, 2), (2, 3, 4)],
-]
-TEXT = [b"eur", b"eur", b"x", b"ab", b"",  b"eur", b"abc",  b"eur", b"", b"eur", b"eur",  b"eur", b"x"]
-VALUES = [b"EUR", b"EUR", b"", b"", b"",  b"", b"eur",  b"", b"", b"EUR", b"",  b"", b"x"]
-FORMATS = [1, 1, 0, 0, 0,  0, 2,  0, 0, 1, 0,  0, 3]
-BOUND = 4
-
-# flags -> (entries [handle, value_bytes, first_doc, first_term, doc_freq, max_count, count], term_dict, doc_offsets, handle_terms)
-EXPECTED = {
-    # the text: (1,"eur") in the documents 0, 2 and 3; "eur" under handle 2 in document 1; "ab" and "abc"; the empty text twice
-    T: ([[1, 3, 0, 0, 3, 3, 6], [1, 2, 0, 1, 1, 1, 1], [2, 1, 0, 2, 2, 1, 2], [3, 0, 0, 3, 2, 1, 2], [1, 3, 1, 0, 1, 1, 1], [2, 3, 1, 1, 1, 1, 1]],
-        [0, 1, 2, 3, 4, 5, 0, 3, 0, 2], [0, 4, 6, 6, 6], [0, 3, 2, 1]),
-    # the values: an unformatted result has the empty value, under three handles three entries
-    V: ([[1, 3, 0, 0, 2, 2, 3], [1, 0, 0, 1, 3, 2, 4], [2, 0, 0, 2, 2, 1, 2], [3, 0, 0, 3, 2, 1, 2], [1, 3, 1, 0, 1, 1, 1], [2, 1, 3, 1, 1, 1, 1]],
-        [0, 1, 2, 3, 4, 2, 1, 0, 3, 1, 5], [0, 4, 5, 5, 6], [0, 3, 2, 1]),
-    # both: the formatted value "eur" of document 1 and the text "eur" of unformatted results of the documents 2 and 3 are one
-    # entry; so are the text "x" of document 0 and the formatted value "x" of document 3
-    V | T: ([[1, 3, 0, 0, 2, 2, 3], [1, 2, 0, 1, 1, 1, 1], [2, 1, 0, 2, 2, 1, 2], [3, 0, 0, 3, 2, 1, 2], [1, 3, 1, 0, 3, 2, 4], [2, 3, 1, 1, 1, 1, 1]],
-            [0, 1, 2, 3, 4, 5, 4, 0, 3, 4, 2], [0, 4, 6, 6, 6], [0, 3, 2, 1]),
-}
-
-
-def _inputs(flags, text_status=None):
-    mb = _batch(DOCS, FORMATS)
-    mv, mt = _family(spa.MatchValues, VALUES, 4), _family(spa.MatchText, TEXT, 4, status=text_status)
-    terms = spa.batchTerms(mb, values=mv, text=mt, handle_bound=BOUND, flags=flags)
-    return mb, mv, mt, terms
 
 
 def _entries(d):

@@ -14,14 +14,12 @@ import pytest
 import struspattern_amd as spa
 from struspattern_amd import capi
 from tests import dictionary_model as model
-from tests.test_pattern_freq_gpu import _bare
-from tests.test_span_text_gpu import Run, Source, _from_device, _stream, _torch
-from tests.test_terms_gpu import _build
+from tests.finished_support import (_bare, _build, EVERY, _from_device, Lexems, _matcher, MONEY, Run, RunAny, Source, _stream, T_LIT, T_PLAIN_A,
+                                    T_PLAIN_B, T_SPAN, _torch, _trip_docs, TRIP_RECORDS, _values)
 
 pytestmark = pytest.mark.gpu
 
 V, T = spa.SP_TERM_VALUES, spa.SP_TERM_TEXT
-EVERY = (1, b"every")
 
 
 def _assert_dictionary(ctx, bound, out=None):
@@ -65,28 +63,6 @@ def _by_term(ctx, mb, terms, got):
     """(handle, value) -> (doc_freq, count, max_count, first_doc)"""
     mt = ctx.finishedTextFetch()
     return {(h, v): (df, c, mx, int(first)) for (h, v, df, c, mx), first in zip(got.entries(mb, terms, text=mt), got.records[:, 2])}
-
-
-def _trip_docs():
-    """Documents of 0, 1, 63, 64, 65 and 129 term records -- the trip edges of a lane per record -- and one whose terms are all
-    known: document k repeats about half of the terms of the documents before it and adds new ones, a third of its terms
-    occur twice in it, and EVERY is in each of them."""
-    rng = np.random.default_rng(3)
-    used, docs, fresh = [], [], 0
-    for n in (0, 1, 63, 64, 65, 129):
-        doc = [EVERY] if n else []
-        doc += [used[int(i)] for i in rng.permutation(len(used))[:max(0, (n - 1) // 2)]]
-        while len(doc) < n:
-            doc.append((1 + fresh % 7, b"t%04d" % fresh + b"x" * (fresh % 19)))
-            fresh += 1
-        used += [t for t in doc if t != EVERY and t not in used]
-        doc = doc + doc[:n // 3]
-        docs.append([doc[int(i)] for i in rng.permutation(len(doc))])
-    docs.append([EVERY] + [used[int(i)] for i in rng.permutation(len(used))[:39]])
-    return docs
-
-
-TRIP_RECORDS = [0, 1, 63, 64, 65, 129, 40]
 
 
 # ---- 1. empty shapes
@@ -174,7 +150,6 @@ def test_hash_bits_leave_identical_bytes():
 
 # ---- 5. formats and failed documents
 def test_values_alone_and_both_flags_with_a_document_whose_values_fail():
-    from tests.test_result_values_gpu import Lexems, RunAny, _matcher, _values, T_LIT, T_SPAN, T_PLAIN_A, T_PLAIN_B
     m = _matcher()
     bound = m.handleBound()
     text = b"eur usd eur chf usd eur ab cd ab cd CHF"
@@ -230,7 +205,6 @@ def _defined_twice():
 
 
 def test_formatted_value_of_one_document_equals_the_text_of_another_under_the_same_handle():
-    from tests.test_result_values_gpu import Lexems, RunAny, _values
     m = _defined_twice()
     text = b"eur CHF"
     L = Lexems()
@@ -371,7 +345,6 @@ def test_exact_engine_against_result_set_mode_after_a_canonical_finish():
 # ---- 9. end to end
 def test_segmented_documents_with_dictionary():
     from struspattern_amd import rulelang, segments
-    from tests.test_result_values_abi import MONEY
     docs = [b"He paid 3'645 Eur\n\nand 3'645 Eur again or 12 sFr. he paid", b"nothing", b"12 sFr. in the year 1984 something happened"]
     for extra, doc_freq in (([], 1), ([b"later 3'645 Eur were paid"], 2)):
         lx, m = spa.PatternLexerInstance(), spa.PatternMatcherInstance()

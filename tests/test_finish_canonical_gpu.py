@@ -13,8 +13,7 @@ import struspattern_amd as spa
 from struspattern_amd import capi, synth
 
 from .canonical_order import canonical_key, in_canonical_order, sorted_batch
-from .test_formats import _apply, _random_program
-from .test_result_set_model import _docs
+from .finished_support import _apply, _docs, _from_device, _random_program
 
 pytestmark = pytest.mark.gpu
 
@@ -55,15 +54,6 @@ def _sized(ctx, run, ndocs, what, failing=()):
             ctx.reserveOutput(int(c["results"] * 1.2) + 1024, int(c["items"] * 1.2) + 1024)
         ctx.growArena()
     raise AssertionError("%s: documents still failing after resizing" % what)
-
-
-def _from_device(ptr, count, dtype):
-    out = np.zeros(count, dtype)
-    if count:
-        fn = capi.lib().hipMemcpy
-        fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        assert fn(out.ctypes.data, ptr, out.nbytes, 2) == 0        # hipMemcpyDeviceToHost
-    return out
 
 
 def _assert_layout(fin, got):

@@ -2,7 +2,6 @@
 through a device entry point, finishes it on the GPU and compares the plain copy of the finished buffers
 (finishedFetch) EXACTLY with what the host regroup of the same batch returns (batchFetch), and with the oracle where a
 run of it is cheap."""
-import ctypes
 import random
 
 import numpy as np
@@ -10,58 +9,12 @@ import pytest
 
 import oracle
 import struspattern_amd as spa
-from struspattern_amd import capi, synth
+from struspattern_amd import synth
 
 from .canonical_order import sorted_batch
-from .test_formats import _apply, _random_program
-from .test_result_set_model import _docs
+from .finished_support import _apply, _docs, _from_device, _random_program, _sized, _stream, _Uploaded
 
 pytestmark = pytest.mark.gpu
-
-
-def _stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
-class _Uploaded:
-    """lexems and document offsets in device memory (kept alive as long as the batch is looked at)"""
-
-    def __init__(self, lex, offs, origseg=None):
-        import torch
-        self.lex = torch.from_numpy(np.ascontiguousarray(lex, dtype=np.uint32).view(np.int32).reshape(-1)).cuda()
-        self.offs = torch.from_numpy(np.ascontiguousarray(offs, dtype=np.uint64).view(np.int64)).cuda()
-        self.seg = torch.from_numpy(np.ascontiguousarray(origseg, dtype=np.uint32).view(np.int32)).cuda() if origseg is not None else None
-        self.ndocs, self.nlex = len(offs) - 1, len(lex)
-
-    def run(self, ctx, stream=None):
-        return ctx.matchDocsDevice(self.lex.data_ptr(), self.offs.data_ptr(), self.ndocs, self.nlex,
-                                   _stream() if stream is None else stream, self.seg.data_ptr() if self.seg is not None else 0)
-
-
-def _sized(ctx, run, ndocs, what):
-    """the device protocol (bench.py size_until_ok): a batch whose output did not fit is rerun with the counted sizes"""
-    for _ in range(6):
-        run()
-        c = ctx.batchCounters()
-        if c["failed_docs"] == 0:
-            return c
-        assert set(int(x) for x in ctx.batchStatus(ndocs) if x) <= {2, 9}, what    # arena / output capacity only
-        if "lexems" in c:
-            ctx.reserveOutput(int(c["lexems"] * 1.2) + 1024)
-        else:
-            ctx.reserveOutput(int(c["results"] * 1.2) + 1024, int(c["items"] * 1.2) + 1024)
-        ctx.growArena()
-    raise AssertionError("%s: documents still failing after resizing" % what)
-
-
-def _from_device(ptr, count, dtype):
-    out = np.zeros(count, dtype)
-    if count:
-        fn = capi.lib().hipMemcpy
-        fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        assert fn(out.ctypes.data, ptr, out.nbytes, 2) == 0        # hipMemcpyDeviceToHost
-    return out
 
 
 def _raw_ranges(ctx, dev):

@@ -13,6 +13,7 @@ import pytest
 import oracle
 import struspattern_amd as spa
 from struspattern_amd import resultformat, rulelang, synth
+from tests.finished_support import _apply, _random_program       # noqa: F401 (tests/micro/sweep_parity.py reads _apply and _random_program from here)
 
 # the program of introduction_struspattern.htm:146-156 (+ the private-pattern example of :138-141); the
 # position ranges are added (the page's loader, part of strusAnalyzer, is not in the reference repository)
@@ -72,44 +73,6 @@ def test_documented_example_on_the_oracle():
     # without a format string the result keeps its items (latest first); `year`, the argument of Year's format, is not among them
     assert ("Plain", None, "in the year 1984 something", [("what", None, "something"), ("when", "1984", "in the year 1984")]) in got
     assert not [g for g in got if g[0] == "Year"]
-
-
-def _random_program(rng, nterms):
-    """token rules with private and public sub-patterns, some with format strings, referenced with variables"""
-    calls, names = [], []
-    for k in range(14):
-        name = "P%d" % k
-
-        def operand(depth=0):
-            if names and rng.random() < (0.45 if depth == 0 else 0.25):
-                calls.append(("pushPattern", rng.choice(names)))
-            elif depth < 2 and rng.random() < 0.2:
-                argc = rng.randint(2, 3)
-                for _ in range(argc):
-                    operand(depth + 1)
-                calls.append(("pushExpression", rng.choice(["sequence", "within", "any"]), argc, rng.randint(3, 8), 0))
-            else:
-                calls.append(("pushTerm", rng.randint(1, nterms)))
-            if rng.random() < 0.7:
-                calls.append(("attachVariable", "v%d" % rng.randint(0, 3)))
-        argc = rng.randint(1, 3)
-        for _ in range(argc):
-            operand()
-        calls.append(("pushExpression", rng.choice(["sequence", "sequence_imm", "within", "any", "sequence_struct"]) if argc > 1 else "any", argc, rng.randint(2, 10), 0))
-        fmt = rng.choice(["", "", "<{v0}>", "{v1|,}+{v2}", "const", "{v0}{v3}"])
-        calls.append(("definePattern", name, fmt, rng.random() < 0.7))
-        names.append(name)
-    return calls
-
-
-def _apply(m, calls):
-    for c in calls:
-        if c[0] == "pushExpression" and c[1] == "sequence_struct":
-            m.pushTerm(1)   # the delimiter operand comes first
-            getattr(m, c[0])(c[1], c[2] + 1, c[3], c[4])
-            continue
-        getattr(m, c[0])(*c[1:])
-    m.compile()
 
 
 @pytest.mark.gpu

@@ -9,32 +9,16 @@ import numpy as np
 import pytest
 
 import struspattern_amd as spa
-from tests.test_result_values_abi import matcher_of
+from tests.finished_support import (matcher_of, TWIN_BAD_OFFSETS as BAD_OFFSETS, _twin_batch as _batch, TWIN_BOUND as BOUND,
+                                    TWIN_RESULT_TEXT as RESULT_TEXT, TWIN_TERM_RECORDS as TERM_RECORDS, TWIN_TERMS as TERMS, TWIN_VALUES as VALUES)
 
 V, T = spa.SP_TERM_VALUES, spa.SP_TERM_TEXT
 TEXT, SEGMENTS = b"abcd", [0, 4]
-BOUND = 3
-BAD_OFFSETS = {"not starting at 0": [1, 2], "descending": [2, 1], "not covering the results": [0, 1]}
-
-
-def _batch():
-    """result 0: handle 2, "ab", format 1 over one item "ab" of variable 1; result 1: handle 1, "cd", no format, one item "d" """
-    results = [[2, 0, 1, 0, 0, 0, 2, 0, 1], [1, 1, 2, 0, 2, 0, 4, 1, 1]]
-    items = [[1, 0, 1, 0, 0, 0, 2], [1, 1, 2, 0, 3, 0, 4]]
-    return spa.MatchBatch(np.array(results, np.uint32), np.array(items, np.uint32), np.array([0, 2], np.uint64), np.zeros((1, 4), np.uint64),
-                          np.zeros(1, np.int32), np.array([1, 0], np.uint32), np.zeros((2, 2), np.uint32))
 
 
 @functools.lru_cache(maxsize=None)
 def _matcher():
     return matcher_of(["<{a}>"])
-
-
-# what the terms and the dictionary are built from, written out by hand: the value of result 0, the text of both, their terms
-VALUES = spa.MatchValues(b"<ab>", np.array([0, 4, 4], np.uint64), None, None, np.zeros(1, np.int32))
-RESULT_TEXT = spa.MatchText(b"abcd", np.array([0, 2, 4], np.uint64), None, None, np.zeros(1, np.int32))
-TERM_RECORDS = [[1, 1, 1, 2, 1, 2], [2, 1, 0, 1, 0, 4]]     # (1, "cd") of result 1, (2, "<ab>") of result 0
-TERMS = spa.MatchTerms(np.array(TERM_RECORDS, np.uint32), np.array([0, 2], np.uint64), np.array([1, 0], np.uint32), np.zeros(1, np.int32), V | T, BOUND)
 
 
 def _text(got):

@@ -4,37 +4,15 @@ captured items, statistics.  Every case runs in four configurations of the same 
 the default capacities, LDS capacities so small that rules and bucket chunks live in the spill area,
 a rule capacity so small that documents are handed over to the general kernel (list mode), and the
 general kernel alone -- all four must give the oracle's output."""
-import os
-
 import numpy as np
 import pytest
 
 import oracle
 import struspattern_amd as spa
 from struspattern_amd import synth
+from tests.finished_support import CONFIGS, _context
 
 pytestmark = pytest.mark.gpu
-
-CONFIGS = {
-    "default": {},
-    "spill": {"SPA_L2_FAST_SIZE": "t"},
-    "handover": {"SPA_L2_FAST_SIZE": "t", "SPA_L2_FAST_MAXRULES": "24", "SPA_L2_FAST_MAXSTAGED": "40"},
-    "general": {"SPA_L2_FAST": "0"},
-}
-
-
-def _context(m, config):
-    env = CONFIGS[config]
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        return m.createContext()
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
 
 
 def _check(build, lex4, offs, config, origseg=None, expect_fast=True, handover=None):

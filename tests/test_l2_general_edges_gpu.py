@@ -14,8 +14,7 @@ import struspattern_amd as spa
 from struspattern_amd import synth
 
 from . import l2_general_cases as cases
-from .test_finish_device_gpu import _Uploaded
-from .test_l2_fast_gpu import _context
+from .finished_support import _context, _Uploaded
 
 pytestmark = pytest.mark.gpu
 

@@ -8,6 +8,7 @@ import oracle
 import struspattern_amd as spa
 from struspattern_amd import synth
 from tests import l2_cases
+from tests.finished_support import _apply, _random_program
 
 pytestmark = pytest.mark.gpu
 
@@ -322,7 +323,6 @@ def test_batch_fetch_of_a_document_range_is_the_slice_of_the_whole_batch(exclusi
     """batchFetch(first_doc, ndocs) copies only the blocks of its documents (csrc/batch_fetch.hpp): it must return what
     batchFetch() returns for them, items and format handles re-based, a failed document inside the range included."""
     import random
-    from .test_formats import _apply, _random_program
     rng = random.Random(9300)
     calls = [c for _ in range(3) for c in _random_program(rng, 6)]         # 42 rules, later ones refer to earlier ones
     if not formats:

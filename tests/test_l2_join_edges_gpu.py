@@ -15,7 +15,7 @@ import struspattern_amd as spa
 from . import l2_join_cases as cases
 from .l2_join_cases import SP_DOC_ERR_OUTPUT
 from .result_set_model import results_multiset
-from .test_finish_device_gpu import _Uploaded, _sized, _stream
+from .finished_support import _sized, _stream, _Uploaded
 
 pytestmark = pytest.mark.gpu
 

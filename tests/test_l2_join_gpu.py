@@ -11,24 +11,9 @@ import pytest
 import oracle
 import struspattern_amd as spa
 from struspattern_amd import synth
+from tests.finished_support import _docs
 
 pytestmark = pytest.mark.gpu
-
-
-def _docs(rng, ndocs, n, nfeat, shared_positions):
-    lex = np.zeros((ndocs * n, 4), np.uint32)
-    offs = np.arange(ndocs + 1, dtype=np.uint64) * n
-    for d in range(ndocs):
-        ids = rng.integers(1, nfeat + 1, size=n)
-        ids[rng.random(n) < 0.06] = synth.DELIM
-        pos = np.arange(1, n + 1)
-        if shared_positions:
-            pos = np.cumsum(rng.random(n) < 0.7) + 1          # several lexems on one position
-        lex[d * n:(d + 1) * n, 0] = ids
-        lex[d * n:(d + 1) * n, 1] = pos
-        lex[d * n:(d + 1) * n, 2] = np.arange(n) * 3
-        lex[d * n:(d + 1) * n, 3] = 2
-    return lex, offs
 
 
 def _sorted_results(batch, d):

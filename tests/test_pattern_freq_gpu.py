@@ -20,36 +20,12 @@ import oracle
 import struspattern_amd as spa
 from struspattern_amd import capi, match, rulelang, synth
 from tests import pattern_freq_model as model
+from tests.finished_support import _bare, _from_device, _stream, _torch
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIELDS = ("records", "doc_offsets", "status", "handle_results", "handle_docs")
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _stream():
-    return _torch().cuda.current_stream().cuda_stream
-
-
-_BARE = {}
-
-
-def _bare(n):
-    """a matcher of n bare-term patterns: the handle of term h is h (compiled once per size)"""
-    if n not in _BARE:
-        m = spa.PatternMatcherInstance()
-        for h in range(1, n + 1):
-            m.pushTerm(h)
-            m.definePattern("p%d" % h, "", True)
-        m.compile()
-        assert m.handleBound() == n + 1 and m.patternId("p1") == 1 and m.patternId("p%d" % n) == n
-        _BARE[n] = m
-    return _BARE[n]
 
 
 def _lexems(docs):
@@ -59,15 +35,6 @@ def _lexems(docs):
         lex += [[t, p, 2 * p, 1] for t, p in doc]
         offs.append(len(lex))
     return np.array(lex, np.uint32).reshape(-1, 4), np.array(offs, np.uint64)
-
-
-def _from_device(ptr, count, dtype):
-    out = np.zeros(count, dtype)
-    if count:
-        fn = capi.lib().hipMemcpy
-        fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        assert fn(out.ctypes.data, ptr, out.nbytes, 2) == 0        # hipMemcpyDeviceToHost
-    return out
 
 
 class Run:

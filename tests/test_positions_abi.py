@@ -10,7 +10,7 @@ import pytest
 import struspattern_amd as spa
 from struspattern_amd import capi
 from tests import positions_model as model
-from tests.test_terms_abi import _batch, _family
+from tests.finished_support import _batch, _family
 
 T = spa.SP_TERM_TEXT
 BOUND = 4

@@ -11,9 +11,8 @@ import pytest
 import struspattern_amd as spa
 from struspattern_amd import capi
 from tests import positions_model as model
-from tests.test_dictionary_gpu import TRIP_RECORDS, _trip_docs
-from tests.test_pattern_freq_gpu import _bare
-from tests.test_span_text_gpu import Run, Source, _from_device, _stream, _torch
+from tests.finished_support import (_bare, _from_device, Lexems, _matcher, MONEY, Run, RunAny, Source, _stream, T_LIT, T_SPAN, _torch, _trip_docs,
+                                    TRIP_RECORDS, _values)
 
 pytestmark = pytest.mark.gpu
 
@@ -186,7 +185,6 @@ def _twice():
 
 
 def test_plain_finish_out_of_position_order():
-    from tests.test_result_values_gpu import _values
     m = _twice()
     # term, ordpos: the sequences start at 1 and at 10, fire at 6 and at 12, behind the bare terms at 1, 3, 4 and 11
     doc = [(2, 1), (1, 1), (1, 3), (1, 4), (3, 6), (2, 10), (1, 11), (3, 12)]
@@ -223,7 +221,6 @@ def test_plain_finish_out_of_position_order():
 
 # ---- 7. a failed document
 def test_a_document_whose_values_fail_has_no_occurrences():
-    from tests.test_result_values_gpu import Lexems, RunAny, _matcher, _values, T_LIT, T_SPAN
     m = _matcher()
     text = b"eur usd eur chf usd eur ab cd ab cd CHF"
 
@@ -360,7 +357,6 @@ def test_exact_engine_against_result_set_mode_after_a_canonical_finish():
 # ---- 10. end to end
 def test_segmented_documents_with_positions():
     from struspattern_amd import rulelang, segments
-    from tests.test_result_values_abi import MONEY
     docs = [b"He paid 3'645 Eur\n\nand 3'645 Eur again or 12 sFr. he paid", b"nothing", b"12 sFr. in the year 1984 something happened",
             b"later 3'645 Eur were paid"]
     lx, m = spa.PatternLexerInstance(), spa.PatternMatcherInstance()

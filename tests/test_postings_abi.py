@@ -10,10 +10,8 @@ import pytest
 import struspattern_amd as spa
 from struspattern_amd import capi
 from tests import postings_model as model
-from tests.test_dictionary_abi import EXPECTED as DICT_EXPECTED
-from tests.test_dictionary_abi import T, V, _inputs
-from tests.test_terms_abi import _batch, _family
-from tests import test_host_twins_abi as twins
+from tests.finished_support import (_batch, DICT_EXPECTED, _dict_inputs, _family, T, TWIN_BAD_OFFSETS, _twin_batch, TWIN_BOUND, TWIN_RESULT_TEXT,
+                                    TWIN_TERMS, TWIN_VALUES, V)
 
 # flags -> (postings per entry [doc, term, count, first_ordpos], entry_offsets, record_posting)
 EXPECTED = {
@@ -30,7 +28,7 @@ EXPECTED = {
 
 
 def _dictionary(flags, **kw):
-    mb, mv, mt, terms = _inputs(flags, **kw)
+    mb, mv, mt, terms = _dict_inputs(flags, **kw)
     return terms, spa.batchDictionary(mb, terms, values=mv, text=mt)
 
 
@@ -196,12 +194,12 @@ def test_error_returns_and_the_same_objects_serve_a_good_call():
     _check(terms, d)
 
 
-@pytest.mark.parametrize("offsets", sorted(twins.BAD_OFFSETS))
+@pytest.mark.parametrize("offsets", sorted(TWIN_BAD_OFFSETS))
 def test_malformed_term_offsets_are_refused_and_the_same_objects_serve_a_good_call(offsets):
-    mb = twins._batch()
-    d = spa.batchDictionary(mb, twins.TERMS, values=twins.VALUES, text=twins.RESULT_TEXT)
-    terms = spa.MatchTerms(twins.TERMS.records, np.array(twins.BAD_OFFSETS[offsets], np.uint64), twins.TERMS.result_term, twins.TERMS.status,
-                           twins.TERMS.flags, twins.BOUND)
+    mb = _twin_batch()
+    d = spa.batchDictionary(mb, TWIN_TERMS, values=TWIN_VALUES, text=TWIN_RESULT_TEXT)
+    terms = spa.MatchTerms(TWIN_TERMS.records, np.array(TWIN_BAD_OFFSETS[offsets], np.uint64), TWIN_TERMS.result_term, TWIN_TERMS.status,
+                           TWIN_TERMS.flags, TWIN_BOUND)
     with pytest.raises(spa.PatternError, match=r"\(-1\)"):
         spa.batchPostings(terms, d)
     terms.doc_offsets = np.array([0, 2], np.uint64)

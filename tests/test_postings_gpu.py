@@ -11,10 +11,8 @@ import pytest
 import struspattern_amd as spa
 from struspattern_amd import capi
 from tests import postings_model as model
-from tests.test_dictionary_gpu import EVERY, TRIP_RECORDS, _trip_docs
-from tests.test_pattern_freq_gpu import _bare
-from tests.test_span_text_gpu import Run, Source, _from_device, _stream, _torch
-from tests.test_terms_gpu import _build
+from tests.finished_support import (_bare, _build, EVERY, _from_device, Lexems, _matcher, MONEY, Run, RunAny, Source, _stream, T_LIT, T_PLAIN_A,
+                                    T_PLAIN_B, T_SPAN, _torch, _trip_docs, TRIP_RECORDS, _values)
 
 pytestmark = pytest.mark.gpu
 
@@ -164,7 +162,6 @@ def test_digit_bits_leave_identical_bytes():
 
 # ---- 6. failed documents
 def test_a_document_whose_values_fail_has_no_posting():
-    from tests.test_result_values_gpu import Lexems, RunAny, _matcher, _values, T_LIT, T_SPAN, T_PLAIN_A, T_PLAIN_B
     m = _matcher()
     text = b"eur usd eur chf usd eur ab cd ab cd CHF"
     L = Lexems()
@@ -307,7 +304,6 @@ def test_exact_engine_against_result_set_mode_after_a_canonical_finish():
 # ---- 9. end to end
 def test_segmented_documents_with_postings():
     from struspattern_amd import rulelang, segments
-    from tests.test_result_values_abi import MONEY
     docs = [b"He paid 3'645 Eur\n\nand 3'645 Eur again or 12 sFr. he paid", b"nothing", b"12 sFr. in the year 1984 something happened",
             b"later 3'645 Eur were paid"]
     lx, m = spa.PatternLexerInstance(), spa.PatternMatcherInstance()

@@ -12,7 +12,7 @@ import struspattern_amd as spa
 from struspattern_amd import synth
 
 from .result_set_model import results_multiset
-from .test_result_set_model import _docs
+from .finished_support import _docs, _sized
 
 pytestmark = pytest.mark.gpu
 
@@ -93,22 +93,6 @@ def test_result_sets_on_the_compiled_headline_rule_set():
     assert len(got.results) == len(ref.results) > 100000
     assert int(ref.stats[:, 1].sum()) > 0
     _assert_same_multisets(got, ref, len(offs) - 1)
-
-
-def _sized(ctx, run, ndocs, what):
-    """the device protocol (bench.py size_until_ok): a batch whose output did not fit is rerun with the counted sizes"""
-    for _ in range(6):
-        run()
-        c = ctx.batchCounters()
-        if c["failed_docs"] == 0:
-            return c
-        assert set(int(x) for x in ctx.batchStatus(ndocs) if x) <= {2, 9}, what    # arena / output capacity only
-        if "lexems" in c:
-            ctx.reserveOutput(int(c["lexems"] * 1.2) + 1024)
-        else:
-            ctx.reserveOutput(int(c["results"] * 1.2) + 1024, int(c["items"] * 1.2) + 1024)
-        ctx.growArena()
-    raise AssertionError("%s: documents still failing after resizing" % what)
 
 
 def test_result_sets_on_the_device_entry_points():

@@ -15,48 +15,11 @@ import oracle
 import struspattern_amd as spa
 from struspattern_amd import capi, resultformat, rulelang, synth
 from tests import result_values_model as model
-from tests.test_formats import _apply, _random_program
+from tests.finished_support import _apply, matcher_of, MONEY, _random_program, TEXT
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SP_ERR_INVALID = -1
 BOTH = model.SP_VALUE_RESULTS | model.SP_VALUE_ITEMS
-
-# the program and text of tests/test_formats.py (introduction_struspattern.htm:146-156)
-MONEY = r'''
-    WORD ^1         : /\b\w+\b/;
-    NUMBER ^2       : /\b[0-9]{4}\b/;
-    AMOUNT^5        : /\b[0-9]{1,3}'[0-9]{3,3}'[0-9]{3,3}\b/;
-    AMOUNT^4        : /\b[0-9]{1,3}'[0-9]{3,3}\b/;
-    AMOUNT^3        : /\b[0-9]{1,3}\b/;
-    CURRENCY_CHF ^3 : /\b[Ss]{0,1}[Ff][Rr][.]{0,1}\b/;
-    CURRENCY_EUR ^3 : /\b[Ee][Uu][Rr][.]{0,1}\b/;
-    Currency        = CURRENCY_CHF ["CHF"];
-    Currency        = CURRENCY_EUR ["EUR"];
-    MoneyAmount     = sequence_imm( value=AMOUNT, currency=Currency | 2) ["{currency} {value}"];
-    .Year           = sequence_imm( WORD "in", WORD "the", WORD "year", year=NUMBER | 4) ["{year}"];
-    Event           = sequence_imm( when=Year, WORD "something", WORD "happened" | 8) ["{when}"];
-    Plain           = sequence( when=Year, what=WORD | 8 );
-'''
-TEXT = b"He paid 3'645 Eur and 12 sFr. in the year 1984 something happened again"
-
-
-def matcher_of(formats, variables=("a", "b", "v")):
-    """a rule set whose variable handles are 1.. in the order of `variables` and whose format handles are 1.. in the order of
-    `formats`; its rules do not matter to the twin"""
-    m = spa.PatternMatcherInstance()
-    m.pushTerm(1)
-    for v in variables:
-        m.pushTerm(1)
-        m.attachVariable(v)
-    m.pushExpression("sequence", len(variables) + 1, 100, 0)
-    m.definePattern("p0", formats[0], True)
-    for k, f in enumerate(formats[1:]):
-        m.pushTerm(2 + k)
-        m.definePattern("p%d" % (k + 1), f, True)
-    m.compile()
-    assert [m.formatString(h + 1) for h in range(m.formatCount())] == list(formats)
-    assert [m.variableId(v) for v in variables] == list(range(1, len(variables) + 1))
-    return m
 
 
 def make_batch(docs):

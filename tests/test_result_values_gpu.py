@@ -11,119 +11,14 @@ import pytest
 import struspattern_amd as spa
 from struspattern_amd import capi, rulelang, segments
 from tests import result_values_model as model
-from tests.test_result_values_abi import MONEY, TEXT
-from tests.test_span_text_gpu import Run, Source, _from_device, _random_text, _stream, _torch
+from tests.finished_support import (_ctx, _from_device, Lexems, _matcher, MONEY, _pairs, _random_text, Run, RunAny, Source, _stream, T_EV, T_J1,
+                                    T_J2, T_J3, T_LIT, T_NONE, T_PLAIN_A, T_PLAIN_B, T_SPAN, T_X1, T_X2, T_YEAR, TEXT, _torch, _values)
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 BOTH = model.SP_VALUE_RESULTS | model.SP_VALUE_ITEMS
 RANGE = model.SP_DOC_ERR_RANGE
-
-# term -> what a lexem of it fires
-T_LIT, T_SPAN, T_J1, T_J2, T_J3, T_NONE, T_YEAR, T_EV, T_PLAIN_A, T_PLAIN_B, T_X1, T_X2 = range(1, 13)
-
-
-def _rules():
-    m = spa.PatternMatcherInstance()
-
-    def term(t, var=None):
-        m.pushTerm(t)
-        if var:
-            m.attachVariable(var)
-
-    def rule(name, fmt, terms, op="sequence", rng=1, visible=True):
-        for t, var in terms:
-            if isinstance(t, str):
-                m.pushPattern(t)
-                if var:
-                    m.attachVariable(var)
-            else:
-                term(t, var)
-        m.pushExpression(op if len(terms) > 1 else "any", len(terms), rng, 0)
-        m.definePattern(name, fmt, visible)
-
-    rule("Lit", "CHF", [(T_LIT, "a")])
-    rule("Span", "{a}", [(T_SPAN, "a")])
-    rule("J2", "{a|, }", [(T_J1, "a"), (T_J2, "a")])
-    rule("J3", "{a|, }", [(T_J1, "a"), (T_J2, "a"), (T_J3, "a")], rng=2)
-    rule("E2", "{a|}", [(T_J1, "a"), (T_J2, "a")])
-    rule("E3", "<{a|}>", [(T_J1, "a"), (T_J2, "a"), (T_J3, "a")], rng=2)
-    rule("None", "[{b}{nosuch}]", [(T_NONE, "a")])
-    rule("Year", "{year}", [(T_YEAR, "year")], visible=False)
-    rule("Event", "{when}", [("Year", "when"), (T_EV, None)])
-    rule("Plain", "", [(T_PLAIN_A, "a"), (T_PLAIN_B, "b")])
-    rule("Sub", "", [(T_X1, None), (T_X2, None)], visible=False)
-    rule("Cross", "({s})", [("Sub", "s")])
-    m.compile()
-    return m
-
-
-def _chain(depth):
-    """P0 = term 1 ["x"], Pk = any(v=P(k-1)) ["{v}"]: Pk's value is `k+1` formats deep; beside the chain Q = any(a=term 2)
-    ["<{a}>"] and R = sequence(b=term 2, b=term 3) without a format, whose items are formatted by nothing"""
-    m = spa.PatternMatcherInstance()
-    m.pushTerm(1); m.pushExpression("any", 1, 1, 0); m.definePattern("P0", "x", True)
-    for k in range(1, depth):
-        m.pushPattern("P%d" % (k - 1)); m.attachVariable("v"); m.pushExpression("any", 1, 1, 0); m.definePattern("P%d" % k, "{v}", True)
-    m.pushTerm(2); m.attachVariable("a"); m.pushExpression("any", 1, 1, 0); m.definePattern("Q", "<{a}>", True)
-    m.pushPattern("Q"); m.attachVariable("q"); m.pushTerm(3); m.pushExpression("sequence", 2, 1, 0); m.definePattern("R", "", True)
-    m.compile()
-    return m
-
-
-_CACHE = {}
-
-
-def _matcher(key="rules"):
-    if key not in _CACHE:
-        _CACHE[key] = _rules() if key == "rules" else _chain(key)
-    return _CACHE[key]
-
-
-class Lexems:
-    """documents of hand-made lexems: add(term, seg, pos, size) at the next ordinal position"""
-
-    def __init__(self):
-        self.lex, self.seg, self.offs, self.ordpos = [], [], [0], 0
-
-    def add(self, term, pos, size, seg=0):
-        self.ordpos += 1
-        self.lex.append([term, self.ordpos, pos, size])
-        self.seg.append(seg)
-        return self
-
-    def gap(self):
-        self.ordpos += 5
-        return self
-
-    def doc(self):
-        self.offs.append(len(self.lex))
-        self.ordpos = 0
-        return self
-
-    def arrays(self):
-        return np.array(self.lex, np.uint32).reshape(-1, 4), np.array(self.seg, np.uint32), np.array(self.offs, np.uint64)
-
-
-class RunAny(Run):
-    """Run that lets documents fail in the matcher with a status the test chose (lexems out of order)"""
-
-    def match(self):
-        for _ in range(6):
-            self.ctx.matchDocsDevice(self.d_lex.data_ptr(), self.d_offs.data_ptr(), self.ndocs, self.nlex, _stream(), self.d_seg.data_ptr())
-            c = self.ctx.batchCounters()
-            bad = set(int(x) for x in self.ctx.batchStatus(self.ndocs) if x)
-            if not bad & {2, 9}:
-                return
-            self.ctx.reserveOutput(int(c["results"] * 1.2) + 1024, int(c["items"] * 1.2) + 1024)
-            self.ctx.growArena()
-        raise AssertionError("documents still failing after resizing")
-
-
-def _values(ctx, src, flags=BOTH, stream=None):
-    return ctx.finishedValuesDevice(src.d_text.data_ptr(), len(src.text), src.d_so.data_ptr(), src.nseg,
-                                    src.d_dso.data_ptr() if src.d_dso is not None else 0, flags=flags, stream=_stream() if stream is None else stream)
 
 
 def _assert_values(m, ctx, src, out=None, flags=BOTH):
@@ -325,7 +220,6 @@ def test_families_alone_and_a_matcher_without_formats():
     for flags in (model.SP_VALUE_RESULTS, model.SP_VALUE_ITEMS):
         m, ctx, src, mb, got = _go(L, [text], flags=flags)
         assert not got.status.any() and (got.result_values if flags == 1 else got.item_values)
-    from tests.test_span_text_gpu import _ctx, _pairs
     lex, seg, offs, want = _pairs([[(0, 1, 0, 9)]], [[40]])
     ctx = _ctx()
     src = Source([text])

@@ -13,120 +13,11 @@ import pytest
 import struspattern_amd as spa
 from struspattern_amd import capi, rulelang, segments
 from tests import span_text_model as model
+from tests.finished_support import _ctx, _from_device, _pairs, _random_text, Run, Source, _stream, _torch
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SENTINEL = 64          # bytes of 0xFF behind every text on the device; the texts themselves hold none
-
-
-def _torch():
-    import torch
-    return torch
-
-
-def _stream():
-    return _torch().cuda.current_stream().cuda_stream
-
-
-def _pair_matcher():
-    m = spa.PatternMatcherInstance()
-    m.pushTerm(1)
-    m.attachVariable("a")
-    m.pushTerm(2)
-    m.attachVariable("b")
-    m.pushExpression("sequence", 2, 1, 0)
-    m.definePattern("pair", "", True)
-    m.compile()
-    return m
-
-
-_MATCHER = []
-
-
-def _ctx():
-    """a context of the pair rule (the rule set is compiled once)"""
-    if not _MATCHER:
-        _MATCHER.append(_pair_matcher())
-    return _MATCHER[0].createContext()
-
-
-def _from_device(ptr, count, dtype):
-    out = np.zeros(count, dtype)
-    if count:
-        fn = capi.lib().hipMemcpy
-        fn.restype, fn.argtypes = ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-        assert fn(out.ctypes.data, ptr, out.nbytes, 2) == 0        # hipMemcpyDeviceToHost
-    return out
-
-
-class Source:
-    """a text of segments on the device, with the sentinel behind it"""
-
-    def __init__(self, pieces, doc_seg_offsets=None):
-        torch = _torch()
-        self.text = b"".join(pieces)
-        assert b"\xff" not in self.text
-        self.so = np.concatenate([[0], np.cumsum([len(p) for p in pieces])]).astype(np.uint64)
-        self.dso = None if doc_seg_offsets is None else np.asarray(doc_seg_offsets, np.uint64)
-        self.nseg = len(pieces)
-        self.d_text = torch.frombuffer(bytearray(self.text + b"\xff" * SENTINEL), dtype=torch.uint8).cuda()
-        self.d_so = torch.from_numpy(self.so.view(np.int64)).cuda()
-        self.d_dso = None if self.dso is None else torch.from_numpy(self.dso.view(np.int64)).cuda()
-
-    def gather(self, ctx, stream=None, **kw):
-        return ctx.finishedTextDevice(self.d_text.data_ptr(), len(self.text), self.d_so.data_ptr(), self.nseg,
-                                      self.d_dso.data_ptr() if self.d_dso is not None else 0, stream=_stream() if stream is None else stream, **kw)
-
-
-def _random_text(rng, n):
-    return bytes(rng.integers(33, 127, n, dtype=np.uint8))
-
-
-def _pairs(docs, seglens):
-    """docs: per document a list of spans (s0, pos, s1, end); seglens: per document the lengths of its segments -> the lexems
-    (n, 4), their origseg, the document offsets, and per document the (result, item a, item b) byte ranges inside it as
-    (s0, pos, s1, end) tuples"""
-    lex, seg, offs, want = [], [], [0], []
-    for spans, lens in zip(docs, seglens):
-        w = []
-        for k, (s0, pos, s1, end) in enumerate(spans):
-            if s0 == s1 and pos <= end:
-                sa = (end - pos) // 2
-                sb = end - pos - sa
-            else:
-                sa, sb = max(0, min(lens[s0] - pos, 2)) if s0 < len(lens) else 0, min(end, 3)
-            lex += [[1, 10 * k + 1, pos, sa], [2, 10 * k + 2, end - sb, sb]]
-            seg += [s0, s1]
-            w.append(((s0, pos, s1, end), (s0, pos, s0, pos + sa), (s1, end - sb, s1, end)))
-        offs.append(len(lex))
-        want.append(w)
-    return np.array(lex, np.uint32).reshape(-1, 4), np.array(seg, np.uint32), np.array(offs, np.uint64), want
-
-
-class Run:
-    """the pair rule over hand-made lexems on the device, finished"""
-
-    def __init__(self, ctx, lex, seg, offs, canonical=False):
-        torch = _torch()
-        self.ctx = ctx
-        self.d_lex = torch.from_numpy(np.ascontiguousarray(lex).view(np.int32).reshape(-1)).cuda()
-        self.d_seg = torch.from_numpy(np.ascontiguousarray(seg).view(np.int32)).cuda()
-        self.d_offs = torch.from_numpy(offs.view(np.int64)).cuda()
-        self.ndocs, self.nlex = len(offs) - 1, len(lex)
-        self.match()
-        self.fin = ctx.batchFinishDevice(_stream(), canonical=canonical)
-
-    def match(self):
-        for _ in range(6):
-            self.ctx.matchDocsDevice(self.d_lex.data_ptr(), self.d_offs.data_ptr(), self.ndocs, self.nlex, _stream(), self.d_seg.data_ptr())
-            c = self.ctx.batchCounters()
-            if c["failed_docs"] == 0:
-                return
-            assert set(int(x) for x in self.ctx.batchStatus(self.ndocs) if x) <= {2, 9}
-            self.ctx.reserveOutput(int(c["results"] * 1.2) + 1024, int(c["items"] * 1.2) + 1024)
-            self.ctx.growArena()
-        raise AssertionError("documents still failing after resizing")
 
 
 def _assert_text(ctx, src, out=None, results=True, items=True):

@@ -9,26 +9,9 @@ import pytest
 import struspattern_amd as spa
 from struspattern_amd import capi
 from tests import terms_model as model
+from tests.finished_support import _batch, _family
 
 V, T = spa.SP_TERM_VALUES, spa.SP_TERM_TEXT
-
-
-def _batch(docs, formats=None, status=None):
-    """docs: per document a list of (handle, ordpos, ordend) -> MatchBatch"""
-    rows, offs = [], [0]
-    for doc in docs:
-        rows += [[h, p, e, 0, 0, 0, 0, 0, 0] for h, p, e in doc]
-        offs.append(len(rows))
-    n = len(docs)
-    return spa.MatchBatch(np.array(rows, np.uint32).reshape(-1, 9), np.zeros((0, 7), np.uint32), np.array(offs, np.uint64),
-                          np.zeros((n, 4), np.uint64), np.zeros(n, np.int32) if status is None else np.array(status, np.int32),
-                          None if formats is None else np.array(formats, np.uint32), None if formats is None else np.zeros((0, 2), np.uint32))
-
-
-def _family(cls, strings, ndocs, status=None, pad=b""):
-    """a MatchValues / MatchText whose result r has the bytes strings[r]"""
-    offs = np.cumsum([0] + [len(s) for s in strings]).astype(np.uint64)
-    return cls(b"".join(strings) + pad, offs, None, None, np.zeros(ndocs, np.int32) if status is None else np.array(status, np.int32))
 
 
 def _check(mb, bound, flags, mv=None, mt=None):

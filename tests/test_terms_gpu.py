@@ -15,27 +15,13 @@ import pytest
 import struspattern_amd as spa
 from struspattern_amd import capi
 from tests import terms_model as model
-from tests.test_pattern_freq_gpu import _bare
-from tests.test_span_text_gpu import Run, Source, _from_device, _stream, _torch
+from tests.finished_support import (_bare, _build, _from_device, Lexems, _matcher, MONEY, Run, RunAny, Source, _stream, T_LIT, T_PLAIN_A, T_PLAIN_B,
+                                    T_SPAN, _torch, _values)
 
 pytestmark = pytest.mark.gpu
 
 V, T = spa.SP_TERM_VALUES, spa.SP_TERM_TEXT
 NONE = 0xFFFFFFFF
-
-
-def _build(docs):
-    """docs: per document a list of (handle, value bytes): every occurrence gets its own copy of the value in the document's
-    text, one behind the other -> pieces, lexems (n, 4), origseg, document offsets"""
-    pieces, lex, offs = [], [], [0]
-    for doc in docs:
-        text = b""
-        for k, (h, value) in enumerate(doc):
-            lex.append([h, k + 1, len(text), len(value)])
-            text += value
-        pieces.append(text)
-        offs.append(len(lex))
-    return pieces, np.array(lex, np.uint32).reshape(-1, 4), np.zeros(len(lex), np.uint32), np.array(offs, np.uint64)
 
 
 def _assert_terms(ctx, bound, flags, out=None):
@@ -164,7 +150,6 @@ def test_hash_bits_leave_identical_bytes():
 
 # ---- 4. values as the source, and both sources
 def test_values_alone_and_both_flags_on_a_matcher_with_formats():
-    from tests.test_result_values_gpu import Lexems, RunAny, _matcher, _values, T_LIT, T_SPAN, T_PLAIN_A, T_PLAIN_B
     m = _matcher()
     bound = m.handleBound()
     text = b"eur usd eur chf usd eur ab cd ab cd"
@@ -278,7 +263,6 @@ def test_call_order_second_batch_and_another_stream():
 # ---- 7. segmented documents end to end
 def test_segmented_documents_with_terms():
     from struspattern_amd import rulelang, segments
-    from tests.test_result_values_abi import MONEY
     docs = [b"He paid 3'645 Eur\n\nand 3'645 Eur again or 12 sFr. he paid", b"nothing", b"12 sFr. in the year 1984 something happened"]
     lx, m = spa.PatternLexerInstance(), spa.PatternMatcherInstance()
     rulelang.load(MONEY, lx, m)
