@@ -691,8 +691,8 @@ int sp_match_batch_terms(const sp_match_batch_t* mb, const sp_match_values_t* va
  * the finished total and no source byte beyond the source's total is read, whatever the records hold; every index read from
  * working memory is compared against its bound before use.
  * LIMIT: N below 2^32 - 1 (indices are 32 bits), else SP_ERR_INVALID.
- * A dictionary sorted by (handle, value bytes) is not offered: it needs a batch-wide stable sort of variable-length keys;
- * first-occurrence order needs only a compaction, is how an indexer numbers new terms, and is fully deterministic. */
+ * First-occurrence order needs only a compaction, is how an indexer numbers new terms, and is fully deterministic.  The
+ * entries ranked by (handle, value bytes) are a product of their own, built from the dictionary ("dictionary order", below). */
 typedef struct sp_dict_term {
 	uint32_t handle;        /* pattern handle */
 	uint32_t value_bytes;   /* length of the value */
@@ -753,6 +753,92 @@ int sp_matcher_ctx_last_dictionary_ms(sp_matcher_ctx_t* c, double* ms);
 int sp_match_batch_dictionary(const sp_match_batch_t* mb, const sp_match_values_t* values, const sp_match_text_t* text,
                               const sp_match_terms_t* terms, sp_match_dictionary_t* out, char* err, size_t errsize);
 
+/* ---- dictionary order: the entries of the batch dictionary ranked by (pattern, value) -- the sorted run of a batch that an
+ * indexer merges with the runs of other batches, searches by bisection and stores as a front-coded term block, and a listing
+ * that does not depend on the order of the documents; built on the device (csrc/l2_dictorder.h) or, for a batch already
+ * fetched, on the host (csrc/match_dictorder.hpp).  The rule is the project's own, unpinned by a reference vector.
+ * INPUT: the dictionary built last on a context (sp_matcher_ctx_finished_dictionary_device), which implies its terms batch and
+ * the sources the terms' flags selected.  Write ndict for the number of entries.  The value of entry e is the value of the
+ * term record (first_doc, first_term), exactly as the dictionary rule defines it.
+ * ORDER: entry a lies before entry b iff handle(a) < handle(b), unsigned, or the handles are equal and value(a) < value(b)
+ * as byte strings: memcmp over the common length, every byte unsigned, and the shorter value first when one is a prefix of
+ * the other.  The empty value is the first of its handle.  Entries are distinct in (handle, bytes), so the order is strict.
+ * OUTPUTS:
+ *   order[ndict]                    (uint32) order[k] is the entry at sorted position k,
+ *   rank[ndict]                     (uint32) the inverse permutation: rank[order[k]] == k,
+ *   prefix_bytes[ndict]             (uint32) parallel to `order`: 0 when k is the first position of its handle, otherwise the
+ *                                   number of leading bytes that the values of order[k-1] and order[k] share: what a
+ *                                   front-coded term block stores,
+ *   handle_offsets[handle_bound+1]  (uint64) the exclusive prefix sums of the dictionary's handle_terms: the entries of handle
+ *                                   h are order[handle_offsets[h] .. handle_offsets[h+1]), handle_offsets[handle_bound] is ndict,
+ *   totals[0]                       ndict.
+ * INVARIANTS: `order` is a permutation of 0..ndict-1; handles do not descend along `order`; for consecutive entries of one
+ * handle prefix_bytes[k] <= min(value_bytes of both), and the byte behind the shared prefix ascends strictly or the left
+ * value ends there.
+ * DETERMINISM: every output word is a function of the dictionary and its sources alone, whatever algorithm produces it (the
+ * device sorts fixed tiles and merges them by rank; no atomic decides where an entry goes).  After a canonical finish the
+ * exact engines and result-set mode leave the same bytes.
+ * SAFETY, as for the dictionary: no byte outside the outputs is written; an entry index is compared against ndict, a record
+ * index against N, a result against the finished total and a source range against the source's total before use, and so is
+ * every index read from working memory; a slot of an output that no valid entry reaches gets 0xFFFFFFFF.  A value whose
+ * range is not inside its source compares as the empty value: it cannot come from this context's own dictionary, and the
+ * host twin refuses it.
+ * LIMIT: that of the dictionary, N below 2^32 - 1.
+ * Neither the dictionary records nor the postings are moved: `order` is the way to them. */
+typedef struct sp_match_dictionary_order_device {
+	size_t ndict;
+	uint32_t handle_bound;
+	void* d_order;               /* uint32_t[ndict] */
+	void* d_rank;                /* uint32_t[ndict] */
+	void* d_prefix_bytes;        /* uint32_t[ndict], parallel to d_order */
+	void* d_handle_offsets;      /* uint64_t[handle_bound+1] */
+	void* d_totals;              /* uint64_t[1]: ndict */
+} sp_match_dictionary_order_device_t;
+/* host copy of a dictionary order (sp_match_dictionary_order_free) */
+typedef struct sp_match_dictionary_order {
+	size_t ndict;
+	uint32_t handle_bound;
+	uint32_t* order;              /* ndict */
+	uint32_t* rank;               /* ndict */
+	uint32_t* prefix_bytes;       /* ndict */
+	uint64_t* handle_offsets;     /* handle_bound+1 */
+	uint64_t totals[1];           /* ndict */
+} sp_match_dictionary_order_t;
+/* Ranks the entries of the dictionary built last on this context.  The host knows ndict from the dictionary call, so this call
+ * enqueues every launch on `stream` and returns without waiting for anything (csrc/l2_dictorder.h): keys (a 64-bit key of the
+ * handle and the first four value bytes per entry), tiles (fixed tiles of sp_matcher_dictionary_order_tile() entries sorted in
+ * LDS), one merge launch per level with the run width doubling, ceil(log2(ceil(ndict / tile))) of them, place (order, rank,
+ * prefix_bytes) and the handle offsets.  A comparison leaves the key only on a tie and then compares the bytes of both values
+ * in their sources.  ndict <= 1 sorts nothing: no tile and no merge launch.  The buffers belong to the context, are allocated
+ * at the first call, only grow (working memory: 2 x 12 x ndict bytes for the two buffers of (key, entry), 12 x ndict for where
+ * the value of every entry lies and how long it is, and one cursor word), and are valid until the next order call; the next
+ * batch, finish, terms or dictionary call invalidates the state, not the buffers.  Postings and positions neither need nor
+ * invalidate the order, nor the reverse.  A `stream` other than the dictionary's is ordered behind the dictionary with an
+ * event (its placement is not waited for by its own call).  SP_ERR_INVALID when no dictionary was built since the last terms
+ * call of the last finish; SP_ERR_NOMEM when a buffer cannot be allocated (the context stays usable, `out` is empty). */
+int sp_matcher_ctx_finished_dictionary_order_device(sp_matcher_ctx_t* c, void* stream, sp_match_dictionary_order_device_t* out);
+/* plain copy of the buffers of the last sp_matcher_ctx_finished_dictionary_order_device to the host (waits for it) */
+int sp_matcher_ctx_finished_dictionary_order_fetch(sp_matcher_ctx_t* c, sp_match_dictionary_order_t* out);
+void sp_match_dictionary_order_free(sp_match_dictionary_order_t* o);
+/* duration of the launches of the last order call in milliseconds (HIP events on its stream round them; waits for them; the
+ * hipMemsetAsync calls that clear the cursor and the total and fill `rank` are enqueued before the first event, as the
+ * clearing of every other product) */
+int sp_matcher_ctx_last_dictionary_order_ms(sp_matcher_ctx_t* c, double* ms);
+/* diagnostics and tests: the entries of one tile of the device's sort; tile k is always the entries [k * tile, (k+1) * tile)
+ * in dictionary order, whichever workgroup takes it */
+uint32_t sp_matcher_dictionary_order_tile(void);
+/* The same rule over host arrays, needs no device, and the yardstick of the device passes: the order of a dictionary already
+ * fetched (or made by sp_match_batch_dictionary), with the batch, the terms and the host copies of the sources the terms were
+ * built from.  Fills `out` (sp_match_dictionary_order_free); SP_ERR_INVALID with the message in `err` for everything that
+ * sp_match_batch_dictionary refuses about `mb`, the sources and `terms`, for a dictionary whose ndocs, nterms, handle bound or
+ * flags are not those of `terms`, for an entry with a handle outside the bound, a first_doc / first_term outside its
+ * document's records, a first_result outside its document, a source range outside the source's bytes, a value_bytes that is
+ * not the length of its range, handle_terms that are not the number of entries of their handle, and two entries with the same
+ * (handle, bytes); SP_ERR_NOMEM when memory runs out. */
+int sp_match_batch_dictionary_order(const sp_match_batch_t* mb, const sp_match_values_t* values, const sp_match_text_t* text,
+                                    const sp_match_terms_t* terms, const sp_match_dictionary_t* dict,
+                                    sp_match_dictionary_order_t* out, char* err, size_t errsize);
+
 /* ---- batch postings: for every entry of the batch dictionary the documents that hold it -- the list (document, term
  * frequency, first position), ascending by document, that an indexer appends to its inverted index, and the way from every
  * term record to its posting; built on the device (csrc/l2_postings.h) or, for a batch already fetched, on the host
@@ -782,8 +868,8 @@ int sp_match_batch_dictionary(const sp_match_batch_t* mb, const sp_match_values_
  * twin refuses such a dictionary).
  * LIMIT: N below 2^32 - 1, which the dictionary enforces.
  * The positions of EVERY occurrence of a term in a document are not part of a posting: they are a product of their own,
- * built from the postings ("posting positions", below).  Postings or entries ordered by (handle, value bytes) are not
- * offered, as for the dictionary. */
+ * built from the postings ("posting positions", below).  The postings stay in dictionary order; the way to them by
+ * (handle, value bytes) is `order` of the "dictionary order" product, below. */
 typedef struct sp_posting {
 	uint32_t doc;           /* the document */
 	uint32_t term;          /* index of the term record inside doc's block: everything else about the occurrence hangs off it */

@@ -12,12 +12,13 @@ import numpy as np
 from . import capi
 from .capi import SpLexem, SpResult, SpResultItem
 from .products import (SP_TERM_TEXT, SP_TERM_VALUES, SP_TEXT_ITEMS, SP_TEXT_RESULTS, SP_VALUE_ITEMS, SP_VALUE_RESULTS,   # noqa: F401 (public names)
-                       MatchBatch, MatchDictionary, MatchPositions, MatchPostings, MatchTerms, MatchText, MatchValues, PatternError, PatternFreq,
-                       batchDictionary, batchPatternFreq, batchPositions, batchPostings, batchTerms, batchText, batchValues,
+                       MatchBatch, MatchDictionary, MatchDictionaryOrder, MatchPositions, MatchPostings, MatchTerms, MatchText, MatchValues, PatternError, PatternFreq,
+                       batchDictionary, batchDictionaryOrder, batchPatternFreq, batchPositions, batchPostings, batchTerms, batchText, batchValues,
                        _match_batch_of, _product, _rows)
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
-           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms", "MatchDictionary", "batchDictionary", "MatchPostings", "batchPostings", "MatchPositions", "batchPositions"]
+           "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms", "MatchDictionary", "batchDictionary", "MatchPostings", "batchPostings", "MatchPositions", "batchPositions",
+           "MatchDictionaryOrder", "batchDictionaryOrder"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
@@ -248,6 +249,20 @@ class PatternMatcherContext:
     def lastDictionaryMs(self):
         """duration of the launches of the last finishedDictionaryDevice in milliseconds"""
         return self._last_ms(self._L.sp_matcher_ctx_last_dictionary_ms, "dictionary call")
+
+    def finishedDictionaryOrderDevice(self, stream=0):
+        """rank the entries of the dictionary built by finishedDictionaryDevice by (handle, value bytes) on the device (everything
+        is asynchronous on `stream`: the call waits for nothing).  Returns the device pointers (capi.SpMatchDictionaryOrderDevice),
+        valid until the next call."""
+        return self._device(self._L.sp_matcher_ctx_finished_dictionary_order_device, capi.SpMatchDictionaryOrderDevice, "ordering the dictionary of the batch on the device", stream or None)
+
+    def finishedDictionaryOrderFetch(self):
+        """plain host copy of the order built by finishedDictionaryOrderDevice: a MatchDictionaryOrder"""
+        return self._fetch_product(MatchDictionaryOrder)
+
+    def lastDictionaryOrderMs(self):
+        """duration of the launches of the last finishedDictionaryOrderDevice in milliseconds"""
+        return self._last_ms(self._L.sp_matcher_ctx_last_dictionary_order_ms, "dictionary order call")
 
     def finishedPostingsDevice(self, stream=0):
         """build the postings of the dictionary built by finishedDictionaryDevice on the device (everything is asynchronous
@@ -756,7 +771,7 @@ class PatternLexer:
 # The products of a finished batch that matchSegmentedDocs builds, in the order it builds, fetches and returns them: the stem of
 # the context's methods (finished<stem>Device, finished<stem>Fetch) and the products it needs
 _SEGMENT_PRODUCTS = (("Text", ()), ("Values", ()), ("Terms", ("Text", "Values")), ("Dictionary", ("Terms",)), ("Postings", ("Dictionary",)),
-                     ("Positions", ("Postings",)))
+                     ("Positions", ("Postings",)), ("DictionaryOrder", ("Dictionary",)))
 
 
 def _rerun(ctx, ndocs, launch, grow, no_room=frozenset((2, 9)), attempts=12):
@@ -773,7 +788,8 @@ def _rerun(ctx, ndocs, launch, grow, no_room=frozenset((2, 9)), attempts=12):
     return c
 
 
-def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False, with_terms=False, with_dictionary=False, with_postings=False, with_positions=False):
+def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False, with_terms=False, with_dictionary=False, with_postings=False, with_positions=False,
+                       with_dictionary_order=False):
     """Segmented documents, host buffers in and out: `text` holds the segments back to back (seg_offsets: nseg+1 byte
     offsets), document d consists of the segments [doc_seg_offsets[d], doc_seg_offsets[d+1]).  Lexer -> stitch on the
     device -> rule matcher -> fetch; only the text goes up and the results come down.  Returns the MatchBatch, whose
@@ -785,8 +801,11 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
     (MatchBatch, MatchText, MatchValues, MatchTerms).  with_dictionary implies with_terms: the dictionary of the terms is built
     there too and returned as a fifth element, a MatchDictionary.  with_postings implies with_dictionary: the postings of
     the dictionary are built there too and returned as a sixth element, a MatchPostings.  with_positions implies
-    with_postings: the positions of every posting are built there too and returned as a seventh element, a MatchPositions."""
-    want = {"Text": with_text, "Values": with_values, "Terms": with_terms, "Dictionary": with_dictionary, "Postings": with_postings, "Positions": with_positions}
+    with_postings: the positions of every posting are built there too and returned as a seventh element, a MatchPositions.
+    with_dictionary_order implies with_dictionary: the entries of the dictionary are ranked by (handle, value) there too and the
+    MatchDictionaryOrder returned as one more element at the end, behind whatever else was asked for."""
+    want = {"Text": with_text, "Values": with_values, "Terms": with_terms, "Dictionary": with_dictionary, "Postings": with_postings, "Positions": with_positions,
+            "DictionaryOrder": with_dictionary_order}
     for name, needs in reversed(_SEGMENT_PRODUCTS):
         if want[name]:
             want.update(dict.fromkeys(needs, True))

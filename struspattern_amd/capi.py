@@ -160,6 +160,20 @@ class SpMatchDictionary(ctypes.Structure):
     ]
 
 
+class SpMatchDictionaryOrderDevice(ctypes.Structure):
+    _fields_ = [
+        ("ndict", ctypes.c_size_t), ("handle_bound", c_u32), ("d_order", c_vp), ("d_rank", c_vp), ("d_prefix_bytes", c_vp),
+        ("d_handle_offsets", c_vp), ("d_totals", c_vp),
+    ]
+
+
+class SpMatchDictionaryOrder(ctypes.Structure):
+    _fields_ = [
+        ("ndict", ctypes.c_size_t), ("handle_bound", c_u32), ("order", P(c_u32)), ("rank", P(c_u32)), ("prefix_bytes", P(c_u32)),
+        ("handle_offsets", P(c_u64)), ("totals", c_u64 * 1),
+    ]
+
+
 class SpPosting(ctypes.Structure):
     _fields_ = [(n, c_u32) for n in ("doc", "term", "count", "first_ordpos")]
 
@@ -281,6 +295,13 @@ SIGNATURES = {
     "sp_match_dictionary_free": (None, [P(SpMatchDictionary)]),
     "sp_matcher_ctx_last_dictionary_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
     "sp_match_batch_dictionary": (ctypes.c_int, [P(SpMatchBatch), P(SpMatchValues), P(SpMatchText), P(SpMatchTerms), P(SpMatchDictionary), ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_matcher_ctx_finished_dictionary_order_device": (ctypes.c_int, [c_vp, c_vp, P(SpMatchDictionaryOrderDevice)]),
+    "sp_matcher_ctx_finished_dictionary_order_fetch": (ctypes.c_int, [c_vp, P(SpMatchDictionaryOrder)]),
+    "sp_match_dictionary_order_free": (None, [P(SpMatchDictionaryOrder)]),
+    "sp_matcher_ctx_last_dictionary_order_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_matcher_dictionary_order_tile": (c_u32, []),
+    "sp_match_batch_dictionary_order": (ctypes.c_int, [P(SpMatchBatch), P(SpMatchValues), P(SpMatchText), P(SpMatchTerms), P(SpMatchDictionary),
+                                                        P(SpMatchDictionaryOrder), ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_ctx_finished_postings_device": (ctypes.c_int, [c_vp, c_vp, P(SpMatchPostingsDevice)]),
     "sp_matcher_ctx_finished_postings_fetch": (ctypes.c_int, [c_vp, P(SpMatchPostings)]),
     "sp_match_postings_free": (None, [P(SpMatchPostings)]),

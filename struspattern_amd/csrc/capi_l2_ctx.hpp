@@ -156,6 +156,14 @@ struct sp_matcher_ctx
 		std::vector<int> launchKind;
 		size_t launches = 0;
 	};
+	// the order of the last dictionary (l2_dictorder.h); nothing is allocated before the first sp_matcher_ctx_finished_dictionary_order_device
+	struct DictOrder
+	{
+		PassRun<2> run;
+		DeviceBuffer dOrder, dRank, dPrefixBytes, dHandleOffsets, dTotals, dKeys[ 2], dIndex[ 2], dValueAt, dValueLen, dCursor;
+		uint32_t handleBound = 0;
+		uint64_t ndict = 0;
+	};
 	// the finish of the last batch and everything made of it (capi_l2_finished.cpp).  A product is a member here and is listed in drop().
 	struct Products
 	{
@@ -167,12 +175,14 @@ struct sp_matcher_ctx
 		Dict dct;
 		Postings pst;
 		Positions pos;
+		DictOrder ord;
 		// a new batch, a new finish: what stands here is of the one before
 		void drop() { fin.run.done = false; txt.run.done = false; val.run.done = false; frq.run.done = false; trm.run.done = false; dropDictionary(); }
 		// a new terms call: a dictionary is that of the terms it was built from, and postings are those of their dictionary
 		void dropDictionary() { dct.run.done = false; dropPostings(); }
-		// a new dictionary call: postings are those of the dictionary they were built from, positions those of their postings
-		void dropPostings() { pst.run.done = false; pos.run.done = false; }
+		// a new dictionary call: postings and an order are those of the dictionary they were built from, positions those of their
+		// postings (postings and order do not touch each other)
+		void dropPostings() { pst.run.done = false; pos.run.done = false; ord.run.done = false; }
 	} prod;
 	// single-document mode
 	struct SingleDoc

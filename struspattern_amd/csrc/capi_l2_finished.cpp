@@ -1,5 +1,5 @@
 // C-ABI of level 2, second half: the last device batch finished on the device and what is made of the finished batch there --
-// matched text, result values, pattern frequencies, index terms, the batch dictionary, the batch postings, the posting positions -- with their fetch and timing calls.  Every product is one
+// matched text, result values, pattern frequencies, index terms, the batch dictionary, its order, the batch postings, the posting positions -- with their fetch and timing calls.  Every product is one
 // ProductCall (capi_l2_ctx.hpp) behind the finish; sp_matcher_ctx::Products::drop() is what a new batch or finish does to them.
 #include "capi_l2_ctx.hpp"
 #include "l2_finish.h"
@@ -8,10 +8,12 @@
 #include "l2_values.h"
 #include "l2_terms.h"
 #include "l2_dict.h"
+#include "l2_dictorder.h"
 #include "l2_postings.h"
 #include "l2_positions.h"
 #include "match_terms.hpp"
 #include "match_dict.hpp"
+#include "match_dictorder.hpp"
 #include "match_postings.hpp"
 #include "match_positions.hpp"
 #include "span_text.hpp"
@@ -143,7 +145,14 @@ struct TermSources
 	void describe( PARAMS& P) const
 	{
 		const unsigned bits = termHashBits().load( std::memory_order_relaxed);
-		P.flags = flags; P.hashMask = bits >= 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
+		P.hashMask = bits >= 32 ? 0xFFFFFFFFu : ((1u << bits) - 1u);
+		describeSources( P);
+	}
+	// ... and what DictOrderParams names as they do: the flags and the sources
+	template <class PARAMS>
+	void describeSources( PARAMS& P) const
+	{
+		P.flags = flags;
 		for (int s=0; s<2; ++s) if (selected( s))
 		{
 			const ByteFamilies& b = *family[ s];
@@ -628,6 +637,91 @@ int sp_matcher_ctx_finished_dictionary_fetch( sp_matcher_ctx_t* c, sp_match_dict
 // duration of the five launches of the last dictionary call in milliseconds (HIP events on its stream; the memsets that clear the
 // table and handle_terms are enqueued before the first event)
 int sp_matcher_ctx_last_dictionary_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.dct.run.ms( 0, 1, ms); }
+
+// ---- the order of the dictionary of the finished batch, sorted on the device (l2_dictorder.h)
+int sp_matcher_ctx_finished_dictionary_order_device( sp_matcher_ctx_t* c, void* stream, sp_match_dictionary_order_device_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		requireFinished( c);
+		const sp_matcher_ctx::Finished& fin = c->prod.fin;
+		const sp_matcher_ctx::Terms& t = c->prod.trm;
+		const sp_matcher_ctx::Dict& d = c->prod.dct;
+		if (!t.run.done || !d.run.done) throw std::runtime_error( "no dictionary of the last terms of the last finished batch (sp_matcher_ctx_finished_dictionary_device)");
+		const TermSources sources( c, d.flags);
+		sp_matcher_ctx::DictOrder& q = c->prod.ord;
+		// (the dictionary call waited for ndict and knows N: nothing is waited for here)
+		ProductCall call( c, q.run, stream, ProductCall::Sized());
+		const size_t ndocs = call.ndocs;
+		const uint64_t nterms = d.nterms, ndict = d.total, nresults = t.nresults;
+		if (d.ndocs != ndocs || t.ndocs != ndocs || t.total != nterms) throw std::runtime_error( "the dictionary is not that of the terms of the finished batch");
+		if (nterms >= 0xFFFFFFFFull || ndict > nterms) throw std::runtime_error( "a dictionary of more entries than term records, or of 2^32 - 1 records or more");
+		sources.requireResults( nresults);
+		const uint32_t bound = d.handleBound;
+		reserveOrNoMem( q.dOrder, (ndict+1)*sizeof(uint32_t));
+		reserveOrNoMem( q.dRank, (ndict+1)*sizeof(uint32_t));
+		reserveOrNoMem( q.dPrefixBytes, (ndict+1)*sizeof(uint32_t));
+		reserveOrNoMem( q.dHandleOffsets, ((size_t)bound+1)*sizeof(uint64_t));
+		for (int i=0; i<2; ++i)
+		{
+			reserveOrNoMem( q.dKeys[ i], (ndict+1)*sizeof(uint64_t));
+			reserveOrNoMem( q.dIndex[ i], (ndict+1)*sizeof(uint32_t));
+		}
+		reserveOrNoMem( q.dValueAt, (ndict+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dValueLen, (ndict+1)*sizeof(uint32_t));
+		// behind the dictionary, whose placement nobody has waited for yet; that runs behind the terms, their sources and the finish
+		call.beginBehind( d.run.stream, d.run.ev[ 1], q.dTotals, 1, q.dCursor, DICTORDER_CURSORS);
+		sources.waitFor( call.stream);
+		HIP_CHECK( hipMemsetAsync( q.dRank.ptr, 0xFF, (ndict+1)*sizeof(uint32_t), call.stream));
+		DictOrderParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.dictRecords = (const uint32_t*)d.dRecords.ptr; P.handleTerms = (const uint32_t*)d.dHandleTerms.ptr;
+		P.terms = (const uint32_t*)t.dRecords.ptr; P.docTermOffsets = (const uint64_t*)t.dDocOffsets.ptr;
+		P.docOffsets = (const uint64_t*)fin.dDocResultOffsets.ptr;
+		P.resultFormat = c->io.withFormats ? (const uint32_t*)fin.dResultFormat.ptr : 0;
+		P.nterms = nterms; P.nresults = nresults; P.ndict = (uint32_t)ndict; P.ndocs = (uint32_t)ndocs; P.handleBound = bound;
+		sources.describeSources( P);
+		P.tiles = l2DictOrderTiles( ndict); P.levels = l2DictOrderLevels( ndict);
+		for (int i=0; i<2; ++i) { P.keys[ i] = (uint64_t*)q.dKeys[ i].ptr; P.index[ i] = (uint32_t*)q.dIndex[ i].ptr; }
+		P.valueAt = (uint64_t*)q.dValueAt.ptr; P.valueLen = (uint32_t*)q.dValueLen.ptr; P.cursor = (uint32_t*)q.dCursor.ptr;
+		P.order = (uint32_t*)q.dOrder.ptr; P.rank = (uint32_t*)q.dRank.ptr; P.prefixBytes = (uint32_t*)q.dPrefixBytes.ptr;
+		P.handleOffsets = (uint64_t*)q.dHandleOffsets.ptr; P.total = (uint64_t*)q.dTotals.ptr;
+		HIP_CHECK( hipEventRecord( q.run.ev[ 0], call.stream));
+		HIP_CHECK( launchL2DictOrder( P, c->numCUs, call.stream));
+		HIP_CHECK( hipEventRecord( q.run.ev[ 1], call.stream));
+		q.run.completed( call.stream);
+		q.ndict = ndict; q.handleBound = bound;
+		if (out)
+		{
+			out->ndict = (size_t)ndict; out->handle_bound = bound;
+			out->d_order = q.dOrder.ptr; out->d_rank = q.dRank.ptr; out->d_prefix_bytes = q.dPrefixBytes.ptr;
+			out->d_handle_offsets = q.dHandleOffsets.ptr; out->d_totals = q.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the order's buffers
+int sp_matcher_ctx_finished_dictionary_order_fetch( sp_matcher_ctx_t* c, sp_match_dictionary_order_t* out)
+{
+	const sp_matcher_ctx::DictOrder& q = c->prod.ord;
+	return fetchProduct( c, q.run, "no order of the last dictionary of this context (sp_matcher_ctx_finished_dictionary_order_device)", out, sp_match_dictionary_order_free, [&]{
+		allocMatchDictionaryOrder( out, q.ndict, q.handleBound);
+		if (q.ndict)
+		{
+			copySync( c->own, out->order, q.dOrder.ptr, q.ndict*sizeof(uint32_t), hipMemcpyDeviceToHost);
+			copySync( c->own, out->rank, q.dRank.ptr, q.ndict*sizeof(uint32_t), hipMemcpyDeviceToHost);
+			copySync( c->own, out->prefix_bytes, q.dPrefixBytes.ptr, q.ndict*sizeof(uint32_t), hipMemcpyDeviceToHost);
+		}
+		copySync( c->own, out->handle_offsets, q.dHandleOffsets.ptr, ((size_t)q.handleBound+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->totals, q.dTotals.ptr, sizeof(uint64_t), hipMemcpyDeviceToHost);
+	});
+}
+
+// duration of the launches of the last order call in milliseconds (HIP events on its stream; the memsets that clear the cursor
+// and the total and fill the rank are enqueued before the first event)
+int sp_matcher_ctx_last_dictionary_order_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.ord.run.ms( 0, 1, ms); }
+
+uint32_t sp_matcher_dictionary_order_tile(void) { return DICTORDER_TILE; }
 
 // ---- the postings of the dictionary of the finished batch, partitioned on the device (l2_postings.h)
 void sp_test_postings_digit_bits( unsigned bits)

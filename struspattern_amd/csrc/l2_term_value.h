@@ -1,5 +1,6 @@
-// What the term passes (l2_terms_kernel.hip) and the dictionary passes (l2_dict_kernel.hip) share on the device: the value of
-// a result in the selected source, the hash of a term, the byte compare, and the read of a word that other lanes write.
+// What the term passes (l2_terms_kernel.hip), the dictionary passes (l2_dict_kernel.hip) and the order passes
+// (l2_dictorder_kernel.hip) share on the device: the value of a result in the selected source, the hash of a term, the byte
+// compares (the same bytes? how many leading bytes?), and the read of a word that other lanes write.
 // The collision rule of both: a hash chooses where the probing starts and decides nothing else; two values are one term
 // only after sameBytes.  Device code only: included by .hip files behind doc_passes.h and l2_terms.h.
 #ifndef SPA_L2_TERM_VALUE_H
@@ -94,6 +95,37 @@ __device__ __forceinline__ bool sameBytes( const uint8_t* p, const uint8_t* q, u
 	}
 	for (; i<len; ++i) if (p[ i] != q[ i]) return false;
 	return true;
+}
+
+// the bytes before the first byte of a word that differs from the same word of the other value (the words are little-endian)
+__device__ __forceinline__ u32 equalBytesOfWord( u32 a, u32 b) { return (u32)__builtin_ctz( a ^ b) >> 3; }
+
+// the leading bytes that p and q share among their first `len`: `len` when they are the same there.  The alignment cases are
+// those of sameBytes.
+__device__ __forceinline__ u32 commonBytes( const uint8_t* p, const uint8_t* q, u32 len)
+{
+	u32 i = 0;
+	if ((((size_t)p | (size_t)q) & 15u) == 0)
+	{
+		for (; i+16<=len; i+=16)
+		{
+			const u32x4 a = *(const u32x4*)(p + i), b = *(const u32x4*)(q + i);
+			if (a.x != b.x) return i + equalBytesOfWord( a.x, b.x);
+			if (a.y != b.y) return i + 4 + equalBytesOfWord( a.y, b.y);
+			if (a.z != b.z) return i + 8 + equalBytesOfWord( a.z, b.z);
+			if (a.w != b.w) return i + 12 + equalBytesOfWord( a.w, b.w);
+		}
+	}
+	if ((((size_t)p | (size_t)q) & 3u) == 0)
+	{
+		for (; i+4<=len; i+=4)
+		{
+			const u32 a = *(const u32*)(p + i), b = *(const u32*)(q + i);
+			if (a != b) return i + equalBytesOfWord( a, b);
+		}
+	}
+	for (; i<len; ++i) if (p[ i] != q[ i]) return i;
+	return len;
 }
 
 } // namespace

@@ -2,7 +2,7 @@
 through the MI355X lexer + rule automaton, print tokens (-K) and results in the reference tool's
 listing format (doc/webpage/introduction_struspattern.htm:178-260).
 
-    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] [--postings] [--positions] file [file ...]
+    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] [--postings] [--positions] [--sorted] file [file ...]
 
 Every file is one document (plain UTF-8 text; the reference tool segments XML with strusAnalyzer's
 segmenters, which are outside this engine -- pass -o to add the offset of the text inside its original
@@ -25,6 +25,9 @@ dictionary lines are followed by one line per entry, in the same order, with the
 occurs in it and the first ordinal position it starts at, built on the GPU from the dictionary (finishedPostingsDevice).
 --positions implies --postings; every FILEINDEX:COUNT@FIRSTPOS is followed by the distinct ordinal positions the term starts at
 in that file, ascending: `FILEINDEX:COUNT@FIRSTPOS[POS,POS,...]`, built on the GPU from the postings (finishedPositionsDevice).
+--sorted implies --dictionary; the `dict` lines, and the `post` lines with them, come by pattern handle and then by value (bytes)
+instead of first occurrence, ranked on the GPU from the dictionary (finishedDictionaryOrderDevice): they are then the same in
+whatever order the files are named, up to the file indices inside the `post` lines.
 All files go to the GPU as one batch.  There is no CPU fallback.
 """
 import argparse
@@ -48,11 +51,12 @@ def main(argv=None):
     ap.add_argument("--dictionary", action="store_true", help="after the last listing, one line per distinct (pattern, value) of all files")
     ap.add_argument("--postings", action="store_true", help="implies --dictionary; after its lines, per distinct (pattern, value) the files that hold it")
     ap.add_argument("--positions", action="store_true", help="implies --postings; after every file of a posting line, the distinct positions of the term in it")
+    ap.add_argument("--sorted", action="store_true", help="implies --dictionary; its lines and those of --postings by pattern, then by value")
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("files", nargs="+")
     args = ap.parse_args(argv)
     args.postings = args.postings or args.positions
-    args.dictionary = args.dictionary or args.postings
+    args.dictionary = args.dictionary or args.postings or args.sorted
 
     with open(args.program, encoding="utf-8") as f:
         program = f.read()
@@ -77,6 +81,7 @@ def main(argv=None):
     dictionary = device_dictionary(mctx) if args.dictionary else None
     postings = device_postings(mctx) if args.postings else None
     positions = device_positions(mctx) if args.positions else None
+    order = device_dictionary_order(mctx) if args.sorted else None
     freq = frequencies(mctx) if args.frequencies else None
     for di, fn in enumerate(args.files):
         print("%s:" % fn)
@@ -91,8 +96,8 @@ def main(argv=None):
             print(line)
         print_frequencies(freq, di, mt)
         print_terms(terms if args.terms else None, di, mt)
-    print_dictionary(dictionary, terms, mt)
-    print_postings(postings, dictionary, terms, mt, positions)
+    print_dictionary(dictionary, terms, mt, order)
+    print_postings(postings, dictionary, terms, mt, positions, order)
     print("OK done")
     return 0
 
@@ -103,17 +108,28 @@ def device_dictionary(mctx):
     return mctx.finishedDictionaryFetch()
 
 
-def dictionary_lines(dictionary, found, pattern_name):
-    """the lines of --dictionary; found: (batch, text, values, terms) of the terms call"""
+def device_dictionary_order(mctx):
+    """--sorted: the entries of the dictionary that device_dictionary built, ranked by (pattern handle, value) on the device"""
+    mctx.finishedDictionaryOrderDevice()
+    return mctx.finishedDictionaryOrderFetch()
+
+
+def in_order(lines, order):
+    """one line per dictionary entry, as they are or in the order of --sorted"""
+    return lines if order is None else [lines[int(e)] for e in order.order]
+
+
+def dictionary_lines(dictionary, found, pattern_name, order=None):
+    """the lines of --dictionary; found: (batch, text, values, terms) of the terms call; order: that of --sorted"""
     mb, mt, mv, terms = found
-    return ["dict %s '%s': docs %d count %d" % (pattern_name(int(h)), value.decode("utf-8", "replace"), docs, count)
-            for h, value, docs, count, _ in dictionary.entries(mb, terms, values=mv, text=mt)]
+    return in_order(["dict %s '%s': docs %d count %d" % (pattern_name(int(h)), value.decode("utf-8", "replace"), docs, count)
+                     for h, value, docs, count, _ in dictionary.entries(mb, terms, values=mv, text=mt)], order)
 
 
-def print_dictionary(dictionary, found, mt):
+def print_dictionary(dictionary, found, mt, order=None):
     if dictionary is None:
         return
-    for line in dictionary_lines(dictionary, found, mt.patternName):
+    for line in dictionary_lines(dictionary, found, mt.patternName, order):
         print(line)
 
 
@@ -129,23 +145,24 @@ def device_positions(mctx):
     return mctx.finishedPositionsFetch()
 
 
-def postings_lines(postings, dictionary, found, pattern_name, positions=None):
-    """the lines of --postings; found: (batch, text, values, terms) of the terms call; positions: those of --positions"""
+def postings_lines(postings, dictionary, found, pattern_name, positions=None, order=None):
+    """the lines of --postings; found: (batch, text, values, terms) of the terms call; positions: those of --positions; order:
+    that of --sorted"""
     mb, mt, mv, terms = found
 
     def where(p):
         return "" if positions is None else "[%s]" % ",".join("%d" % pos for pos in positions.positions(p).tolist())
 
-    return ["post %s '%s': %s" % (pattern_name(int(h)), value.decode("utf-8", "replace"),
-                                  " ".join("%d:%d@%d%s" % (doc, count, first, where(int(postings.entry_offsets[e]) + k))
-                                           for k, (doc, _, count, first) in enumerate(postings.entry(e).tolist())))
-            for e, (h, value, _, _, _) in enumerate(dictionary.entries(mb, terms, values=mv, text=mt))]
+    return in_order(["post %s '%s': %s" % (pattern_name(int(h)), value.decode("utf-8", "replace"),
+                                           " ".join("%d:%d@%d%s" % (doc, count, first, where(int(postings.entry_offsets[e]) + k))
+                                                    for k, (doc, _, count, first) in enumerate(postings.entry(e).tolist())))
+                     for e, (h, value, _, _, _) in enumerate(dictionary.entries(mb, terms, values=mv, text=mt))], order)
 
 
-def print_postings(postings, dictionary, found, mt, positions=None):
+def print_postings(postings, dictionary, found, mt, positions=None, order=None):
     if postings is None:
         return
-    for line in postings_lines(postings, dictionary, found, mt.patternName, positions):
+    for line in postings_lines(postings, dictionary, found, mt.patternName, positions, order):
         print(line)
 
 
@@ -221,7 +238,11 @@ def paragraphs(args, prg, lx, mt, docs):
     # (terms need text and values; every later product implies the ones before it)
     with_terms = args.terms or args.dictionary
     found = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_values=args.device_values, with_terms=with_terms,
-                                   with_dictionary=args.dictionary, with_postings=args.postings, with_positions=args.positions)
+                                   with_dictionary=args.dictionary, with_postings=args.postings, with_positions=args.positions,
+                                   with_dictionary_order=args.sorted)
+    order = None
+    if args.sorted:
+        found, order = found[:-1], found[-1]                                    # (the order comes last, whatever else was asked for)
     names = ("batch", "text", "values", "terms", "dictionary", "postings", "positions") if with_terms else ("batch", "values")
     got = dict(zip(names, found if isinstance(found, tuple) else (found,)))     # (the products asked for, a prefix of the names)
     mb, dictionary, postings, positions = got["batch"], got.get("dictionary"), got.get("postings"), got.get("positions")
@@ -252,8 +273,8 @@ def paragraphs(args, prg, lx, mt, docs):
             print(line)
         print_frequencies(freq, di, mt)
         print_terms(terms if args.terms else None, di, mt)
-    print_dictionary(dictionary, terms, mt)
-    print_postings(postings, dictionary, terms, mt, positions)
+    print_dictionary(dictionary, terms, mt, order)
+    print_postings(postings, dictionary, terms, mt, positions, order)
     print("OK done")
     return 0
 

@@ -367,6 +367,53 @@ def batchDictionary(mb, terms, values=None, text=None, handle_bound=0):
     return _twin(MatchDictionary, "sp_match_batch_dictionary", ctypes.byref(b), _ref(v), _ref(x), ctypes.byref(t))
 
 
+class MatchDictionaryOrder:
+    """The order of a dictionary (host copies): its entries ranked by (handle, value bytes), the inverse permutation, per sorted
+    position the leading bytes its value shares with the one before it inside a handle, and where the entries of every handle
+    start (include/strus_pattern_amd.h "dictionary order")."""
+    _C, _SCALARS, _TOTAL, _WHAT = capi.SpMatchDictionaryOrder, (), "ndict", "order of the dictionary"
+    _FREE, _FETCH = "sp_match_dictionary_order_free", "sp_matcher_ctx_finished_dictionary_order_fetch"
+    _ARRAYS = (
+        Arr("order", "order", "ndict", 0, 0, u32),                  # the entry at every sorted position
+        Arr("rank", "rank", "ndict", 0, 0, u32),                    # the sorted position of every entry
+        Arr("prefix_bytes", "prefix_bytes", "ndict", 0, 0, u32),    # parallel to order: bytes shared with the position before, 0 at the first of a handle
+        Arr("handle_offsets", "handle_offsets", "handle_bound", 1, 0, u64),   # the entries of handle h are order[handle_offsets[h]:handle_offsets[h+1]]
+    )
+
+    def __init__(self, order, rank, prefix_bytes, handle_offsets):
+        self.order, self.rank, self.prefix_bytes, self.handle_offsets = order, rank, prefix_bytes, handle_offsets
+
+    def handle(self, h):
+        """the entries of handle h, ascending by value"""
+        return self.order[int(self.handle_offsets[h]):int(self.handle_offsets[h + 1])]
+
+    def find(self, handle, value, mb, terms, dictionary, values=None, text=None):
+        """the entry (handle, value bytes) by bisection over the entries of the handle, or None; mb: the finished batch, terms,
+        dictionary: the MatchTerms and the MatchDictionary the order was built from, values / text: the sources of the terms"""
+        if not 0 <= handle < len(self.handle_offsets) - 1:
+            return None
+        value, lo, hi = bytes(value), int(self.handle_offsets[handle]), int(self.handle_offsets[handle + 1])
+        while lo < hi:
+            mid = (lo + hi) // 2
+            _, _, d, t = dictionary.records[int(self.order[mid])][:4].tolist()
+            other = bytes(_term_value(terms.flags, mb, values, text, int(mb.doc_offsets[d]) + int(terms.doc(d)[t][4])))
+            if other == value:
+                return int(self.order[mid])
+            lo, hi = (mid + 1, hi) if other < value else (lo, mid)
+        return None
+
+
+def batchDictionaryOrder(mb, terms, dictionary, values=None, text=None):
+    """The order of a dictionary already on the host (terms: the MatchTerms, dictionary: the MatchDictionary built from them,
+    mb, values, text: what the terms were built from: the fetches of a context, or the twins), by the rule of the device call,
+    without a device.  Returns a MatchDictionaryOrder."""
+    b, keep = _host_batch(mb, formats="results", status=True)       # (keep: until the call has returned)
+    v, x = _host_source(values, keep), _host_source(text, keep)
+    bound = terms.handle_bound or len(dictionary.handle_terms)      # (terms made by hand may carry none: that of the dictionary then)
+    t, d = _to_c(terms, keep, handle_bound=bound), _to_c(dictionary, keep, flags=terms.flags)
+    return _twin(MatchDictionaryOrder, "sp_match_batch_dictionary_order", ctypes.byref(b), _ref(v), _ref(x), ctypes.byref(t), ctypes.byref(d))
+
+
 class MatchPostings:
     """The postings of a dictionary (host copies): per term record one posting (doc, term, count, first_ordpos), the postings
     of dictionary entry e together and ascending by document, and per term record the index of its posting
