@@ -1,4 +1,4 @@
-// Launch parameters of the level-1 lexer kernels (shared by l1_kernel.hip, l1_image.cpp and capi_l1.cpp).  No HIP header: the
+// Launch parameters of the level-1 lexer kernels (shared by the l1_*_kernel.hip files, l1_image.cpp and capi_l1.cpp).  No HIP header: the
 // host-only sources that include it compile without the runtime.
 #ifndef SPA_L1_DEVICE_H
 #define SPA_L1_DEVICE_H

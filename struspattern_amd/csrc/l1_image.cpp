@@ -129,7 +129,7 @@ L1LaunchPlan planL1Launch( const LexTables& T, const L1Images& img, unsigned num
 	if (p.laneGrid == 0) p.laneGrid = 1;
 
 	// the post-processing kernel (and the approximate-matching kernel) has its own number of waves: one event array each
-	const unsigned postPerCU = sw.postWavesPerCU ? sw.postWavesPerCU : 4u*6u;	// (6 per SIMD: the register budget of the kernel, l1_kernel.hip)
+	const unsigned postPerCU = sw.postWavesPerCU ? sw.postWavesPerCU : 4u*6u;	// (6 per SIMD: the register budget of the kernel, l1_post_kernel.hip)
 	p.postSlots = numCUs*postPerCU;
 	p.postWaves = (unsigned)atMost<size_t>( ndocs, (size_t)p.postSlots);
 	p.postWaves = (p.postWaves + 3u) & ~3u;

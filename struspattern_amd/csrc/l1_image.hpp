@@ -48,7 +48,7 @@ L1Images buildL1Images( const LexTables& T, const L1Switches& sw);
 
 enum L1Route {L1_ROUTE_NONE /*nothing to scan*/, L1_ROUTE_APPROX, L1_ROUTE_LANES, L1_ROUTE_PASSES};
 
-// Everything a launch decides, decided once.  launchL1Lex (l1_kernel.hip) follows it; the kernel names reported are the plan's.
+// Everything a launch decides, decided once.  launchL1Lex (l1_launch.cpp) follows it; the kernel names reported are the plan's.
 struct L1LaunchPlan
 {
 	uint32_t chunkBytes = 0;	// documents longer than a chunk are scanned as several units

@@ -1,5 +1,5 @@
-// Level-1 device tables shared by the host regex compiler (l1_compile.cpp) and the HIP lexer kernel
-// (l1_kernel.hip).
+// Level-1 device tables shared by the host regex compiler (l1_compile.cpp) and the HIP lexer kernels
+// (l1_wave.h and the l1_*_kernel.hip files that include it).
 //
 // Model: every regex is compiled to a Glushkov position automaton (one state bit per byte-consuming
 // position).  A pattern occupies a contiguous bit range inside ONE 64-bit word; words are grouped

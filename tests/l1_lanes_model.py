@@ -1,5 +1,5 @@
 """Test utility: a pure-Python model of the lane-per-stream scan kernel of the lexer (scanUnitLanes,
-l1_kernel.hip) on top of tests/l1_table_sim.Tables: how a unit is cut into 64 pieces, the warm-up proof
+l1_scan_lanes_kernel.hip) on top of tests/l1_table_sim.Tables: how a unit is cut into 64 pieces, the warm-up proof
 of a piece's start state, which documents go to the sequential re-scan, how many report records a lane
 writes into its part of the unit's queue slice and how large that part is.  It restates the kernel's
 arithmetic, so the CPU tests can say what a GPU batch is going to exercise before it runs.  Test code

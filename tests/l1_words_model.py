@@ -1,5 +1,5 @@
 """Test utility: a pure-Python model of the words kernel of the lexer (wordsUnit, wordsFlush, confirmWalk and
-runStartBefore, l1_kernel.hip) on top of tests/l1_table_sim.Tables: where a unit begins after its back-off, which run
+runStartBefore, l1_words_kernel.hip) on top of tests/l1_table_sim.Tables: where a unit begins after its back-off, which run
 ends it owns, the candidates of an end (the whole-word literal and one key per shape variant), the records it queues
 (with the leftmost start and the dead mark of the confirming walk), how many ends wait from tile to tile, when a batch
 of them is flushed and whether a walk leaves the ring.  It restates the kernel's arithmetic, so the CPU tests can say

@@ -1,6 +1,6 @@
 #!/bin/bash
 # registers, spills, LDS and scratch of the kernels of one source file (device-only compile into a scratch directory)
-#   usage: tests/micro/kernel_resources.sh struspattern_amd/csrc/l1_kernel.hip [name filter] [extra flags]
+#   usage: tests/micro/kernel_resources.sh struspattern_amd/csrc/l1_post_kernel.hip [name filter] [extra flags]
 set -e
 SRC=$(realpath "$1"); FILTER=${2:-.}; shift; shift || true
 W=$(mktemp -d); trap 'rm -rf "$W"' EXIT

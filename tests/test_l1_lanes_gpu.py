@@ -1,5 +1,5 @@
 """GPU tests of the lane-per-stream scan kernel of the lexer (spa_l1_scan_lanes_kernel: scanUnitLanes /
-scanDocumentsLanes, l1_kernel.hip) at the edges of its pieces, of its warm-up proof and of its per-lane queue
+scanDocumentsLanes, l1_scan_lanes_kernel.hip) at the edges of its pieces, of its warm-up proof and of its per-lane queue
 regions.  Every case runs on the lane-per-stream kernel and, with SPA_L1_NO_LANES, on the wave-per-unit kernel, says
 which kernel ran, and compares status, lexem offsets and lexems with the CPU oracle; the units of the batch, the
 documents scanned again and the documents short of queue space are the ones tests/l1_lanes_model.py predicts

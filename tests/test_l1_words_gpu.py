@@ -1,5 +1,5 @@
 """GPU tests of the words kernel of the lexer (spa_l1_words_kernel_w16 / spa_l1_words_kernel: wordsUnit, wordsFlush,
-confirmWalk, runStartBefore, l1_kernel.hip) at the edges of its runs, keys, tiles, ring and chunks.  Every case runs on
+confirmWalk, runStartBefore, l1_words_kernel.hip) at the edges of its runs, keys, tiles, ring and chunks.  Every case runs on
 the 16-wave instance, on the 12-wave instance (SPA_L1_WORD_WAVES) and, as a control, without the kernel (the table
 compiled under SPA_L1_SHAPES=0, the context created under SPA_L1_NO_WORDS_KERNEL: scan kernels and the post kernel's own
 literal probe), says which kernel ran, and compares status, lexem offsets and lexems with the CPU oracle, no tolerance
