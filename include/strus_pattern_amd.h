@@ -839,6 +839,117 @@ int sp_match_batch_dictionary_order(const sp_match_batch_t* mb, const sp_match_v
                                     const sp_match_terms_t* terms, const sp_match_dictionary_t* dict,
                                     sp_match_dictionary_order_t* out, char* err, size_t errsize);
 
+/* ---- term blocks: the sorted dictionary of a batch written down as front-coded blocks -- the first product of a finished batch
+ * that OWNS ITS BYTES: the immutable run of one batch that an indexer stores, merges with the run of the next batch or searches
+ * later without the batch, its text or its values; built on the device (csrc/l2_termblocks.h) or, for a batch already fetched,
+ * on the host (csrc/match_termblocks.hpp).  The rule is the project's own, unpinned by a reference vector.  (It is the run of
+ * ONE batch: no dictionary that lives across batches is kept anywhere.)
+ * INPUT: the dictionary order built last on a context (sp_matcher_ctx_finished_dictionary_order_device), which implies its
+ * dictionary, its terms batch and the sources the terms' flags selected.  Write ndict for the number of entries.
+ * BLOCK SIZE: B = sp_matcher_term_block_entries(), 16 by default.
+ * BLOCKS: block j covers the sorted positions [j B, min((j+1) B, ndict)); nblocks = ceil(ndict / B).  Blocks are cut over the
+ * sorted positions of the whole batch, not per handle.
+ * THE CODE OF POSITION k: let e = order[k]; position k is the HEAD of its block iff k % B == 0.  The code is five unsigned
+ * LEB128 varints followed by the suffix bytes; a varint is seven bits per byte, low bits first, the high bit set on every byte
+ * but the last, in minimal length:
+ *   1  hdelta     0 at a head, otherwise handle(order[k]) - handle(order[k-1]), never negative along `order`,
+ *   2  shared     0 at a head, otherwise prefix_bytes[k] (already 0 at the first position of a handle),
+ *   3  suffix     value_bytes(e) - shared,
+ *   4  doc_freq(e),
+ *   5  count(e)   64 bits, up to ten bytes,
+ *   then the `suffix` bytes value(e)[shared:].
+ * OUTPUTS:
+ *   bytes[nbytes]              (uint8)  the codes of all positions in sorted order, without gaps,
+ *   block_offsets[nblocks+1]   (uint64) where block j starts in `bytes`; the last element is nbytes,
+ *   block_handles[nblocks]     (uint32) the handle of the head of block j,
+ *   totals[4]                  (uint64) {nblocks, nbytes, B, the sum of value_bytes over all entries}: the fourth is what the
+ *                              values cost uncoded.
+ * With block_handles[j] a block decodes from its own bytes alone; a head carries its value in full.
+ * INVARIANTS: decoding reproduces, for every sorted position, exactly (handle, value bytes, doc_freq, count) of order[k];
+ * block_offsets ascends; a block is never empty (a code is at least five bytes).
+ * DETERMINISM: every output byte is a function of the dictionary, its order and its sources alone (the one atomic of the
+ * device adds to a sum).  After a canonical finish the exact engines and result-set mode leave the same bytes.
+ * SAFETY, as for the order: no byte outside the outputs is written; every byte written for block j lies inside
+ * [block_offsets[j], block_offsets[j+1]), and that range inside nbytes; every source byte read lies inside its source; an entry
+ * index, a record index, a result and a source range are compared against their bounds before use, as the order call does.  A
+ * value whose range is not inside its source is coded as the empty value, which is how the order treats it: it cannot come
+ * from this context's own dictionary, and the host twin refuses it.
+ * LIMIT: that of the dictionary, N below 2^32 - 1. */
+/* one decoded position of a block (sp_match_term_blocks_decode_block) */
+typedef struct sp_term_block_entry {
+	uint32_t handle;        /* pattern handle */
+	uint32_t value_bytes;   /* length of the full value */
+	uint64_t value_offset;  /* where the full value starts in the `values` of the decode call */
+	uint32_t doc_freq;
+	uint32_t reserved;      /* 0 */
+	uint64_t count;         /* the collection frequency */
+} sp_term_block_entry_t;
+typedef struct sp_match_term_blocks_device {
+	size_t ndict;
+	size_t nblocks;
+	size_t nbytes;
+	uint32_t block_entries;      /* B */
+	void* d_bytes;               /* uint8_t[nbytes] */
+	void* d_block_offsets;       /* uint64_t[nblocks+1] */
+	void* d_block_handles;       /* uint32_t[nblocks] */
+	void* d_totals;              /* uint64_t[4]: nblocks, nbytes, B, the sum of value_bytes */
+} sp_match_term_blocks_device_t;
+/* host copy of the term blocks (sp_match_term_blocks_free) */
+typedef struct sp_match_term_blocks {
+	size_t ndict;
+	size_t nblocks;
+	size_t nbytes;
+	uint32_t block_entries;       /* B */
+	uint8_t* bytes;               /* nbytes */
+	uint64_t* block_offsets;      /* nblocks+1 */
+	uint32_t* block_handles;      /* nblocks */
+	uint64_t totals[4];           /* nblocks, nbytes, B, the sum of value_bytes */
+} sp_match_term_blocks_t;
+/* the positions of a block, B: 16 unless sp_test_term_block_entries chose another */
+uint32_t sp_matcher_term_block_entries(void);
+/* tests and diagnostics only, like sp_test_postings_digit_bits: B from 1, 2, 4, 8, 16, 32, 64 for the device calls and the
+ * twin that follow; 0 (and any other number) restores the default.  B = 1 means no front coding at all. */
+void sp_test_term_block_entries(unsigned n);
+/* Writes the term blocks of the order built last on this context.  Three launches on `stream` (sizes, offsets, emit:
+ * csrc/l2_termblocks.h); the call enqueues the first two, waits for them only to read nbytes, sizes `bytes`, enqueues the third
+ * and returns.  block_offsets and block_handles are sized by nblocks, which the host knows, before the wait.  ndict == 0 launches
+ * nothing: nblocks = nbytes = 0, block_offsets = [0].  Where a value lies and how long it is is read from the working memory of
+ * the order call, which is valid as long as the order's state is.  The buffers belong to the context, are allocated at the
+ * first call, only grow (working memory: 8 bytes a block), and are valid until the next term-blocks call; whatever invalidates
+ * the order -- the next batch, finish, terms or dictionary call -- and a new order call invalidate the state, not the buffers.
+ * Postings and positions neither need nor invalidate the blocks, nor the reverse.  A `stream` other than the order's is ordered
+ * behind the order with an event.  SP_ERR_INVALID when no order was built since the last dictionary call; SP_ERR_NOMEM when a
+ * buffer cannot be allocated (the context stays usable, `out` is empty). */
+int sp_matcher_ctx_finished_term_blocks_device(sp_matcher_ctx_t* c, void* stream, sp_match_term_blocks_device_t* out);
+/* plain copy of the buffers of the last sp_matcher_ctx_finished_term_blocks_device to the host (waits for it): this fetch
+ * replaces those of the batch and of its text or values for a caller who wants the sorted dictionary with its strings */
+int sp_matcher_ctx_finished_term_blocks_fetch(sp_matcher_ctx_t* c, sp_match_term_blocks_t* out);
+void sp_match_term_blocks_free(sp_match_term_blocks_t* tb);
+/* duration of the launches of the last term-blocks call in milliseconds (HIP events on its stream round them; waits for them;
+ * the host's wait for nbytes between offsets and emit lies inside; the hipMemsetAsync calls that clear the totals are enqueued
+ * before the first event, as the clearing of every other product) */
+int sp_matcher_ctx_last_term_blocks_ms(sp_matcher_ctx_t* c, double* ms);
+/* The same rule over host arrays, needs no device, and the yardstick of the device passes: the blocks of an order already
+ * fetched (or made by sp_match_batch_dictionary_order), with the batch, the terms, the dictionary and the host copies of the
+ * sources the terms were built from.  Fills `out` (sp_match_term_blocks_free); SP_ERR_INVALID with the message in `err` for
+ * everything that sp_match_batch_dictionary_order refuses, for an order whose ndict or handle bound is not the dictionary's, an
+ * `order` that is not a permutation, handles that descend along it, a prefix_bytes[k] above the length of either neighbour, and
+ * a prefix_bytes[k] that is not what the two values share (0 at the first position of a handle); SP_ERR_NOMEM when memory
+ * runs out. */
+int sp_match_batch_term_blocks(const sp_match_batch_t* mb, const sp_match_values_t* values, const sp_match_text_t* text,
+                               const sp_match_terms_t* terms, const sp_match_dictionary_t* dict, const sp_match_dictionary_order_t* order,
+                               sp_match_term_blocks_t* out, char* err, size_t errsize);
+/* The reader: decodes block j of `tb` alone, from bytes[block_offsets[j] .. block_offsets[j+1]) and block_handles[j], into
+ * `entries` (room for nentries_cap records; a block holds at most block_entries) and the full values, one behind the other, into
+ * `values` (room for values_cap bytes).  *nentries and *nvalues get what the block holds, also when the room does not suffice;
+ * with entries == NULL and values == NULL the call only counts.  Needs no device.  SP_ERR_INVALID with the message in `err` for
+ * j >= nblocks, block offsets that descend or leave `bytes`, room that does not suffice, and a malformed block: a varint that
+ * runs past the block, a varint longer than ten bytes, a `shared` above the previous value's length (above 0 at the head), a
+ * suffix that runs past the block, a handle or a value length that leaves 32 bits, an empty block and one of more than
+ * block_entries codes. */
+int sp_match_term_blocks_decode_block(const sp_match_term_blocks_t* tb, size_t j, sp_term_block_entry_t* entries, size_t nentries_cap,
+                                      uint8_t* values, size_t values_cap, size_t* nentries, size_t* nvalues, char* err, size_t errsize);
+
 /* ---- batch postings: for every entry of the batch dictionary the documents that hold it -- the list (document, term
  * frequency, first position), ascending by document, that an indexer appends to its inverted index, and the way from every
  * term record to its posting; built on the device (csrc/l2_postings.h) or, for a batch already fetched, on the host

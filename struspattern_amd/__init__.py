@@ -12,13 +12,13 @@ import numpy as np
 from . import capi
 from .capi import SpLexem, SpResult, SpResultItem
 from .products import (SP_TERM_TEXT, SP_TERM_VALUES, SP_TEXT_ITEMS, SP_TEXT_RESULTS, SP_VALUE_ITEMS, SP_VALUE_RESULTS,   # noqa: F401 (public names)
-                       MatchBatch, MatchDictionary, MatchDictionaryOrder, MatchPositions, MatchPostings, MatchTerms, MatchText, MatchValues, PatternError, PatternFreq,
-                       batchDictionary, batchDictionaryOrder, batchPatternFreq, batchPositions, batchPostings, batchTerms, batchText, batchValues,
+                       MatchBatch, MatchDictionary, MatchDictionaryOrder, MatchPositions, MatchPostings, MatchTermBlocks, MatchTerms, MatchText, MatchValues, PatternError, PatternFreq,
+                       batchDictionary, batchDictionaryOrder, batchPatternFreq, batchPositions, batchPostings, batchTermBlocks, batchTerms, batchText, batchValues,
                        _match_batch_of, _product, _rows)
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
            "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms", "MatchDictionary", "batchDictionary", "MatchPostings", "batchPostings", "MatchPositions", "batchPositions",
-           "MatchDictionaryOrder", "batchDictionaryOrder"]
+           "MatchDictionaryOrder", "batchDictionaryOrder", "MatchTermBlocks", "batchTermBlocks"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
@@ -263,6 +263,20 @@ class PatternMatcherContext:
     def lastDictionaryOrderMs(self):
         """duration of the launches of the last finishedDictionaryOrderDevice in milliseconds"""
         return self._last_ms(self._L.sp_matcher_ctx_last_dictionary_order_ms, "dictionary order call")
+
+    def finishedTermBlocksDevice(self, stream=0):
+        """write the dictionary ranked by finishedDictionaryOrderDevice as front-coded term blocks on the device (the call waits
+        once, for the number of bytes; the emitting launch is asynchronous on `stream`): the first product that owns its bytes.
+        Returns the device pointers (capi.SpMatchTermBlocksDevice), valid until the next call."""
+        return self._device(self._L.sp_matcher_ctx_finished_term_blocks_device, capi.SpMatchTermBlocksDevice, "coding the term blocks of the batch on the device", stream or None)
+
+    def finishedTermBlocksFetch(self):
+        """plain host copy of the blocks written by finishedTermBlocksDevice: a MatchTermBlocks"""
+        return self._fetch_product(MatchTermBlocks)
+
+    def lastTermBlocksMs(self):
+        """duration of the launches of the last finishedTermBlocksDevice in milliseconds"""
+        return self._last_ms(self._L.sp_matcher_ctx_last_term_blocks_ms, "term blocks call")
 
     def finishedPostingsDevice(self, stream=0):
         """build the postings of the dictionary built by finishedDictionaryDevice on the device (everything is asynchronous
@@ -771,7 +785,7 @@ class PatternLexer:
 # The products of a finished batch that matchSegmentedDocs builds, in the order it builds, fetches and returns them: the stem of
 # the context's methods (finished<stem>Device, finished<stem>Fetch) and the products it needs
 _SEGMENT_PRODUCTS = (("Text", ()), ("Values", ()), ("Terms", ("Text", "Values")), ("Dictionary", ("Terms",)), ("Postings", ("Dictionary",)),
-                     ("Positions", ("Postings",)), ("DictionaryOrder", ("Dictionary",)))
+                     ("Positions", ("Postings",)), ("DictionaryOrder", ("Dictionary",)), ("TermBlocks", ("DictionaryOrder",)))
 
 
 def _rerun(ctx, ndocs, launch, grow, no_room=frozenset((2, 9)), attempts=12):
@@ -789,7 +803,7 @@ def _rerun(ctx, ndocs, launch, grow, no_room=frozenset((2, 9)), attempts=12):
 
 
 def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False, with_terms=False, with_dictionary=False, with_postings=False, with_positions=False,
-                       with_dictionary_order=False):
+                       with_dictionary_order=False, with_term_blocks=False):
     """Segmented documents, host buffers in and out: `text` holds the segments back to back (seg_offsets: nseg+1 byte
     offsets), document d consists of the segments [doc_seg_offsets[d], doc_seg_offsets[d+1]).  Lexer -> stitch on the
     device -> rule matcher -> fetch; only the text goes up and the results come down.  Returns the MatchBatch, whose
@@ -803,9 +817,11 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
     the dictionary are built there too and returned as a sixth element, a MatchPostings.  with_positions implies
     with_postings: the positions of every posting are built there too and returned as a seventh element, a MatchPositions.
     with_dictionary_order implies with_dictionary: the entries of the dictionary are ranked by (handle, value) there too and the
-    MatchDictionaryOrder returned as one more element at the end, behind whatever else was asked for."""
+    MatchDictionaryOrder returned as one more element at the end, behind whatever else was asked for.  with_term_blocks implies
+    with_dictionary_order: the sorted dictionary is written as front-coded term blocks there too and the MatchTermBlocks returned
+    as the last element, behind the order."""
     want = {"Text": with_text, "Values": with_values, "Terms": with_terms, "Dictionary": with_dictionary, "Postings": with_postings, "Positions": with_positions,
-            "DictionaryOrder": with_dictionary_order}
+            "DictionaryOrder": with_dictionary_order, "TermBlocks": with_term_blocks}
     for name, needs in reversed(_SEGMENT_PRODUCTS):
         if want[name]:
             want.update(dict.fromkeys(needs, True))

@@ -174,6 +174,24 @@ class SpMatchDictionaryOrder(ctypes.Structure):
     ]
 
 
+class SpTermBlockEntry(ctypes.Structure):
+    _fields_ = [("handle", c_u32), ("value_bytes", c_u32), ("value_offset", c_u64), ("doc_freq", c_u32), ("reserved", c_u32), ("count", c_u64)]
+
+
+class SpMatchTermBlocksDevice(ctypes.Structure):
+    _fields_ = [
+        ("ndict", ctypes.c_size_t), ("nblocks", ctypes.c_size_t), ("nbytes", ctypes.c_size_t), ("block_entries", c_u32),
+        ("d_bytes", c_vp), ("d_block_offsets", c_vp), ("d_block_handles", c_vp), ("d_totals", c_vp),
+    ]
+
+
+class SpMatchTermBlocks(ctypes.Structure):
+    _fields_ = [
+        ("ndict", ctypes.c_size_t), ("nblocks", ctypes.c_size_t), ("nbytes", ctypes.c_size_t), ("block_entries", c_u32),
+        ("bytes", P(ctypes.c_uint8)), ("block_offsets", P(c_u64)), ("block_handles", P(c_u32)), ("totals", c_u64 * 4),
+    ]
+
+
 class SpPosting(ctypes.Structure):
     _fields_ = [(n, c_u32) for n in ("doc", "term", "count", "first_ordpos")]
 
@@ -302,6 +320,16 @@ SIGNATURES = {
     "sp_matcher_dictionary_order_tile": (c_u32, []),
     "sp_match_batch_dictionary_order": (ctypes.c_int, [P(SpMatchBatch), P(SpMatchValues), P(SpMatchText), P(SpMatchTerms), P(SpMatchDictionary),
                                                         P(SpMatchDictionaryOrder), ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_matcher_term_block_entries": (c_u32, []),
+    "sp_test_term_block_entries": (None, [ctypes.c_uint]),
+    "sp_matcher_ctx_finished_term_blocks_device": (ctypes.c_int, [c_vp, c_vp, P(SpMatchTermBlocksDevice)]),
+    "sp_matcher_ctx_finished_term_blocks_fetch": (ctypes.c_int, [c_vp, P(SpMatchTermBlocks)]),
+    "sp_match_term_blocks_free": (None, [P(SpMatchTermBlocks)]),
+    "sp_matcher_ctx_last_term_blocks_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_match_batch_term_blocks": (ctypes.c_int, [P(SpMatchBatch), P(SpMatchValues), P(SpMatchText), P(SpMatchTerms), P(SpMatchDictionary),
+                                                   P(SpMatchDictionaryOrder), P(SpMatchTermBlocks), ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_match_term_blocks_decode_block": (ctypes.c_int, [P(SpMatchTermBlocks), ctypes.c_size_t, P(SpTermBlockEntry), ctypes.c_size_t, P(ctypes.c_uint8),
+                                                          ctypes.c_size_t, P(ctypes.c_size_t), P(ctypes.c_size_t), ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_ctx_finished_postings_device": (ctypes.c_int, [c_vp, c_vp, P(SpMatchPostingsDevice)]),
     "sp_matcher_ctx_finished_postings_fetch": (ctypes.c_int, [c_vp, P(SpMatchPostings)]),
     "sp_match_postings_free": (None, [P(SpMatchPostings)]),

@@ -164,6 +164,14 @@ struct sp_matcher_ctx
 		uint32_t handleBound = 0;
 		uint64_t ndict = 0;
 	};
+	// the term blocks of the last order (l2_termblocks.h); nothing is allocated before the first sp_matcher_ctx_finished_term_blocks_device
+	struct TermBlocks
+	{
+		PassRun<2> run;
+		DeviceBuffer dBytes, dBlockOffsets, dBlockHandles, dTotals, dBlockSize, dCursor;
+		uint32_t blockEntries = 0;
+		uint64_t ndict = 0, nblocks = 0, nbytes = 0;
+	};
 	// the finish of the last batch and everything made of it (capi_l2_finished.cpp).  A product is a member here and is listed in drop().
 	struct Products
 	{
@@ -176,13 +184,16 @@ struct sp_matcher_ctx
 		Postings pst;
 		Positions pos;
 		DictOrder ord;
+		TermBlocks blk;
 		// a new batch, a new finish: what stands here is of the one before
 		void drop() { fin.run.done = false; txt.run.done = false; val.run.done = false; frq.run.done = false; trm.run.done = false; dropDictionary(); }
 		// a new terms call: a dictionary is that of the terms it was built from, and postings are those of their dictionary
 		void dropDictionary() { dct.run.done = false; dropPostings(); }
 		// a new dictionary call: postings and an order are those of the dictionary they were built from, positions those of their
 		// postings (postings and order do not touch each other)
-		void dropPostings() { pst.run.done = false; pos.run.done = false; ord.run.done = false; }
+		void dropPostings() { pst.run.done = false; pos.run.done = false; dropOrder(); }
+		// a new order call: term blocks are those of the order they were built from
+		void dropOrder() { ord.run.done = false; blk.run.done = false; }
 	} prod;
 	// single-document mode
 	struct SingleDoc

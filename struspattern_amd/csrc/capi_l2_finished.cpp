@@ -1,5 +1,5 @@
 // C-ABI of level 2, second half: the last device batch finished on the device and what is made of the finished batch there --
-// matched text, result values, pattern frequencies, index terms, the batch dictionary, its order, the batch postings, the posting positions -- with their fetch and timing calls.  Every product is one
+// matched text, result values, pattern frequencies, index terms, the batch dictionary, its order, the term blocks, the batch postings, the posting positions -- with their fetch and timing calls.  Every product is one
 // ProductCall (capi_l2_ctx.hpp) behind the finish; sp_matcher_ctx::Products::drop() is what a new batch or finish does to them.
 #include "capi_l2_ctx.hpp"
 #include "l2_finish.h"
@@ -9,11 +9,13 @@
 #include "l2_terms.h"
 #include "l2_dict.h"
 #include "l2_dictorder.h"
+#include "l2_termblocks.h"
 #include "l2_postings.h"
 #include "l2_positions.h"
 #include "match_terms.hpp"
 #include "match_dict.hpp"
 #include "match_dictorder.hpp"
+#include "match_termblocks.hpp"
 #include "match_postings.hpp"
 #include "match_positions.hpp"
 #include "span_text.hpp"
@@ -650,6 +652,7 @@ int sp_matcher_ctx_finished_dictionary_order_device( sp_matcher_ctx_t* c, void* 
 		if (!t.run.done || !d.run.done) throw std::runtime_error( "no dictionary of the last terms of the last finished batch (sp_matcher_ctx_finished_dictionary_device)");
 		const TermSources sources( c, d.flags);
 		sp_matcher_ctx::DictOrder& q = c->prod.ord;
+		c->prod.dropOrder();			// (term blocks are those of the order they were built from)
 		// (the dictionary call waited for ndict and knows N: nothing is waited for here)
 		ProductCall call( c, q.run, stream, ProductCall::Sized());
 		const size_t ndocs = call.ndocs;
@@ -722,6 +725,83 @@ int sp_matcher_ctx_finished_dictionary_order_fetch( sp_matcher_ctx_t* c, sp_matc
 int sp_matcher_ctx_last_dictionary_order_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.ord.run.ms( 0, 1, ms); }
 
 uint32_t sp_matcher_dictionary_order_tile(void) { return DICTORDER_TILE; }
+
+// ---- the term blocks of the order of the finished batch, coded on the device (l2_termblocks.h)
+int sp_matcher_ctx_finished_term_blocks_device( sp_matcher_ctx_t* c, void* stream, sp_match_term_blocks_device_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		requireFinished( c);
+		const sp_matcher_ctx::Dict& d = c->prod.dct;
+		const sp_matcher_ctx::DictOrder& o = c->prod.ord;
+		if (!c->prod.trm.run.done || !d.run.done || !o.run.done)
+			throw std::runtime_error( "no order of the last dictionary of the last finished batch (sp_matcher_ctx_finished_dictionary_order_device)");
+		const TermSources sources( c, d.flags);
+		sp_matcher_ctx::TermBlocks& q = c->prod.blk;
+		// (the dictionary call waited for ndict: the one wait of this call is for nbytes)
+		ProductCall call( c, q.run, stream, ProductCall::Sized());
+		const uint64_t ndict = d.total;
+		if (o.ndict != ndict || ndict >= 0xFFFFFFFFull) throw std::runtime_error( "the order is not that of the dictionary of the finished batch");
+		const uint32_t B = termBlockEntries();
+		const uint64_t nblocks = l2TermBlocksCount( ndict, B);
+		reserveOrNoMem( q.dBlockOffsets, (nblocks+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dBlockHandles, (nblocks+1)*sizeof(uint32_t));
+		reserveOrNoMem( q.dBlockSize, (nblocks+1)*sizeof(uint64_t));
+		// behind the order, which nobody has waited for yet; that runs behind the dictionary, the terms, their sources and the finish
+		call.beginBehind( o.run.stream, o.run.ev[ 1], q.dTotals, 4, q.dCursor, 1);
+		sources.waitFor( call.stream);
+		TermBlocksParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.dictRecords = (const uint32_t*)d.dRecords.ptr; P.order = (const uint32_t*)o.dOrder.ptr; P.prefixBytes = (const uint32_t*)o.dPrefixBytes.ptr;
+		P.valueAt = (const uint64_t*)o.dValueAt.ptr; P.valueLen = (const uint32_t*)o.dValueLen.ptr;
+		sources.describeSources( P);
+		P.ndict = (uint32_t)ndict; P.blockEntries = B; P.nblocks = (uint32_t)nblocks;
+		P.blockSize = (uint64_t*)q.dBlockSize.ptr; P.blockOffsets = (uint64_t*)q.dBlockOffsets.ptr; P.blockHandles = (uint32_t*)q.dBlockHandles.ptr;
+		P.totals = (uint64_t*)q.dTotals.ptr;
+		uint64_t totals[ 4] = { 0, 0, B, 0};
+		if (ndict)
+		{
+			call.passes( P, launchL2TermBlocksCount, launchL2TermBlocksPlace, q.dTotals, totals, 4, [&]{
+				reserveOrNoMem( q.dBytes, totals[ 1] + 16);
+				P.bytes = (uint8_t*)q.dBytes.ptr; P.capacity = totals[ 1];
+			});
+		}
+		else
+		{
+			// nothing to code, nothing to launch: block_offsets = [0], the totals {0, 0, B, 0}
+			HIP_CHECK( hipEventRecord( q.run.ev[ 0], call.stream));
+			HIP_CHECK( hipMemsetAsync( q.dBlockOffsets.ptr, 0, sizeof(uint64_t), call.stream));
+			HIP_CHECK( hipMemsetD32Async( (hipDeviceptr_t)((uint64_t*)q.dTotals.ptr + 2), (int)B, 1, call.stream));
+			HIP_CHECK( hipEventRecord( q.run.ev[ 1], call.stream));
+			q.run.completed( call.stream);
+		}
+		q.ndict = ndict; q.nblocks = nblocks; q.nbytes = totals[ 1]; q.blockEntries = B;
+		if (out)
+		{
+			out->ndict = (size_t)ndict; out->nblocks = (size_t)nblocks; out->nbytes = (size_t)totals[ 1]; out->block_entries = B;
+			out->d_bytes = q.dBytes.ptr; out->d_block_offsets = q.dBlockOffsets.ptr; out->d_block_handles = q.dBlockHandles.ptr;
+			out->d_totals = q.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the blocks' buffers
+int sp_matcher_ctx_finished_term_blocks_fetch( sp_matcher_ctx_t* c, sp_match_term_blocks_t* out)
+{
+	const sp_matcher_ctx::TermBlocks& q = c->prod.blk;
+	return fetchProduct( c, q.run, "no term blocks of the last order of this context (sp_matcher_ctx_finished_term_blocks_device)", out, sp_match_term_blocks_free, [&]{
+		allocMatchTermBlocks( out, q.ndict, q.nblocks, q.blockEntries);
+		allocMatchTermBlockBytes( out, q.nbytes);
+		if (q.nbytes) copySync( c->own, out->bytes, q.dBytes.ptr, q.nbytes, hipMemcpyDeviceToHost);
+		copySync( c->own, out->block_offsets, q.dBlockOffsets.ptr, (q.nblocks+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		if (q.nblocks) copySync( c->own, out->block_handles, q.dBlockHandles.ptr, q.nblocks*sizeof(uint32_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->totals, q.dTotals.ptr, 4*sizeof(uint64_t), hipMemcpyDeviceToHost);
+	});
+}
+
+// duration of the launches of the last term-blocks call in milliseconds (HIP events on its stream; the memsets that clear the
+// totals are enqueued before the first event; the host's one wait lies inside)
+int sp_matcher_ctx_last_term_blocks_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.blk.run.ms( 0, 1, ms); }
 
 // ---- the postings of the dictionary of the finished batch, partitioned on the device (l2_postings.h)
 void sp_test_postings_digit_bits( unsigned bits)

@@ -33,25 +33,6 @@ __device__ __forceinline__ TermValue valueOfEntry( const DictOrderParams& P, u32
 	return v;
 }
 
-// [p, p + len) lies inside the bytes of source s
-__device__ __forceinline__ bool insideSource( const DictOrderParams& P, int s, u64 p, u32 len)
-{
-	const u64 at = p - (u64)(size_t)P.source[ s].bytes;		// (wraps to a large number for an address before the bytes)
-	return p >= (u64)(size_t)P.source[ s].bytes && at <= P.source[ s].total && len <= P.source[ s].total - at;
-}
-
-// the value of entry e (e < P.ndict) as the keys pass left it in working memory, compared against both sources again
-__device__ __forceinline__ TermValue storedValue( const DictOrderParams& P, u32 e)
-{
-	TermValue v;
-	const u64 p = P.valueAt[ e];
-	v.len = P.valueLen[ e];
-	v.ok = v.len == 0 || insideSource( P, 0, p, v.len) || insideSource( P, 1, p, v.len);
-	if (!v.ok) v.len = 0;
-	v.p = (const uint8_t*)(size_t)p;
-	return v;
-}
-
 // ---- the comparator: (key, entry) a lies before (key, entry) b.  Total whatever the arrays hold: the key, then -- for two valid
 // entries -- the bytes and the length, then the index.
 __device__ __forceinline__ bool entryBefore( const DictOrderParams& P, u64 ka, u32 ia, u64 kb, u32 ib)

@@ -40,6 +40,28 @@ __device__ __forceinline__ TermValue valueOf( const PARAMS& P, u64 r)
 	return v;
 }
 
+// [p, p + len) lies inside the bytes of source s
+template <class PARAMS>
+__device__ __forceinline__ bool insideSource( const PARAMS& P, int s, u64 p, u32 len)
+{
+	const u64 at = p - (u64)(size_t)P.source[ s].bytes;		// (wraps to a large number for an address before the bytes)
+	return p >= (u64)(size_t)P.source[ s].bytes && at <= P.source[ s].total && len <= P.source[ s].total - at;
+}
+
+// The value of entry e (e < P.ndict) as the keys pass of the order left it in working memory (valueAt, valueLen of
+// l2_dictorder.h), compared against both sources again: the order passes, and the term-block passes that run on the same memory.
+template <class PARAMS>
+__device__ __forceinline__ TermValue storedValue( const PARAMS& P, u32 e)
+{
+	TermValue v;
+	const u64 p = P.valueAt[ e];
+	v.len = P.valueLen[ e];
+	v.ok = v.len == 0 || insideSource( P, 0, p, v.len) || insideSource( P, 1, p, v.len);
+	if (!v.ok) v.len = 0;
+	v.p = (const uint8_t*)(size_t)p;
+	return v;
+}
+
 __device__ __forceinline__ u32 termHashMix( u32 h, u32 w)
 {
 	h = (h ^ w) * 0x9E3779B1u;

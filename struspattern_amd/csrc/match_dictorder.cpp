@@ -17,10 +17,9 @@ void allocMatchDictionaryOrder( sp_match_dictionary_order_t* out, uint64_t ndict
 	out->handle_offsets = filledArray<uint64_t>( (uint64_t)handleBound + 1, 0);
 }
 
-void matchDictionaryOrder( const sp_match_term_t* records, uint64_t nrecords, const uint64_t* docTermOffsets, const uint64_t* docOffsets,
-			   uint64_t nresults, const uint32_t* resultFormat, size_t ndocs, const TermSource (&source)[ 2], uint32_t handleBound,
-			   uint32_t flags, const sp_dict_term_t* entries, uint64_t ndict, const uint32_t* handleTerms,
-			   sp_match_dictionary_order_t* out)
+std::vector<std::string_view> dictionaryValues( const sp_match_term_t* records, uint64_t nrecords, const uint64_t* docTermOffsets, const uint64_t* docOffsets,
+						uint64_t nresults, const uint32_t* resultFormat, size_t ndocs, const TermSource (&source)[ 2], uint32_t handleBound,
+						uint32_t flags, const sp_dict_term_t* entries, uint64_t ndict, const uint32_t* handleTerms)
 {
 	if (!flags || (flags & ~(uint32_t)(SP_TERM_VALUES | SP_TERM_TEXT))) throw std::runtime_error( "unknown or no term flags");
 	if (!handleBound) throw std::runtime_error( "a handle bound of 0 leaves no valid handle");
@@ -69,7 +68,16 @@ void matchDictionaryOrder( const sp_match_term_t* records, uint64_t nrecords, co
 	{
 		if (handleTerms[ h] != perHandle[ h]) throw std::runtime_error( "handle_terms that are not the number of entries of their handle");
 	}
+	return value;
+}
 
+void matchDictionaryOrder( const sp_match_term_t* records, uint64_t nrecords, const uint64_t* docTermOffsets, const uint64_t* docOffsets,
+			   uint64_t nresults, const uint32_t* resultFormat, size_t ndocs, const TermSource (&source)[ 2], uint32_t handleBound,
+			   uint32_t flags, const sp_dict_term_t* entries, uint64_t ndict, const uint32_t* handleTerms,
+			   sp_match_dictionary_order_t* out)
+{
+	const std::vector<std::string_view> value = dictionaryValues( records, nrecords, docTermOffsets, docOffsets, nresults, resultFormat, ndocs, source,
+									 handleBound, flags, entries, ndict, handleTerms);
 	// (std::string_view compares as memcmp over the common length does, unsigned, then by length)
 	std::vector<uint32_t> order( (size_t)ndict);
 	for (uint64_t e=0; e<ndict; ++e) order[ (size_t)e] = (uint32_t)e;

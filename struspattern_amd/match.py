@@ -2,7 +2,7 @@
 through the MI355X lexer + rule automaton, print tokens (-K) and results in the reference tool's
 listing format (doc/webpage/introduction_struspattern.htm:178-260).
 
-    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] [--postings] [--positions] [--sorted] file [file ...]
+    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] [--postings] [--positions] [--sorted] [--blocks] file [file ...]
 
 Every file is one document (plain UTF-8 text; the reference tool segments XML with strusAnalyzer's
 segmenters, which are outside this engine -- pass -o to add the offset of the text inside its original
@@ -28,6 +28,10 @@ in that file, ascending: `FILEINDEX:COUNT@FIRSTPOS[POS,POS,...]`, built on the G
 --sorted implies --dictionary; the `dict` lines, and the `post` lines with them, come by pattern handle and then by value (bytes)
 instead of first occurrence, ranked on the GPU from the dictionary (finishedDictionaryOrderDevice): they are then the same in
 whatever order the files are named, up to the file indices inside the `post` lines.
+--blocks implies --sorted; the sorted dictionary is written as front-coded term blocks on the GPU (finishedTermBlocksDevice) and,
+read back from the blocks alone, listed behind the other lines: one line per block, `block J NAME: entries N bytes M head 'VALUE'`
+-- the pattern and the value of its head --, and `blocks J bytes M uncoded value bytes U`.  These lines do not depend on the
+order of the files.
 All files go to the GPU as one batch.  There is no CPU fallback.
 """
 import argparse
@@ -52,10 +56,12 @@ def main(argv=None):
     ap.add_argument("--postings", action="store_true", help="implies --dictionary; after its lines, per distinct (pattern, value) the files that hold it")
     ap.add_argument("--positions", action="store_true", help="implies --postings; after every file of a posting line, the distinct positions of the term in it")
     ap.add_argument("--sorted", action="store_true", help="implies --dictionary; its lines and those of --postings by pattern, then by value")
+    ap.add_argument("--blocks", action="store_true", help="implies --sorted; after its lines, the front-coded term blocks of the sorted dictionary")
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("files", nargs="+")
     args = ap.parse_args(argv)
     args.postings = args.postings or args.positions
+    args.sorted = args.sorted or args.blocks
     args.dictionary = args.dictionary or args.postings or args.sorted
 
     with open(args.program, encoding="utf-8") as f:
@@ -82,6 +88,7 @@ def main(argv=None):
     postings = device_postings(mctx) if args.postings else None
     positions = device_positions(mctx) if args.positions else None
     order = device_dictionary_order(mctx) if args.sorted else None
+    blocks = device_term_blocks(mctx) if args.blocks else None
     freq = frequencies(mctx) if args.frequencies else None
     for di, fn in enumerate(args.files):
         print("%s:" % fn)
@@ -98,6 +105,7 @@ def main(argv=None):
         print_terms(terms if args.terms else None, di, mt)
     print_dictionary(dictionary, terms, mt, order)
     print_postings(postings, dictionary, terms, mt, positions, order)
+    print_blocks(blocks, mt)
     print("OK done")
     return 0
 
@@ -112,6 +120,29 @@ def device_dictionary_order(mctx):
     """--sorted: the entries of the dictionary that device_dictionary built, ranked by (pattern handle, value) on the device"""
     mctx.finishedDictionaryOrderDevice()
     return mctx.finishedDictionaryOrderFetch()
+
+
+def device_term_blocks(mctx):
+    """--blocks: the dictionary in the order that device_dictionary_order built, front-coded in blocks on the device"""
+    mctx.finishedTermBlocksDevice()
+    return mctx.finishedTermBlocksFetch()
+
+
+def block_lines(blocks, pattern_name):
+    """the lines of --blocks, from the blocks alone"""
+    lines = []
+    for j in range(len(blocks.block_handles)):
+        entries = blocks.block(j)
+        lines.append("block %d %s: entries %d bytes %d head '%s'" % (j, pattern_name(entries[0][0]), len(entries), int(blocks.block_offsets[j + 1] - blocks.block_offsets[j]),
+                                                                      entries[0][1].decode("utf-8", "replace")))
+    return lines + ["blocks %d bytes %d uncoded value bytes %d" % (len(blocks.block_handles), len(blocks.bytes), int(blocks.totals[3]))]
+
+
+def print_blocks(blocks, mt):
+    if blocks is None:
+        return
+    for line in block_lines(blocks, mt.patternName):
+        print(line)
 
 
 def in_order(lines, order):
@@ -239,8 +270,10 @@ def paragraphs(args, prg, lx, mt, docs):
     with_terms = args.terms or args.dictionary
     found = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_values=args.device_values, with_terms=with_terms,
                                    with_dictionary=args.dictionary, with_postings=args.postings, with_positions=args.positions,
-                                   with_dictionary_order=args.sorted)
-    order = None
+                                   with_dictionary_order=args.sorted, with_term_blocks=args.blocks)
+    order = blocks = None
+    if args.blocks:
+        found, blocks = found[:-1], found[-1]                                   # (the blocks come last, behind the order)
     if args.sorted:
         found, order = found[:-1], found[-1]                                    # (the order comes last, whatever else was asked for)
     names = ("batch", "text", "values", "terms", "dictionary", "postings", "positions") if with_terms else ("batch", "values")
@@ -275,6 +308,7 @@ def paragraphs(args, prg, lx, mt, docs):
         print_terms(terms if args.terms else None, di, mt)
     print_dictionary(dictionary, terms, mt, order)
     print_postings(postings, dictionary, terms, mt, positions, order)
+    print_blocks(blocks, mt)
     print("OK done")
     return 0
 

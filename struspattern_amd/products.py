@@ -414,6 +414,75 @@ def batchDictionaryOrder(mb, terms, dictionary, values=None, text=None):
     return _twin(MatchDictionaryOrder, "sp_match_batch_dictionary_order", ctypes.byref(b), _ref(v), _ref(x), ctypes.byref(t), ctypes.byref(d))
 
 
+def _bytes_of(array, n):
+    """the first n bytes of a ctypes array of uint8"""
+    return ctypes.string_at(array, n) if n else b""
+
+
+class MatchTermBlocks:
+    """The term blocks of a dictionary order (host copies): the sorted dictionary front-coded in blocks of block_entries
+    positions, each block decodable from its own bytes and its handle (include/strus_pattern_amd.h "term blocks").  The first
+    product that owns its bytes: neither the batch nor its text or values are needed to read it."""
+    _C, _SCALARS, _TOTAL, _WHAT = capi.SpMatchTermBlocks, ("ndict", "block_entries"), None, "term blocks of the batch"
+    _FREE, _FETCH = "sp_match_term_blocks_free", "sp_matcher_ctx_finished_term_blocks_fetch"
+    _ARRAYS = (
+        Arr("bytes", "bytes", "nbytes", 0, 0, ctypes.c_uint8),             # the codes of all sorted positions, without gaps
+        Arr("block_offsets", "block_offsets", "nblocks", 1, 0, u64),       # block j is bytes[block_offsets[j]:block_offsets[j+1]]
+        Arr("block_handles", "block_handles", "nblocks", 0, 0, u32),       # the handle of the head of every block
+        Arr("totals", "totals", None, 4, 0, u64),                          # nblocks, nbytes, block_entries, the sum of value_bytes
+    )
+
+    def __init__(self, bytes, block_offsets, block_handles, totals, ndict=0, block_entries=16):
+        self.bytes, self.block_offsets, self.block_handles, self.totals = bytes, block_offsets, block_handles, totals
+        self.ndict, self.block_entries = ndict, block_entries
+
+    def block(self, j):
+        """the entries of block j, decoded by the library's reader from the block alone: a list of (handle, value bytes,
+        doc_freq, count) in sorted order"""
+        keep = []
+        s = _to_c(self, keep)                                          # (keep: until the calls have returned)
+        n, nv, err = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.create_string_buffer(256)
+        call = capi.lib().sp_match_term_blocks_decode_block
+        rc = call(ctypes.byref(s), j, None, 0, None, 0, ctypes.byref(n), ctypes.byref(nv), err, 256)
+        if rc == 0:
+            entries, values = (capi.SpTermBlockEntry * max(n.value, 1))(), (ctypes.c_uint8 * max(nv.value, 1))()
+            rc = call(ctypes.byref(s), j, entries, n.value, values, nv.value, ctypes.byref(n), ctypes.byref(nv), err, 256)
+        if rc != 0:
+            raise PatternError("no block %d of the %s (%d): %s" % (j, self._WHAT, rc, err.value.decode()))
+        data = _bytes_of(values, nv.value)
+        return [(e.handle, data[e.value_offset:e.value_offset + e.value_bytes], e.doc_freq, e.count) for e in entries[:n.value]]
+
+    def entries(self):
+        """all entries in sorted order: (handle, value bytes, doc_freq, count)"""
+        return [entry for j in range(len(self.block_handles)) for entry in self.block(j)]
+
+    def find(self, handle, value):
+        """the sorted position of the entry (handle, value bytes), or None, from the product alone: bisects the block heads by
+        (block_handles[j], head value), then decodes one block"""
+        key, lo, hi = (int(handle), bytes(value)), 0, len(self.block_handles)
+        while lo < hi:                                                  # the last block whose head is not behind the key
+            mid = (lo + hi) // 2
+            head = self.block(mid)[0]
+            lo, hi = (mid + 1, hi) if (head[0], head[1]) <= key else (lo, mid)
+        if not lo:
+            return None
+        for k, (h, v, _, _) in enumerate(self.block(lo - 1)):
+            if (h, v) == key:
+                return (lo - 1) * int(self.block_entries) + k
+        return None
+
+
+def batchTermBlocks(mb, terms, dictionary, order, values=None, text=None):
+    """The term blocks of a dictionary order already on the host (terms: the MatchTerms, dictionary: the MatchDictionary built
+    from them, order: its MatchDictionaryOrder, mb, values, text: what the terms were built from: the fetches of a context, or
+    the twins), by the rule of the device call, without a device.  Returns a MatchTermBlocks."""
+    b, keep = _host_batch(mb, formats="results", status=True)       # (keep: until the call has returned)
+    v, x = _host_source(values, keep), _host_source(text, keep)
+    bound = terms.handle_bound or len(dictionary.handle_terms)      # (terms made by hand may carry none: that of the dictionary then)
+    t, d, o = _to_c(terms, keep, handle_bound=bound), _to_c(dictionary, keep, flags=terms.flags), _to_c(order, keep)
+    return _twin(MatchTermBlocks, "sp_match_batch_term_blocks", ctypes.byref(b), _ref(v), _ref(x), ctypes.byref(t), ctypes.byref(d), ctypes.byref(o))
+
+
 class MatchPostings:
     """The postings of a dictionary (host copies): per term record one posting (doc, term, count, first_ordpos), the postings
     of dictionary entry e together and ascending by document, and per term record the index of its posting
