@@ -151,7 +151,6 @@ struct Wave
 	u32 lbase;				// lexem index of the event being processed, relative to the document
 	u32 spill;				// something of this document lives in the spill area: the two-place accessors run
 	u32 why;				// reason of a hand-over (diagnostics)
-	u32 posLexems;				// lexems at the current position (the key lexem of a rule is kept modulo 4096)
 	// per-lane values (not uniform)
 	u32 stopLex, stopOrd, stopTs;		// stop-word log {lexem index, ordpos, timestamp}: lane = stop word index - 1
 	u32 bsizeV, bmetaV;			// lane b < 16: size and region of bucket b (mirrors of L.bsize / L.bmeta for uniform reads without an LDS round trip)
@@ -669,13 +668,25 @@ static __device__ __forceinline__ void setCurrentPos( LR L, Wave& w, KP P, u32 p
 	u32 wcnt = 0;
 	while (!w.err)
 	{
-		// the next position with rules to expire, if the position advances that far
+		// the next position with rules to expire, if the position advances that far (found by one ballot over the row lengths; a walk
+		// position by position cost a readlane and two increments per position)
 		u32 n = 0, row = 0;
-		while (wcnt < W && w.curpos < pos && !n)
+		if (wcnt < W && w.curpos < pos)
 		{
-			row = w.curpos & (W-1u);
-			n = (u32)__builtin_amdgcn_readlane( w.expCntV, row);
-			++wcnt; ++w.curpos;
+			// one bit per row that holds rules, turned so that bit 0 is the row of curpos: the next such row among the positions ahead
+			const u32 ahead = (pos - w.curpos) < (W - wcnt) ? (pos - w.curpos) : (W - wcnt);		// 1 .. W
+			const u32 s = w.curpos & (W-1u);
+			u64 em = __ballot( w.expCntV != 0);
+			em = (em >> s) | ((em << 1) << (W - 1u - s));
+			em &= ~0ull >> (64u - ahead);
+			u32 step = ahead;
+			if (em)
+			{
+				step = (u32)__builtin_ctzll( em) + 1u;
+				row = (s + step - 1u) & (W-1u);
+				n = (u32)__builtin_amdgcn_readlane( w.expCntV, row);
+			}
+			wcnt += step; w.curpos += step;
 		}
 		u32 nD = w.nDispose;
 		if (!n && !nD) break;
@@ -1271,7 +1282,7 @@ static __device__ __forceinline__ void runKernel()
 		w.bmetaV = P.bucketMeta[ LANE & 15u]; w.bsizeV = 0; w.expCntV = 0;
 		if (LANE < 16u) { L.bsize[ LANE] = 0; L.bmeta[ LANE] = w.bmetaV; }
 		L.expCnt[ LANE] = 0;
-		w.stopLex = 0; w.stopOrd = 0; w.stopTs = 0; w.posLexems = 0;
+		w.stopLex = 0; w.stopOrd = 0; w.stopTs = 0;
 		w.curpos = 0; w.timestamp = 0; w.nInstalled = 0; w.nAlt = 0; w.nSignals = 0; w.nTrig = 0; w.openLo = 0; w.openHi = 0;
 		w.freeN = 0; w.usedL = 0; w.sFreeN = 0; w.usedS = 0;
 		w.nDispose = 0; w.nStaged = 0; w.nStagedItems = 0; w.err = 0; w.lbase = 0; w.why = 0; w.spill = 0;
@@ -1283,7 +1294,7 @@ static __device__ __forceinline__ void runKernel()
 		u64 lbeg, lend;
 		docLexems( P.io, doc, lbeg, lend);
 		if (lend - lbeg >= (1ull << 24)) FALLBACK( FB_LEXEMS);	// lexem indices are kept in 24 bits beside the variable
-		u32 curPosition = 0, nEvents = 0;
+		u32 edgePos = 0, edgeRun = 0, nEvents = 0;
 		for (u64 tile=lbeg; tile<lend && !w.err; tile+=64)
 		{
 			// coalesced fetch of up to 64 lexems (16 B each); every lane also looks its own lexem's event up in the key
@@ -1309,24 +1320,41 @@ static __device__ __forceinline__ void runKernel()
 				}
 			}
 			const u32 cnt = (lend - tile) < 64 ? (u32)(lend - tile) : 64u;
+			// PatternMatcherContext::putInput (patternMatcher.cpp:131-162), once per tile: every lane judges its own lexem against the
+			// one before it (lane 0: the last of the tile before).  `stop` is the status that ends the document AT this lexem, by the
+			// precedence of the per-event tests it replaces: position descends, a field out of range on a lexem that stays on the
+			// position, id out of range, more than 60 lexems on one position (key lexems are kept modulo 4096: ldKl).  Only the first
+			// lexem with a status counts -- up to it the positions ascend, so the lexem before holds the running position --, and the
+			// event loop ends in front of it.
+			u32 stop = 0;
+			{
+				// (what crosses the tile edge stays in lane 0 of two vector registers: the position and the run length of lane 63)
+				const u32 below = (u32)__builtin_amdgcn_ds_bpermute( (int)(((LANE - 1u) & 63u) << 2), (int)lx.y);
+				const u32 prev = LANE ? below : edgePos;
+				const u64 advM = __ballot( mine && prev < lx.y) & (lanesBelow() | (1ull << LANE));	// positions that begin at or below my lexem
+				const u32 posLexems = advM ? (LANE - (63u - (u32)__builtin_clzll( advM)) + 1u) : ((u32)__builtin_amdgcn_readfirstlane( edgeRun) + LANE + 1u);
+				if (mine)
+				{
+					if (prev > lx.y) stop = SPD_ERR_ORDER;
+					else if (prev == lx.y && (lx.w >= 0x7FFFFFFFu || seg >= 0x7FFFFFFFu || lx.z >= 0x7FFFFFFFu)) stop = SPD_ERR_RANGE;
+					else if (lx.x >= (1u<<29)) stop = SPD_ERR_RANGE;
+					else if (posLexems > 60u) stop = SPD_FAST_FALLBACK;
+				}
+				edgePos = below;
+				edgeRun = (u32)__builtin_amdgcn_ds_bpermute( (int)(((LANE - 1u) & 63u) << 2), (int)posLexems);
+			}
+			u32 nRun = cnt;
+			{ const u64 stopM = __ballot( stop != 0); if (stopM) nRun = (u32)__builtin_ctzll( stopM); }
 #ifdef SPA_PROF
 			if (__ballot( kBegin == 0xFFFFFFFFu)) break;	// (the probes complete here)
 #endif
 			PROF_ADD( 5);
-			for (u32 k=0; k<cnt && !w.err; ++k)
+			for (u32 k=0; k<nRun; ++k)
 			{
 				const u32 id = __builtin_amdgcn_readlane( lx.x, k), ordpos = __builtin_amdgcn_readlane( lx.y, k);
-				const u32 origpos = __builtin_amdgcn_readlane( lx.z, k), origsize = __builtin_amdgcn_readlane( lx.w, k);
-				const u32 origseg = __builtin_amdgcn_readlane( seg, k);
-				// PatternMatcherContext::putInput (patternMatcher.cpp:131-162)
-				if (curPosition > ordpos) { w.err = SPD_ERR_ORDER; break; }
-				else if (curPosition < ordpos) { curPosition = ordpos; w.posLexems = 0; }
-				else if (origsize >= 0x7FFFFFFFu || origseg >= 0x7FFFFFFFu || origpos >= 0x7FFFFFFFu) { w.err = SPD_ERR_RANGE; break; }
 				// expiry up to the event's position + the rules the transition before has finished or deleted
 				if (w.curpos != ordpos || w.nDispose) { setCurrentPos( L, w, P, ordpos); PROF_ADD( 3); if (w.err) break; }
-				if (id >= (1u<<29)) { w.err = SPD_ERR_RANGE; break; }
 				w.lbase = (u32)(tile - lbeg) + k;
-				if (++w.posLexems > 60u) { FALLBACK( FB_POSLEXEMS); break; }	// (key lexems are kept modulo 4096: ldKl)
 				// ---- doTransition (cpp:981-1064) for an input term: no follow events in a flat rule set
 				{
 					const u32 lo = w.openLo + w.nTrig;
@@ -1357,6 +1385,16 @@ static __device__ __forceinline__ void runKernel()
 				}
 				PROF_ADD( 2);
 				++nEvents;
+			}
+			if (!w.err)
+			{
+				// (the ballot again, out of the lanes: a mask kept across the event loop would be two more live scalars)
+				const u64 stopM = __ballot( stop != 0);
+				if (stopM)
+				{
+					w.err = (u32)__builtin_amdgcn_readlane( stop, (u32)__builtin_ctzll( stopM));
+					if (w.err == SPD_FAST_FALLBACK) w.why = FB_POSLEXEMS;
+				}
 			}
 		}
 
