@@ -1131,6 +1131,124 @@ int sp_matcher_ctx_last_positions_launch_ms(sp_matcher_ctx_t* c, double ms[6]);
  * or beyond N, and a posting whose count is not the number of its results; SP_ERR_NOMEM when memory runs out. */
 int sp_match_batch_positions(const sp_match_batch_t* mb, const sp_match_terms_t* terms, const sp_match_postings_t* postings,
                              sp_match_positions_t* out, char* err, size_t errsize);
+
+/* ---- posting blocks: the posting lists of a batch, with their positions, written down in the sorted order of the dictionary,
+ * cut into the blocks of the term blocks and delta-coded with varints -- the second product of a finished batch that OWNS ITS
+ * BYTES: position k of the term blocks and list k of the posting blocks are the same term, and the two products together are
+ * the index segment of the batch, which an indexer stores, merges or searches without the batch; built on the device
+ * (csrc/l2_postingblocks.h) or, for arrays already fetched, on the host (csrc/match_postingblocks.hpp).  The rule is the
+ * project's own, unpinned by a reference vector.  (It is the run of ONE batch: no state that lives across batches is kept.)
+ * INPUT: the dictionary order, the postings and the posting positions built last on a context, all three of the current
+ * dictionary.  Write ndict for the number of entries, N for the number of postings, e = order[k] for the entry at sorted
+ * position k.  The LIST of k is postings[entry_offsets[e] .. entry_offsets[e+1]): doc_freq(e) postings, ascending by `doc`.
+ * BLOCKS: B = sp_matcher_term_block_entries(), the switch of the term blocks (sp_test_term_block_entries); block j covers the
+ * sorted positions [j B, min((j+1) B, ndict)); nblocks = ceil(ndict / B).  Block j of both products covers the same terms.
+ * THE CODE OF SORTED POSITION k, in the unsigned LEB128 varints of the term blocks, minimal length:
+ *   1  body       the number of bytes of the posting codes that follow, 64 bits: a reader skips a whole list with it,
+ *   2  for every posting p of the list in order:
+ *        ddelta     doc(p) for the first posting of the list, otherwise doc(p) - doc(p-1), at least 1,
+ *        count(p)   the term frequency: the number of occurrences,
+ *        npos       posting_positions[p]: the number of distinct ordinal positions,
+ *        npos varints: the smallest ordpos of the posting as it is, then every later DISTINCT ordpos less the distinct one
+ *                   before it, at least 1.
+ * Occurrences that repeat an ordpos contribute no byte; the `result` word of an occurrence is not stored.  The number of
+ * postings of a list is not stored: the list ends where `body` ends, and that number is the doc_freq that its term-block
+ * position carries.
+ * OUTPUTS:
+ *   bytes[nbytes]              (uint8)  the codes of all sorted positions, without gaps,
+ *   block_offsets[nblocks+1]   (uint64) where block j starts in `bytes`; the last element is nbytes,
+ *   totals[4]                  (uint64) {nblocks, nbytes, B, the number of position varints written}: the fourth equals
+ *                              totals[1] of the positions product.
+ * A block decodes from its own bytes alone.
+ * INVARIANTS: decoding list k reproduces, for every posting of order[k], exactly (doc, count, the distinct ordpos ascending);
+ * block_offsets ascends; a block is never empty (a list is at least `body` and one posting of four varints).
+ * DETERMINISM: every byte is a function of the dictionary, its order, the postings and the positions alone (the one global
+ * atomic of the device adds to the fourth total).  The codes hold positions and no `result` index, so a plain and a canonical
+ * finish leave the same bytes, and after a canonical finish the exact engines and result-set mode do too.
+ * SAFETY, as for the term blocks: no byte outside the outputs is written; every byte written for block j lies inside
+ * [block_offsets[j], block_offsets[j+1]), and that range inside the capacity the host allocated; an entry is compared
+ * against ndict, a posting against N, an occurrence against nocc and a document against ndocs before use, and so is every
+ * index read from working memory.  Arrays that this context cannot produce: a posting whose entry, index or document fails
+ * one of those comparisons, and a posting without an occurrence (`count` 0 means an empty occurrence range here: the range,
+ * not the word, says how many occurrences are walked), costs nothing and writes nothing, for nobody carries its header;
+ * documents that do not ascend inside a list and positions that do not ascend inside a posting wrap in 32 bits;
+ * posting_positions is written as it is, above `count` too.  The sizing and the emitting pass go through one function for what
+ * a posting costs (csrc/posting_block_code.h), so they agree on all of these; such bytes need not decode, a byte of `bytes`
+ * that no code reaches keeps what the buffer held, and a span of 64 occurrences one of which would leave the range of its
+ * block is not written.  The host twin refuses these inputs.
+ * LIMIT: those of the dictionary and the positions: N and the finished total below 2^32 - 1. */
+/* one decoded posting of a block (sp_match_posting_blocks_decode_block) */
+typedef struct sp_block_posting {
+	uint32_t doc;
+	uint32_t count;            /* the term frequency */
+	uint32_t npos;             /* the number of distinct positions */
+	uint32_t reserved;         /* 0 */
+	uint64_t position_offset;  /* where its npos positions start in the `positions` of the decode call */
+} sp_block_posting_t;
+typedef struct sp_match_posting_blocks_device {
+	size_t ndict;
+	size_t nblocks;
+	size_t nbytes;
+	uint32_t block_entries;      /* B */
+	void* d_bytes;               /* uint8_t[nbytes] */
+	void* d_block_offsets;       /* uint64_t[nblocks+1] */
+	void* d_totals;              /* uint64_t[4]: nblocks, nbytes, B, the position varints written */
+} sp_match_posting_blocks_device_t;
+/* host copy of the posting blocks (sp_match_posting_blocks_free) */
+typedef struct sp_match_posting_blocks {
+	size_t ndict;
+	size_t nblocks;
+	size_t nbytes;
+	uint32_t block_entries;       /* B */
+	uint8_t* bytes;               /* nbytes */
+	uint64_t* block_offsets;      /* nblocks+1 */
+	uint64_t totals[4];           /* nblocks, nbytes, B, the position varints written */
+} sp_match_posting_blocks_t;
+/* Writes the posting blocks of the order, the postings and the positions built last on this context.  Six launches on `stream`
+ * (lists, sizes, prefix, blocks, offsets, emit: csrc/l2_postingblocks.h); the call enqueues the first five, waits for them only
+ * to read nbytes, sizes `bytes`, enqueues the sixth and returns.  block_offsets is sized by nblocks, which the host knows,
+ * before the wait.  ndict == 0 launches nothing: nblocks = nbytes = 0, block_offsets = [0].  The buffers belong to the context,
+ * are allocated at the first call, only grow (working memory: 8 bytes a posting, 16 a sorted position, 8 a block), and are
+ * valid until the next posting-blocks call; a new order, postings or positions call, and whatever invalidates those -- the next
+ * batch, finish, terms or dictionary call --, invalidate the state, not the buffers.  The term blocks neither need nor
+ * invalidate the posting blocks, nor the reverse.  A `stream` other than those of the order, the postings and the positions is
+ * ordered behind each with an event.  SP_ERR_INVALID unless an order, postings and positions were all built since the last
+ * dictionary call of the last finish; SP_ERR_NOMEM when a buffer cannot be allocated (the context stays usable, `out` is empty). */
+int sp_matcher_ctx_finished_posting_blocks_device(sp_matcher_ctx_t* c, void* stream, sp_match_posting_blocks_device_t* out);
+/* plain copy of the buffers of the last sp_matcher_ctx_finished_posting_blocks_device to the host (waits for it): this fetch
+ * replaces those of the postings, the positions, the dictionary and the order for a caller who wants the inverted lists in the
+ * order of the term blocks */
+int sp_matcher_ctx_finished_posting_blocks_fetch(sp_matcher_ctx_t* c, sp_match_posting_blocks_t* out);
+void sp_match_posting_blocks_free(sp_match_posting_blocks_t* pb);
+/* duration of the launches of the last posting-blocks call in milliseconds (HIP events on its stream round them; waits for
+ * them; the host's wait for nbytes between offsets and emit lies inside; the hipMemsetAsync calls that clear the totals are
+ * enqueued before the first event, as the clearing of every other product) */
+int sp_matcher_ctx_last_posting_blocks_ms(sp_matcher_ctx_t* c, double* ms);
+/* The same rule over host arrays, needs no device, no batch and no source, and the yardstick of the device passes: the blocks of
+ * a dictionary, its order, its postings and their positions already fetched (or made by their twins).  Fills `out`
+ * (sp_match_posting_blocks_free); SP_ERR_INVALID with the message in `err` for a NULL argument; an order or postings whose ndict
+ * is not the dictionary's; positions whose number of postings is not that of the postings; an `order` that is not a
+ * permutation; entry offsets that do not ascend or do not cover the postings; a doc_freq that is not the length of its list;
+ * posting offsets that do not ascend or do not cover the occurrences; a posting with `count` 0; a posting without an
+ * occurrence; documents that do not ascend inside a list; positions
+ * that do not ascend inside a posting; a posting_positions that is 0, above `count` or not the number of distinct positions;
+ * SP_ERR_NOMEM when memory runs out. */
+int sp_match_batch_posting_blocks(const sp_match_dictionary_t* dict, const sp_match_dictionary_order_t* order,
+                                  const sp_match_postings_t* postings, const sp_match_positions_t* positions,
+                                  sp_match_posting_blocks_t* out, char* err, size_t errsize);
+/* The reader: decodes block j of `pb` alone, from bytes[block_offsets[j] .. block_offsets[j+1]): per list its number of postings
+ * into `list_postings` (room for nlists_cap numbers; a block holds at most block_entries lists), the postings of all its lists
+ * one behind the other into `postings` (room for npostings_cap records) and their positions, ascending, into `positions` (room
+ * for npositions_cap numbers).  *nlists, *npostings and *npositions get what the block holds, also when the room does not
+ * suffice; with the three outputs NULL the call only counts.  Needs no device.  SP_ERR_INVALID with the message in `err` for
+ * j >= nblocks, block offsets that descend or leave `bytes`, room that does not suffice, and a malformed block: a varint that
+ * runs past the block or is longer than ten bytes; a `body` that runs past the block; a `body` of 0; a posting that ends
+ * beyond its `body`; a ddelta of 0 behind the first posting of a list, or a position gap of 0 behind the first position of a
+ * posting; an npos of 0 or above `count`; a document, a count or a position that leaves 32 bits; an empty block and one of more
+ * than block_entries lists. */
+int sp_match_posting_blocks_decode_block(const sp_match_posting_blocks_t* pb, size_t j, uint32_t* list_postings, size_t nlists_cap,
+                                         sp_block_posting_t* postings, size_t npostings_cap, uint32_t* positions, size_t npositions_cap,
+                                         size_t* nlists, size_t* npostings, size_t* npositions, char* err, size_t errsize);
 /* copies the results of the last device batch to the host, grouped by document (as sp_matcher_ctx_match_docs
  * returns them, `exclusive` elimination included) */
 int sp_matcher_ctx_batch_fetch(sp_matcher_ctx_t* c, sp_match_batch_t* out);

@@ -12,13 +12,13 @@ import numpy as np
 from . import capi
 from .capi import SpLexem, SpResult, SpResultItem
 from .products import (SP_TERM_TEXT, SP_TERM_VALUES, SP_TEXT_ITEMS, SP_TEXT_RESULTS, SP_VALUE_ITEMS, SP_VALUE_RESULTS,   # noqa: F401 (public names)
-                       MatchBatch, MatchDictionary, MatchDictionaryOrder, MatchPositions, MatchPostings, MatchTermBlocks, MatchTerms, MatchText, MatchValues, PatternError, PatternFreq,
-                       batchDictionary, batchDictionaryOrder, batchPatternFreq, batchPositions, batchPostings, batchTermBlocks, batchTerms, batchText, batchValues,
+                       MatchBatch, MatchDictionary, MatchDictionaryOrder, MatchPositions, MatchPostingBlocks, MatchPostings, MatchTermBlocks, MatchTerms, MatchText, MatchValues, PatternError, PatternFreq,
+                       batchDictionary, batchDictionaryOrder, batchPatternFreq, batchPositions, batchPostingBlocks, batchPostings, batchTermBlocks, batchTerms, batchText, batchValues,
                        _match_batch_of, _product, _rows)
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
            "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms", "MatchDictionary", "batchDictionary", "MatchPostings", "batchPostings", "MatchPositions", "batchPositions",
-           "MatchDictionaryOrder", "batchDictionaryOrder", "MatchTermBlocks", "batchTermBlocks"]
+           "MatchDictionaryOrder", "batchDictionaryOrder", "MatchTermBlocks", "batchTermBlocks", "MatchPostingBlocks", "batchPostingBlocks"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document
@@ -277,6 +277,21 @@ class PatternMatcherContext:
     def lastTermBlocksMs(self):
         """duration of the launches of the last finishedTermBlocksDevice in milliseconds"""
         return self._last_ms(self._L.sp_matcher_ctx_last_term_blocks_ms, "term blocks call")
+
+    def finishedPostingBlocksDevice(self, stream=0):
+        """write the posting lists of the batch, with their positions, in the order of finishedDictionaryOrderDevice as delta-coded
+        posting blocks on the device, from the postings of finishedPostingsDevice and the positions of finishedPositionsDevice (the
+        call waits once, for the number of bytes; the emitting launch is asynchronous on `stream`): list k is position k of the
+        term blocks.  Returns the device pointers (capi.SpMatchPostingBlocksDevice), valid until the next call."""
+        return self._device(self._L.sp_matcher_ctx_finished_posting_blocks_device, capi.SpMatchPostingBlocksDevice, "coding the posting blocks of the batch on the device", stream or None)
+
+    def finishedPostingBlocksFetch(self):
+        """plain host copy of the blocks written by finishedPostingBlocksDevice: a MatchPostingBlocks"""
+        return self._fetch_product(MatchPostingBlocks)
+
+    def lastPostingBlocksMs(self):
+        """duration of the launches of the last finishedPostingBlocksDevice in milliseconds"""
+        return self._last_ms(self._L.sp_matcher_ctx_last_posting_blocks_ms, "posting blocks call")
 
     def finishedPostingsDevice(self, stream=0):
         """build the postings of the dictionary built by finishedDictionaryDevice on the device (everything is asynchronous
@@ -783,9 +798,12 @@ class PatternLexer:
 
 
 # The products of a finished batch that matchSegmentedDocs builds, in the order it builds, fetches and returns them: the stem of
-# the context's methods (finished<stem>Device, finished<stem>Fetch) and the products it needs
+# the context's methods (finished<stem>Device, finished<stem>Fetch) and the products it needs.  (The posting blocks are built in
+# front of the term blocks, whose row stays the last, and returned behind them: _SEGMENT_LAST.)
 _SEGMENT_PRODUCTS = (("Text", ()), ("Values", ()), ("Terms", ("Text", "Values")), ("Dictionary", ("Terms",)), ("Postings", ("Dictionary",)),
-                     ("Positions", ("Postings",)), ("DictionaryOrder", ("Dictionary",)), ("TermBlocks", ("DictionaryOrder",)))
+                     ("Positions", ("Postings",)), ("DictionaryOrder", ("Dictionary",)), ("PostingBlocks", ("DictionaryOrder", "Positions")),
+                     ("TermBlocks", ("DictionaryOrder",)))
+_SEGMENT_LAST = "PostingBlocks"
 
 
 def _rerun(ctx, ndocs, launch, grow, no_room=frozenset((2, 9)), attempts=12):
@@ -803,7 +821,7 @@ def _rerun(ctx, ndocs, launch, grow, no_room=frozenset((2, 9)), attempts=12):
 
 
 def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text=False, with_values=False, with_terms=False, with_dictionary=False, with_postings=False, with_positions=False,
-                       with_dictionary_order=False, with_term_blocks=False):
+                       with_dictionary_order=False, with_term_blocks=False, with_posting_blocks=False):
     """Segmented documents, host buffers in and out: `text` holds the segments back to back (seg_offsets: nseg+1 byte
     offsets), document d consists of the segments [doc_seg_offsets[d], doc_seg_offsets[d+1]).  Lexer -> stitch on the
     device -> rule matcher -> fetch; only the text goes up and the results come down.  Returns the MatchBatch, whose
@@ -819,9 +837,11 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
     with_dictionary_order implies with_dictionary: the entries of the dictionary are ranked by (handle, value) there too and the
     MatchDictionaryOrder returned as one more element at the end, behind whatever else was asked for.  with_term_blocks implies
     with_dictionary_order: the sorted dictionary is written as front-coded term blocks there too and the MatchTermBlocks returned
-    as the last element, behind the order."""
+    as the last element, behind the order.  with_posting_blocks implies with_dictionary_order and with_positions: the posting
+    lists are written as delta-coded posting blocks in the sorted order there too and the MatchPostingBlocks returned as the very
+    last element, behind the term blocks where both were asked for."""
     want = {"Text": with_text, "Values": with_values, "Terms": with_terms, "Dictionary": with_dictionary, "Postings": with_postings, "Positions": with_positions,
-            "DictionaryOrder": with_dictionary_order, "TermBlocks": with_term_blocks}
+            "DictionaryOrder": with_dictionary_order, "TermBlocks": with_term_blocks, "PostingBlocks": with_posting_blocks}
     for name, needs in reversed(_SEGMENT_PRODUCTS):
         if want[name]:
             want.update(dict.fromkeys(needs, True))
@@ -849,7 +869,7 @@ def matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_text
         for name in chosen:
             getattr(mctx, "finished%sDevice" % name)(*(source if name in ("Text", "Values") else ()), stream=stream)
         mb = mctx.finishedFetch()
-        products = tuple(getattr(mctx, "finished%sFetch" % name)() for name in chosen)
+        products = tuple(getattr(mctx, "finished%sFetch" % name)() for name in sorted(chosen, key=lambda name: name == _SEGMENT_LAST))
     else:
         mb = mctx.batchFetch()
     stitch_status = lctx.stitchedStatus()

@@ -192,6 +192,24 @@ class SpMatchTermBlocks(ctypes.Structure):
     ]
 
 
+class SpBlockPosting(ctypes.Structure):
+    _fields_ = [("doc", c_u32), ("count", c_u32), ("npos", c_u32), ("reserved", c_u32), ("position_offset", c_u64)]
+
+
+class SpMatchPostingBlocksDevice(ctypes.Structure):
+    _fields_ = [
+        ("ndict", ctypes.c_size_t), ("nblocks", ctypes.c_size_t), ("nbytes", ctypes.c_size_t), ("block_entries", c_u32),
+        ("d_bytes", c_vp), ("d_block_offsets", c_vp), ("d_totals", c_vp),
+    ]
+
+
+class SpMatchPostingBlocks(ctypes.Structure):
+    _fields_ = [
+        ("ndict", ctypes.c_size_t), ("nblocks", ctypes.c_size_t), ("nbytes", ctypes.c_size_t), ("block_entries", c_u32),
+        ("bytes", P(ctypes.c_uint8)), ("block_offsets", P(c_u64)), ("totals", c_u64 * 4),
+    ]
+
+
 class SpPosting(ctypes.Structure):
     _fields_ = [(n, c_u32) for n in ("doc", "term", "count", "first_ordpos")]
 
@@ -345,6 +363,15 @@ SIGNATURES = {
     "sp_test_positions_launch_events": (None, [ctypes.c_uint]),
     "sp_matcher_ctx_last_positions_launch_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
     "sp_match_batch_positions": (ctypes.c_int, [P(SpMatchBatch), P(SpMatchTerms), P(SpMatchPostings), P(SpMatchPositions), ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_matcher_ctx_finished_posting_blocks_device": (ctypes.c_int, [c_vp, c_vp, P(SpMatchPostingBlocksDevice)]),
+    "sp_matcher_ctx_finished_posting_blocks_fetch": (ctypes.c_int, [c_vp, P(SpMatchPostingBlocks)]),
+    "sp_match_posting_blocks_free": (None, [P(SpMatchPostingBlocks)]),
+    "sp_matcher_ctx_last_posting_blocks_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_match_batch_posting_blocks": (ctypes.c_int, [P(SpMatchDictionary), P(SpMatchDictionaryOrder), P(SpMatchPostings), P(SpMatchPositions),
+                                                      P(SpMatchPostingBlocks), ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_match_posting_blocks_decode_block": (ctypes.c_int, [P(SpMatchPostingBlocks), ctypes.c_size_t, P(c_u32), ctypes.c_size_t, P(SpBlockPosting), ctypes.c_size_t,
+                                                             P(c_u32), ctypes.c_size_t, P(ctypes.c_size_t), P(ctypes.c_size_t), P(ctypes.c_size_t),
+                                                             ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_ctx_batch_counters": (ctypes.c_int, [c_vp, P(c_u64)]),
     "sp_matcher_ctx_last_kernel_ms": (ctypes.c_double, [c_vp]),
     "sp_matcher_ctx_kernel_kind": (ctypes.c_int, [c_vp]),

@@ -172,6 +172,15 @@ struct sp_matcher_ctx
 		uint32_t blockEntries = 0;
 		uint64_t ndict = 0, nblocks = 0, nbytes = 0;
 	};
+	// the posting blocks of the last order, postings and positions (l2_postingblocks.h); nothing is allocated before the first
+	// sp_matcher_ctx_finished_posting_blocks_device
+	struct PostingBlocks
+	{
+		PassRun<2> run;
+		DeviceBuffer dBytes, dBlockOffsets, dTotals, dListOffsets, dListStart, dPostingBytes, dBlockSize, dCursor;
+		uint32_t blockEntries = 0;
+		uint64_t ndict = 0, nblocks = 0, nbytes = 0;
+	};
 	// the finish of the last batch and everything made of it (capi_l2_finished.cpp).  A product is a member here and is listed in drop().
 	struct Products
 	{
@@ -185,15 +194,18 @@ struct sp_matcher_ctx
 		Positions pos;
 		DictOrder ord;
 		TermBlocks blk;
+		PostingBlocks pbk;
 		// a new batch, a new finish: what stands here is of the one before
 		void drop() { fin.run.done = false; txt.run.done = false; val.run.done = false; frq.run.done = false; trm.run.done = false; dropDictionary(); }
 		// a new terms call: a dictionary is that of the terms it was built from, and postings are those of their dictionary
 		void dropDictionary() { dct.run.done = false; dropPostings(); }
 		// a new dictionary call: postings and an order are those of the dictionary they were built from, positions those of their
 		// postings (postings and order do not touch each other)
-		void dropPostings() { pst.run.done = false; pos.run.done = false; dropOrder(); }
-		// a new order call: term blocks are those of the order they were built from
-		void dropOrder() { ord.run.done = false; blk.run.done = false; }
+		void dropPostings() { pst.run.done = false; dropPositions(); dropOrder(); }
+		// a new postings call: positions are those of the postings they were built from, posting blocks those of their positions
+		void dropPositions() { pos.run.done = false; pbk.run.done = false; }
+		// a new order call: term blocks and posting blocks are those of the order they were built from
+		void dropOrder() { ord.run.done = false; blk.run.done = false; pbk.run.done = false; }
 	} prod;
 	// single-document mode
 	struct SingleDoc

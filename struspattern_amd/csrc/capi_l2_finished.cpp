@@ -1,5 +1,5 @@
 // C-ABI of level 2, second half: the last device batch finished on the device and what is made of the finished batch there --
-// matched text, result values, pattern frequencies, index terms, the batch dictionary, its order, the term blocks, the batch postings, the posting positions -- with their fetch and timing calls.  Every product is one
+// matched text, result values, pattern frequencies, index terms, the batch dictionary, its order, the term blocks, the batch postings, the posting positions, the posting blocks -- with their fetch and timing calls.  Every product is one
 // ProductCall (capi_l2_ctx.hpp) behind the finish; sp_matcher_ctx::Products::drop() is what a new batch or finish does to them.
 #include "capi_l2_ctx.hpp"
 #include "l2_finish.h"
@@ -12,12 +12,14 @@
 #include "l2_termblocks.h"
 #include "l2_postings.h"
 #include "l2_positions.h"
+#include "l2_postingblocks.h"
 #include "match_terms.hpp"
 #include "match_dict.hpp"
 #include "match_dictorder.hpp"
 #include "match_termblocks.hpp"
 #include "match_postings.hpp"
 #include "match_positions.hpp"
+#include "match_postingblocks.hpp"
 #include "span_text.hpp"
 #include "pattern_freq.hpp"
 #include "finished_host.hpp"
@@ -818,7 +820,7 @@ int sp_matcher_ctx_finished_postings_device( sp_matcher_ctx_t* c, void* stream, 
 		const sp_matcher_ctx::Dict& d = c->prod.dct;
 		if (!t.run.done || !d.run.done) throw std::runtime_error( "no dictionary of the last terms of the last finished batch (sp_matcher_ctx_finished_dictionary_device)");
 		sp_matcher_ctx::Postings& q = c->prod.pst;
-		c->prod.pos.run.done = false;		// (positions are those of the postings they were built from)
+		c->prod.dropPositions();		// (positions are those of the postings they were built from)
 		// (the dictionary call waited for ndict and knows N: nothing is waited for here)
 		ProductCall call( c, q.run, stream, ProductCall::Sized());
 		const size_t ndocs = call.ndocs;
@@ -892,6 +894,7 @@ int sp_matcher_ctx_finished_positions_device( sp_matcher_ctx_t* c, void* stream,
 		if (!t.run.done || !c->prod.dct.run.done || !s.run.done)
 			throw std::runtime_error( "no postings of the last dictionary of the last finished batch (sp_matcher_ctx_finished_postings_device)");
 		sp_matcher_ctx::Positions& q = c->prod.pos;
+		c->prod.pbk.run.done = false;		// (posting blocks are those of the positions they were built from)
 		q.launches = 0;
 		// (the terms call read the finished total and the postings call knows N: the one wait of this call is for nocc and the largest ordpos)
 		ProductCall call( c, q.run, stream, ProductCall::Sized());
@@ -983,5 +986,85 @@ int sp_matcher_ctx_last_positions_launch_ms( sp_matcher_ctx_t* c, double ms[ 6])
 }
 
 uint32_t sp_matcher_positions_tile(void) { return POSITIONS_TILE; }
+
+// ---- the posting blocks of the order, the postings and the positions of the finished batch, coded on the device (l2_postingblocks.h)
+int sp_matcher_ctx_finished_posting_blocks_device( sp_matcher_ctx_t* c, void* stream, sp_match_posting_blocks_device_t* out)
+{
+	if (out) std::memset( out, 0, sizeof(*out));
+	return guardedCall( c->lasterror, SP_ERR_INVALID, [&]{
+		requireFinished( c);
+		const sp_matcher_ctx::Dict& d = c->prod.dct;
+		const sp_matcher_ctx::DictOrder& o = c->prod.ord;
+		const sp_matcher_ctx::Postings& s = c->prod.pst;
+		const sp_matcher_ctx::Positions& x = c->prod.pos;
+		if (!c->prod.trm.run.done || !d.run.done || !o.run.done || !s.run.done || !x.run.done)
+			throw std::runtime_error( "no order, postings and positions of the last dictionary of the last finished batch (sp_matcher_ctx_finished_dictionary_order_device, sp_matcher_ctx_finished_postings_device, sp_matcher_ctx_finished_positions_device)");
+		sp_matcher_ctx::PostingBlocks& q = c->prod.pbk;
+		// (the dictionary call waited for ndict, the positions call for nocc: the one wait of this call is for nbytes)
+		ProductCall call( c, q.run, stream, ProductCall::Sized());
+		const uint64_t ndict = d.total, nterms = s.nterms, nocc = x.nocc;
+		if (o.ndict != ndict || s.ndict != ndict || x.nterms != nterms || s.ndocs != call.ndocs || ndict >= 0xFFFFFFFFull || nterms >= 0xFFFFFFFFull || (ndict && !nterms))
+			throw std::runtime_error( "the order, the postings or the positions are not those of the dictionary of the finished batch");
+		const uint32_t B = termBlockEntries();
+		const uint64_t nblocks = (ndict + B - 1) / B;
+		reserveOrNoMem( q.dBlockOffsets, (nblocks+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dBlockSize, (nblocks+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dListOffsets, (ndict+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dListStart, (ndict+1)*sizeof(uint64_t));
+		reserveOrNoMem( q.dPostingBytes, (nterms+1)*sizeof(uint64_t));
+		// behind the order, the postings and the positions, which nobody has waited for yet
+		call.beginBehind( o.run.stream, o.run.ev[ 1], q.dTotals, 4, q.dCursor, 1);
+		if (call.stream != s.run.stream) HIP_CHECK( hipStreamWaitEvent( call.stream, s.run.ev[ 1], 0));
+		if (call.stream != x.run.stream) HIP_CHECK( hipStreamWaitEvent( call.stream, x.run.ev[ 1], 0));
+		PostingBlocksParams P;
+		std::memset( &P, 0, sizeof(P));
+		P.order = (const uint32_t*)o.dOrder.ptr; P.entryOffsets = (const uint64_t*)s.dEntryOffsets.ptr; P.postings = (const uint32_t*)s.dPostings.ptr;
+		P.postingOffsets = (const uint64_t*)x.dPostingOffsets.ptr; P.postingPositions = (const uint32_t*)x.dPostingPositions.ptr;
+		P.occurrences = (const uint32_t*)x.dOccurrences.ptr;
+		P.ndict = (uint32_t)ndict; P.ndocs = (uint32_t)call.ndocs; P.nterms = nterms; P.nocc = nocc; P.blockEntries = B; P.nblocks = (uint32_t)nblocks;
+		P.listOffsets = (uint64_t*)q.dListOffsets.ptr; P.listStart = (uint64_t*)q.dListStart.ptr; P.postingBytes = (uint64_t*)q.dPostingBytes.ptr;
+		P.blockSize = (uint64_t*)q.dBlockSize.ptr; P.blockOffsets = (uint64_t*)q.dBlockOffsets.ptr; P.totals = (uint64_t*)q.dTotals.ptr;
+		uint64_t totals[ 4] = { 0, 0, B, 0};
+		if (ndict)
+		{
+			call.passes( P, launchL2PostingBlocksCount, launchL2PostingBlocksPlace, q.dTotals, totals, 4, [&]{
+				reserveOrNoMem( q.dBytes, totals[ 1] + 16);
+				P.bytes = (uint8_t*)q.dBytes.ptr; P.capacity = totals[ 1];
+			});
+		}
+		else
+		{
+			// nothing to code, nothing to launch: block_offsets = [0], the totals {0, 0, B, 0}
+			HIP_CHECK( hipEventRecord( q.run.ev[ 0], call.stream));
+			HIP_CHECK( hipMemsetAsync( q.dBlockOffsets.ptr, 0, sizeof(uint64_t), call.stream));
+			HIP_CHECK( hipMemsetD32Async( (hipDeviceptr_t)((uint64_t*)q.dTotals.ptr + 2), (int)B, 1, call.stream));
+			HIP_CHECK( hipEventRecord( q.run.ev[ 1], call.stream));
+			q.run.completed( call.stream);
+		}
+		q.ndict = ndict; q.nblocks = nblocks; q.nbytes = totals[ 1]; q.blockEntries = B;
+		if (out)
+		{
+			out->ndict = (size_t)ndict; out->nblocks = (size_t)nblocks; out->nbytes = (size_t)totals[ 1]; out->block_entries = B;
+			out->d_bytes = q.dBytes.ptr; out->d_block_offsets = q.dBlockOffsets.ptr; out->d_totals = q.dTotals.ptr;
+		}
+	});
+}
+
+// plain copy of the blocks' buffers
+int sp_matcher_ctx_finished_posting_blocks_fetch( sp_matcher_ctx_t* c, sp_match_posting_blocks_t* out)
+{
+	const sp_matcher_ctx::PostingBlocks& q = c->prod.pbk;
+	return fetchProduct( c, q.run, "no posting blocks of the last order, postings and positions of this context (sp_matcher_ctx_finished_posting_blocks_device)", out, sp_match_posting_blocks_free, [&]{
+		allocMatchPostingBlocks( out, q.ndict, q.nblocks, q.blockEntries);
+		allocMatchPostingBlockBytes( out, q.nbytes);
+		if (q.nbytes) copySync( c->own, out->bytes, q.dBytes.ptr, q.nbytes, hipMemcpyDeviceToHost);
+		copySync( c->own, out->block_offsets, q.dBlockOffsets.ptr, (q.nblocks+1)*sizeof(uint64_t), hipMemcpyDeviceToHost);
+		copySync( c->own, out->totals, q.dTotals.ptr, 4*sizeof(uint64_t), hipMemcpyDeviceToHost);
+	});
+}
+
+// duration of the launches of the last posting-blocks call in milliseconds (HIP events on its stream; the memsets that clear the
+// totals are enqueued before the first event; the host's one wait lies inside)
+int sp_matcher_ctx_last_posting_blocks_ms( sp_matcher_ctx_t* c, double* ms) { return c->prod.pbk.run.ms( 0, 1, ms); }
 
 } // extern "C"

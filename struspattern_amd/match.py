@@ -2,7 +2,7 @@
 through the MI355X lexer + rule automaton, print tokens (-K) and results in the reference tool's
 listing format (doc/webpage/introduction_struspattern.htm:178-260).
 
-    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] [--postings] [--positions] [--sorted] [--blocks] file [file ...]
+    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] [--postings] [--positions] [--sorted] [--blocks] [--posting-blocks] file [file ...]
 
 Every file is one document (plain UTF-8 text; the reference tool segments XML with strusAnalyzer's
 segmenters, which are outside this engine -- pass -o to add the offset of the text inside its original
@@ -32,6 +32,10 @@ whatever order the files are named, up to the file indices inside the `post` lin
 read back from the blocks alone, listed behind the other lines: one line per block, `block J NAME: entries N bytes M head 'VALUE'`
 -- the pattern and the value of its head --, and `blocks J bytes M uncoded value bytes U`.  These lines do not depend on the
 order of the files.
+--posting-blocks implies --blocks and --positions; the posting lists with their positions are written in the sorted order as
+delta-coded posting blocks on the GPU (finishedPostingBlocksDevice) and, read back from the blocks alone, listed behind the `block`
+lines: one line per block, `postblock J: lists N postings M positions Q bytes X`, and `postblocks J bytes X positions Q`.  List k
+of these blocks is the term at position k of the term blocks.  The lines do not depend on the order of the files.
 All files go to the GPU as one batch.  There is no CPU fallback.
 """
 import argparse
@@ -57,9 +61,12 @@ def main(argv=None):
     ap.add_argument("--positions", action="store_true", help="implies --postings; after every file of a posting line, the distinct positions of the term in it")
     ap.add_argument("--sorted", action="store_true", help="implies --dictionary; its lines and those of --postings by pattern, then by value")
     ap.add_argument("--blocks", action="store_true", help="implies --sorted; after its lines, the front-coded term blocks of the sorted dictionary")
+    ap.add_argument("--posting-blocks", action="store_true", help="implies --blocks and --positions; after the term blocks, the delta-coded posting blocks in the same order")
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("files", nargs="+")
     args = ap.parse_args(argv)
+    args.blocks = args.blocks or args.posting_blocks
+    args.positions = args.positions or args.posting_blocks
     args.postings = args.postings or args.positions
     args.sorted = args.sorted or args.blocks
     args.dictionary = args.dictionary or args.postings or args.sorted
@@ -89,6 +96,7 @@ def main(argv=None):
     positions = device_positions(mctx) if args.positions else None
     order = device_dictionary_order(mctx) if args.sorted else None
     blocks = device_term_blocks(mctx) if args.blocks else None
+    posting_blocks = device_posting_blocks(mctx) if args.posting_blocks else None
     freq = frequencies(mctx) if args.frequencies else None
     for di, fn in enumerate(args.files):
         print("%s:" % fn)
@@ -106,6 +114,7 @@ def main(argv=None):
     print_dictionary(dictionary, terms, mt, order)
     print_postings(postings, dictionary, terms, mt, positions, order)
     print_blocks(blocks, mt)
+    print_posting_blocks(posting_blocks)
     print("OK done")
     return 0
 
@@ -136,6 +145,30 @@ def block_lines(blocks, pattern_name):
         lines.append("block %d %s: entries %d bytes %d head '%s'" % (j, pattern_name(entries[0][0]), len(entries), int(blocks.block_offsets[j + 1] - blocks.block_offsets[j]),
                                                                       entries[0][1].decode("utf-8", "replace")))
     return lines + ["blocks %d bytes %d uncoded value bytes %d" % (len(blocks.block_handles), len(blocks.bytes), int(blocks.totals[3]))]
+
+
+def device_posting_blocks(mctx):
+    """--posting-blocks: the postings and their positions in the order that device_dictionary_order built, delta-coded in the
+    blocks of the term blocks on the device"""
+    mctx.finishedPostingBlocksDevice()
+    return mctx.finishedPostingBlocksFetch()
+
+
+def posting_block_lines(blocks):
+    """the lines of --posting-blocks, from the blocks alone"""
+    lines = []
+    for j in range(len(blocks.block_offsets) - 1):
+        lists = blocks.block(j)
+        lines.append("postblock %d: lists %d postings %d positions %d bytes %d" % (j, len(lists), sum(len(q) for q in lists), sum(len(p[2]) for q in lists for p in q),
+                                                                                    int(blocks.block_offsets[j + 1] - blocks.block_offsets[j])))
+    return lines + ["postblocks %d bytes %d positions %d" % (len(blocks.block_offsets) - 1, len(blocks.bytes), int(blocks.totals[3]))]
+
+
+def print_posting_blocks(blocks):
+    if blocks is None:
+        return
+    for line in posting_block_lines(blocks):
+        print(line)
 
 
 def print_blocks(blocks, mt):
@@ -270,8 +303,10 @@ def paragraphs(args, prg, lx, mt, docs):
     with_terms = args.terms or args.dictionary
     found = spa.matchSegmentedDocs(lctx, mctx, text, seg_offsets, doc_seg_offsets, with_values=args.device_values, with_terms=with_terms,
                                    with_dictionary=args.dictionary, with_postings=args.postings, with_positions=args.positions,
-                                   with_dictionary_order=args.sorted, with_term_blocks=args.blocks)
-    order = blocks = None
+                                   with_dictionary_order=args.sorted, with_term_blocks=args.blocks, with_posting_blocks=args.posting_blocks)
+    order = blocks = posting_blocks = None
+    if args.posting_blocks:
+        found, posting_blocks = found[:-1], found[-1]                           # (the posting blocks come last, behind the term blocks)
     if args.blocks:
         found, blocks = found[:-1], found[-1]                                   # (the blocks come last, behind the order)
     if args.sorted:
@@ -309,6 +344,7 @@ def paragraphs(args, prg, lx, mt, docs):
     print_dictionary(dictionary, terms, mt, order)
     print_postings(postings, dictionary, terms, mt, positions, order)
     print_blocks(blocks, mt)
+    print_posting_blocks(posting_blocks)
     print("OK done")
     return 0
 

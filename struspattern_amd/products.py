@@ -549,3 +549,62 @@ def batchPositions(mb, terms, postings):
     b, keep = _host_batch(mb)                                        # (keep: until the call has returned)
     t, q = _to_c(terms, keep), _to_c(postings, keep, ndocs=len(terms.doc_offsets) - 1)
     return _twin(MatchPositions, "sp_match_batch_positions", ctypes.byref(b), ctypes.byref(t), ctypes.byref(q))
+
+
+class MatchPostingBlocks:
+    """The posting blocks of a batch (host copies): the posting lists with their positions in the sorted order of the dictionary,
+    cut into the blocks of the term blocks and delta-coded, each block decodable from its own bytes
+    (include/strus_pattern_amd.h "posting blocks").  List k is the term at position k of the MatchTermBlocks of the same batch:
+    the two together are the index segment of the batch."""
+    _C, _SCALARS, _TOTAL, _WHAT = capi.SpMatchPostingBlocks, ("ndict", "block_entries"), None, "posting blocks of the batch"
+    _FREE, _FETCH = "sp_match_posting_blocks_free", "sp_matcher_ctx_finished_posting_blocks_fetch"
+    _ARRAYS = (
+        Arr("bytes", "bytes", "nbytes", 0, 0, ctypes.c_uint8),             # the codes of all sorted positions, without gaps
+        Arr("block_offsets", "block_offsets", "nblocks", 1, 0, u64),       # block j is bytes[block_offsets[j]:block_offsets[j+1]]
+        Arr("totals", "totals", None, 4, 0, u64),                          # nblocks, nbytes, block_entries, the position varints written
+    )
+
+    def __init__(self, bytes, block_offsets, totals, ndict=0, block_entries=16):
+        self.bytes, self.block_offsets, self.totals = bytes, block_offsets, totals
+        self.ndict, self.block_entries = ndict, block_entries
+
+    def block(self, j):
+        """the lists of block j, decoded by the library's reader from the block alone: per sorted position a list of
+        (doc, count, [positions]) in document order"""
+        keep = []
+        s = _to_c(self, keep)                                          # (keep: until the calls have returned)
+        nl, np_, nq, err = ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.c_size_t(0), ctypes.create_string_buffer(256)
+        counts = (ctypes.byref(nl), ctypes.byref(np_), ctypes.byref(nq), err, 256)
+        call = capi.lib().sp_match_posting_blocks_decode_block
+        rc = call(ctypes.byref(s), j, None, 0, None, 0, None, 0, *counts)
+        if rc == 0:
+            lists, postings, positions = (u32 * max(nl.value, 1))(), (capi.SpBlockPosting * max(np_.value, 1))(), (u32 * max(nq.value, 1))()
+            rc = call(ctypes.byref(s), j, lists, nl.value, postings, np_.value, positions, nq.value, *counts)
+        if rc != 0:
+            raise PatternError("no block %d of the %s (%d): %s" % (j, self._WHAT, rc, err.value.decode()))
+        out, at = [], 0
+        for n in lists[:nl.value]:
+            out.append([(p.doc, p.count, list(positions[p.position_offset:p.position_offset + p.npos])) for p in postings[at:at + n]])
+            at += n
+        return out
+
+    def lists(self):
+        """all lists in sorted order: per sorted position [(doc, count, [positions])]"""
+        return [entry for j in range(len(self.block_offsets) - 1) for entry in self.block(j)]
+
+    def postings(self, k):
+        """the list of sorted position k -- MatchTermBlocks.find(handle, value) gives the k -- as [(doc, count, [positions])],
+        decoding only its block"""
+        B = int(self.block_entries)
+        if not 0 <= k < self.ndict:
+            raise PatternError("no sorted position %d in the %s" % (k, self._WHAT))
+        return self.block(k // B)[k % B]
+
+
+def batchPostingBlocks(dictionary, order, postings, positions):
+    """The posting blocks of a dictionary already on the host (dictionary: the MatchDictionary, order: its MatchDictionaryOrder,
+    postings: its MatchPostings, positions: their MatchPositions: the fetches of a context, or the twins), by the rule of the
+    device call, without a device, a batch or a source.  Returns a MatchPostingBlocks."""
+    keep = []                                                        # (until the call has returned)
+    d, o, q, x = _to_c(dictionary, keep), _to_c(order, keep), _to_c(postings, keep), _to_c(positions, keep)
+    return _twin(MatchPostingBlocks, "sp_match_batch_posting_blocks", ctypes.byref(d), ctypes.byref(o), ctypes.byref(q), ctypes.byref(x))
