@@ -4,6 +4,13 @@
 
 namespace {
 
+// SPA_WORDS_ABLATE (measurement builds only, never the product: the records come out wrong): bit 0 leaves out the confirming walks
+// (every shape candidate stays dead), bit 1 the shape probes, bit 2 the literal probe, bit 3 the whole flush.  The instruction
+// counters of two such builds differ by what the phase left out retires (the words kernel's table).
+#ifndef SPA_WORDS_ABLATE
+#define SPA_WORDS_ABLATE 0
+#endif
+
 // ---------------------------------------------------------------- words kernel: whole-word literals and word shapes
 // A lane per byte, a wave per scan unit (a document, or a chunk of a long one): everything here is parallel over the text.
 // Where a run of word characters ends, the lane behind it knows the run (start, length, polynomial hash -- one ballot and one
@@ -58,28 +65,35 @@ __device__ __forceinline__ u32 confirmWalk( const unsigned char* doc, u32 docLen
 	if (!R) return to;
 	const u64 shiftDst = T.at( T.oShift + pass*64 + ln), selfLoop = T.at( T.oSelf + pass*64 + ln);
 	const u32 nEx = P.exCount[ pass];
+	u32 nExWave = 0;			// the most exceptions a pass of the wave's walks has: a wave-uniform bound for the loop over them
+	while (__ballot( nEx > nExWave)) ++nExWave;
 	u32 from = to;
 	u32 j = to;				// R = positions that consumed byte j-1
-	while (R && j > 0)
+	// One loop condition and selects inside: a step costs the scalar unit the loop control alone.  The walk leaves the ring at the
+	// first j with 2 <= j and j-2 < ringLo: j counts down by one from `to`, so that is j == ringLo+1 (or `to` itself when it is
+	// below already), and never when ringLo is 0 or the walk begins at 1 -- jStop.  The step of j == 1 (the byte before the text is
+	// the edge) goes through the transition too: what it leaves in R is not looked at again, j is 0 then.
+	const u32 jStop = (ringLo > 0 && to >= 2u) ? ringLo + 1u : 0u;
+	while ((R != 0) & (j > jStop))
 	{
-		if (j >= 2u && j-2u < ringLo)
-		{
-			// (rare: a match longer than the ring) the rest of the walk from global memory
-			const u32 f = leftmostStart<LDS,false>( doc, docLen, P, T, word, mask, j, R);
-			return f < j ? f : from;
-		}
-		const u32 cc = j >= 2u ? (u32)ring[ (j-2u) & (WORD_RING-1)] : ((u32)CTX_EDGE << 8);
-		if (R & T.at( T.oStart + (pass*CTX_COUNT + (cc >> 8))*64 + ln)) from = j-1u;
-		if (j == 1u) break;
+		const u32 inRing = ring[ (j-2u) & (WORD_RING-1)];
+		const u32 cc = j >= 2u ? inRing : ((u32)CTX_EDGE << 8);
+		from = (R & T.at( T.oStart + (pass*CTX_COUNT + (cc >> 8))*64 + ln)) ? j-1u : from;
 		u64 Rp = ((R & shiftDst) >> 1) | (R & selfLoop);
-		for (u32 e=0; e<nEx; ++e)
+		for (u32 e=0; e<nExWave; ++e)
 		{
-			const u32 at = (pass*P.maxExceptions + e)*64 + ln;
+			const u32 at = (pass*P.maxExceptions + (e < nEx ? e : 0u))*64 + ln;
 			const u64 es = T.at( T.oExSrc + at), ed = T.at( T.oExDst + at);
-			Rp |= (R & ed) ? es : 0ull;
+			Rp |= ((e < nEx) & ((R & ed) != 0)) ? es : 0ull;
 		}
 		R = Rp & mask & T.at( T.oChar + (pass*P.nofClasses + (cc & 0xFFu))*64 + ln);
 		--j;
+	}
+	if ((R != 0) & (j > 0))			// (stopped at jStop with positions alive)
+	{
+		// (rare: a match longer than the ring) the rest of the walk from global memory
+		const u32 f = leftmostStart<LDS,false>( doc, docLen, P, T, word, mask, j, R);
+		return f < j ? f : from;
 	}
 	return from;
 }
@@ -89,6 +103,7 @@ __device__ __forceinline__ u32 confirmWalk( const unsigned char* doc, u32 docLen
 template <bool LDS>
 __device__ __forceinline__ void wordsFlush( LexWave& w, const L1Params& P, const LexTab<LDS>& T, const unsigned short* ring, const u32 ringLo, u32* ends, const u32 count, const u32 nVar)
 {
+	if (SPA_WORDS_ABLATE & 8) return;
 	const u32 len = w.docLen;
 	const bool emit = LANE < count;
 	u32 to = 0, pFrom = 0, pH = 0, qH = 0, pLen = 0, qLen = 0;
@@ -107,7 +122,7 @@ __device__ __forceinline__ void wordsFlush( LexWave& w, const L1Params& P, const
 	u32 total = 0, lit0 = 0;
 	if (emit)
 	{
-		if (P.nofLiterals && pLen <= 64u)
+		if (!(SPA_WORDS_ABLATE & 4) && P.nofLiterals && pLen <= 64u)
 		{
 			// whole-word literal (the probe of tileLiterals)
 			const u32 h = literalHashFinish( pH);
@@ -150,7 +165,7 @@ __device__ __forceinline__ void wordsFlush( LexWave& w, const L1Params& P, const
 	}
 	// ---- shape variants: the key bytes come out of two unaligned words of the text (the run's first four bytes, its last
 	// four); the compact table (fingerprint, pattern or list) sits in LDS beside the automaton tables: no global round trip
-	if (nVar)
+	if (nVar && !(SPA_WORDS_ABLATE & 2))
 	{
 		u32 first4 = 0, last4 = 0;
 		if (emit)
@@ -158,6 +173,12 @@ __device__ __forceinline__ void wordsFlush( LexWave& w, const L1Params& P, const
 			if (pFrom + 4u <= len) first4 = ld32u( w.doc + pFrom); else for (u32 i=0; i<4u && pFrom+i<len; ++i) first4 |= (u32)w.doc[ pFrom+i] << (8*i);
 			if (to >= 4u) last4 = ld32u( w.doc + to - 4u); else for (u32 i=0; i<to; ++i) last4 |= (u32)w.doc[ i] << (8*(4u-to+i));
 		}
+		// (the key of every kind by selects on the variant's wave-uniform fields -- no branch per kind and lane; the first two
+		//  probes as straight-line code, both entries requested before the first compare: the loop is entered only when a ballot
+		//  says that a lane still probes)
+		const u32 prevTag = (emit && qLen >= 1u && qLen <= 64u) ? ((u32)SHAPE_PREVWORD | (qLen << 8)) : 0u;
+		const u32 prevKey = literalHashFinish( qH);
+		const u32 shapeMask = uni( P.shapeMask), fpOffset = uni( P.shapeFpOffset), salt = uni( P.shapeSalt);
 #pragma unroll
 		for (int v=0; v<SHAPE_MAXVARIANTS; ++v)
 		{
@@ -166,30 +187,38 @@ __device__ __forceinline__ void wordsFlush( LexWave& w, const L1Params& P, const
 				const u32 var = uni( P.shapeVariants[ v]);
 				const u32 kind = var & 3u, o = (var >> 2) & 3u, k = (var >> 4) & 7u;
 				const u32 kmask = k >= 4u ? 0xFFFFFFFFu : ((1u << (8*k)) - 1u);
-				if (emit)
+				const bool isPrev = kind == (u32)SHAPE_PREVWORD, isPrefix = kind == (u32)SHAPE_PREFIX;
+				const u32 need = isPrefix ? o + k : k;
+				const u32 shift = isPrefix ? 8*o : (k >= 4u ? 0u : 8*(4u-k));
+				u32 tag = isPrev ? prevTag : ((emit && pLen >= need) ? var : 0u);
+				u32 key = isPrev ? prevKey : (((isPrefix ? first4 : last4) >> shift) & kmask);
+				if (isPrefix && o + k > 4u)
 				{
-					u32 tag = 0, key = 0;
-					if (kind == (u32)SHAPE_PREVWORD) { if (qLen >= 1u && qLen <= 64u) { tag = (u32)SHAPE_PREVWORD | (qLen << 8); key = literalHashFinish( qH); } }
-					else if (kind == (u32)SHAPE_PREFIX)
+					// (a prefix key that reaches behind the run's first four bytes: byte by byte)
+					key = 0;
+					if (tag) for (u32 i=0; i<k; ++i) key |= (u32)w.doc[ pFrom + o + i] << (8*i);
+				}
+				const u32 fp = shapeFingerprint( tag, key, salt);
+				u32 slot = shapeSlotHash( tag, key) & shapeMask;
+				const u64 e0 = T.at( fpOffset + slot), e1 = T.at( fpOffset + ((slot+1) & shapeMask));	// fingerprint | (count << 24 | pattern or list) << 32
+				const bool hit0 = tag && (u32)e0 == fp;
+				const bool second = tag && (u32)e0 && (u32)e0 != fp && shapeMask >= 1u;
+				const bool hit1 = second && (u32)e1 == fp;
+				const bool more = second && (u32)e1 && (u32)e1 != fp && shapeMask >= 2u;
+				const u32 eh = (u32)((hit0 ? e0 : e1) >> 32);
+				lb[ 1+v] = (hit0 || hit1) ? (eh & 0xFFFFFFu) : 0u;
+				lc[ 1+v] = (hit0 || hit1) ? (eh >> 24) : 0u;
+				if (__ballot( more))
+				{
+					if (more)
 					{
-						if (pLen >= o + k)
+						slot = (slot+2) & shapeMask;
+						for (u32 probes=2; probes<=shapeMask; ++probes)
 						{
-							tag = var;
-							if (o + k <= 4u) key = (first4 >> (8*o)) & kmask;
-							else for (u32 i=0; i<k; ++i) key |= (u32)w.doc[ pFrom + o + i] << (8*i);
-						}
-					}
-					else if (pLen >= k) { tag = var; key = k >= 4u ? last4 : (last4 >> (8*(4u-k))); }
-					if (tag)
-					{
-						const u32 fp = shapeFingerprint( tag, key, P.shapeSalt);
-						u32 slot = shapeSlotHash( tag, key) & P.shapeMask;
-						for (u32 probes=0; probes<=P.shapeMask; ++probes)
-						{
-							const u64 e = T.at( P.shapeFpOffset + slot);		// fingerprint | (count << 24 | pattern or list) << 32
+							const u64 e = T.at( fpOffset + slot);
 							if (!(u32)e) break;
 							if ((u32)e == fp) { lb[ 1+v] = (u32)(e >> 32) & 0xFFFFFFu; lc[ 1+v] = (u32)(e >> 56); break; }
-							slot = (slot+1) & P.shapeMask;
+							slot = (slot+1) & shapeMask;
 						}
 					}
 				}
@@ -280,7 +309,8 @@ __device__ __forceinline__ void wordsFlush( LexWave& w, const L1Params& P, const
 			const uint4 cnd = stage[ LANE];
 			u32 fromOut = cnd.z, flags = (u32)L1_LITERAL_FLAG;
 			const u32 pi = cnd.y & ~(u32)L1_LITERAL_FLAG;
-			if (!(cnd.y & (u32)L1_LITERAL_FLAG))
+			if ((SPA_WORDS_ABLATE & 1) && !(cnd.y & (u32)L1_LITERAL_FLAG)) flags |= (u32)L1_DEAD_FLAG;
+			else if (!(cnd.y & (u32)L1_LITERAL_FLAG))
 			{
 				const uint2 pw = *(const uint2*)((const u32*)&P.patterns[ pi] + 5);	// {maskLo, maskHi}
 				const u32 word = ((const u32*)&P.patterns[ pi])[ 1];
@@ -336,11 +366,13 @@ __device__ __forceinline__ void wordsUnit( LexWave& w, const L1Params& P, const 
 		{
 			const u32 Hs = (u32)__shfl_up( (int)H, d), Ms = (u32)__shfl_up( (int)M, d);
 			const bool take = isW && (int)LANE >= d && (int)LANE - d >= ss;
-			if (take) { H = Hs * M + H; M = Ms * M; }
+			// (a lane that takes nothing multiplies by the neutral pair: selects, no exec-mask branch per step)
+			const u32 Ht = take ? Hs : 0u, Mt = take ? Ms : 1u;
+			H = Ht * M + H; M = Mt * M;
 		}
 		const bool carried = isW && ss < 0;
 		const u32 Htot = carried ? c.hash * M + H : H;
-		u32 runLen = isW ? (carried ? c.len + LANE + 1u : LANE - (u32)ss + 1u) : 0u;
+		u32 runLen = isW ? (carried ? c.len : 0u - (u32)ss) + LANE + 1u : 0u;
 		if (runLen > 65u) runLen = 65u;
 		const u32 from = carried ? c.start : tile + (u32)(ss < 0 ? 0 : ss);
 		u32 pH = (u32)__shfl_up( (int)Htot, 1), pLen = (u32)__shfl_up( (int)runLen, 1), pFrom = (u32)__shfl_up( (int)from, 1);
@@ -354,11 +386,11 @@ __device__ __forceinline__ void wordsUnit( LexWave& w, const L1Params& P, const 
 			const u32 src = want - tile;			// lane that saw it end, if in this tile
 			const u32 sH = (u32)__builtin_amdgcn_ds_bpermute( (int)((src & 63u) << 2), (int)pH);
 			const u32 sLen = (u32)__builtin_amdgcn_ds_bpermute( (int)((src & 63u) << 2), (int)pLen);
-			if (isEnd && pFrom >= 2u)
-			{
-				if (want >= tile) { if ((endMask >> (src & 63u)) & 1ull) { qH = sH; qLen = sLen; } }
-				else if (c.lastValid && c.lastTo == want) { qH = c.lastHash; qLen = c.lastLen; }
-			}
+			const bool inTile = want >= tile;
+			const bool fromTile = inTile && ((endMask >> (src & 63u)) & 1ull), fromCarry = !inTile && c.lastValid && c.lastTo == want;
+			const bool hasPrev = isEnd && pFrom >= 2u && (fromTile || fromCarry);
+			qH = hasPrev ? (fromTile ? sH : c.lastHash) : 0u;
+			qLen = hasPrev ? (fromTile ? sLen : c.lastLen) : 0u;
 		}
 		// ---- the ends that count go behind the ones that wait
 		const bool emit = isEnd && pLen >= 1u && ((to >= segBeg && to < segEnd) || (to == segEnd && segEnd == len));
