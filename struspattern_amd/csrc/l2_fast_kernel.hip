@@ -67,6 +67,17 @@ enum {NIL16=0xFFFFu};
 #define PROF_ADD( SLOT) do {} while (0)
 #endif
 
+// Measurement builds of the install path (EXTRA=-DSPA_FAST_ABLATE=N through the Makefile; the records of such a build are wrong,
+// only its counters are read).  Every level N >= 1 empties the document's rule state after each event -- bucket sizes, expiry rows,
+// rule ids, dispose list --, so nothing an install stores is ever seen by a scan or an expiry and every store lands where it lands
+// in a document's first event.  Levels, each on top of the one before: 1 the installs run whole (what it leaves out is everything
+// downstream of them), 2 no stores of the compact form, 3 no stores of the static form, 4 no rule id allocation, 5 no install at all.
+// A phase is the difference of two neighbours.  (The bucket capacity check is in no level: it is what keeps the stores of the
+// other levels inside their regions.)
+#ifndef SPA_FAST_ABLATE
+#define SPA_FAST_ABLATE 0
+#endif
+
 __device__ __forceinline__ u64 lanesBelow() { return (1ull << LANE) - 1ull; }
 __device__ __forceinline__ u32 evhash( u32 a)		// src/ruleMatcherAutomaton.cpp:34-40
 {
@@ -1094,26 +1105,34 @@ static __device__ __forceinline__ void installBatch( LR L, Wave& w, KP P, u32 kb
 			const u32 row = (sord + (c1.y & FSM_RANGE_MASK)) & ((1u << P.expShift) - 1u);
 			u32 cnt = 0, oldB[ 2] = {0,0}, metaB[ 2] = {0,0};
 			bool inst[ 3] = {false,false,false}; u32 hB[ 3] = {0,0,0};
-			if (have)
 			{
+				// (every lane reads: a lane without a program or without that trigger has a zero line -- the row of range 0, bucket 0 --
+				// and reads counts it never uses; a lane-conditional region per read costs more than the reads)
 				cnt = (u32)L.expCnt[ row];
 #pragma unroll
 				for (int t=0; t<2; ++t)
 				{
-					if (info[ t] & FSI_PRESENT) { hB[ t] = (info[ t] >> FSI_BUCKET_SHIFT) & 15u; inst[ t] = true; oldB[ t] = L.bsize[ hB[ t]]; metaB[ t] = L.bmeta[ hB[ t]]; }
+					hB[ t] = (info[ t] >> FSI_BUCKET_SHIFT) & 15u; inst[ t] = (info[ t] & FSI_PRESENT) != 0;
+					oldB[ t] = L.bsize[ hB[ t]]; metaB[ t] = L.bmeta[ hB[ t]];
 				}
 			}
 			w.nInstalled += nb;
 			u32 r;
+#if SPA_FAST_ABLATE < 4
 			if (!allocRuleIds( L, w, P, __ballot( have), r)) return;
+#else
+			r = LANE < (u32)R ? LANE : 0u;
+#endif
 			if (!w.spill)
 			{
 				if (__ballot( have && cnt + nb > ((u32)FAST_EXPCAP >> P.expShift))) w.spill = 1;	// (upper bound: the whole batch in my row)
 			}
 			if (!checkBuckets( L, w, P, uni( c1.w) & 0xFFu, inst, hB)) return;
 			PROF_I( 7, cnt + oldB[ 0] + oldB[ 1] + r);
+#if SPA_FAST_ABLATE < 2
 			if (w.spill) installCompactT<true>( L, w, P, kb + base, nb, sord, r, c0, c1, row, cnt, oldB, metaB);
 			else installCompactT<false>( L, w, P, kb + base, nb, sord, r, c0, c1, row, cnt, oldB, metaB);
+#endif
 			PROF_I( 11, 0u);
 			w.bsizeV = L.bsize[ LANE & 15u];
 			continue;
@@ -1200,7 +1219,11 @@ static __device__ __forceinline__ void installBatch( LR L, Wave& w, KP P, u32 kb
 			w.nSignals += (u32)__builtin_amdgcn_readlane( incl, 63);
 		}
 		u32 r;
+#if SPA_FAST_ABLATE < 4
 		if (!allocRuleIds( L, w, P, matMask, r)) return;
+#else
+		r = LANE < (u32)R ? LANE : 0u;
+#endif
 		// ---- an expiry row or a bucket that outgrows its LDS region switches the document to the two-place accessors
 		if (nmat && !w.spill)
 		{
@@ -1217,8 +1240,10 @@ static __device__ __forceinline__ void installBatch( LR L, Wave& w, KP P, u32 kb
 		}
 		if (isStatic)
 		{
+#if SPA_FAST_ABLATE < 3
 			if (w.spill) installStaticT<true>( L, w, P, kb + base, nb, sord, r, q0, q1, q2, q3);
 			else installStaticT<false>( L, w, P, kb + base, nb, sord, r, q0, q1, q2, q3);
+#endif
 		}
 		else if (w.spill) installBatchT<true>( L, w, P, kb, nb, sord, matMask, r, q0, q1, q2, sim);
 		else installBatchT<false>( L, w, P, kb, nb, sord, matMask, r, q0, q1, q2, sim);
@@ -1372,7 +1397,15 @@ static __device__ __forceinline__ void runKernel()
 				}
 				PROF_ADD( 0);
 				if (w.err) break;
+#if SPA_FAST_ABLATE < 5
 				if (kc) installBatch( L, w, P, kb, kc, ordpos, pc0, pc1);
+#endif
+#if SPA_FAST_ABLATE >= 1
+				if (LANE < 16u) L.bsize[ LANE] = 0;
+				L.expCnt[ LANE] = 0;
+				w.bsizeV = 0; w.expCntV = 0; w.nDispose = 0; w.nTrig = 0; w.freeN = 0; w.usedL = 0; w.sFreeN = 0; w.usedS = 0; w.spill = 0;
+				WAVE_FENCE();
+#endif
 				PROF_ADD( 1);
 				if (w.err) break;
 				// (the rules that finished or were deleted are deactivated at the top of the next event, together with the rules that expire there)
