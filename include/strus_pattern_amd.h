@@ -1249,6 +1249,138 @@ int sp_match_batch_posting_blocks(const sp_match_dictionary_t* dict, const sp_ma
 int sp_match_posting_blocks_decode_block(const sp_match_posting_blocks_t* pb, size_t j, uint32_t* list_postings, size_t nlists_cap,
                                          sp_block_posting_t* postings, size_t npostings_cap, uint32_t* positions, size_t npositions_cap,
                                          size_t* nlists, size_t* npostings, size_t* npositions, char* err, size_t errsize);
+
+/* ---- segment lookups: the read side of an index segment -- the term blocks and the posting blocks of one batch -- on the device:
+ * a segment object that owns device copies of the two products and holds no reference to a context, the lookup of many terms at
+ * once, exact or by prefix, and the decoded posting lists of what was found (csrc/l2_segment.h); for host copies the same rule
+ * without a device (csrc/match_segment.hpp).  The rule is the project's own, unpinned by a reference vector.
+ * THE ORDER of a segment: handles unsigned, bytes as memcmp does, a prefix before what it is a prefix of.
+ * WHAT A QUERY (h, q) MATCHES: `first` is the first sorted position whose (handle, value) is not below (h, q), ndict if there is
+ * none; the matching positions are the run from `first` on whose handle is h and whose value equals q -- under SP_LOOKUP_PREFIX:
+ * starts with q; the empty q then selects the whole handle.  The order makes the run contiguous.  An exact run has one position
+ * at most.
+ * OUTPUTS, the selection being the runs of the queries one behind the other, nsel positions (a position that two queries select
+ * appears twice):
+ *   q_first[nq], q_count[nq], q_status[nq]  (uint32) the run of every query and its status, 0 or an SP_LOOKUP_ERR_*,
+ *   q_sel_offsets[nq+1]                     (uint64) where the run of a query starts in the selection,
+ *   selections[nsel]                        one 24-byte sp_segment_selection_t per selected position,
+ *   sel_value_offsets[nsel+1]               (uint64) into `values`: the full values, reconstructed,
+ *   sel_posting_offsets[nsel+1]             (uint64) into `postings`,
+ *   postings[npostings]                     one 16-byte sp_segment_posting_t per posting of a selected position,
+ *   posting_position_offsets[npostings+1]   (uint64) into `positions`,
+ *   positions[npositions]                   (uint32) the distinct ordinal positions, absolute and ascending,
+ *   totals[4]                               (uint64) {nsel, npostings, npositions, the bytes of `values`}.
+ * INVARIANTS: every number equals what sp_match_term_blocks_decode_block and sp_match_posting_blocks_decode_block give for that
+ * position.  DETERMINISM: every output byte is a function of the segment and the queries alone.
+ * SAFETY: the bytes of a segment may come from a file.  Every read of `bytes` is bounded by the range of its block and that
+ * range by nbytes; nothing is written outside the outputs, and the emitting pass writes exactly what the sizing pass counted.
+ * A walk that meets a malformed code ends with a status: met while the run is looked for, the query gets the status and an
+ * empty run (q_first 0); met at a selected position -- the place of the run in the selection is fixed by then --, that position
+ * is selected empty (all numbers of its record but `position` are 0, no value, no posting) and its query gets the status, the
+ * largest of its positions.  The malformations are those of the two readers.
+ * KNOWN WEAKNESS: a list is walked by one lane, so a list of a megabyte is serial.
+ * LIMITS: nq, nsel, npostings and npositions below 2^32 - 1. */
+#define SP_LOOKUP_PREFIX 1u
+enum {
+	SP_LOOKUP_ERR_VARINT = 1, /* a varint that runs past its block or its list, or is longer than ten bytes */
+	SP_LOOKUP_ERR_HEAD = 2,   /* a head that does not carry its handle and its value in full */
+	SP_LOOKUP_ERR_SHARED = 3, /* a `shared` above the length of the value before */
+	SP_LOOKUP_ERR_SUFFIX = 4, /* a suffix that runs past the block */
+	SP_LOOKUP_ERR_BODY = 5,   /* a `body` of 0 or past the block, or a posting that ends beyond its `body` */
+	SP_LOOKUP_ERR_DELTA = 6,  /* a ddelta of 0 behind the first posting of a list, or a position gap of 0 behind the first position */
+	SP_LOOKUP_ERR_NPOS = 7,   /* an npos of 0 or above `count` */
+	SP_LOOKUP_ERR_RANGE = 8   /* a handle, a value length, a doc_freq, a document, a count or a position that leaves 32 bits */
+};
+typedef struct sp_segment sp_segment_t;
+typedef struct sp_segment_selection {
+	uint32_t position;      /* the sorted position */
+	uint32_t handle;
+	uint32_t doc_freq;
+	uint32_t value_bytes;
+	uint64_t count;         /* the collection frequency */
+} sp_segment_selection_t;
+typedef struct sp_segment_posting {
+	uint32_t doc;
+	uint32_t count;         /* the term frequency */
+	uint32_t npos;          /* the number of distinct positions */
+	uint32_t reserved;      /* 0 */
+} sp_segment_posting_t;
+typedef struct sp_segment_lookup_device {
+	size_t nq;
+	size_t nsel;
+	size_t npostings;
+	size_t npositions;
+	size_t nvalue_bytes;
+	uint32_t flags;
+	void* d_q_first;                   /* uint32_t[nq] */
+	void* d_q_count;                   /* uint32_t[nq] */
+	void* d_q_status;                  /* uint32_t[nq] */
+	void* d_q_sel_offsets;             /* uint64_t[nq+1] */
+	void* d_selections;                /* sp_segment_selection_t[nsel] */
+	void* d_sel_value_offsets;         /* uint64_t[nsel+1] */
+	void* d_sel_posting_offsets;       /* uint64_t[nsel+1] */
+	void* d_values;                    /* uint8_t[nvalue_bytes] */
+	void* d_postings;                  /* sp_segment_posting_t[npostings] */
+	void* d_posting_position_offsets;  /* uint64_t[npostings+1] */
+	void* d_positions;                 /* uint32_t[npositions] */
+	void* d_totals;                    /* uint64_t[4]: nsel, npostings, npositions, nvalue_bytes */
+} sp_segment_lookup_device_t;
+/* host copy of a lookup (sp_segment_lookup_free) */
+typedef struct sp_segment_lookup {
+	size_t nq;
+	size_t nsel;
+	size_t npostings;
+	size_t npositions;
+	size_t nvalue_bytes;
+	uint32_t flags;
+	uint32_t* q_first;
+	uint32_t* q_count;
+	uint32_t* q_status;
+	uint64_t* q_sel_offsets;
+	sp_segment_selection_t* selections;
+	uint64_t* sel_value_offsets;
+	uint64_t* sel_posting_offsets;
+	uint8_t* values;
+	sp_segment_posting_t* postings;
+	uint64_t* posting_position_offsets;
+	uint32_t* positions;
+	uint64_t totals[4];
+} sp_segment_lookup_t;
+/* Uploads host copies of the two products -- fetches, twin output, or bytes read back from a file -- to the current device and
+ * keeps nothing of the host arrays.  Only the tables are checked, on the host; the bytes are not decoded.  SP_ERR_INVALID with
+ * the message in `err` when ndict, nblocks or block_entries differ between the two products, nblocks is not ceil(ndict / B), B is
+ * not one of 1, 2, 4, .. 64, a block_offsets array descends, does not end at nbytes or has an empty block, or block_handles
+ * descends; SP_ERR_NOMEM and SP_ERR_DEVICE as elsewhere.  *out is NULL after a failure.  A segment is immutable; it owns its
+ * device memory and the working buffers of its lookups (sp_segment_free). */
+int sp_segment_open(const sp_match_term_blocks_t* tb, const sp_match_posting_blocks_t* pb, sp_segment_t** out, char* err, size_t errsize);
+/* The same of the term blocks and the posting blocks built last on a context, copied device-to-device on `stream` behind the two
+ * calls; the call waits for the copies, so the segment outlives the context and its next batch.  SP_ERR_INVALID (the message is
+ * the context's last error) unless both block products are valid on that context. */
+int sp_segment_from_ctx(sp_matcher_ctx_t* c, void* stream, sp_segment_t** out);
+void sp_segment_free(sp_segment_t* s);
+const char* sp_segment_last_error(sp_segment_t* s);
+/* Looks nq queries up: query i is the handle query_handles[i] with the bytes query_bytes[query_offsets[i] .. query_offsets[i+1])
+ * (host arrays, uploaded by the call, of which nothing is kept); flags is 0 for exact queries or SP_LOOKUP_PREFIX.  Everything
+ * runs on `stream`, kernel boundaries are the only ordering, no flag is spun on and no atomic decides where a byte goes (the one
+ * atomic is a maximum into q_status).  Five launches (find, runs, sizes, offsets, emit: csrc/l2_segment.h); the host waits once,
+ * behind `offsets`, for the totals that size `values`, `postings` and `positions` -- and under SP_LOOKUP_PREFIX once more behind
+ * `runs` for nsel, which an exact lookup bounds by nq.  nq == 0 or ndict == 0 launches nothing.  The outputs are device buffers
+ * of the segment, only grow and are valid until the next lookup on that segment.  SP_ERR_INVALID for unknown flags, query
+ * offsets that descend, and -- after the wait, the segment staying usable -- a limit that is reached. */
+int sp_segment_lookup_device(sp_segment_t* s, const uint32_t* query_handles, const uint64_t* query_offsets, const uint8_t* query_bytes,
+                             size_t nq, uint32_t flags, void* stream, sp_segment_lookup_device_t* out);
+/* plain copy of the buffers of the last lookup of the segment to the host (waits for it) */
+int sp_segment_lookup_fetch(sp_segment_t* s, sp_segment_lookup_t* out);
+void sp_segment_lookup_free(sp_segment_lookup_t* lk);
+/* duration of the last lookup in milliseconds (HIP events on its stream round the upload of the queries and the launches; the
+ * host's waits lie inside) */
+int sp_segment_last_lookup_ms(sp_segment_t* s, double* ms);
+/* The same rule over host copies of the two products, needs no device, and the yardstick of the device passes: the same walks
+ * (csrc/segment_walk.h), the same statuses.  Fills `out` (sp_segment_lookup_free); SP_ERR_INVALID with the message in `err` for
+ * what sp_segment_open and sp_segment_lookup_device refuse. */
+int sp_match_segment_lookup(const sp_match_term_blocks_t* tb, const sp_match_posting_blocks_t* pb, const uint32_t* query_handles,
+                            const uint64_t* query_offsets, const uint8_t* query_bytes, size_t nq, uint32_t flags,
+                            sp_segment_lookup_t* out, char* err, size_t errsize);
 /* copies the results of the last device batch to the host, grouped by document (as sp_matcher_ctx_match_docs
  * returns them, `exclusive` elimination included) */
 int sp_matcher_ctx_batch_fetch(sp_matcher_ctx_t* c, sp_match_batch_t* out);

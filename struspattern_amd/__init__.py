@@ -14,11 +14,12 @@ from .capi import SpLexem, SpResult, SpResultItem
 from .products import (SP_TERM_TEXT, SP_TERM_VALUES, SP_TEXT_ITEMS, SP_TEXT_RESULTS, SP_VALUE_ITEMS, SP_VALUE_RESULTS,   # noqa: F401 (public names)
                        MatchBatch, MatchDictionary, MatchDictionaryOrder, MatchPositions, MatchPostingBlocks, MatchPostings, MatchTermBlocks, MatchTerms, MatchText, MatchValues, PatternError, PatternFreq,
                        batchDictionary, batchDictionaryOrder, batchPatternFreq, batchPositions, batchPostingBlocks, batchPostings, batchTermBlocks, batchTerms, batchText, batchValues,
+                       SP_LOOKUP_PREFIX, Segment, SegmentLookup, segmentLookup,
                        _match_batch_of, _product, _rows)
 
 __all__ = ["PatternMatcher", "PatternMatcherInstance", "PatternMatcherContext", "PatternLexer", "PatternLexerInstance",
            "PatternLexerContext", "PatternError", "JOIN_OP", "POSITION_BIND", "matchSegmentedDocs", "MatchText", "batchText", "MatchValues", "batchValues", "PatternFreq", "batchPatternFreq", "MatchTerms", "batchTerms", "MatchDictionary", "batchDictionary", "MatchPostings", "batchPostings", "MatchPositions", "batchPositions",
-           "MatchDictionaryOrder", "batchDictionaryOrder", "MatchTermBlocks", "batchTermBlocks", "MatchPostingBlocks", "batchPostingBlocks"]
+           "MatchDictionaryOrder", "batchDictionaryOrder", "MatchTermBlocks", "batchTermBlocks", "MatchPostingBlocks", "batchPostingBlocks", "Segment", "SegmentLookup", "segmentLookup"]
 
 SP_CTX_RESULT_SETS = 1      # include/strus_pattern_amd.h: context flag of result-set mode
 SP_FINISH_CANONICAL = 1     # include/strus_pattern_amd.h: finish flag of the canonical order inside a document

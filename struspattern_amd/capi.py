@@ -210,6 +210,29 @@ class SpMatchPostingBlocks(ctypes.Structure):
     ]
 
 
+class SpSegmentSelection(ctypes.Structure):
+    _fields_ = [("position", c_u32), ("handle", c_u32), ("doc_freq", c_u32), ("value_bytes", c_u32), ("count", c_u64)]
+
+
+class SpSegmentPosting(ctypes.Structure):
+    _fields_ = [(n, c_u32) for n in ("doc", "count", "npos", "reserved")]
+
+
+class SpSegmentLookupDevice(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_size_t) for n in ("nq", "nsel", "npostings", "npositions", "nvalue_bytes")] + [("flags", c_u32)] + [
+        (n, c_vp) for n in ("d_q_first", "d_q_count", "d_q_status", "d_q_sel_offsets", "d_selections", "d_sel_value_offsets", "d_sel_posting_offsets",
+                            "d_values", "d_postings", "d_posting_position_offsets", "d_positions", "d_totals")]
+
+
+class SpSegmentLookup(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_size_t) for n in ("nq", "nsel", "npostings", "npositions", "nvalue_bytes")] + [
+        ("flags", c_u32), ("q_first", P(c_u32)), ("q_count", P(c_u32)), ("q_status", P(c_u32)), ("q_sel_offsets", P(c_u64)),
+        ("selections", P(SpSegmentSelection)), ("sel_value_offsets", P(c_u64)), ("sel_posting_offsets", P(c_u64)),
+        ("values", P(ctypes.c_uint8)), ("postings", P(SpSegmentPosting)), ("posting_position_offsets", P(c_u64)), ("positions", P(c_u32)),
+        ("totals", c_u64 * 4),
+    ]
+
+
 class SpPosting(ctypes.Structure):
     _fields_ = [(n, c_u32) for n in ("doc", "term", "count", "first_ordpos")]
 
@@ -372,6 +395,16 @@ SIGNATURES = {
     "sp_match_posting_blocks_decode_block": (ctypes.c_int, [P(SpMatchPostingBlocks), ctypes.c_size_t, P(c_u32), ctypes.c_size_t, P(SpBlockPosting), ctypes.c_size_t,
                                                              P(c_u32), ctypes.c_size_t, P(ctypes.c_size_t), P(ctypes.c_size_t), P(ctypes.c_size_t),
                                                              ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_segment_open": (ctypes.c_int, [P(SpMatchTermBlocks), P(SpMatchPostingBlocks), P(c_vp), ctypes.c_char_p, ctypes.c_size_t]),
+    "sp_segment_from_ctx": (ctypes.c_int, [c_vp, c_vp, P(c_vp)]),
+    "sp_segment_free": (None, [c_vp]),
+    "sp_segment_last_error": (c_cp, [c_vp]),
+    "sp_segment_lookup_device": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_u32, c_vp, P(SpSegmentLookupDevice)]),
+    "sp_segment_lookup_fetch": (ctypes.c_int, [c_vp, P(SpSegmentLookup)]),
+    "sp_segment_lookup_free": (None, [P(SpSegmentLookup)]),
+    "sp_segment_last_lookup_ms": (ctypes.c_int, [c_vp, P(ctypes.c_double)]),
+    "sp_match_segment_lookup": (ctypes.c_int, [P(SpMatchTermBlocks), P(SpMatchPostingBlocks), c_vp, c_vp, c_vp, ctypes.c_size_t, c_u32,
+                                                P(SpSegmentLookup), ctypes.c_char_p, ctypes.c_size_t]),
     "sp_matcher_ctx_batch_counters": (ctypes.c_int, [c_vp, P(c_u64)]),
     "sp_matcher_ctx_last_kernel_ms": (ctypes.c_double, [c_vp]),
     "sp_matcher_ctx_kernel_kind": (ctypes.c_int, [c_vp]),

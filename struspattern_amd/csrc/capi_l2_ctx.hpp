@@ -1,5 +1,6 @@
 // The rule compiler handle and the GPU match context behind the C-ABI of level 2, shared by its two translation units:
 // capi_l2.cpp (handle, context, batch launch, host entry points) and capi_l2_finished.cpp (what is made of a finished batch).
+// capi_segment.cpp reads the two block products of a context through it (sp_segment_from_ctx).
 #ifndef SPA_CAPI_L2_CTX_HPP
 #define SPA_CAPI_L2_CTX_HPP
 #include "l2_plan.hpp"
@@ -7,7 +8,7 @@
 #include "capi_util.hpp"
 #include <mutex>
 
-using namespace spa;	// (the two handles are global names of the C header; this header is only for the two files above)
+using namespace spa;	// (the two handles are global names of the C header; this header is only for the files above)
 
 struct sp_matcher
 {

@@ -2,7 +2,7 @@
 through the MI355X lexer + rule automaton, print tokens (-K) and results in the reference tool's
 listing format (doc/webpage/introduction_struspattern.htm:178-260).
 
-    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] [--postings] [--positions] [--sorted] [--blocks] [--posting-blocks] file [file ...]
+    python -m struspattern_amd.match -p program.rul [-K] [-o ORIGIN] [--paragraphs] [--frequencies] [--device-values] [--terms] [--dictionary] [--postings] [--positions] [--sorted] [--blocks] [--posting-blocks] [--lookup NAME=VALUE ...] [--lookup-prefix] file [file ...]
 
 Every file is one document (plain UTF-8 text; the reference tool segments XML with strusAnalyzer's
 segmenters, which are outside this engine -- pass -o to add the offset of the text inside its original
@@ -36,6 +36,10 @@ order of the files.
 delta-coded posting blocks on the GPU (finishedPostingBlocksDevice) and, read back from the blocks alone, listed behind the `block`
 lines: one line per block, `postblock J: lists N postings M positions Q bytes X`, and `postblocks J bytes X positions Q`.  List k
 of these blocks is the term at position k of the term blocks.  The lines do not depend on the order of the files.
+--lookup NAME=VALUE (repeatable) implies --blocks and --posting-blocks; the two block products are copied into a segment on the GPU
+(Segment.fromContext) and the terms of pattern NAME with the value VALUE -- with --lookup-prefix: whose value starts with VALUE --
+looked up there, all queries in one call (lookupDevice): behind the `postblock` lines one line `lookup NAME 'VALUE': terms N` per
+query and per term found its `post` line as --positions prints it, decoded from the segment instead of read from the fetched arrays.
 All files go to the GPU as one batch.  There is no CPU fallback.
 """
 import argparse
@@ -62,9 +66,12 @@ def main(argv=None):
     ap.add_argument("--sorted", action="store_true", help="implies --dictionary; its lines and those of --postings by pattern, then by value")
     ap.add_argument("--blocks", action="store_true", help="implies --sorted; after its lines, the front-coded term blocks of the sorted dictionary")
     ap.add_argument("--posting-blocks", action="store_true", help="implies --blocks and --positions; after the term blocks, the delta-coded posting blocks in the same order")
+    ap.add_argument("--lookup", action="append", default=[], metavar="NAME=VALUE", help="implies --blocks and --posting-blocks; the postings of the term, looked up in the segment on the device")
+    ap.add_argument("--lookup-prefix", action="store_true", help="the terms of --lookup are those whose value starts with VALUE")
     ap.add_argument("-d", "--device", type=int, default=0)
     ap.add_argument("files", nargs="+")
     args = ap.parse_args(argv)
+    args.posting_blocks = args.posting_blocks or bool(args.lookup)
     args.blocks = args.blocks or args.posting_blocks
     args.positions = args.positions or args.posting_blocks
     args.postings = args.postings or args.positions
@@ -115,6 +122,7 @@ def main(argv=None):
     print_postings(postings, dictionary, terms, mt, positions, order)
     print_blocks(blocks, mt)
     print_posting_blocks(posting_blocks)
+    print_lookups(args, mctx, mt)
     print("OK done")
     return 0
 
@@ -162,6 +170,40 @@ def posting_block_lines(blocks):
         lines.append("postblock %d: lists %d postings %d positions %d bytes %d" % (j, len(lists), sum(len(q) for q in lists), sum(len(p[2]) for q in lists for p in q),
                                                                                     int(blocks.block_offsets[j + 1] - blocks.block_offsets[j])))
     return lines + ["postblocks %d bytes %d positions %d" % (len(blocks.block_offsets) - 1, len(blocks.bytes), int(blocks.totals[3]))]
+
+
+def lookup_lines(segment, queries, prefix, pattern_name):
+    """the lines of --lookup; queries: (handle, value bytes) each, looked up in one call"""
+    segment.lookupDevice(queries, prefix=prefix)
+    found = segment.lookupFetch()
+    lines = []
+    for i, (h, q) in enumerate(queries):
+        if int(found.q_status[i]) != 0:
+            raise spa.PatternError("lookup of %s '%s' failed: status %d" % (pattern_name(h), q.decode("utf-8", "replace"), int(found.q_status[i])))
+        lines.append("lookup %s '%s': terms %d" % (pattern_name(h), q.decode("utf-8", "replace"), int(found.q_count[i])))
+        for handle, value, _, _, postings in found.query(i):
+            lines.append("post %s '%s': %s" % (pattern_name(handle), value.decode("utf-8", "replace"),
+                                               " ".join("%d:%d@%d[%s]" % (doc, count, pos[0], ",".join("%d" % x for x in pos)) for doc, count, pos in postings)))
+    return lines
+
+
+def print_lookups(args, mctx, mt):
+    """--lookup: a segment of the blocks built last on the context answers the queries"""
+    if not args.lookup:
+        return
+    queries = []
+    for spec in args.lookup:
+        name, sep, value = spec.partition("=")
+        handle = mt.patternId(name)
+        if not sep or not handle:
+            raise spa.PatternError("--lookup wants NAME=VALUE with the name of a pattern: '%s'" % spec)
+        queries.append((handle, value.encode("utf-8")))
+    segment = spa.Segment.fromContext(mctx)
+    try:
+        for line in lookup_lines(segment, queries, args.lookup_prefix, mt.patternName):
+            print(line)
+    finally:
+        segment.close()
 
 
 def print_posting_blocks(blocks):
@@ -345,6 +387,7 @@ def paragraphs(args, prg, lx, mt, docs):
     print_postings(postings, dictionary, terms, mt, positions, order)
     print_blocks(blocks, mt)
     print_posting_blocks(posting_blocks)
+    print_lookups(args, mctx, mt)
     print("OK done")
     return 0
 

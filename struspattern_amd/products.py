@@ -608,3 +608,135 @@ def batchPostingBlocks(dictionary, order, postings, positions):
     keep = []                                                        # (until the call has returned)
     d, o, q, x = _to_c(dictionary, keep), _to_c(order, keep), _to_c(postings, keep), _to_c(positions, keep)
     return _twin(MatchPostingBlocks, "sp_match_batch_posting_blocks", ctypes.byref(d), ctypes.byref(o), ctypes.byref(q), ctypes.byref(x))
+
+
+SP_LOOKUP_PREFIX = 1    # include/strus_pattern_amd.h: the flag of a lookup by prefix
+
+
+class SegmentLookup:
+    """The answer to the queries of one lookup in an index segment (host copies): per query its run of sorted positions, the
+    runs one behind the other being the selection, and per selected position its record, its full value and its decoded posting
+    list (include/strus_pattern_amd.h "segment lookups")."""
+    _C, _SCALARS, _TOTAL, _WHAT = capi.SpSegmentLookup, ("flags",), None, "lookup in the segment"
+    _FREE, _FETCH = "sp_segment_lookup_free", "sp_segment_lookup_fetch"
+    _ARRAYS = (
+        Arr("q_first", "q_first", "nq", 0, 0, u32),                        # the first sorted position not below the query
+        Arr("q_count", "q_count", "nq", 0, 0, u32),                        # the length of its run
+        Arr("q_status", "q_status", "nq", 0, 0, u32),                      # 0, or an SP_LOOKUP_ERR_* for a walk that met a malformed code
+        Arr("q_sel_offsets", "q_sel_offsets", "nq", 1, 0, u64),            # the run of query i is the selection [q_sel_offsets[i], q_sel_offsets[i+1])
+        Arr("selections", "selections", "nsel", 0, 6, u32),                # position, handle, doc_freq, value_bytes, count (low, high)
+        Arr("sel_value_offsets", "sel_value_offsets", "nsel", 1, 0, u64),  # into values
+        Arr("sel_posting_offsets", "sel_posting_offsets", "nsel", 1, 0, u64),   # into postings
+        Arr("values", "values", "nvalue_bytes", 0, 0, ctypes.c_uint8),     # the full values of the selected positions
+        Arr("postings", "postings", "npostings", 0, 4, u32),               # doc, count, npos, 0
+        Arr("posting_position_offsets", "posting_position_offsets", "npostings", 1, 0, u64),   # into positions
+        Arr("positions", "positions", "npositions", 0, 0, u32),            # the distinct ordinal positions, absolute and ascending
+        Arr("totals", "totals", None, 4, 0, u64),                          # nsel, npostings, npositions, the bytes of values
+    )
+
+    def __init__(self, q_first, q_count, q_status, q_sel_offsets, selections, sel_value_offsets, sel_posting_offsets, values, postings,
+                 posting_position_offsets, positions, totals, flags=0):
+        self.q_first, self.q_count, self.q_status, self.q_sel_offsets = q_first, q_count, q_status, q_sel_offsets
+        self.selections, self.sel_value_offsets, self.sel_posting_offsets = selections, sel_value_offsets, sel_posting_offsets
+        self.values, self.postings, self.posting_position_offsets, self.positions = values, postings, posting_position_offsets, positions
+        self.totals, self.flags = totals, flags
+        self.counts = np.ascontiguousarray(selections[:, 4:6]).view(np.uint64).reshape(-1)    # (nsel,) u64: the collection frequencies
+
+    def selection(self, s):
+        """selected position s: (handle, value bytes, doc_freq, count, [(doc, count, [positions])])"""
+        _, handle, doc_freq, _, _, _ = self.selections[s].tolist()
+        value = self.values[int(self.sel_value_offsets[s]):int(self.sel_value_offsets[s + 1])].tobytes()
+        postings = []
+        for p in range(int(self.sel_posting_offsets[s]), int(self.sel_posting_offsets[s + 1])):
+            doc, count, _, _ = self.postings[p].tolist()
+            postings.append((doc, count, self.positions[int(self.posting_position_offsets[p]):int(self.posting_position_offsets[p + 1])].tolist()))
+        return handle, value, doc_freq, int(self.counts[s]), postings
+
+    def query(self, i):
+        """what query i found, in sorted order: [(handle, value bytes, doc_freq, count, [(doc, count, [positions])])]"""
+        return [self.selection(s) for s in range(int(self.q_sel_offsets[i]), int(self.q_sel_offsets[i + 1]))]
+
+
+def _host_queries(queries):
+    """The query arguments of a lookup call (handles, offsets, bytes, nq) for an iterable of (handle, value bytes), and the arrays
+    they point into: the caller holds them until its C call has returned"""
+    queries = [(int(h), bytes(v)) for h, v in queries]
+    handles = np.ascontiguousarray([h for h, _ in queries], dtype=np.uint32)
+    offsets = np.zeros(len(queries) + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(v) for _, v in queries], dtype=np.uint64)
+    data = ctypes.create_string_buffer(b"".join(v for _, v in queries), int(offsets[-1]) + 1)   # (a pointer that is not null for no bytes)
+    return (handles.ctypes.data, offsets.ctypes.data, ctypes.addressof(data), len(queries)), [handles, offsets, data]
+
+
+def segmentLookup(term_blocks, posting_blocks, queries, prefix=False):
+    """The lookup of `queries` -- an iterable of (handle, value bytes) -- in the segment made of a MatchTermBlocks and the
+    MatchPostingBlocks of the same batch, exact or by prefix, by the rule of Segment.lookupDevice, without a device.  Returns a
+    SegmentLookup."""
+    keep = []                                                        # (until the call has returned)
+    t, p = _to_c(term_blocks, keep), _to_c(posting_blocks, keep)
+    args, held = _host_queries(queries)
+    return _twin(SegmentLookup, "sp_match_segment_lookup", ctypes.byref(t), ctypes.byref(p), *args, SP_LOOKUP_PREFIX if prefix else 0)
+
+
+class Segment:
+    """An index segment on the device: copies of the term blocks and the posting blocks of one batch that live without the
+    context that built them, and the buffers of the lookups in it (include/strus_pattern_amd.h "segment lookups")."""
+
+    def __init__(self, handle):
+        self._L, self._h = capi.lib(), handle
+
+    @classmethod
+    def open(cls, term_blocks, posting_blocks):
+        """the segment of a MatchTermBlocks and the MatchPostingBlocks of the same batch: fetches, twin output, or what was read
+        back from a file; only the tables are checked"""
+        keep, h, err = [], ctypes.c_void_p(), ctypes.create_string_buffer(256)
+        t, p = _to_c(term_blocks, keep), _to_c(posting_blocks, keep)
+        rc = capi.lib().sp_segment_open(ctypes.byref(t), ctypes.byref(p), ctypes.byref(h), err, 256)
+        if rc != 0:
+            raise PatternError("no segment (%d): %s" % (rc, err.value.decode()))
+        return cls(h)
+
+    @classmethod
+    def fromContext(cls, ctx, stream=0):
+        """the segment of the term blocks and the posting blocks built last on the PatternMatcherContext `ctx`, copied on the
+        device; it outlives the context and its next batch"""
+        h = ctypes.c_void_p()
+        rc = capi.lib().sp_segment_from_ctx(ctx._h, stream or None, ctypes.byref(h))
+        if rc != 0:
+            raise PatternError("no segment of the context (%d): %s" % (rc, ctx._err()))
+        return cls(h)
+
+    def _err(self):
+        return self._L.sp_segment_last_error(self._h).decode(errors="replace")
+
+    def lookupDevice(self, queries, prefix=False, stream=0):
+        """look `queries` -- an iterable of (handle, value bytes) -- up on the device, exact or by prefix: their runs, and the
+        records, values and decoded posting lists of what they select (the call waits once for the sizes, under prefix=True
+        twice; the emitting launch is asynchronous on `stream`).  Returns the device pointers (capi.SpSegmentLookupDevice), valid
+        until the next lookup on this segment."""
+        args, held = _host_queries(queries)                          # (held: until the call has returned)
+        out = capi.SpSegmentLookupDevice()
+        rc = self._L.sp_segment_lookup_device(self._h, *args, SP_LOOKUP_PREFIX if prefix else 0, stream or None, ctypes.byref(out))
+        if rc != 0:
+            raise PatternError("lookup in the segment failed (%d): %s" % (rc, self._err()))
+        return out
+
+    def lookupFetch(self):
+        """plain host copy of the last lookupDevice: a SegmentLookup"""
+        return _product(SegmentLookup, lambda s: self._L.sp_segment_lookup_fetch(self._h, ctypes.byref(s)),
+                        lambda rc: "fetching the %s failed (%d): %s" % (SegmentLookup._WHAT, rc, self._err()))
+
+    def lastLookupMs(self):
+        """duration of the last lookupDevice in milliseconds"""
+        ms = ctypes.c_double(-1.0)
+        if self._L.sp_segment_last_lookup_ms(self._h, ctypes.byref(ms)) != 0:
+            raise PatternError("no timed lookup")
+        return ms.value
+
+    def close(self):
+        if self._h:
+            self._L.sp_segment_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
